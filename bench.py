@@ -207,6 +207,28 @@ def cpu_baseline(shape, budget_s=60.0):
             "ms_per_step": best[2] * 1e3}
 
 
+DUMP_TABLE_ROWS = 4096              # --dump-outputs: seeded sample of embedding-table rows (the whole table is 55 MB)
+
+
+def dump_outputs(out_dir, model, loss_sum):
+    """--dump-outputs: what the last timed step handed its caller -- the loss sum Model.train_step returned, the click
+    scores of that step's forward and every parameter after its Adam update -- as <out_dir>/<name>.npy (float64 loss,
+    float32 otherwise).  The word-embedding table is sampled: DUMP_TABLE_ROWS rows drawn without replacement by
+    numpy.random.default_rng(0), in ascending order; every other parameter is written whole (about 8 MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_sum": np.asarray(float(loss_sum), dtype=np.float64),
+              "scores": model._last_scores.detach().float().cpu().numpy()}
+    for name, p in model.state_dict().items():
+        p = p.detach()
+        if name == "news_encoder.word_embedding.0.weight":
+            rows = np.sort(np.random.default_rng(0).choice(p.shape[0], size=min(DUMP_TABLE_ROWS, p.shape[0]), replace=False))
+            p, name = p[torch.from_numpy(rows).to(p.device)], name + ".sampled_rows"
+        arrays["param." + name] = p.float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("dumped %d outputs of the last timed step to %s (%.1f MB)" % (len(arrays), out_dir, sum(a.nbytes for a in arrays.values()) / 1e6))
+
+
 def timed(fn, n, sync=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -460,7 +482,13 @@ def main():
                     help="fp16 (default): fused one-wave-per-title kernels, scores inside 1e-4 of the oracle at 512 users "
                          "(the measured maximum is in the JSON line); bf16x3: split-bf16 projections (2e-6); fp32 = exact f32 MFMA; "
                          "bf16 misses the bar (3e-4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed (loss sum, click scores, updated "
+                         "parameters; a fixed sample of the embedding table) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    # the dropout seeds derive from torch.initial_seed(), which torch otherwise draws afresh per process: fixed here so that
+    # the same arguments give the same inputs, dropout masks included, from run to run
+    torch.manual_seed(0)
 
     # N > 1: have RCCL write its topology / algorithm choices (rings, trees, channels, transports) to a per-rank file so
     # the first multi-GPU record says what it ran on (parsed into data_parallel.rccl_info below)
@@ -581,6 +609,8 @@ def main():
     dt = parallel.max_over_ranks(dt, dev)
     loss = float(loss_sum) / B
     log("timed region: %d steps in %.3f s" % (args.steps, dt))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss_sum)      # before any later step changes the model
     eng.check_ids()
 
     # ---- data-parallel facts (every rank takes part; rank 0 reports)

@@ -19,7 +19,7 @@ reference's own classes:
                 mask (h=6, d_k=50).
   g4_auc.npz    evaluation.auc_score per padded impression + the mean (train_eval.py:219-271).
   g5_adam.npz   nrms_v0 + torch.optim.Adam(lr=1e-3) for 3 steps, dropout=0: losses and the
-                parameters afterwards (64 sampled table rows).
+                parameters afterwards, in float32 and (``losses64``, ``param64/``) in float64.
   g6_dataset.npz  the batch-dict items of the reference's own ``MyDataset.__getitem__``
                 (data_handler.py:185-250; ``np.int = int`` shim for numpy 2, stub ``nltk``) on the
                 hand-written samples of ``synth.dataset_fixture_inputs()``: all 13 keys, train (type 0)
@@ -205,27 +205,37 @@ def gen_g4():
 
 
 def gen_g5():
+    """The same 3 steps twice: in float32 (the reference as it runs) and in float64.  At this shape the user encoder's
+    additive-attention gradients are 1e-10 ... 6e-9, at Adam's eps, so their float32 updates carry the rounding of
+    the host's summation order; the float64 run pins those parameters independently of it."""
     shape = synth.G1_ODD
     params = synth.make_params(shape, seed=51)
-    model = build_ref_model(shape, params, dropout=0.0)
-    model.train()
-    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
-    crit = torch.nn.CrossEntropyLoss()
-    losses = []
-    for t in range(3):
-        batch = synth.make_batch(shape, seed=52 + t, ragged=True, min_title=1)
-        with cpu_device_patch():
-            out = model(torch_batch(batch))
-        model.zero_grad()
-        loss = crit(out, torch.zeros(len(out)).long())
-        losses.append(float(loss))
-        loss.backward()
-        opt.step()
-    outd = {"losses": np.array(losses)}
-    for n, p in model.named_parameters():
-        outd["param/" + n] = p.detach().numpy().copy()
+    outd = {}
+    for dtype, tag in ((torch.float32, ""), (torch.float64, "64")):
+        torch.set_default_dtype(dtype)         # the reference allocates its own intermediates in the default dtype
+        try:
+            model = build_ref_model(shape, params, dropout=0.0).to(dtype)
+            model.train()
+            opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+            crit = torch.nn.CrossEntropyLoss()
+            losses = []
+            for t in range(3):
+                batch = synth.make_batch(shape, seed=52 + t, ragged=True, min_title=1)
+                with cpu_device_patch():
+                    out = model(torch_batch(batch))
+                model.zero_grad()
+                loss = crit(out, torch.zeros(len(out)).long())
+                losses.append(float(loss))
+                loss.backward()
+                opt.step()
+        finally:
+            torch.set_default_dtype(torch.float32)
+        outd["losses" + tag] = np.array(losses)
+        for n, p in model.named_parameters():
+            assert p.dtype == dtype, (n, p.dtype)
+            outd["param%s/%s" % (tag, n)] = p.detach().numpy().copy()
+        print("g5", tag or "32", losses)
     np.savez_compressed(os.path.join(HERE, "g5_adam.npz"), **outd)
-    print("g5", losses)
 
 
 def gen_g6():

@@ -117,15 +117,24 @@ def test_g5_adam_three_steps(golden_dir):
     out, losses = orc.train_steps(params, batches, shape.num_attention_heads, lr=1e-3)
     np.testing.assert_allclose(losses, g["losses"], atol=TOL)
     for n in synth.param_names():
-        if n.endswith("W_K.bias"):
+        if n.endswith("W_K.bias") or n.startswith("user_encoder.additive_attention."):
             # dL/d(b_K) is analytically 0 (adding q.b_K to every key of a query leaves the
             # softmax unchanged), so the reference's own gradient there is rounding noise
             # (~1e-10) that Adam normalises to +-lr steps: only the 3*lr bound is meaningful.
+            # The user encoder's additive-attention gradients are 1e-10 ... 6e-9 here, at Adam's
+            # eps, so their float32 updates follow the host's summation order (AVX-512 against
+            # AVX2 kernels: up to 8e-5 apart).  The float64 run below pins all of them.
             assert np.abs(out[n] - params[n]).max() <= 3.1e-3
             assert np.abs(g["param/" + n] - params[n]).max() <= 3.1e-3
             continue
         # Adam's first steps move a weight by ~lr whatever |g|; compare at 1% of one step
         np.testing.assert_allclose(out[n], g["param/" + n], rtol=0, atol=1e-5, err_msg=n)
+    # the same 3 steps in float64 against the reference's own float64 run: every parameter, no rounding noise left
+    out64, losses64 = orc.train_steps(params, batches, shape.num_attention_heads, lr=1e-3, dtype=torch.float64)
+    np.testing.assert_allclose(losses64, g["losses64"], rtol=0, atol=1e-12)
+    for n in synth.param_names():
+        assert out64[n].dtype == np.float64 and g["param64/" + n].dtype == np.float64
+        np.testing.assert_allclose(out64[n], g["param64/" + n], rtol=0, atol=1e-10, err_msg=n)
 
 
 def test_dropout_keep_mask_semantics():
