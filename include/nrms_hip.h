@@ -281,6 +281,25 @@ int nrms_grad_guard(size_t n, float* grad, int32_t* n_nonfinite, void* stream);
 int nrms_impression_auc(int32_t n_imp, int32_t max_c, const float* scores, const uint8_t* labels,
                         const int32_t* lens, double* auc, void* stream);
 
+/* The four MIND scores per impression and the submission ranks of test(), in one pass (same inputs as
+ * nrms_impression_auc; only the prefix n = min(lens[i], max_c) of a row counts; a label != 0 is a positive).
+ * Every output is a nullable device pointer; at least one must be given (n_imp = 0: a no-op, any pointer may be null).
+ *   auc    [n_imp] f64: bit-identical to nrms_impression_auc (NaN when the prefix holds one class only).
+ *   mrr    [n_imp] f64: sum over positives of 1 / rank_m, over n_pos.
+ *   ndcg_a [n_imp] f64: sum over positives with rank_m <= k_a of 1 / log2(rank_m + 1), over
+ *                       sum_{r=1}^{min(n_pos, k_a)} 1 / log2(r + 1)  (k_a > n: the whole prefix).  ndcg_b: k_b.
+ *          MRR and nDCG are NaN when the prefix has no positive or holds a NaN score.
+ *   ranks  [n_imp, max_c] i32: the rank (1 = best) of each shown candidate, 0 past the prefix.
+ * Tie rule.  The metrics rank among equal scores the LATER slot first (np.argsort(s, kind="stable")[::-1], the
+ * reference's mrr_score / ndcg_score whenever its sort keeps equal keys in index order):
+ *     rank_m(i) = 1 + #{j : s_j > s_i} + #{j > i : s_j == s_i}.
+ * The submission ranks put the EARLIER slot first (np.argsort(-s, kind="stable"), train_eval._cal_test), NaN after
+ * every number and NaNs in slot order:  rank_s(i) = 1 + #{j : s_j > s_i} + #{j < i : s_j == s_i}.
+ * Counts are integers and the f64 sums have a fixed order: two runs are bit-identical. */
+int nrms_impression_metrics(int32_t n_imp, int32_t max_c, const float* scores, const uint8_t* labels,
+                            const int32_t* lens, int32_t k_a, int32_t k_b, double* auc, double* mrr, double* ndcg_a,
+                            double* ndcg_b, int32_t* ranks, void* stream);
+
 /* ---- nrms_naml pieces around the two encoder passes (model/nrms_naml.py) ----
  * LayerNorm over the last dimension (nn.LayerNorm(news_feature_size) on the history vectors, nrms_naml.py:207,238):
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance.  stats [n_rows, 2] = (mean, 1/std) is written when

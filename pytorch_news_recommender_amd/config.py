@@ -47,6 +47,9 @@ class Config(object):
         self.require_improvement = 10000
         self.warm_up_steps = 500
         self.warm_up = False
+        # train(): evaluate with train_eval.evaluate_metrics (AUC, MRR, nDCG@5, nDCG@10) instead of evaluate (AUC only);
+        # checkpoints are still picked by the AUC
+        self.eval_metrics = False
         # HIP path only: "fp32" (exact f32 MFMA), "bf16x3" (split-bf16 projections), "bf16", or "fp16" (fused
         # one-wavefront-per-title fp16 news encoder; the user encoder -- 3 % of the flops -- stays in bf16x3 unless
         # fp16_user_encoder is set, which keeps the scores inside the 1e-4 bar with margin)

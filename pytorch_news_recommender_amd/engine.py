@@ -101,6 +101,25 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def impression_metrics(lib, device, scores, labels, lens, ks=(5, 10), ranks=False):
+    """NRMSEngine.impression_metrics without an engine (evaluation.score_submission): ``lib`` is _lib.load()."""
+    k_a, k_b = (int(k) for k in ks)
+    n, cmax = scores.shape
+    f64 = dict(dtype=torch.float64, device=device)
+    out = dict(auc=torch.empty(n, **f64), mrr=torch.empty(n, **f64))
+    nd_a, nd_b = torch.empty(n, **f64), torch.empty(n, **f64)
+    rk = torch.empty(n, cmax, dtype=torch.int32, device=device) if ranks else None
+    scores, labels, lens = scores.contiguous(), labels.contiguous(), lens.contiguous()
+    rc = lib.nrms_impression_metrics(n, cmax, _lib.ptr(scores), _lib.ptr(labels), _lib.ptr(lens), k_a, k_b,
+                                     _lib.ptr(out["auc"]), _lib.ptr(out["mrr"]), _lib.ptr(nd_a), _lib.ptr(nd_b),
+                                     _lib.ptr(rk), _stream())
+    _lib.check(rc, "nrms_impression_metrics")
+    out["ndcg@%d" % k_a], out["ndcg@%d" % k_b] = nd_a, nd_b
+    if ranks:
+        out["ranks"] = rk
+    return out
+
+
 class NRMSEngine:
     """One NRMS forward / backward / optimizer step on one GPU."""
 
@@ -552,6 +571,13 @@ class NRMSEngine:
                                           _lib.ptr(lens.contiguous()), _lib.ptr(auc), _stream())
         _lib.check(rc, "nrms_impression_auc")
         return auc
+
+    def impression_metrics(self, scores, labels, lens, ks=(5, 10), ranks=False):
+        """scores [n, Cmax] fp32, labels [n, Cmax] uint8, lens [n] int32 (device) -> dict of device tensors:
+        float64 [n] ``auc``, ``mrr``, ``ndcg@<k>`` for both cutoffs of ``ks``, and with ranks=True the int32 [n, Cmax]
+        submission ranks ``ranks`` (0 past each prefix).  Tie rule and NaN cases: include/nrms_hip.h
+        nrms_impression_metrics."""
+        return impression_metrics(self.lib, self.device, scores, labels, lens, ks, ranks)
 
     # ---- inference with unique-title caching (SURVEY f-1) -------------------------------------
     def group_rows(self, rows):

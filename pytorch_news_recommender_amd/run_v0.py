@@ -41,6 +41,7 @@ def build_parser():
     parser.add_argument('--feed', type=str, default='device', help="device: batches assembled in HBM from a resident news "
                         "table (DeviceFeed); loader: the reference's DataLoader(MyDataset) with --num_workers processes")
     parser.add_argument('--data_path', type=str, default=None, help='overrides config.data_path (./data_processed/)')
+    parser.add_argument('--metrics', action='store_true', help='evaluate on AUC, MRR, nDCG@5 and nDCG@10 (config.eval_metrics)')
     parser.add_argument('--save_path', type=str, default=None, help='overrides config.save_path (./save_model/)')
     return parser
 
@@ -57,6 +58,7 @@ def main(argv=None):
         config.precision = args.precision
     config.num_epochs = 6 if args.epochs is None else args.epochs
     config.mode = args.dataset
+    config.eval_metrics = args.metrics
     if args.data_path:
         config.data_path = os.path.join(args.data_path, '')
     if args.save_path:
@@ -109,6 +111,10 @@ def main(argv=None):
                      max_batches=args.max_batches, verbose=rank == 0)
         if rank == 0:
             print('final dev AUC:', hist['aucs'][-1] if hist['aucs'] else None)
+            if hist['metrics']:
+                m = hist['metrics'][-1][1]
+                print('final dev AUC: {:.4f}  MRR: {:.4f}  nDCG@5: {:.4f}  nDCG@10: {:.4f}'.format(
+                    m['auc'], m['mrr'], m['ndcg5'], m['ndcg10']))
         return hist
     else:
         # run_v0.py:93-111: the test set through the checkpoint named by --load (or the best one by file-name AUC)

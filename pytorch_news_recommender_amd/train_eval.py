@@ -9,7 +9,9 @@ train():    Adam(lr=config.learning_rate) + CrossEntropy with label 0, loss aver
             (``model(batch)`` -> criterion -> backward -> torch.optim.Adam) through the same kernels.
 evaluate(): per-impression AUC on the un-padded prefix, unweighted mean (train_eval.py:219-271), with
             the scores never leaving the GPU (``nrms_impression_auc``) instead of a fork pool.
-test():     per-impression rank lists in the MIND submission format (train_eval.py:280-286,335-341).
+evaluate_metrics(): the same loop scored on AUC, MRR, nDCG@5 and nDCG@10 (``nrms_impression_metrics``).
+test():     per-impression rank lists in the MIND submission format (train_eval.py:280-286,335-341), ranked on the
+            GPU batch by batch; ``_cal_test`` is the host statement of the same ranks.
 """
 from __future__ import annotations
 
@@ -38,14 +40,10 @@ def _pad_labels(y_true, max_c, device):
     return torch.from_numpy(lab).to(device), torch.from_numpy(lens).to(device)
 
 
-def evaluate(config, model, data_iter, y_true=None, AUC_best=None, verbose=True):
-    """y_true: list (one entry per impression, in data_iter order) of 0/1 label lists -- the
-    reference keeps it in the module global ``_y_true`` read from dev_behaviors.csv (:36-39); None reads
-    that file (data_handler.read_dev_labels).
-
-    Deviation, on purpose: the reference calls ``model.eval()`` here and never ``model.train()`` again (its
-    re-enable is commented out, train_eval.py:122,230), so after its first evaluation it trains with dropout
-    off.  This evaluate() restores the mode it found."""
+def _eval_scores(config, model, data_iter, y_true):
+    """The scoring loop of evaluate() and evaluate_metrics(): every impression scored in eval mode on the persistent
+    news-vector cache, ids checked, the train / eval mode restored.  Returns (net, scores [n, Cmax] device, padded
+    labels, lens)."""
     if y_true is None:
         from .data_handler import read_dev_labels
         y_true = read_dev_labels(config)
@@ -61,16 +59,47 @@ def evaluate(config, model, data_iter, y_true=None, AUC_best=None, verbose=True)
                 scores.append(net(datas))
     finally:
         net.last_eval_cache = eng.news_cache_end()
+    net.train(was_training)
     rank_score = torch.cat(scores, dim=0)
     eng.check_ids()
     lab, lens = _pad_labels(y_true[:rank_score.shape[0]], rank_score.shape[1], rank_score.device)
-    aucs = eng.impression_auc(rank_score, lab, lens)
+    return net, rank_score, lab, lens
+
+
+def evaluate(config, model, data_iter, y_true=None, AUC_best=None, verbose=True):
+    """y_true: list (one entry per impression, in data_iter order) of 0/1 label lists -- the
+    reference keeps it in the module global ``_y_true`` read from dev_behaviors.csv (:36-39); None reads
+    that file (data_handler.read_dev_labels).
+
+    Deviation, on purpose: the reference calls ``model.eval()`` here and never ``model.train()`` again (its
+    re-enable is commented out, train_eval.py:122,230), so after its first evaluation it trains with dropout
+    off.  This evaluate() restores the mode it found."""
+    net, rank_score, lab, lens = _eval_scores(config, model, data_iter, y_true)
+    aucs = net.engine.impression_auc(rank_score, lab, lens)
     AUC = float(aucs.mean().item())
     net.last_eval_scores, net.last_eval_aucs = rank_score, aucs      # diagnostics (per-impression values of this evaluation)
     if verbose:
         print('AUC:', AUC)
-    net.train(was_training)
     return AUC
+
+
+def evaluate_metrics(config, model, data_iter, y_true=None, verbose=True):
+    """The four MIND scores of the dev set: dict(auc, mrr, ndcg5, ndcg10), each the unweighted mean over impressions
+    (the reference's commented-out lines, train_eval.py:263-270).  Same scoring loop as evaluate(), so ``auc`` is the
+    number evaluate() returns on the same weights; the per-impression values come from one nrms_impression_metrics
+    pass and are kept in ``last_eval_metrics`` (dict of device tensors: auc, mrr, ndcg@5, ndcg@10).  Tie rule:
+    include/nrms_hip.h."""
+    net, rank_score, lab, lens = _eval_scores(config, model, data_iter, y_true)
+    m = net.engine.impression_metrics(rank_score, lab, lens, ks=(5, 10))
+    means = torch.stack([m[k].mean() for k in ("auc", "mrr", "ndcg@5", "ndcg@10")]).cpu().tolist()
+    res = dict(zip(("auc", "mrr", "ndcg5", "ndcg10"), means))
+    net.last_eval_scores, net.last_eval_aucs, net.last_eval_metrics = rank_score, m["auc"], m
+    if verbose:
+        print('AUC:', res['auc'])
+        print('MRR:', res['mrr'])
+        print('nDCG@5:', res['ndcg5'])
+        print('nDCG@10:', res['ndcg10'])
+    return res
 
 
 def log_res(config, step, auc):
@@ -105,7 +134,8 @@ def warmup_iterations(warm_up_steps=500):
 
 def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autograd=False, max_batches=None,
           verbose=True):
-    """Returns dict(losses=[...per batch...], aucs=[(batch, auc), ...], ckpts=[...]).
+    """Returns dict(losses=[...per batch...], aucs=[(batch, auc), ...], ckpts=[...], metrics=[(batch, dict), ...]);
+    ``metrics`` is filled when config.eval_metrics is set (evaluate_metrics instead of evaluate at every evaluation).
     With config.warm_up the epochs are preceded by the reference's warm-up pass over the first
     batches of train_iter with a linearly increasing learning rate (train_eval.py:64-99)."""
     net = _inner(model)
@@ -122,7 +152,15 @@ def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autogra
         # model/nrms_hip.py _NRMSFunction.backward)
         net.reuse_grad_buffer = True
     total_batch, AUC_best, STEP_SIZE = 0, 0.56, 100          # train_eval.py:59,61
-    hist = dict(losses=[], aucs=[], ckpts=[], warmup_losses=[])
+    hist = dict(losses=[], aucs=[], ckpts=[], warmup_losses=[], metrics=[])
+
+    def dev_auc():
+        if not getattr(config, 'eval_metrics', False):
+            return evaluate(config, model, dev_iter, dev_labels, AUC_best, verbose)
+        m = evaluate_metrics(config, model, dev_iter, dev_labels, verbose)
+        hist['metrics'].append((total_batch, m))
+        return m['auc']              # checkpoints are still picked by the dev AUC alone
+
     window = []
     done = False
     if getattr(config, 'warm_up', False):
@@ -180,7 +218,7 @@ def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autogra
                         total_batch, float(np.mean(vals)), time.time() - start))
             total_batch += 1
             if dev_iter is not None and total_batch % config.eval_step == 0:
-                auc = evaluate(config, model, dev_iter, dev_labels, AUC_best, verbose)
+                auc = dev_auc()
                 hist['aucs'].append((total_batch, auc))
                 log_res(config, auc, total_batch)
                 if auc > AUC_best:
@@ -191,7 +229,7 @@ def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autogra
                 done = True
                 break
         if dev_iter is not None:
-            auc = evaluate(config, model, dev_iter, dev_labels, AUC_best, verbose)
+            auc = dev_auc()
             hist['aucs'].append((total_batch, auc))
             log_res(config, auc, 'epoch_{}'.format(epoch))
             if auc > AUC_best:
@@ -205,7 +243,8 @@ def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autogra
 
 
 def _cal_test(scores, n):
-    """Rank (1 = best) of each shown candidate (train_eval.py:280-286)."""
+    """Rank (1 = best) of each shown candidate (train_eval.py:280-286).  Host reference of the submission ranks that
+    test() computes on the GPU (nrms_impression_metrics)."""
     res = np.argsort(-np.asarray(scores[:n]), kind="stable")
     rank = [0] * n
     for pos, v in enumerate(res):
@@ -251,17 +290,26 @@ def test(config, model, data_iter, test_list_nums=None, ckpt_file=None, out_file
         from .data_handler import get_Test_List
         test_list_nums = get_Test_List(config)
     net.eval()
-    scores = []
-    net.engine.news_cache_begin()
+    eng = net.engine
+    ranks = []
+    eng.news_cache_begin()
     try:
         with torch.no_grad():
             for datas in data_iter:
-                scores.append(net(datas).cpu())
+                # each batch ranked on the GPU (nrms_impression_metrics, the tie rule of _cal_test); only int32 ranks come back
+                s = net(datas)
+                nums = [int(n) for n in test_list_nums[len(ranks):len(ranks) + s.shape[0]]]
+                if not nums:
+                    continue
+                s = s[:len(nums)]
+                lens = torch.tensor(nums, dtype=torch.int32).to(s.device)
+                lab = torch.zeros(s.shape, dtype=torch.uint8, device=s.device)
+                rk = eng.impression_metrics(s, lab, lens, ranks=True)["ranks"].cpu().numpy()
+                # a row shorter than its shown count keeps _cal_test's trailing zeros
+                ranks.extend(rk[i, :n].tolist() + [0] * (n - rk.shape[1]) for i, n in enumerate(nums))
     finally:
-        net.engine.news_cache_end()
-    net.engine.check_ids()
-    test_rank_score = np.concatenate([s.numpy() for s in scores])
-    ranks = [_cal_test(test_rank_score[i], int(n)) for i, n in enumerate(test_list_nums[:len(test_rank_score)])]
+        eng.news_cache_end()
+    eng.check_ids()
     file_name = out_file or 'sumbit_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
     with open(file_name, 'w') as f:
         for i, r in enumerate(ranks):
