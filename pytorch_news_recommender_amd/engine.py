@@ -62,35 +62,44 @@ def role_names(style: str, output_proj: bool):
     return out
 
 
-class FlatLayout:
-    """Offsets (in floats) of the reference-named tensors inside the flat buffer.
-    W_Q/W_K/W_V (and their biases) are adjacent so the kernels see one [3d, d] matrix."""
+def nrms_entries(dims: ModelDims):
+    """The (name, shape, encoder, role) entries of v0 / v1 in flat-buffer order (role_names with their shapes)."""
+    V, d, q = dims.n_words, dims.word_embed_size, dims.query_vector_dim
+    if d % 4 or q % 4:
+        raise ValueError("word_embed_size and query_vector_dim must be multiples of 4")
+    shapes = {"table": (V, d), "wq": (d, d), "wk": (d, d), "wv": (d, d), "bq": (d,), "bk": (d,), "bv": (d,),
+              "wo": (d, d), "bo": (d,), "wa": (q, d), "ba": (q,), "qv": (q,)}
+    return [(name, shapes[role], enc, role) for name, enc, role in role_names(dims.style, dims.output_proj)]
 
-    def __init__(self, dims: ModelDims):
-        V, d, q = dims.n_words, dims.word_embed_size, dims.query_vector_dim
-        if d % 4 or q % 4:
-            raise ValueError("word_embed_size and query_vector_dim must be multiples of 4")
+
+class FlatLayout:
+    """Offsets (in floats) of the reference-named tensors inside the flat buffer, from an ordered list of
+    (name, shape, encoder, role) entries (encoder and role None for a tensor outside the encoder descriptors;
+    default: nrms_entries(dims)).  The embedding table comes first; W_Q/W_K/W_V (and their biases) are adjacent
+    so the kernels see one [3w, w] matrix."""
+
+    def __init__(self, dims, entries=None):
         self.dims = dims
-        self.entries = {}
-        self.blocks = {enc: {} for enc in ENCODERS}
-        shapes = {"table": (V, d), "wq": (d, d), "wk": (d, d), "wv": (d, d), "bq": (d,), "bk": (d,), "bv": (d,),
-                  "wo": (d, d), "bo": (d,), "wa": (q, d), "ba": (q,), "qv": (q,)}
+        self.entries, self.blocks, widths = {}, {}, {}
         off = 0
-        for name, enc, role in role_names(dims.style, dims.output_proj):
-            shp = shapes[role]
+        for name, shape, enc, role in (nrms_entries(dims) if entries is None else entries):
             n = 1
-            for x in shp:
+            for x in shape:
                 n *= x
-            self.entries[name] = (off, shp, n)
-            self.blocks[enc][role] = off
+            self.entries[name] = (off, tuple(shape), n)
+            if enc is not None:
+                self.blocks.setdefault(enc, {})[role] = off
+                if role == "wq":
+                    widths[enc] = shape[0]
             off += n
         self.total = off
         self.names = list(self.entries)
-        for enc in ENCODERS:
+        for enc, w in widths.items():
             b = self.blocks[enc]
-            assert b["wk"] == b["wq"] + d * d and b["wv"] == b["wq"] + 2 * d * d      # adjacency the kernels rely on
-            assert b["bk"] == b["bq"] + d and b["bv"] == b["bq"] + 2 * d
+            assert b["wk"] == b["wq"] + w * w and b["wv"] == b["wq"] + 2 * w * w      # adjacency the kernels rely on
+            assert b["bk"] == b["bq"] + w and b["bv"] == b["bq"] + 2 * w
         self.table = self.blocks["news_encoder"]["table"]
+        assert self.table == 0, "the embedding table must be the first entry"
 
     def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
         off, shp, n = self.entries[name]
@@ -123,11 +132,11 @@ def impression_metrics(lib, device, scores, labels, lens, ks=(5, 10), ranks=Fals
 class NRMSEngine:
     """One NRMS forward / backward / optimizer step on one GPU."""
 
-    def __init__(self, dims: ModelDims, device, precision="fp32"):
+    def __init__(self, dims, device, precision="fp32", layout=None):
         self.lib = _lib.load()
         self.dims = dims
         self.set_precision(precision)
-        self.layout = FlatLayout(dims)
+        self.layout = FlatLayout(dims) if layout is None else layout
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.NrmsError("the NRMS HIP engine needs a GPU device (got %s); there is no CPU path" % device)

@@ -29,20 +29,16 @@ import ctypes as C
 import torch
 
 from .. import _lib
-from ..engine import ModelDims, NRMSEngine, _stream
+from ..engine import FlatLayout, ModelDims, NRMSEngine, _stream
 from ..segpool import SegmentPool
 from . import nrms_hip
-from ._flat_model import AdditiveParams, FlatHipModel, FlatLayout2, additive_entries
+from ._flat_model import FlatHipModel, additive_entries, news_encoder_entries
 
 LEVELS = ("neighbor_attention", "user_attention")
 
 
 class GraphEngine(NRMSEngine):
     """Forward / backward of the graph encoder on one GPU: the NRMS engine's news encoder, two segment pools, click scores."""
-
-    def __init__(self, dims, layout, device, precision):
-        super().__init__(dims, device, precision=precision)
-        self.layout = layout
 
     def _csr(self, key, lists, n_rows):
         n_seg, K = lists.shape
@@ -148,18 +144,18 @@ class Model(FlatHipModel):
         V, d = table.shape
         q = int(config.query_vector_dim)
         self.news_encoder = nrms_hip._NewsEncoderParams(config, table)
-        self.neighbor_attention = AdditiveParams(q, d)
-        self.user_attention = AdditiveParams(q, d)
+        self.neighbor_attention = nrms_hip._AdditiveAttentionParams(q, d)
+        self.user_attention = nrms_hip._AdditiveAttentionParams(q, d)
         self._dims = ModelDims(n_words=int(V), word_embed_size=int(d), num_attention_heads=int(config.num_attention_heads), query_vector_dim=q)
         extra = []
         for lv in LEVELS:
             extra += additive_entries(lv, q, d)
-        self._finish(FlatLayout2(self._dims, extra), table.device)
+        self._finish(FlatLayout(self._dims, news_encoder_entries(self._dims, extra)), table.device)
 
     def _make_engine(self, device, precision):
-        return GraphEngine(self._dims, self._layout, device, precision)
+        return GraphEngine(self._dims, device, precision=precision, layout=self._layout)
 
-    def _device_batch(self, batch, dev):
+    def _engine_args(self, batch, dev):
         if (batch.get("neighbor_rows") if hasattr(batch, "get") else None) is None:
             # a loader that knows no graph (data_handler.MyDataset): sample the neighbours from the click graph induced on this batch
             from ..graph_sampler import induced_neighbor_rows
@@ -168,4 +164,4 @@ class Model(FlatHipModel):
             batch = dict(batch)
             batch["neighbor_rows"] = induced_neighbor_rows(cpu(batch["browsed_titles"]), cpu(batch["browsed_mask"]), cpu(batch["candidate_titles"]),
                                                            int(getattr(self.config, "graph_neighbors", 8)), seed=self._sampled)
-        return super()._device_batch(batch, dev)
+        return super()._engine_args(batch, dev)

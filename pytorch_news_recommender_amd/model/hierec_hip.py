@@ -28,10 +28,10 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import ModelDims, NRMSEngine, _stream
+from ..engine import FlatLayout, ModelDims, NRMSEngine, _stream
 from ..segpool import SegmentPool
 from . import nrms_hip
-from ._flat_model import AdditiveParams, FlatHipModel, FlatLayout2, additive_entries
+from ._flat_model import FlatHipModel, additive_entries, news_encoder_entries
 
 LEVELS = ("subtopic_attention", "topic_attention", "user_attention")
 
@@ -42,15 +42,14 @@ def hier_layout(dims: ModelDims, n_sub: int, n_top: int):
     extra = [("subtopic_embedding.weight", (n_sub, d)), ("topic_embedding.weight", (n_top, d))]
     for lv in LEVELS:
         extra += additive_entries(lv, q, d)
-    return FlatLayout2(dims, extra)
+    return FlatLayout(dims, news_encoder_entries(dims, extra))
 
 
 class HieRecEngine(NRMSEngine):
     """Forward / backward of the hierarchical model on one GPU: the NRMS engine's news encoder + the index and aggregation calls."""
 
     def __init__(self, dims, layout, device, precision, n_sub, n_top, lambda_sub, lambda_top):
-        super().__init__(dims, device, precision=precision)
-        self.layout = layout
+        super().__init__(dims, device, precision=precision, layout=layout)
         self.n_sub, self.n_top = int(n_sub), int(n_top)
         self.lambda_sub, self.lambda_top = float(lambda_sub), float(lambda_top)
         self._pools = None
@@ -209,9 +208,9 @@ class Model(FlatHipModel):
         self.news_encoder = nrms_hip._NewsEncoderParams(config, table)
         self.subtopic_embedding = nn.Embedding(int(config.subcategory_nums), d, padding_idx=0)
         self.topic_embedding = nn.Embedding(int(config.category_nums), d, padding_idx=0)
-        self.subtopic_attention = AdditiveParams(q, d)
-        self.topic_attention = AdditiveParams(q, d)
-        self.user_attention = AdditiveParams(q, d)
+        self.subtopic_attention = nrms_hip._AdditiveAttentionParams(q, d)
+        self.topic_attention = nrms_hip._AdditiveAttentionParams(q, d)
+        self.user_attention = nrms_hip._AdditiveAttentionParams(q, d)
         self._dims = ModelDims(n_words=int(V), word_embed_size=int(d), num_attention_heads=int(config.num_attention_heads), query_vector_dim=q)
         self._finish(hier_layout(self._dims, int(config.subcategory_nums), int(config.category_nums)), table.device)
 

@@ -14,13 +14,11 @@ weights); the nn.Linear / nn.Embedding forwards are never called.
 from __future__ import annotations
 
 import numpy as np
-import os
-
 import torch
 import torch.nn as nn
 
-from .. import _lib
 from ..engine import FlatLayout, ModelDims, NRMSEngine
+from ._flat_model import FlatHipModel
 
 
 class _MultiHeadSelfAttentionParams(nn.Module):
@@ -86,42 +84,7 @@ def _ids_on(dev, x):
     return t.to(dev, dtype=torch.int32 if t.dtype == torch.int32 else torch.int64, non_blocking=True)
 
 
-class _NRMSFunction(torch.autograd.Function):
-    """scores = NRMS(batch; params) with the backward in HIP (autograd sees one node)."""
-
-    @staticmethod
-    def forward(ctx, model, bt, ct, mask, p_drop, seed, *params):
-        ctx.model = model
-        scores = model._engine.forward(model._flat, bt, ct, mask, training=True, p_drop=p_drop, seed=seed)
-        ctx.gen = model._engine._saved["gen"]
-        return scores
-
-    @staticmethod
-    def backward(ctx, dscores):
-        model = ctx.model
-        # Default: a fresh flat gradient buffer per backward -- autograd adopts the returned views as .grad, and a tensor
-        # the caller kept from an earlier step (a saved p.grad, a hook's argument) must keep its values, as torch guarantees.
-        # model.reuse_grad_buffer = True (set by train_eval.train for the reference's loop, which zeroes the gradients
-        # before every backward, train_eval.py:115, and keeps nothing) opts into ONE persistent 57.6 MB buffer instead;
-        # even then a fresh buffer is used while gradients are being accumulated (.grad still set).
-        reuse = bool(getattr(model, "reuse_grad_buffer", False)) and not any(p.grad is not None for p in model.parameters())
-        gflat = model._autograd_grad if reuse else None
-        if gflat is None or gflat.shape != model._flat.shape or gflat.device != model._flat.device:
-            gflat = torch.empty_like(model._flat)
-            if reuse:
-                model._autograd_grad = gflat
-        gflat.zero_()
-        model._engine.backward(model._flat, gflat, dscores, gen=ctx.gen)
-        if model._engine.precision == "fp16":
-            # the caller's own optimizer follows (torch.optim.Adam, train_eval.py:127): inf / nan elements of an overflowing
-            # fp16 backward become 0 and are counted; the engine lowers its loss scale when the count reaches the host
-            model._engine.grad_guard(gflat)
-            model._engine.note_grad_check()
-        grads = tuple(model._layout.view(gflat, n) for n in model._names)
-        return (None, None, None, None, None, None) + grads
-
-
-class Model(nn.Module):
+class Model(FlatHipModel):
     """NRMS network: 1+K candidate titles and the clicked-title history -> click logits."""
 
     def __init__(self, config, pretrained_word_embedding=None):
@@ -133,23 +96,7 @@ class Model(nn.Module):
             raise ValueError("embedding width %d != config.word_embed_size %d" % (d, config.word_embed_size))
         self._build_modules(config, table)
         self._dims = self._make_dims(config, int(V), int(d))
-        self._layout = self._make_layout(self._dims)
-        self._names = self._layout.names
-        named = dict(self.named_parameters())
-        missing = [n for n in self._names if n not in named]
-        assert not missing and len(named) == len(self._names), (missing, sorted(named))
-        self._flat = None
-        self._pad_zero = None
-        self._engine = None
-        self._opt = None
-        self._calls = 0
-        self._autograd_grad = None
-        self.reuse_grad_buffer = False      # autograd path: see _NRMSFunction.backward
-        self._flatten(table.device)
-        # a load through ANY parent (the dispatch wrapper of model/__init__.py included) may change the embedding
-        # table: nn.Module.load_state_dict recurses via _load_from_state_dict and never calls a child's
-        # load_state_dict, so the reset lives in a post-hook, which fires on recursive loads too
-        self.register_load_state_dict_post_hook(Model._reset_pad_flag)
+        self._finish(self._make_layout(self._dims), table.device)
 
     # ---- topology hooks (overridden by model/nrms_v1_hip.py) ---------------------------------------
     def _build_modules(self, config, table):
@@ -164,100 +111,31 @@ class Model(nn.Module):
         return FlatLayout(dims)
 
     def _make_engine(self, device, precision):
-        return NRMSEngine(self._dims, device, precision=precision)
+        return NRMSEngine(self._dims, device, precision=precision, layout=self._layout)
 
-    # ---- flat parameter storage ----------------------------------------------------------
-    def _flatten(self, device):
-        """(Re)build the flat parameter buffer on `device` and point every Parameter at its slice."""
-        named = dict(self.named_parameters())
-        flat = torch.empty(self._layout.total, dtype=torch.float32, device=device)
-        for n in self._names:
-            v = self._layout.view(flat, n)
-            v.copy_(named[n].data)
-            named[n].data = v
-        self._flat = flat
-        self._opt = None
-        self._pad_zero = None
-
-    @staticmethod
-    def _reset_pad_flag(module, incompatible_keys):
-        module._pad_zero = None                    # the embedding table may have changed
-
-    def refresh_pad_row_flag(self):
-        """Re-evaluate NRMS_FLAG_PAD_ROW_ZERO (include/nrms_hip.h) after writing into the embedding table by
-        hand.  Training never needs it: row 0 has an identically zero gradient (padding_idx), so Adam leaves
-        it where it was when the weights were loaded."""
-        self._pad_zero = None
-
-    def _views_intact(self):
-        base = self._flat.data_ptr()
-        named = dict(self.named_parameters())
-        for n in self._names:
-            off = self._layout.entries[n][0]
-            p = named[n]
-            if p.data_ptr() != base + 4 * off or p.device != self._flat.device:
-                return False
-        return True
-
-    def _prepare(self):
-        """Make sure parameters live in one flat GPU buffer (``.to(device)`` replaces tensors)."""
-        dev = next(self.parameters()).device
-        if not self._views_intact():
-            self._flatten(dev)
-        if self._flat.device.type != "cuda":
-            raise _lib.NrmsError("NRMS HIP model parameters are on %s: move the model to a GPU "
-                                 "(there is no CPU fallback)" % self._flat.device)
-        prec = getattr(self.config, "precision", "fp32")
-        if self._engine is None or self._engine.device != self._flat.device:
-            self._engine = self._make_engine(self._flat.device, prec)
-        elif self._engine.precision != prec:
-            self._engine.set_precision(prec)
-        self._prepare_calls = getattr(self, "_prepare_calls", 0) + 1
-        if getattr(self, "_pad_zero", None) is None or self._prepare_calls % 256 == 0:
-            # one host sync per weight load (and a cheap re-validation every 256 calls, should somebody write
-            # into the table by hand without refresh_pad_row_flag()): is the padding row all zeros?
-            tname = [n for n in self._names if n.endswith("word_embedding.0.weight") or n.endswith("word_embedding.weight")][0]
-            self._pad_zero = bool((self._layout.view(self._flat, tname)[0] == 0).all().item())
-        self._engine.fp16_user_encoder = bool(getattr(self.config, "fp16_user_encoder", False))
-        self._engine.fp16_inference = bool(getattr(self.config, "fp16_inference", False))
-        self._engine.fp16_wide_heads = bool(getattr(self.config, "fp16_v1_news_encoder", False))
-        self._engine.pad_row_zero = self._pad_zero and bool(getattr(self.config, "skip_padding_tokens", True))
-        return self._flat.device
-
-    def _next_seed(self):
-        self._calls += 1
-        return (int(torch.initial_seed()) * 0x9E3779B97F4A7C15 + self._calls * 0xD1B54A32D192ED03
-                + getattr(self, "_rank_salt", 0)) & 0xFFFFFFFFFFFFFFFF
-
-    # ---- reference API ----------------------------------------------------------------------
-    def forward(self, batch):
-        """batch: the collated dict of data_handler.MyDataset (CPU or GPU tensors); only
-        'browsed_titles' [B,H,L], 'candidate_titles' [B,C,L] and 'candidate_mask' [B,C] are read
-        (nrms_v0.py:248,250,272).  Returns click logits [B,C] on the GPU."""
-        dev = self._prepare()
+    def _engine_args(self, batch, dev):
+        """Only 'browsed_titles' [B,H,L], 'candidate_titles' [B,C,L] and 'candidate_mask' [B,C] are read
+        (nrms_v0.py:248,250,272)."""
         bt, ct = _ids_on(dev, batch["browsed_titles"]), _ids_on(dev, batch["candidate_titles"])
         mask = batch.get("candidate_mask") if hasattr(batch, "get") else batch["candidate_mask"]
         if mask is not None:
             mask = torch.as_tensor(mask).to(dev, dtype=torch.uint8, non_blocking=True)
-        p_drop = float(self.config.dropout) if self.training else 0.0
-        seed = self._next_seed() if p_drop > 0 else 0
-        params = [p for _, p in self._ordered_params()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _NRMSFunction.apply(self, bt, ct, mask, p_drop, seed, *params)
+        return bt, ct, mask
+
+    def _infer(self, batch, args, p_drop, seed):
         if p_drop == 0.0 and getattr(self, "dedup_inference", True):
+            bt, ct, mask = args
             get = batch.get if hasattr(batch, "get") else (lambda k: None)
             bn, cn = get("browsed_ids"), get("candidate_ids")
             if self._engine._news_cache is not None and bn is not None and cn is not None:
                 # inside train_eval.evaluate / test: news vectors are cached across batches by news id
+                dev = self._flat.device
                 return self._engine.forward_cached(self._flat, bt, ct, torch.as_tensor(bn).to(dev), torch.as_tensor(cn).to(dev), mask)
             scores, self.last_unique_titles = self._engine.forward_dedup(self._flat, bt, ct, mask)
             return scores
-        return self._engine.forward(self._flat, bt, ct, mask, training=False, p_drop=p_drop, seed=seed)
+        return super()._infer(batch, args, p_drop, seed)
 
-    def _ordered_params(self):
-        named = dict(self.named_parameters())
-        return [(n, named[n]) for n in self._names]
-
+    # ---- reference API (beside forward) ---------------------------------------------------
     def get_news_vector(self, news):
         """news [N, L] title ids -> [N, d] (nrms_v0.py:278-289); inference only."""
         dev = self._prepare()
@@ -279,78 +157,3 @@ class Model(nn.Module):
         nv = torch.as_tensor(news_vector).to(dev, dtype=torch.float32).contiguous().unsqueeze(0)
         uv = torch.as_tensor(user_vector).to(dev, dtype=torch.float32).contiguous().unsqueeze(0)
         return self._engine.click_scores(nv, uv).squeeze(0)
-
-    # ---- fused training step (the build's own loop; same math as train_eval.py:111-127) -----
-    def train_step(self, batch, lr=None, betas=(0.9, 0.999), eps=1e-8, world_size=1, all_reduce=None,
-                   global_batch=None):
-        """forward + CE(label 0) + backward + [gradient all-reduce] + Adam, all in HIP on flat
-        buffers, no host sync.  Returns the local loss SUM over the batch as a device scalar
-        (divide by the batch size for the reference's mean loss).
-
-        all_reduce: callable(flat_grad_tensor) that sums gradients over data-parallel ranks
-        (RCCL); gradients are scaled by 1/global_batch so the summed result is the gradient of
-        the mean loss over the global batch."""
-        dev = self._prepare()
-        eng = self._engine
-        bt, ct = _ids_on(dev, batch["browsed_titles"]), _ids_on(dev, batch["candidate_titles"])
-        mask = batch.get("candidate_mask")
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(dev, dtype=torch.uint8, non_blocking=True)
-        if self._opt is None:
-            self._opt = dict(step=0, g=torch.zeros_like(self._flat), m=torch.zeros_like(self._flat),
-                             v=torch.zeros_like(self._flat))
-        st = self._opt
-        p_drop = float(self.config.dropout) if self.training else 0.0
-        seed = self._next_seed() if p_drop > 0 else 0
-        B = bt.shape[0]
-        gb = B * world_size if global_batch is None else global_batch
-        scores = eng.forward(self._flat, bt, ct, mask, training=True, p_drop=p_drop, seed=seed)
-        loss_sum, dscores = eng.ce_loss(scores, grad_scale=1.0 / gb)
-        st["g"].zero_()
-        lr_ = float(self.config.learning_rate if lr is None else lr)
-        overlap = not os.environ.get("NRMS_NO_OVERLAP")
-        if all_reduce is not None and hasattr(all_reduce, "owned"):
-            # parallel.ShardedGradSync: reduce-scatter (the table region underneath the deferred weight-gradient GEMMs),
-            # Adam on the 1/world of the parameters this rank owns, all-gather of the updated parameters
-            pending = []
-            if overlap:
-                eng.backward(self._flat, st["g"], dscores, table_grad_ready=lambda: pending.append(all_reduce.start(st["g"], 0)))
-            else:
-                eng.backward(self._flat, st["g"], dscores)
-                pending.append(all_reduce.start(st["g"], 0))
-            pending.append(all_reduce.start(st["g"], 1))
-            for h in pending:
-                h.wait()
-            st["step"] += 1
-            for lo, hi, gshard in all_reduce.owned():
-                eng.adam_step(self._flat[lo:hi], gshard, st["m"][lo:hi], st["v"][lo:hi], st["step"], lr=lr_, betas=betas, eps=eps)
-            if eng.precision == "fp16":
-                eng.note_grad_check()
-            all_reduce.gather(self._flat)
-            self._last_scores = scores
-            return loss_sum
-        if all_reduce is not None and hasattr(all_reduce, "start") and overlap:
-            # the table gradient (first V*d floats of the flat buffer, 95 % of the bytes) is reduced underneath
-            # the deferred d(W_qkv) GEMM; the remaining 2.6 MB follow when the backward has been enqueued
-            n_table = self._dims.n_words * self._dims.word_embed_size
-            pending = []
-            eng.backward(self._flat, st["g"], dscores,
-                         table_grad_ready=lambda: pending.append(all_reduce.start(st["g"][:n_table])))
-            all_reduce(st["g"][n_table:])
-            for h in pending:
-                h.wait()
-        else:
-            eng.backward(self._flat, st["g"], dscores)
-            if all_reduce is not None:
-                all_reduce(st["g"])
-        st["step"] += 1
-        eng.adam_step(self._flat, st["g"], st["m"], st["v"], st["step"], lr=lr_, betas=betas, eps=eps)
-        if eng.precision == "fp16":
-            eng.note_grad_check()
-        self._last_scores = scores
-        return loss_sum
-
-    @property
-    def engine(self):
-        self._prepare()
-        return self._engine

@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..naml_engine import NamlDims, NamlEngine, NamlLayout
+from ..engine import FlatLayout
+from ..naml_engine import NamlDims, NamlEngine, naml_entries
 from . import nrms_hip
 
 ID_KEYS = ("browsed_titles", "browsed_absts", "browsed_categ_ids", "browsed_subcateg_ids",
@@ -60,32 +61,6 @@ class _UserEncoderParams(nn.Module):
         self.additive_attention = _AdditiveAttentionParams(config.query_vector_dim_large, config.news_feature_size)
 
 
-class _NamlFunction(torch.autograd.Function):
-    """scores = nrms_naml(batch; params) with the backward in HIP (autograd sees one node)."""
-
-    @staticmethod
-    def forward(ctx, model, ids, mask, p_drop, seed, *params):
-        ctx.model = model
-        scores = model._engine.forward(model._flat, ids, mask, training=True, p_drop=p_drop, seed=seed)
-        ctx.gen = model._engine._saved["gen"]
-        return scores
-
-    @staticmethod
-    def backward(ctx, dscores):
-        model = ctx.model
-        # fresh buffer per backward unless the caller opted into reuse (model.reuse_grad_buffer: nrms_hip._NRMSFunction)
-        reuse = bool(getattr(model, "reuse_grad_buffer", False)) and not any(p.grad is not None for p in model.parameters())
-        gflat = model._autograd_grad if reuse else None
-        if gflat is None or gflat.shape != model._flat.shape or gflat.device != model._flat.device:
-            gflat = torch.empty_like(model._flat)
-            if reuse:
-                model._autograd_grad = gflat
-        gflat.zero_()
-        model._engine.backward(model._flat, gflat, dscores, gen=ctx.gen)
-        grads = tuple(model._layout.view(gflat, n) for n in model._names)
-        return (None, None, None, None, None) + grads
-
-
 class Model(nrms_hip.Model):
     def _build_modules(self, config, table):
         if int(config.news_feature_size) != 2 * int(config.word_embed_size) + 2 * int(config.cate_embed_size):
@@ -102,57 +77,24 @@ class Model(nrms_hip.Model):
                         user_heads_num=int(config.user_heads_num), query_vector_dim_large=int(config.query_vector_dim_large))
 
     def _make_layout(self, dims):
-        return NamlLayout(dims)
+        return FlatLayout(dims, naml_entries(dims))
 
     def _make_engine(self, device, precision):
         return NamlEngine(self._dims, device, precision=precision)
 
-    def _inputs(self, batch, dev):
+    def _engine_args(self, batch, dev):
         ids = {k: torch.as_tensor(batch[k]).to(dev, dtype=torch.int64, non_blocking=True) for k in ID_KEYS}
         mask = batch.get("candidate_mask") if hasattr(batch, "get") else batch["candidate_mask"]
         if mask is not None:
             mask = torch.as_tensor(mask).to(dev, dtype=torch.uint8, non_blocking=True)
         return ids, mask
 
-    def forward(self, batch):
-        """batch: the collated dict of data_handler.MyDataset.  Returns click logits [B, C] on the GPU."""
-        dev = self._prepare()
-        ids, mask = self._inputs(batch, dev)
-        p_drop = float(self.config.dropout) if self.training else 0.0
-        seed = self._next_seed() if p_drop > 0 else 0
-        params = [p for _, p in self._ordered_params()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _NamlFunction.apply(self, ids, mask, p_drop, seed, *params)
+    def _infer(self, batch, args, p_drop, seed):
         # evaluation: every distinct news item of the batch is encoded once (model.dedup_inference = False: every slot)
         self._engine.dedup_inference = bool(getattr(self, "dedup_inference", True))
-        return self._engine.forward(self._flat, ids, mask, training=False, p_drop=p_drop, seed=seed)
+        return self._engine.forward(self._flat, *args, training=False, p_drop=p_drop, seed=seed)
 
     def get_news_vector(self, *a, **k):
         raise _lib.NrmsError("nrms_naml has no get_news_vector / get_user_vector / get_prediction (nrms_naml.py:196-257)")
 
     get_user_vector = get_prediction = get_news_vector
-
-    def train_step(self, batch, lr=None, betas=(0.9, 0.999), eps=1e-8, world_size=1, all_reduce=None, global_batch=None):
-        """forward + CE(label 0) + backward + [gradient all-reduce] + Adam on flat buffers (train_eval.py:111-127)."""
-        dev = self._prepare()
-        eng = self._engine
-        ids, mask = self._inputs(batch, dev)
-        if self._opt is None:
-            self._opt = dict(step=0, g=torch.zeros_like(self._flat), m=torch.zeros_like(self._flat),
-                             v=torch.zeros_like(self._flat))
-        st = self._opt
-        p_drop = float(self.config.dropout) if self.training else 0.0
-        seed = self._next_seed() if p_drop > 0 else 0
-        B = ids["browsed_titles"].shape[0]
-        gb = B * world_size if global_batch is None else global_batch
-        scores = eng.forward(self._flat, ids, mask, training=True, p_drop=p_drop, seed=seed)
-        loss_sum, dscores = eng.ce_loss(scores, grad_scale=1.0 / gb)
-        st["g"].zero_()
-        eng.backward(self._flat, st["g"], dscores)
-        if all_reduce is not None:
-            all_reduce(st["g"])
-        st["step"] += 1
-        eng.adam_step(self._flat, st["g"], st["m"], st["v"], st["step"],
-                      lr=float(self.config.learning_rate if lr is None else lr), betas=betas, eps=eps)
-        self._last_scores = scores
-        return loss_sum

@@ -18,7 +18,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .engine import NRMSEngine, _stream
+from .engine import FlatLayout, NRMSEngine, _stream
 
 ENCODERS = ("news_encoder", "user_encoder")
 
@@ -51,74 +51,33 @@ class NamlDims:
         return self.query_vector_dim if enc == "news_encoder" else self.query_vector_dim_large
 
 
-class NamlLayout:
-    """Offsets (floats) of the reference-named tensors of nrms_naml.Model.state_dict() inside the flat buffer."""
-
-    def __init__(self, dims: NamlDims):
-        self.dims = dims
-        d, c = dims.word_embed_size, dims.cate_embed_size
-        if d % 4 or c % 4 or dims.query_vector_dim % 4 or dims.query_vector_dim_large % 4:
-            raise ValueError("word_embed_size, cate_embed_size and the query vector sizes must be multiples of 4")
-        self.entries, self.blocks = {}, {enc: {} for enc in ENCODERS}
-        off = 0
-
-        def put(name, shape, enc=None, role=None):
-            nonlocal off
-            n = 1
-            for x in shape:
-                n *= x
-            self.entries[name] = (off, tuple(shape), n)
-            if enc is not None:
-                self.blocks[enc][role] = off
-            off += n
-
-        put("news_encoder.word_embedding.weight", (dims.n_words, d), "news_encoder", "table")
-        put("news_encoder.category_embedding.weight", (dims.category_nums, c))
-        put("news_encoder.subcategory_embedding.weight", (dims.subcategory_nums, c))
-        for enc in ENCODERS:
-            w, q = dims.width(enc), dims.q(enc)
-            a = enc + ".multi_head_self_attention."
-            for i, r in enumerate(("wq", "wk", "wv")):
-                put(a + "linear_layers.%d.weight" % i, (w, w), enc, r)
-            for i, r in enumerate(("bq", "bk", "bv")):
-                put(a + "linear_layers.%d.bias" % i, (w,), enc, r)
-            put(a + "output_linear.weight", (w, w), enc, "wo")
-            put(a + "output_linear.bias", (w,), enc, "bo")
-            put(enc + ".additive_attention.linear.weight", (q, w), enc, "wa")
-            put(enc + ".additive_attention.linear.bias", (q,), enc, "ba")
-            put(enc + ".additive_attention.query_vector", (q,), enc, "qv")
-        put("norm.weight", (dims.news_feature_size,))
-        put("norm.bias", (dims.news_feature_size,))
-        assert self.entries["norm.bias"][0] == self.entries["norm.weight"][0] + dims.news_feature_size
-        self.total = off
-        self.names = list(self.entries)
-        self.table = 0
-
-    def view(self, flat, name):
-        off, shp, n = self.entries[name]
-        return flat[off:off + n].view(shp)
+def naml_entries(dims: NamlDims):
+    """The (name, shape, encoder, role) entries of nrms_naml.Model.state_dict() in flat-buffer order (norm.bias right after
+    norm.weight: nrms_layernorm_bwd writes both gradients through one pointer)."""
+    d, c = dims.word_embed_size, dims.cate_embed_size
+    if d % 4 or c % 4 or dims.query_vector_dim % 4 or dims.query_vector_dim_large % 4:
+        raise ValueError("word_embed_size, cate_embed_size and the query vector sizes must be multiples of 4")
+    out = [("news_encoder.word_embedding.weight", (dims.n_words, d), "news_encoder", "table"),
+           ("news_encoder.category_embedding.weight", (dims.category_nums, c), None, None),
+           ("news_encoder.subcategory_embedding.weight", (dims.subcategory_nums, c), None, None)]
+    for enc in ENCODERS:
+        w, q = dims.width(enc), dims.q(enc)
+        a = enc + ".multi_head_self_attention."
+        out += [(a + "linear_layers.%d.weight" % i, (w, w), enc, r) for i, r in enumerate(("wq", "wk", "wv"))]
+        out += [(a + "linear_layers.%d.bias" % i, (w,), enc, r) for i, r in enumerate(("bq", "bk", "bv"))]
+        out += [(a + "output_linear.weight", (w, w), enc, "wo"), (a + "output_linear.bias", (w,), enc, "bo"),
+                (enc + ".additive_attention.linear.weight", (q, w), enc, "wa"),
+                (enc + ".additive_attention.linear.bias", (q,), enc, "ba"),
+                (enc + ".additive_attention.query_vector", (q,), enc, "qv")]
+    return out + [("norm.weight", (dims.news_feature_size,), None, None), ("norm.bias", (dims.news_feature_size,), None, None)]
 
 
 class NamlEngine(NRMSEngine):
     """One nrms_naml forward / backward on one GPU.  Inherits the shape-independent pieces of the NRMS engine (buffers,
-    id validation, click scores, CE, Adam, AUC, timers)."""
+    id validation, click scores, CE, Adam and its overflow guard, AUC, timers)."""
 
     def __init__(self, dims: NamlDims, device, precision="fp32"):
-        self.lib = _lib.load()
-        self.dims = dims
-        self.layout = NamlLayout(dims)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.NrmsError("the NRMS HIP engine needs a GPU device (got %s); there is no CPU path" % device)
-        self.set_precision(precision)
-        self._bufs = {}
-        self._saved = None
-        self._gen = 0
-        self.loss_scale = 0.0
-        self._bad_ids = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self._bad_event = None
-        self._news_cache = None
+        super().__init__(dims, device, precision=precision, layout=FlatLayout(dims, naml_entries(dims)))
         # all-padding title / abstract sequences (history padding slots: 41 % of a MIND-shaped batch) in closed form
         # (nrms_encoder_empty_fwd / _bwd) while the kernel chain runs on the others, compacted; needs a zero padding row
         self.closed_form_empty = True
@@ -139,13 +98,6 @@ class NamlEngine(NRMSEngine):
                                 precision=_lib.PRECISIONS[self.precision], use_output_proj=1, mask_mode=0,
                                 flags=(_lib.NRMS_FLAG_PAD_ROW_ZERO if (self.pad_row_zero and enc == "news_encoder") else 0),
                                 seed=int(seed) & 0xFFFFFFFFFFFFFFFF, loss_scale=0.0, p_drop_attn=float(p_attn))
-
-    def _ptrs(self, cls, flat, enc):
-        b = self.layout.blocks[enc]
-        base = flat.data_ptr()
-        p = lambda role: (base + 4 * b[role]) if role in b else None
-        return cls(table=p("table"), w_qkv=p("wq"), b_qkv=p("bq"), w_o=p("wo"), b_o=p("bo"), w_add=p("wa"),
-                   b_add=p("ba"), q_vec=p("qv"))
 
     def _acts(self, tag, desc, gather):
         M, d, q = desc.n_seq * desc.seq_len, desc.d_model, desc.q_dim

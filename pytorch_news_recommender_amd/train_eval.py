@@ -149,7 +149,7 @@ def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autogra
         criterion = nn.CrossEntropyLoss()
         # this loop zeroes the gradients before every backward and keeps no reference to an old .grad: the backward may
         # hand autograd views of ONE persistent flat buffer instead of 57.6 MB of fresh memory per step (opt-in contract,
-        # model/nrms_hip.py _NRMSFunction.backward)
+        # model/_flat_model.py _FlatFunction.backward)
         net.reuse_grad_buffer = True
     total_batch, AUC_best, STEP_SIZE = 0, 0.56, 100          # train_eval.py:59,61
     hist = dict(losses=[], aucs=[], ckpts=[], warmup_losses=[], metrics=[])

@@ -140,23 +140,62 @@ def test_deferred_wqkv_backward_equals_plain_backward():
             assert torch.equal(a, b), n
 
 
-def _rccl_worker(rank, port, out_dir, precision, sync="allreduce"):
+DP_SHAPE = dict(n_words=400, word_embed_size=300, num_attention_heads=10, query_vector_dim=200, batch_size=6, history_len=50,
+                n_candidates=5, n_words_title=30)
+
+
+def _setup(kind, precision):
+    """A small model of every kind with seeded parameters (the one-GPU data-parallel shape), and its batch maker."""
+    from pytorch_news_recommender_amd import synth
+    shape = synth.Shape(**DP_SHAPE)
+    if kind == "nrms":
+        return _build(shape, synth.make_params(shape, seed=9), precision), lambda s: synth.make_batch(shape, seed=s, ragged=True)
+    if kind == "v1":
+        from tests.test_hip_v1 import make_v1
+        return make_v1(shape, synth.make_params_v1(shape, seed=9), 6, precision=precision).train(), \
+            lambda s: synth.make_batch(shape, seed=s, ragged=True)
+    if kind == "naml":
+        from tests.test_hip_naml import make_model
+        ns = synth.NamlShape(n_words=400, batch_size=6)
+        return make_model(ns, synth.make_params_naml(ns, seed=9), precision=precision).train(), lambda s: synth.make_batch_naml(ns, seed=s)
+    if kind == "hierec":
+        from tests.test_hip_hierec import N_SUB, N_TOP, make_hierec
+        return make_hierec(shape, synth.make_params_hierec(shape, N_SUB, N_TOP, seed=9), precision=precision).train(), \
+            lambda s: synth.make_batch_hierec(shape, N_SUB, N_TOP, seed=s)
+    from tests.test_hip_graph import make_graph
+    return make_graph(shape, synth.make_params_graph(shape, seed=9), precision=precision).train(), lambda s: synth.make_batch_graph(shape, seed=s)
+
+
+@pytest.mark.parametrize("kind", ["nrms", "v1", "naml", "hierec", "graph"])
+def test_every_engine_carries_the_gradient_overflow_guard(kind):
+    """Every model's engine is built by NRMSEngine.__init__, so the guarded optimizer and the overflow counter that the fused
+    train step and the autograd backward use exist on all of them."""
+    model, _ = _setup(kind, "fp32")
+    eng = model.engine
+    g, m, v = (torch.zeros_like(model._flat) for _ in range(3))
+    before = model._flat.clone()
+    eng.adam_step(model._flat, g, m, v, 1, guard=True)
+    eng.grad_guard(g)
+    eng.note_grad_check()
+    assert eng.poll_grad_overflow(block=True) == 0 and eng.grad_overflow_steps == 0
+    assert torch.equal(model._flat, before)                 # a zero gradient moves nothing
+
+
+def _rccl_worker(rank, port, out_dir, precision, sync="allreduce", kind="nrms"):
     sys.path.insert(0, ROOT)
     import torch.distributed as dist
-    from pytorch_news_recommender_amd import parallel, synth
+    from pytorch_news_recommender_amd import parallel
     torch.cuda.set_device(0)
     dist.init_process_group(backend="nccl", init_method="tcp://127.0.0.1:%d" % port, rank=0, world_size=1)
     assert dist.get_backend() == "nccl"
-    shape = synth.Shape(n_words=400, word_embed_size=300, num_attention_heads=10, query_vector_dim=200,
-                        batch_size=6, history_len=50, n_candidates=5, n_words_title=30)
-    model = _build(shape, synth.make_params(shape, seed=9), precision)
+    model, make_batch = _setup(kind, precision)
     model.engine
     parallel.broadcast_parameters(model._flat, src=0)
     reduce = _sync(sync, model, force=True)
     assert reduce.active
     losses = []
     for t in range(3):
-        gbatch = {k: torch.from_numpy(v) for k, v in synth.make_batch(shape, seed=20 + t, ragged=True).items()}
+        gbatch = {k: torch.from_numpy(np.asarray(v)) for k, v in make_batch(20 + t).items()}
         losses.append(float(model.train_step(gbatch, world_size=1, all_reduce=reduce)))
     torch.cuda.synchronize()
     np.save(os.path.join(out_dir, "rccl_flat.npy"), model._flat.detach().cpu().numpy())
@@ -164,21 +203,23 @@ def _rccl_worker(rank, port, out_dir, precision, sync="allreduce"):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("precision,sync", [("fp32", "allreduce"), ("fp16", "allreduce"), ("fp16", "sharded")])
-def test_rccl_collectives_on_one_gpu(tmp_path, precision, sync):
+RCCL_CASES = [("fp32", "allreduce", "nrms"), ("fp16", "allreduce", "nrms"), ("fp16", "sharded", "nrms"),
+              ("fp32", "allreduce", "naml"), ("fp32", "sharded", "naml"), ("fp32", "allreduce", "hierec"), ("fp32", "sharded", "hierec")]
+
+
+@pytest.mark.parametrize("precision,sync,kind", RCCL_CASES, ids=["-".join(c if c[2] != "nrms" else c[:2]) for c in RCCL_CASES])
+def test_rccl_collectives_on_one_gpu(tmp_path, precision, sync, kind):
     """The data-parallel step through REAL RCCL calls (backend "nccl", a one-rank group: two ranks cannot share a GPU under
     RCCL): asynchronous all-reduce of the table gradient started from inside the backward, the deferred d(W_qkv) GEMMs
     enqueued under it, the second all-reduce, the waits, Adam -- must equal the plain single-process step
     (a one-rank sum is the identity), i.e. the stream ordering between the kernels and RCCL's stream holds.
-    sync = "sharded": the same through ncclReduceScatter / ncclAllGather (parallel.ShardedGradSync; one rank owns it all)."""
-    from pytorch_news_recommender_amd import synth
-    mp.spawn(_rccl_worker, args=(_free_port(), str(tmp_path), precision, sync), nprocs=1, join=True)
-    shape = synth.Shape(n_words=400, word_embed_size=300, num_attention_heads=10, query_vector_dim=200,
-                        batch_size=6, history_len=50, n_candidates=5, n_words_title=30)
-    model = _build(shape, synth.make_params(shape, seed=9), precision)
+    sync = "sharded": the same through ncclReduceScatter / ncclAllGather (parallel.ShardedGradSync; one rank owns it all).
+    kind: nrms_naml and the HieRec-style model run the same train step (model/_flat_model.py)."""
+    mp.spawn(_rccl_worker, args=(_free_port(), str(tmp_path), precision, sync, kind), nprocs=1, join=True)
+    model, make_batch = _setup(kind, precision)
     tot = []
     for t in range(3):
-        gbatch = {k: torch.from_numpy(v) for k, v in synth.make_batch(shape, seed=20 + t, ragged=True).items()}
+        gbatch = {k: torch.from_numpy(np.asarray(v)) for k, v in make_batch(20 + t).items()}
         tot.append(float(model.train_step(gbatch)))
     single = model._flat.detach().cpu().numpy()
     got = np.load(tmp_path / "rccl_flat.npy")
