@@ -300,6 +300,23 @@ int nrms_impression_metrics(int32_t n_imp, int32_t max_c, const float* scores, c
                             const int32_t* lens, int32_t k_a, int32_t k_b, double* auc, double* mrr, double* ndcg_a,
                             double* ndcg_b, int32_t* ranks, void* stream);
 
+/* ---- Top-k retrieval over a whole catalogue (serving: "which k of all N items should user b see?") ----
+ * For each user b < B: the k catalogue items n of largest score s(b, n) = user[b] . items[n], never forming the [B, N]
+ * score matrix.  user [B, d], items [N, d] fp32 row-major; exclude [B, n_exclude] int64, nullable: ids that user b must
+ * not get (duplicates allowed; ids outside [0, N) are ignored); top_scores [B, k] fp32, top_ids [B, k] int64.
+ * Score.  One fp32 chain per (b, n): a single accumulator over all of d on v_mfma_f32_32x32x2_f32, no split-K (k order
+ *   32m, 32m+16, 32m+1, 32m+17, ... in each whole block of 32, then 8g, 8g+4, 8g+1, ... in groups of 8 for the rest).  A returned score therefore has the same bits for the same
+ *   (user row, item row) whatever B, N, k, the row's position, the exclude list or the run.
+ * Eligible: n is not in exclude[b, :] and s(b, n) is not NaN.
+ * Order.  Score descending (+inf first); equal scores put the SMALLER n first; -0.0 equals +0.0 (and is returned as +0.0).
+ * Output.  Row b holds the first min(k, #eligible) items in that order; the remaining slots hold id -1 and score -inf.
+ * Limits: 1 <= k <= 256, d >= 1, 0 <= N <= 0x7FFF0000, B >= 0; B = 0 is a no-op, N = 0 writes all-padding rows.
+ * Workspace: nrms_topk_dot_workspace_bytes(B, N, d, k) bytes, 8-byte aligned, O(B * slices * k) (0 = arguments rejected).
+ * Two kernels on `stream`, no host synchronisation. */
+size_t nrms_topk_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items, const int64_t* exclude,
+                  int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- nrms_naml pieces around the two encoder passes (model/nrms_naml.py) ----
  * LayerNorm over the last dimension (nn.LayerNorm(news_feature_size) on the history vectors, nrms_naml.py:207,238):
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance.  stats [n_rows, 2] = (mean, 1/std) is written when

@@ -588,6 +588,43 @@ class NRMSEngine:
         nrms_impression_metrics."""
         return impression_metrics(self.lib, self.device, scores, labels, lens, ks, ranks)
 
+    # ---- retrieval over a whole catalogue ---------------------------------------------------------
+    def top_k(self, user_vec, items, k, exclude=None):
+        """user_vec [B, d], items [N, d] fp32, exclude [B, n_exclude] int64 or None (device, contiguous) -> (scores [B, k]
+        fp32, ids [B, k] int64): per user the k items of largest user . item, no [B, N] matrix (nrms_topk_dot).  Order:
+        score descending, then the smaller id; rows with fewer than k eligible items end in id -1 / score -inf; excluded
+        ids and NaN scores are never returned.  include/nrms_hip.h states the contract."""
+        k = int(k)
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32)):
+            if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NrmsError("top_k: %s must be a contiguous 2-D %s tensor on %s (got %s %s on %s%s)"
+                                     % (name, dt, self.device, tuple(t.shape), t.dtype, t.device,
+                                        "" if t.is_contiguous() else ", not contiguous"))
+        B, d = user_vec.shape
+        N = items.shape[0]
+        if items.shape[1] != d:
+            raise _lib.NrmsError("top_k: items width %d != user_vec width %d" % (items.shape[1], d))
+        n_ex = 0
+        if exclude is not None:
+            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
+                    or not exclude.is_contiguous()):
+                raise _lib.NrmsError("top_k: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
+                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
+            n_ex = exclude.shape[1]
+            if n_ex == 0:
+                exclude = None
+        nbytes = self.lib.nrms_topk_dot_workspace_bytes(B, N, d, k)
+        if nbytes == 0:
+            raise _lib.NrmsError("top_k: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (B, N, d, k))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(exclude), n_ex,
+                                    _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_topk_dot")
+        return scores, ids
+
     # ---- inference with unique-title caching (SURVEY f-1) -------------------------------------
     def group_rows(self, rows):
         """rows [N, L] int64 (device) -> (inverse [N] int32, rep_rows [U] int32, U): exact grouping of equal rows

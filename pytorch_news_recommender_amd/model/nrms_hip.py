@@ -17,6 +17,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from ..engine import FlatLayout, ModelDims, NRMSEngine
 from ._flat_model import FlatHipModel
 
@@ -157,3 +158,62 @@ class Model(FlatHipModel):
         nv = torch.as_tensor(news_vector).to(dev, dtype=torch.float32).contiguous().unsqueeze(0)
         uv = torch.as_tensor(user_vector).to(dev, dtype=torch.float32).contiguous().unsqueeze(0)
         return self._engine.click_scores(nv, uv).squeeze(0)
+
+    # ---- retrieval over the whole catalogue ----------------------------------------------------
+    @torch.no_grad()
+    def encode_catalogue(self, titles):
+        """titles [N, L] word ids, row r = news id r (e.g. ``DeviceFeed.titles``, row 0 = the padding title) -> news
+        vectors [N, d]: the evaluation-precision, dropout-free vectors forward_cached keeps per news id, whatever the
+        module's train / eval mode.  encode_titles works through the table in chunks of 32 768 titles."""
+        dev = self._prepare()
+        return self._engine.encode_titles(self._flat, _ids_on(dev, titles), tag="news_eval")
+
+    @torch.no_grad()
+    def recommend(self, batch, k, catalogue, exclude_history=True):
+        """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores
+        [B, k] fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_dot).
+
+        catalogue: encode_catalogue(titles) [N, d].  Only ``browsed_ids`` [B, H] (news ids, 0 = padding slot) is read:
+        the user vector is encode_users over catalogue rows browsed_ids, the vectors forward_cached scores with (ids
+        outside the catalogue are read as padding and counted: check_recommend_ids raises on them).  News
+        id 0, the padding title, is never returned; with exclude_history neither is a browsed id.  A user with fewer
+        than k eligible news gets id -1 / score -inf in the remaining slots."""
+        get = batch.get if hasattr(batch, "get") else batch.__getitem__
+        browsed = get("browsed_ids")
+        if browsed is None:
+            raise KeyError("recommend: the batch dict lacks 'browsed_ids' (the news ids of the clicked history)")
+        dev = self._prepare()
+        cat = torch.as_tensor(catalogue)
+        d = self._dims.word_embed_size
+        if cat.dim() != 2 or cat.shape[1] != d or cat.dtype != torch.float32 or cat.device != dev:
+            raise _lib.NrmsError("recommend: catalogue must be [N, %d] float32 on %s (encode_catalogue), got %s %s on %s"
+                                 % (d, dev, tuple(cat.shape), cat.dtype, cat.device))
+        cat = cat.contiguous()
+        browsed = torch.as_tensor(browsed).to(dev, dtype=torch.int64).contiguous()
+        B, H = browsed.shape
+        N = cat.shape[0]
+        # ids outside the catalogue are counted on the device and read as padding (no host synchronisation per batch);
+        # check_recommend_ids() raises on them
+        bad = (browsed < 0) | (browsed >= N)
+        browsed = browsed.masked_fill(bad, 0)
+        if self._bad_browsed is None or self._bad_browsed.device != dev:
+            self._bad_browsed = torch.zeros((), dtype=torch.int64, device=dev)
+        self._bad_browsed += bad.sum()
+        user = self._engine.encode_users(self._flat, cat.index_select(0, browsed.view(-1)).view(B, H, d), tag="user_eval")
+        # the kernel runs on rows 1.. (the padding title is never a candidate); history ids shift with them, which sends
+        # the padding slots (id 0) out of range, where the kernel ignores them
+        exclude = browsed - 1 if exclude_history else None
+        scores, ids = self._engine.top_k(user, cat[1:], k, exclude)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    _bad_browsed = None
+    CATALOGUE_RETRIEVAL = True          # recommend / encode_catalogue are available (run_v0 --recommend checks this)
+
+    def check_recommend_ids(self):
+        """Raises if a recommend() call since the last check met browsed_ids outside its catalogue (those slots were read
+        as padding).  One host synchronisation."""
+        n = 0 if self._bad_browsed is None else int(self._bad_browsed.item())
+        if n:
+            self._bad_browsed.zero_()
+            raise _lib.NrmsError("recommend: %d browsed_ids outside the catalogue were read as padding" % n)
+

@@ -98,3 +98,11 @@ class Model(nrms_hip.Model):
         raise _lib.NrmsError("nrms_naml has no get_news_vector / get_user_vector / get_prediction (nrms_naml.py:196-257)")
 
     get_user_vector = get_prediction = get_news_vector
+
+    def recommend(self, *a, **k):
+        raise NotImplementedError("nrms_naml: catalogue retrieval needs a category and sub-category per news item, and "
+                                  "there is no per-news category table (DeviceFeed carries them per sample)")
+
+    encode_catalogue = recommend
+    CATALOGUE_RETRIEVAL = False
+

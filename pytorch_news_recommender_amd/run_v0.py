@@ -12,6 +12,7 @@ run_demo.py:28) lets BASELINE config 0 (batch 32) run through the same entry.
 import argparse
 import os
 import time
+from importlib import import_module
 
 import numpy as np
 import torch
@@ -21,7 +22,7 @@ from . import parallel
 from .config import Config
 from .data_handler import DeviceFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
 from .model import Model
-from .train_eval import test, train
+from .train_eval import recommend, test, train
 
 
 def build_parser():
@@ -43,11 +44,29 @@ def build_parser():
     parser.add_argument('--data_path', type=str, default=None, help='overrides config.data_path (./data_processed/)')
     parser.add_argument('--metrics', action='store_true', help='evaluate on AUC, MRR, nDCG@5 and nDCG@10 (config.eval_metrics)')
     parser.add_argument('--save_path', type=str, default=None, help='overrides config.save_path (./save_model/)')
+    parser.add_argument('--recommend', type=int, default=None, metavar='K', help='finally write the top K news of the whole '
+                        'catalogue per impression: dev split with the trained weights, or with --test the test split with '
+                        'the checkpoint --test loaded (nrms_v0 / nrms_v1 models)')
+    parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     return parser
+
+
+def check_recommend_args(args):
+    """--recommend fails before any data is read or any step is trained: K in [1, 256], a model that can recommend."""
+    if args.recommend is None:
+        return
+    if not 1 <= args.recommend <= 256:
+        raise SystemExit('--recommend K: K must be in [1, 256] (got %d)' % args.recommend)
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_RETRIEVAL', False):
+        raise SystemExit('--recommend: model %r cannot recommend from the whole catalogue (nrms_v0 / nrms_v1 only)' % args.model)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    check_recommend_args(args)
     rank, local_rank, world = parallel.init_process_group()
     torch.manual_seed(422)
     torch.cuda.manual_seed_all(422)
@@ -106,6 +125,12 @@ def main(argv=None):
                           num_workers=args.num_workers, drop_last=(world > 1 and typ == 0), shuffle=shuffle,
                           pin_memory=True)
 
+    def recommend_top(samples):
+        # the catalogue is the feed's title table (row r = news id r), so this step always runs on a DeviceFeed
+        feed = DeviceFeed(config, samples, type=1, id2title_dict=titles, id2abst_dict=absts, batch_size=config.batch_size,
+                          device=config.device)
+        return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out)
+
     if not args.test:
         hist = train(config, recommender, loader(train_samples, 0, True), loader(dev_samples, 1, False), dev_labels,
                      max_batches=args.max_batches, verbose=rank == 0)
@@ -115,6 +140,8 @@ def main(argv=None):
                 m = hist['metrics'][-1][1]
                 print('final dev AUC: {:.4f}  MRR: {:.4f}  nDCG@5: {:.4f}  nDCG@10: {:.4f}'.format(
                     m['auc'], m['mrr'], m['ndcg5'], m['ndcg10']))
+        if args.recommend is not None and rank == 0:
+            print('recommendations saved to', recommend_top(dev_samples))
         return hist
     else:
         # run_v0.py:93-111: the test set through the checkpoint named by --load (or the best one by file-name AUC)
@@ -125,6 +152,8 @@ def main(argv=None):
         out = test(config, recommender, loader(test_samples, 1, False), shown, ckpt_file=args.load,
                    pick_best=args.load is None)
         print('saved to', out)
+        if args.recommend is not None and rank == 0:
+            print('recommendations saved to', recommend_top(test_samples))
         return out
 
 

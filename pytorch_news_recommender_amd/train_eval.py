@@ -12,6 +12,8 @@ evaluate(): per-impression AUC on the un-padded prefix, unweighted mean (train_e
 evaluate_metrics(): the same loop scored on AUC, MRR, nDCG@5 and nDCG@10 (``nrms_impression_metrics``).
 test():     per-impression rank lists in the MIND submission format (train_eval.py:280-286,335-341), ranked on the
             GPU batch by batch; ``_cal_test`` is the host statement of the same ranks.
+recommend(): per impression the k news ids of the WHOLE catalogue the model ranks highest (``model.recommend``, the
+            fused top-k kernel nrms_topk_dot), written in test()'s line format.
 """
 from __future__ import annotations
 
@@ -316,3 +318,25 @@ def test(config, model, data_iter, test_list_nums=None, ckpt_file=None, out_file
             f.write(str(i + 1) + ' ')
             f.write(str(r).replace(' ', '') + '\n')
     return file_name
+
+
+def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True):
+    """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
+    of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
+    (``DeviceFeed.titles``); it is encoded once.  With exclude_history the user's browsed news are left out.  Should the
+    catalogue hold fewer than k eligible news for a user, the line is shorter.  Returns the file name."""
+    net = _inner(model)
+    catalogue = net.encode_catalogue(titles)
+    lines = []
+    for datas in data_iter:
+        ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history)
+        lines.extend(ids.cpu().tolist())
+    net.engine.check_ids()
+    net.check_recommend_ids()
+    file_name = out_file or 'recommend_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
+    with open(file_name, 'w') as f:
+        for i, row in enumerate(lines):
+            f.write(str(i + 1) + ' ')
+            f.write(str([n for n in row if n >= 0]).replace(' ', '') + '\n')
+    return file_name
+
