@@ -317,6 +317,29 @@ size_t nrms_topk_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k)
 int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items, const int64_t* exclude,
                   int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Top-k with a query per (user, item group): the catalogue is split into G groups and user b scores item n with the query
+ * row of n's group, s(b, n) = query[b, g(n)] . items[n] (HieRec's hierarchical matching, whose user side depends only on the
+ * candidate's (topic, sub-topic) pair: nrms_hier_query).  query [B, G, d], items [N, d] fp32 row-major, stored group after
+ * group: group g is rows [group_ptr[g], group_ptr[g + 1]) (group_ptr int64 [G + 1], nondecreasing from 0 to N; groups may be
+ * empty or of any length, nothing is padded by the caller).  item_ids int32 [N]: the id of each row, distinct, in [0, 2^31),
+ * in any order; exclude [B, n_exclude] int64, nullable: ids (not rows) user b must not get (duplicates and ids that are no
+ * item's are ignored).  top_scores [B, k] fp32, top_ids [B, k] int64 (item ids).
+ * The contract of nrms_topk_dot, with ids in place of rows:
+ * Score.  The chain of nrms_topk_dot for (query row, item row): its bits do not depend on B, N, k, G, the grouping of the
+ *   other items, the item's row or the run.  With G = 1 and item_ids[n] = n the result is bit-identical to nrms_topk_dot.
+ * Eligible: the id is not in exclude[b, :] and s(b, n) is not NaN.  Order: score descending, equal scores put the SMALLER id
+ *   first, -0.0 equals +0.0 (returned as +0.0).  Output: the first min(k, #eligible) items, then id -1 / score -inf.
+ * Limits: 1 <= k <= 256, d >= 1, G >= 1, B >= 0, 0 <= N and N + 32 G <= 0x7FFF0000; B = 0 is a no-op, N = 0 writes
+ *   all-padding rows.  A group_ptr outside its contract reads no row outside [0, N) (groups are clamped), but the result is
+ *   then unspecified.
+ * Workspace: nrms_topk_grouped_dot_workspace_bytes(B, N, d, k, G) bytes, 16-byte aligned (0 = arguments rejected): the tile
+ *   table of the grouped layout (each group padded to whole 32-row tiles, at most N / 32 + G tiles) and O(B * slices * k).
+ * Three kernels on `stream`, no host synchronisation. */
+size_t nrms_topk_grouped_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G);
+int nrms_topk_grouped_dot(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, const float* query, const float* items,
+                          const int32_t* item_ids, const int64_t* group_ptr, const int64_t* exclude, int32_t n_exclude,
+                          float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- nrms_naml pieces around the two encoder passes (model/nrms_naml.py) ----
  * LayerNorm over the last dimension (nn.LayerNorm(news_feature_size) on the history vectors, nrms_naml.py:207,238):
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance.  stats [n_rows, 2] = (mean, 1/std) is written when
@@ -449,6 +472,16 @@ int nrms_hier_match(int32_t B, int32_t C, int32_t H, const int64_t* cand_topic, 
 int nrms_hier_score_fwd(int32_t B, int32_t C, int32_t d, const float* cand, const float* u1, const float* u2, const float* ug,
                         const int32_t* sub_slot, const float* sub_frac, const int32_t* top_slot, const float* top_frac,
                         const uint8_t* mask, float lambda_sub, float lambda_top, float* scores, void* stream);
+/* nrms_hier_query: the user side of nrms_hier_score_fwd per catalogue group.  Group g has the ids (group_topic[g],
+ * group_subtopic[g]) (int64 [G] each); query [B, G, d] is written with
+ *   query[b, g] = cs * u1[ss] + ct * u2[ts] + lg * ug[b],   cs = l_s f_s, ct = l_t f_t, lg = 1 - l_s - l_t,
+ * where (ss, f_s) and (ts, f_t) are the slots and shares nrms_hier_match gives a candidate with group g's ids, and a term
+ * whose slot is -1 is 0 -- the element expression of nrms_hier_score_fwd, so query[b, g] . n is user b's score for a news
+ * vector n of group g.  1 <= H <= 64, G >= 1; B = 0 is a no-op.  One kernel on `stream`. */
+int nrms_hier_query(int32_t B, int32_t H, int32_t G, int32_t d, const int64_t* group_topic, const int64_t* group_subtopic,
+                    const int32_t* l1_sub, const int32_t* l1_cnt, const int32_t* l2_top, const int32_t* l2_cnt,
+                    const int32_t* n_valid, const float* u1, const float* u2, const float* ug, float lambda_sub,
+                    float lambda_top, float* query, void* stream);
 int nrms_hier_score_bwd(int32_t B, int32_t C, int32_t d, const float* cand, const float* u1, const float* u2, const float* ug,
                         const int32_t* sub_slot, const float* sub_frac, const int32_t* top_slot, const float* top_frac,
                         const uint8_t* mask, float lambda_sub, float lambda_top, const float* dscores, float* dcand, float* du1,

@@ -5,6 +5,7 @@
 //   nrms_hier_add_embedding_fwd / _bwd   interest = aggregate + the (sub-)topic's embedding; table gradient without atomics
 //   nrms_hier_match, nrms_hier_score_fwd / _bwd   hierarchical matching: a candidate against the user's interest in ITS sub-topic
 //                          and topic (weighted by the share of the user's clicks there) and against the overall interest
+//   nrms_hier_query        the same matching per catalogue group (topic, sub-topic): the query row the grouped top-k scores with
 // Everything here is HBM-bound byte / index work: one wavefront per user (a history has at most 64 slots = one lane each,
 // grouping by wave ballots, no sorting), fixed per-user strides (slot b * H + g), a single-block scan for the packed lists.
 #include "gemm.h"
@@ -245,6 +246,47 @@ __global__ __launch_bounds__(256) void hier_match_kernel(int B, int C, int H, co
     sub_slot[i] = ss; sub_frac[i] = sf; top_slot[i] = ts; top_frac[i] = tf;
 }
 
+// query[b, g] = cs * u1[ss] + ct * u2[ts] + lg * ug[b] for a catalogue group g = (topic, sub-topic): the slots and shares
+// hier_match finds for a candidate with those ids (lane j tests slot j, the lowest match wins, as the match kernel's first
+// hit), and the element expression of hier_score_fwd, so that <n, query[b, g(n)]> is the score of n as user b's candidate.
+// One wave per (user, group), users outermost (a user's interest rows stay in cache across its groups).
+template <bool VEC>
+__global__ __launch_bounds__(64 * HIER_WPB) void hier_query_kernel(int B, int H, int G, int d, const int64_t* __restrict__ group_topic,
+                                                                  const int64_t* __restrict__ group_sub, const int* __restrict__ l1_sub,
+                                                                  const int* __restrict__ l1_cnt, const int* __restrict__ l2_top,
+                                                                  const int* __restrict__ l2_cnt, const int* __restrict__ n_valid,
+                                                                  const float* __restrict__ u1, const float* __restrict__ u2,
+                                                                  const float* __restrict__ ug, float ls, float lt, float lg,
+                                                                  float* __restrict__ query) {
+    const int lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * HIER_WPB + (threadIdx.x >> 6);
+    if (i >= (long)B * G) return;
+    const int b = (int)(i / G), g = (int)(i - (long)b * G);
+    const int cs_id = (int)group_sub[g], ct_id = (int)group_topic[g];
+    const long s = (long)b * H + lane;
+    const unsigned long long m1 = __ballot(lane < H && l1_cnt[s] > 0 && l1_sub[s] == cs_id);
+    const unsigned long long m2 = __ballot(lane < H && l2_cnt[s] > 0 && l2_top[s] == ct_id);
+    const float inv = n_valid[b] > 0 ? 1.0f / (float)n_valid[b] : 0.f;
+    const int ss = m1 ? (int)((long)b * H + __ffsll((long long)m1) - 1) : -1;
+    const int ts = m2 ? (int)((long)b * H + __ffsll((long long)m2) - 1) : -1;
+    const float sf = ss >= 0 ? l1_cnt[ss] * inv : 0.f, tf = ts >= 0 ? l2_cnt[ts] * inv : 0.f;
+    const float cs = ss >= 0 ? ls * sf : 0.f, ct = ts >= 0 ? lt * tf : 0.f;
+    const float* p1 = u1 + (long)(ss >= 0 ? ss : 0) * d;
+    const float* p2 = u2 + (long)(ts >= 0 ? ts : 0) * d;
+    const float* pg = ug + (long)b * d;
+    float* q = query + i * d;
+    if (VEC) {
+        for (int k = 4 * lane; k < d; k += 256) {
+            const float4 a1 = *reinterpret_cast<const float4*>(p1 + k), a2 = *reinterpret_cast<const float4*>(p2 + k);
+            const float4 ag = *reinterpret_cast<const float4*>(pg + k);
+            *reinterpret_cast<float4*>(q + k) = make_float4(cs * a1.x + ct * a2.x + lg * ag.x, cs * a1.y + ct * a2.y + lg * ag.y,
+                                                            cs * a1.z + ct * a2.z + lg * ag.z, cs * a1.w + ct * a2.w + lg * ag.w);
+        }
+    } else {
+        for (int k = lane; k < d; k += 64) q[k] = cs * p1[k] + ct * p2[k] + lg * pg[k];
+    }
+}
+
 struct HierScoreArgs {
     int B, C, d;
     const float* cand;      // [B, C, d]
@@ -388,6 +430,26 @@ extern "C" int nrms_hier_match(int32_t B, int32_t C, int32_t H, const int64_t* c
     hipLaunchKernelGGL(hier_match_kernel, dim3(cdiv((long)B * C, 256)), dim3(256), 0, s, B, C, H, cand_topic, cand_subtopic, l1_sub, l1_cnt,
                        l2_top, l2_cnt, n_valid, sub_slot, sub_frac, top_slot, top_frac);
     return check_launch("hier_match");
+}
+
+extern "C" int nrms_hier_query(int32_t B, int32_t H, int32_t G, int32_t d, const int64_t* group_topic, const int64_t* group_subtopic,
+                               const int32_t* l1_sub, const int32_t* l1_cnt, const int32_t* l2_top, const int32_t* l2_cnt,
+                               const int32_t* n_valid, const float* u1, const float* u2, const float* ug, float lambda_sub,
+                               float lambda_top, float* query, void* stream) {
+    NRMS_REQUIRE(B >= 0 && G >= 1 && H >= 1 && H <= 64 && d >= 1, "hier_query: B=%d G=%d H=%d d=%d (G >= 1, 1 <= H <= 64)", B, G, H, d);
+    if (B == 0) return NRMS_OK;
+    NRMS_REQUIRE(group_topic && group_subtopic && l1_sub && l1_cnt && l2_top && l2_cnt && n_valid && u1 && u2 && ug && query,
+                 "hier_query: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = (d & 3) == 0 && (((uintptr_t)u1 | (uintptr_t)u2 | (uintptr_t)ug | (uintptr_t)query) & 15) == 0;
+    const dim3 grid((unsigned)cdiv((long)B * G, HIER_WPB));
+    const float lg = 1.0f - lambda_sub - lambda_top;
+    TimingScope ts("hier_query", s);
+    if (vec) hipLaunchKernelGGL(hier_query_kernel<true>, grid, dim3(64 * HIER_WPB), 0, s, B, H, G, d, group_topic, group_subtopic, l1_sub,
+                                l1_cnt, l2_top, l2_cnt, n_valid, u1, u2, ug, lambda_sub, lambda_top, lg, query);
+    else hipLaunchKernelGGL(hier_query_kernel<false>, grid, dim3(64 * HIER_WPB), 0, s, B, H, G, d, group_topic, group_subtopic, l1_sub,
+                            l1_cnt, l2_top, l2_cnt, n_valid, u1, u2, ug, lambda_sub, lambda_top, lg, query);
+    return check_launch("hier_query");
 }
 
 static int hier_score_args(HierScoreArgs* a, int32_t B, int32_t C, int32_t d, const float* cand, const float* u1, const float* u2,

@@ -13,6 +13,11 @@
 // An entry is one uint64: the score as an order-preserving 32-bit key (-0.0 canonicalised to +0.0) above the complement of
 // the 32-bit item id, so larger entry = higher score, then smaller id.  Entry 0 lies below every real entry and is padding.
 // The order is total, so the result does not depend on the slice count, the launch geometry or the order of insertion.
+//
+// nrms_topk_grouped_dot runs the same two kernels with a query per (user, item group): the catalogue, stored group after
+// group, is laid out in 32-row tiles that never straddle a group (each group padded to a whole number of tiles; the table is
+// written by topk_tiles_kernel into the workspace), so every MFMA column tile has one A operand, the tile's group's query
+// rows.  Scores keep the chain of nrms_topk_dot, and entries carry item_ids[row] instead of the row.
 #include "common.h"
 
 namespace nrms {
@@ -29,6 +34,11 @@ constexpr int TK_MIN_SLICE = 4 * TK_IT;        // no slice shorter than this: ea
 constexpr int TK_MAX_N = 0x7FFF0000;           // ids are held in 32 bits
 
 typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
+
+// One 32-row tile of a grouped catalogue: rows [row, row + len) of group grp (len 0: an unused tile past the last group).
+struct TkTile {
+    int row, len, grp, pad;
+};
 
 __device__ __forceinline__ uint64_t tk_entry(float s, uint32_t id) {
     uint32_t u = __float_as_uint(s == 0.0f ? 0.0f : s);       // -0.0 == +0.0
@@ -148,11 +158,17 @@ __device__ void tk_drop_excluded(uint64_t* buf, int cnt, const int32_t* ex, cons
 // L1).  The next block of k is loaded into registers while the MFMAs of this one run.  Lane (r, h) feeds A[user r][k'=h]
 // and B[k'=h][item r]; MFMA t of block m sums k = 32m + t (h = 0) and 32m + 16 + t (h = 1).  The rest of d goes in groups of
 // 8 (8g + t and 8g + 4 + t, zero past d).  The same fixed chain for every (user, item) pair.
-template <int P, int W, bool VEC>
+//
+// GROUPED (nrms_topk_grouped_dot): the slices run over the tiles of `tiles` (32 rows each, slice_len and IT are whole tiles),
+// user = the query [B, G, d], and each of a wave's two column tiles takes its A operand from query[user, the tile's group];
+// rows past a tile's len are masked, and the id of row n is item_ids[n].
+template <int P, int W, bool VEC, bool GROUPED>
 __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d, int k, int slice_len, int S,
                                                             const float* __restrict__ user, const float* __restrict__ items,
                                                             const int64_t* __restrict__ exclude, int n_exclude,
-                                                            uint64_t* __restrict__ ws) {
+                                                            uint64_t* __restrict__ ws, int G, int n_tiles,
+                                                            const TkTile* __restrict__ tiles,
+                                                            const int32_t* __restrict__ item_ids) {
     __shared__ uint64_t buf[TK_UT][P];
     __shared__ uint64_t thr[TK_UT];
     __shared__ int cnt[TK_UT];
@@ -164,7 +180,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     const int u0 = blockIdx.x * TK_UT;
     const int slice = blockIdx.y;
     const int n_begin = slice * slice_len;
-    const int n_end = min(N, n_begin + slice_len);
+    const int n_end = min(GROUPED ? 32 * n_tiles : N, n_begin + slice_len);      // (grouped: tile rows, not catalogue rows)
     const bool ex_lds = n_exclude <= TK_EX_LDS;
 
     if (threadIdx.x < TK_UT) {
@@ -175,7 +191,8 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         for (int i = threadIdx.x; i < TK_UT * n_exclude; i += 64 * W) {
             const int u = i / n_exclude, e = i - u * n_exclude;
             const int64_t v = u0 + u < B ? exclude[(long)(u0 + u) * n_exclude + e] : -1;
-            ex[u][e] = (v >= n_begin && v < n_end) ? (int32_t)v : -1;
+            if constexpr (GROUPED) ex[u][e] = (v >= 0 && v <= 0x7FFFFFFF) ? (int32_t)v : -1;    // ids, in any slice
+            else ex[u][e] = (v >= n_begin && v < n_end) ? (int32_t)v : -1;
         }
     __syncthreads();
 
@@ -186,7 +203,9 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     };
 
     const int r = lane & 31, h = lane >> 5;
-    const float* arow = user + (long)min(u0 + r, B - 1) * d;
+    constexpr int NA = GROUPED ? TK_TN : 1;           // A operands per k-block: one per column tile when grouped
+    const float* arow[NA];
+    if constexpr (!GROUPED) arow[0] = user + (long)min(u0 + r, B - 1) * d;
     float* st = stage[wave];
     const int m_full = d / 32;
     for (int n0 = n_begin; n0 < n_end; n0 += IT) {
@@ -194,10 +213,26 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         tk_f32x16 acc[TK_TN];
 #pragma unroll
         for (int c = 0; c < TK_TN; ++c) acc[c] = tk_f32x16{};
-        if (nw < n_end) {
+        // grouped: the wave's two tiles (row of their first item, valid rows, group); wave-uniform
+        int trow[TK_TN] = {}, tlen[TK_TN] = {};
+        if constexpr (GROUPED) {
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) {
+                const int t = nw / 32 + c;
+                TkTile tl{0, 0, 0, 0};
+                if (t < n_tiles) tl = tiles[t];
+                trow[c] = __builtin_amdgcn_readfirstlane(tl.row);
+                tlen[c] = __builtin_amdgcn_readfirstlane(tl.len);
+                arow[c] = user + ((long)min(u0 + r, B - 1) * G + __builtin_amdgcn_readfirstlane(tl.grp)) * d;
+            }
+        }
+        if (nw < n_end && (!GROUPED || tlen[0] + tlen[1] > 0)) {
             const float* srow[8];           // rows this lane stages: 8j + lane / 8
 #pragma unroll
-            for (int j = 0; j < 8; ++j) srow[j] = items + (long)min(nw + 8 * j + (lane >> 3), N - 1) * d + 4 * (lane & 7);
+            for (int j = 0; j < 8; ++j) {
+                if constexpr (GROUPED) srow[j] = items + (long)min(trow[j >> 2] + 8 * (j & 3) + (lane >> 3), N - 1) * d + 4 * (lane & 7);
+                else srow[j] = items + (long)min(nw + 8 * j + (lane >> 3), N - 1) * d + 4 * (lane & 7);
+            }
 #define TK_GLOAD(m)                                                                                                        \
     do {                                                                                                               \
         const int k0_ = 32 * (m);                                                                                      \
@@ -209,11 +244,12 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) g[j][e_] = srow[j][k0_ + e_];                         \
             }                                                                                                          \
         }                                                                                                              \
-        _Pragma("unroll") for (int t = 0; t < 16; ++t) a[t] = arow[k0_ + 16 * h + t];                                  \
+        _Pragma("unroll") for (int c_ = 0; c_ < NA; ++c_)                                                              \
+            _Pragma("unroll") for (int t = 0; t < 16; ++t) a[c_][t] = arow[c_][k0_ + 16 * h + t];                      \
     } while (0)
             if (m_full > 0) {
                 float g[8][4];
-                float a[16];
+                float a[NA][16];
                 TK_GLOAD(0);
                 for (int m = 0; m < m_full; ++m) {
 #pragma unroll
@@ -229,15 +265,17 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                             const float4 v = *reinterpret_cast<const float4*>(st + (32 * c + r) * TK_BP + 16 * h + 4 * t);
                             b[c][4 * t] = v.x; b[c][4 * t + 1] = v.y; b[c][4 * t + 2] = v.z; b[c][4 * t + 3] = v.w;
                         }
-                    float acur[16];
+                    float acur[NA][16];
 #pragma unroll
-                    for (int t = 0; t < 16; ++t) acur[t] = a[t];
+                    for (int c = 0; c < NA; ++c)
+#pragma unroll
+                        for (int t = 0; t < 16; ++t) acur[c][t] = a[c][t];
                     if (m + 1 < m_full) TK_GLOAD(m + 1);
 #pragma unroll
                     for (int t = 0; t < 16; ++t)
 #pragma unroll
                         for (int c = 0; c < TK_TN; ++c)
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[t], b[c][t], acc[c], 0, 0, 0);
+                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[GROUPED ? c : 0][t], b[c][t], acc[c], 0, 0, 0);
                     tk_wave_sync();        // this block's LDS reads stay ahead of the next block's writes
                 }
             }
@@ -246,11 +284,12 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 const int k0 = 8 * g8 + 4 * h;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const float at = tk_ld(arow, k0 + t, d);
+                    const float at = tk_ld(arow[0], k0 + t, d);
 #pragma unroll
                     for (int c = 0; c < TK_TN; ++c) {
-                        const float* brow = items + (long)min(nw + 32 * c + r, N - 1) * d;
-                        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(at, tk_ld(brow, k0 + t, d), acc[c], 0, 0, 0);
+                        const float* brow = items + (long)min(GROUPED ? trow[c] + r : nw + 32 * c + r, N - 1) * d;
+                        const float ac = GROUPED ? tk_ld(arow[GROUPED ? c : 0], k0 + t, d) : at;
+                        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, tk_ld(brow, k0 + t, d), acc[c], 0, 0, 0);
                     }
                 }
             }
@@ -258,13 +297,19 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         // filter.  C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5).
         // Bit 16 c + q of `pend`: that score still has to be offered.
         uint32_t pend = 0;
+        uint32_t gid[TK_TN] = {};           // grouped: the id of this lane's item in column tile c
 #pragma unroll
         for (int c = 0; c < TK_TN; ++c) {
             const int n = nw + 32 * c + r;
+            bool live = n < n_end;
+            if constexpr (GROUPED) {
+                live = live && r < tlen[c];
+                if (live) gid[c] = (uint32_t)item_ids[trow[c] + r];
+            }
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int b = u0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if (n < n_end && b < B && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
+                if (live && b < B && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
             }
         }
         bool first = true;
@@ -292,7 +337,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                     const uint32_t bit = 1u << (16 * c + q);
                     if (!(pend & bit)) continue;
                     const int i = (q & 3) + 8 * (q >> 2) + 4 * h;
-                    const uint64_t e = tk_entry(acc[c][q], (uint32_t)n);
+                    const uint64_t e = tk_entry(acc[c][q], GROUPED ? gid[c] : (uint32_t)n);
                     bool keep = false;
                     if (e > thr[i]) {
                         const int slot = atomicAdd(&cnt[i], 1);
@@ -347,6 +392,44 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(int B, int k, int S, con
     }
 }
 
+// One block: the tile table of a grouped catalogue.  Group g (rows [group_ptr[g], group_ptr[g + 1]), clamped to [0, N])
+// gets ceil(len / 32) consecutive tiles, the groups in order; tiles [total, n_tiles) are unused (len 0).  A group_ptr that is
+// not nondecreasing from 0 to N cannot send a row outside [0, N) or a tile past n_tiles.
+__global__ __launch_bounds__(1024) void topk_tiles_kernel(int N, int G, int n_tiles, const int64_t* __restrict__ group_ptr,
+                                                          TkTile* __restrict__ tiles) {
+    __shared__ long part[1024];
+    const int per = (G + 1023) / 1024;
+    const int lo = min(G, (int)threadIdx.x * per), hi = min(G, lo + per);
+    auto span = [&](int g, int& row, int& len) {
+        const long a = min((long)N, max(0L, (long)group_ptr[g]));
+        const long e = min((long)N, max(0L, (long)group_ptr[g + 1]));
+        row = (int)a;
+        len = (int)max(0L, e - a);
+    };
+    long s = 0;
+    for (int g = lo; g < hi; ++g) {
+        int row, len;
+        span(g, row, len);
+        s += (len + 31) / 32;
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long run = 0;
+        for (int i = 0; i < 1024; ++i) { const long t = part[i]; part[i] = run; run += t; }
+        part[0] = run;              // (thread 0's own offset is 0: kept in `first` below)
+    }
+    __syncthreads();
+    const long total = part[0];
+    long t = threadIdx.x == 0 ? 0 : part[threadIdx.x];
+    for (int g = lo; g < hi; ++g) {
+        int row, len;
+        span(g, row, len);
+        for (int j = 0; j < len && t < n_tiles; j += 32, ++t) tiles[t] = TkTile{row + j, min(32, len - j), g, 0};
+    }
+    for (long u = total + threadIdx.x; u < n_tiles; u += 1024) tiles[u] = TkTile{0, 0, 0, 0};
+}
+
 struct TopkGeom {
     int tiles, S, slice_len;
 };
@@ -363,6 +446,54 @@ static TopkGeom topk_geom(int32_t B, int64_t N) {
 
 static bool topk_args_ok(int32_t B, int64_t N, int32_t d, int32_t k) {
     return B >= 0 && N >= 0 && N <= TK_MAX_N && d >= 1 && k >= 1 && k <= TK_MAX_K;
+}
+
+// Tiles of a grouped catalogue: at most floor(N / 32) + G of them (each group wastes less than one tile); 0 when N = 0.
+static int64_t topk_grouped_tiles(int64_t N, int32_t G) { return N == 0 ? 0 : (N + 31 * (int64_t)G) / 32; }
+
+static bool topk_grouped_args_ok(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G) {
+    return topk_args_ok(B, N, d, k) && G >= 1 && N + 32 * (int64_t)G <= TK_MAX_N;
+}
+
+static size_t topk_tile_bytes(int64_t n_tiles) { return ((size_t)n_tiles * sizeof(TkTile) + 255) / 256 * 256; }
+
+// Both kernels of one call.  grouped: `user` is the query [B, G, d], the slices run over the tile rows of `tiles`.
+static int topk_launch(bool grouped, int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int64_t n_tiles, const float* user,
+                       const float* items, const int32_t* item_ids, const TkTile* tiles, const int64_t* exclude, int32_t n_exclude,
+                       float* top_scores, int64_t* top_ids, uint64_t* ws, hipStream_t s, const char* who) {
+    const TopkGeom g = topk_geom(B, grouped ? 32 * n_tiles : N);
+    char what[64];
+    if (g.S > 0) {
+        const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
+        const dim3 grid(g.tiles, g.S);
+        const int n = (int)N, nt = (int)n_tiles;
+#define TK_LAUNCH_G(P, W, V, GR)                                                                                           \
+    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, GR>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S, user, items, \
+                       exclude, n_exclude, ws, G, nt, tiles, item_ids)
+#define TK_LAUNCH(P, W)                                                                                                    \
+    do {                                                                                                                   \
+        if (grouped) {                                                                                                     \
+            if (vec) TK_LAUNCH_G(P, W, true, true);                                                                        \
+            else TK_LAUNCH_G(P, W, false, true);                                                                           \
+        } else {                                                                                                           \
+            if (vec) TK_LAUNCH_G(P, W, true, false);                                                                       \
+            else TK_LAUNCH_G(P, W, false, false);                                                                          \
+        }                                                                                                                  \
+    } while (0)
+        if (k + 64 <= 128) TK_LAUNCH(128, TK_WAVES);
+        else if (k + 64 <= 256) TK_LAUNCH(256, TK_WAVES);
+        else TK_LAUNCH(512, 2);
+#undef TK_LAUNCH
+#undef TK_LAUNCH_G
+        snprintf(what, sizeof what, "%s(slices)", who);
+        const int rc = check_launch(what);
+        if (rc != NRMS_OK) return rc;
+    }
+    if (k + 64 <= 128) hipLaunchKernelGGL(topk_merge_kernel<128>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
+    else if (k + 64 <= 256) hipLaunchKernelGGL(topk_merge_kernel<256>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
+    else hipLaunchKernelGGL(topk_merge_kernel<512>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
+    snprintf(what, sizeof what, "%s(merge)", who);
+    return check_launch(what);
 }
 
 }  // namespace nrms
@@ -396,30 +527,54 @@ extern "C" int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const f
     }
     NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "topk_dot: workspace must be 8-byte aligned");
     if (!exclude) n_exclude = 0;
-    const TopkGeom g = topk_geom(B, N);
     hipStream_t s = (hipStream_t)stream;
     TimingScope ts("topk_dot", s);
-    uint64_t* ws = (uint64_t*)workspace;
-    if (g.S > 0) {
-        const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
-        const dim3 grid(g.tiles, g.S);
-        const int n = (int)N;
-#define TK_LAUNCH(P, W)                                                                                                    \
-    do {                                                                                                                   \
-        if (vec) hipLaunchKernelGGL((topk_slice_kernel<P, W, true>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S, \
-                                    user, items, exclude, n_exclude, ws);                                                  \
-        else hipLaunchKernelGGL((topk_slice_kernel<P, W, false>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S,    \
-                                user, items, exclude, n_exclude, ws);                                                      \
-    } while (0)
-        if (k + 64 <= 128) TK_LAUNCH(128, TK_WAVES);
-        else if (k + 64 <= 256) TK_LAUNCH(256, TK_WAVES);
-        else TK_LAUNCH(512, 2);
-#undef TK_LAUNCH
-        const int rc = check_launch("topk_dot(slices)");
+    return topk_launch(false, B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids,
+                       (uint64_t*)workspace, s, "topk_dot");
+}
+
+extern "C" size_t nrms_topk_grouped_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G) {
+    if (!topk_grouped_args_ok(B, N, d, k, G)) return 0;
+    const int64_t nt = topk_grouped_tiles(N, G);
+    const TopkGeom g = topk_geom(B, 32 * nt);
+    return 256 + topk_tile_bytes(nt) + (size_t)B * (size_t)g.S * (size_t)k * sizeof(uint64_t);
+}
+
+extern "C" int nrms_topk_grouped_dot(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, const float* query, const float* items,
+                                     const int32_t* item_ids, const int64_t* group_ptr, const int64_t* exclude, int32_t n_exclude,
+                                     float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    NRMS_REQUIRE(B >= 0, "topk_grouped_dot: B must be >= 0 (B=%d)", B);
+    NRMS_REQUIRE(G >= 1, "topk_grouped_dot: G must be >= 1 (G=%d)", G);
+    NRMS_REQUIRE(N >= 0 && N + 32 * (int64_t)G <= TK_MAX_N, "topk_grouped_dot: N must be in [0, %d - 32 G] (N=%lld, G=%d)",
+                 TK_MAX_N, (long long)N, G);
+    NRMS_REQUIRE(d >= 1, "topk_grouped_dot: d must be >= 1 (d=%d)", d);
+    NRMS_REQUIRE(k >= 1 && k <= TK_MAX_K, "topk_grouped_dot: k must be in [1, %d] (k=%d)", TK_MAX_K, k);
+    NRMS_REQUIRE(n_exclude >= 0, "topk_grouped_dot: n_exclude must be >= 0 (n_exclude=%d)", n_exclude);
+    if (B == 0) return NRMS_OK;
+    NRMS_REQUIRE(query, "topk_grouped_dot: query is null");
+    NRMS_REQUIRE(items || N == 0, "topk_grouped_dot: items is null");
+    NRMS_REQUIRE(item_ids || N == 0, "topk_grouped_dot: item_ids is null");
+    NRMS_REQUIRE(group_ptr || N == 0, "topk_grouped_dot: group_ptr is null");
+    NRMS_REQUIRE(top_scores, "topk_grouped_dot: top_scores is null");
+    NRMS_REQUIRE(top_ids, "topk_grouped_dot: top_ids is null");
+    NRMS_REQUIRE(workspace, "topk_grouped_dot: workspace is null");
+    const size_t need = nrms_topk_grouped_dot_workspace_bytes(B, N, d, k, G);
+    if (workspace_bytes < need) {
+        set_error("topk_grouped_dot: workspace %zu < required %zu bytes", workspace_bytes, need);
+        return NRMS_EWORKSPACE;
+    }
+    NRMS_REQUIRE(((uintptr_t)workspace & 15) == 0, "topk_grouped_dot: workspace must be 16-byte aligned");
+    if (!exclude) n_exclude = 0;
+    hipStream_t s = (hipStream_t)stream;
+    TimingScope ts("topk_grouped_dot", s);
+    const int64_t nt = topk_grouped_tiles(N, G);
+    TkTile* tiles = (TkTile*)workspace;
+    uint64_t* ws = (uint64_t*)((char*)workspace + topk_tile_bytes(nt));
+    if (nt > 0) {
+        hipLaunchKernelGGL(topk_tiles_kernel, dim3(1), dim3(1024), 0, s, (int)N, G, (int)nt, group_ptr, tiles);
+        const int rc = check_launch("topk_grouped_dot(tiles)");
         if (rc != NRMS_OK) return rc;
     }
-    if (k + 64 <= 128) hipLaunchKernelGGL(topk_merge_kernel<128>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
-    else if (k + 64 <= 256) hipLaunchKernelGGL(topk_merge_kernel<256>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
-    else hipLaunchKernelGGL(topk_merge_kernel<512>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
-    return check_launch("topk_dot(merge)");
+    return topk_launch(true, B, N, d, k, G, nt, query, items, item_ids, tiles, exclude, n_exclude, top_scores, top_ids, ws, s,
+                       "topk_grouped_dot");
 }

@@ -308,6 +308,14 @@ class NRMSEngine:
         self._bad_event = ev
         return dst
 
+    def note_bad_ids(self):
+        """After nrms_sanitize_ids calls made outside sanitize_ids (category tables): their count reaches the host as
+        sanitize_ids' does, for poll_ids / check_ids."""
+        self._bad_host.copy_(self._bad_ids, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._bad_event = ev
+
     def _raise_bad_ids(self):
         n = int(self._bad_host.item())
         if n:
@@ -623,6 +631,64 @@ class NRMSEngine:
         rc = self.lib.nrms_topk_dot(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(exclude), n_ex,
                                     _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
         _lib.check(rc, "nrms_topk_dot")
+        return scores, ids
+
+    # user chunks of top_k_grouped (and of the HieRec query that feeds it) keep the query plus the workspace under this
+    retrieval_chunk_bytes = 256 << 20
+
+    def grouped_chunk_users(self, B, N, d, k, G):
+        """Users per chunk of a grouped top-k: the most (at least 1) whose [b, G, d] fp32 query and kernel workspace fit in
+        ``retrieval_chunk_bytes``."""
+        per_user = 4 * G * d + 8 * k * max(1, -(-(N + 31 * G) // 2048))     # query row + at most one k-list per 2048 items
+        b = max(1, min(int(B), int(self.retrieval_chunk_bytes) // per_user))
+        return b if b < 32 or b == B else b // 32 * 32          # whole 32-user tiles
+
+    def top_k_grouped(self, query, items, item_ids, group_ptr, k, exclude=None):
+        """query [B, G, d] fp32, items [N, d] fp32 stored group after group (group g = rows group_ptr[g] .. group_ptr[g + 1]),
+        item_ids [N] int32 (distinct, >= 0), group_ptr [G + 1] int64, exclude [B, n_exclude] int64 ids or None (device,
+        contiguous) -> (scores [B, k] fp32, ids [B, k] int64): per user the k items of largest query[b, g(n)] . items[n], no
+        [B, N] matrix (nrms_topk_grouped_dot).  Order and padding as top_k, with item ids in place of rows.  Users go in
+        chunks of grouped_chunk_users; the result does not depend on the chunking."""
+        k = int(k)
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        for name, t, dt, nd in (("query", query, torch.float32, 3), ("items", items, torch.float32, 2),
+                                ("item_ids", item_ids, torch.int32, 1), ("group_ptr", group_ptr, torch.int64, 1)):
+            if t.dim() != nd or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NrmsError("top_k_grouped: %s must be a contiguous %d-D %s tensor on %s (got %s %s on %s%s)"
+                                     % (name, nd, dt, self.device, tuple(t.shape), t.dtype, t.device,
+                                        "" if t.is_contiguous() else ", not contiguous"))
+        B, G, d = query.shape
+        N = items.shape[0]
+        if items.shape[1] != d:
+            raise _lib.NrmsError("top_k_grouped: items width %d != query width %d" % (items.shape[1], d))
+        if item_ids.shape[0] != N or group_ptr.shape[0] != G + 1:
+            raise _lib.NrmsError("top_k_grouped: item_ids must be [%d] and group_ptr [%d] (got %s, %s)"
+                                 % (N, G + 1, tuple(item_ids.shape), tuple(group_ptr.shape)))
+        n_ex = 0
+        if exclude is not None:
+            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
+                    or not exclude.is_contiguous()):
+                raise _lib.NrmsError("top_k_grouped: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
+                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
+            n_ex = exclude.shape[1]
+            if n_ex == 0:
+                exclude = None
+        if self.lib.nrms_topk_grouped_dot_workspace_bytes(B, N, d, k, G) == 0:
+            raise _lib.NrmsError("top_k_grouped: arguments rejected (B=%d, N=%d, d=%d, k=%d, G=%d; 1 <= k <= 256, G >= 1)"
+                                 % (B, N, d, k, G))
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        step = self.grouped_chunk_users(B, N, d, k, G)
+        for b0 in range(0, B, step):
+            b1 = min(B, b0 + step)
+            nbytes = self.lib.nrms_topk_grouped_dot_workspace_bytes(b1 - b0, N, d, k, G)
+            ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+            ex = None if exclude is None else exclude[b0:b1]
+            rc = self.lib.nrms_topk_grouped_dot(b1 - b0, C.c_int64(N), d, k, G, _lib.ptr(query[b0:b1]), _lib.ptr(items),
+                                                _lib.ptr(item_ids), _lib.ptr(group_ptr), _lib.ptr(ex), n_ex,
+                                                _lib.ptr(scores[b0:b1]), _lib.ptr(ids[b0:b1]), _lib.ptr(ws),
+                                                C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_topk_grouped_dot")
         return scores, ids
 
     # ---- inference with unique-title caching (SURVEY f-1) -------------------------------------

@@ -60,11 +60,41 @@ class HieRecEngine(NRMSEngine):
     def _i32(self, key, n):
         return self._buf(key, n, torch.int32)[:n]
 
+    def _interests(self, flat, hist, valid, topic, sub, B, H, sfx):
+        """The user side that forward and recommend share: the interest tree of B users' H history slots (hist [B * H, d] news
+        vectors, valid uint8 [B, H], topic / sub int64 [B * H] validated category ids), built on the device, then the three
+        aggregations with their embedding adds -> (index lists t, u1 [B * H, d], u2 [B * H, d], ug [B, d], pools)."""
+        d, q = self.dims.word_embed_size, self.dims.query_vector_dim
+        n = B * H
+        t = {k: self._i32(k + sfx, m) for k, m in (("l1_ptr", n + 1), ("l1_idx", n), ("l1_sub", n), ("l1_top", n), ("l1_cnt", n),
+                                                    ("l2_ptr", n + 1), ("l2_idx", n), ("l2_top", n), ("l2_cnt", n), ("l3_ptr", B + 1),
+                                                    ("l3_idx", n), ("n_valid", B))}
+        sb = int(self.lib.nrms_hier_tree_scratch_bytes(B, H))
+        scratch = self._buf("hier_scratch", (sb + 3) // 4 + 2)
+        rc = self.lib.nrms_hier_tree_build(B, H, _lib.ptr(valid), _lib.ptr(topic), _lib.ptr(sub), *[_lib.ptr(t[k]) for k in (
+            "l1_ptr", "l1_idx", "l1_sub", "l1_top", "l1_cnt", "l2_ptr", "l2_idx", "l2_top", "l2_cnt", "l3_ptr", "l3_idx", "n_valid")],
+            _lib.ptr(scratch), C.c_size_t(scratch.numel() * 4), _stream())
+        _lib.check(rc, "nrms_hier_tree_build")
+        # ---- three aggregations
+        lay = self.layout
+        W = {lv: (lay.view(flat, lv + ".linear.weight"), lay.view(flat, lv + ".linear.bias"), lay.view(flat, lv + ".attention_query_vector"))
+             for lv in LEVELS}
+        prec = self._pool_precision()
+        pools = [SegmentPool(d, q, prec, rows_unique=True) for _ in range(3)]
+        u1 = pools[0].forward(hist, *W[LEVELS[0]], t["l1_ptr"], t["l1_idx"])
+        _lib.check(self.lib.nrms_hier_add_embedding_fwd(C.c_int64(n), d, self.n_sub, _lib.ptr(t["l1_sub"]), _lib.ptr(t["l1_cnt"]),
+                                                        _lib.ptr(lay.view(flat, "subtopic_embedding.weight")), _lib.ptr(u1), _stream()), "add_embedding")
+        u2 = pools[1].forward(u1, *W[LEVELS[1]], t["l2_ptr"], t["l2_idx"])
+        _lib.check(self.lib.nrms_hier_add_embedding_fwd(C.c_int64(n), d, self.n_top, _lib.ptr(t["l2_top"]), _lib.ptr(t["l2_cnt"]),
+                                                        _lib.ptr(lay.view(flat, "topic_embedding.weight")), _lib.ptr(u2), _stream()), "add_embedding")
+        ug = pools[2].forward(u2, *W[LEVELS[2]], t["l3_ptr"], t["l3_idx"])
+        return t, u1, u2, ug, pools
+
     def forward(self, flat, batch, training, p_drop=0.0, seed=0):
         bt, ct = batch["browsed_titles"], batch["candidate_titles"]
         B, H, L = bt.shape
         Cn = ct.shape[1]
-        d, q = self.dims.word_embed_size, self.dims.query_vector_dim
+        d = self.dims.word_embed_size
         if H > 64:
             raise _lib.NrmsError("hierec: history_len %d > 64" % H)
         N = B * (H + Cn)
@@ -89,28 +119,8 @@ class HieRecEngine(NRMSEngine):
             s_ = src.reshape(-1).to(torch.int64).contiguous()
             _lib.check(self.lib.nrms_sanitize_ids(_lib.ptr(s_), _lib.ptr(dst), C.c_int64(s_.numel()), int(vocab), _lib.ptr(self._bad_ids),
                                                   _stream()), "nrms_sanitize_ids")
-        t = {k: self._i32(k + sfx, m) for k, m in (("l1_ptr", n + 1), ("l1_idx", n), ("l1_sub", n), ("l1_top", n), ("l1_cnt", n),
-                                                    ("l2_ptr", n + 1), ("l2_idx", n), ("l2_top", n), ("l2_cnt", n), ("l3_ptr", B + 1),
-                                                    ("l3_idx", n), ("n_valid", B), ("sub_slot", B * Cn), ("top_slot", B * Cn))}
-        sb = int(self.lib.nrms_hier_tree_scratch_bytes(B, H))
-        scratch = self._buf("hier_scratch", (sb + 3) // 4 + 2)
-        rc = self.lib.nrms_hier_tree_build(B, H, _lib.ptr(valid), _lib.ptr(topic), _lib.ptr(sub), *[_lib.ptr(t[k]) for k in (
-            "l1_ptr", "l1_idx", "l1_sub", "l1_top", "l1_cnt", "l2_ptr", "l2_idx", "l2_top", "l2_cnt", "l3_ptr", "l3_idx", "n_valid")],
-            _lib.ptr(scratch), C.c_size_t(scratch.numel() * 4), _stream())
-        _lib.check(rc, "nrms_hier_tree_build")
-        # ---- three aggregations
-        lay = self.layout
-        W = {lv: (lay.view(flat, lv + ".linear.weight"), lay.view(flat, lv + ".linear.bias"), lay.view(flat, lv + ".attention_query_vector"))
-             for lv in LEVELS}
-        prec = self._pool_precision()
-        pools = [SegmentPool(d, q, prec, rows_unique=True) for _ in range(3)]
-        u1 = pools[0].forward(hist, *W[LEVELS[0]], t["l1_ptr"], t["l1_idx"])
-        _lib.check(self.lib.nrms_hier_add_embedding_fwd(C.c_int64(n), d, self.n_sub, _lib.ptr(t["l1_sub"]), _lib.ptr(t["l1_cnt"]),
-                                                        _lib.ptr(lay.view(flat, "subtopic_embedding.weight")), _lib.ptr(u1), _stream()), "add_embedding")
-        u2 = pools[1].forward(u1, *W[LEVELS[1]], t["l2_ptr"], t["l2_idx"])
-        _lib.check(self.lib.nrms_hier_add_embedding_fwd(C.c_int64(n), d, self.n_top, _lib.ptr(t["l2_top"]), _lib.ptr(t["l2_cnt"]),
-                                                        _lib.ptr(lay.view(flat, "topic_embedding.weight")), _lib.ptr(u2), _stream()), "add_embedding")
-        ug = pools[2].forward(u2, *W[LEVELS[2]], t["l3_ptr"], t["l3_idx"])
+        t, u1, u2, ug, pools = self._interests(flat, hist, valid, topic, sub, B, H, sfx)
+        t["sub_slot"], t["top_slot"] = self._i32("sub_slot" + sfx, B * Cn), self._i32("top_slot" + sfx, B * Cn)
         # ---- hierarchical matching
         sub_frac = self._buf("sub_frac" + sfx, B * Cn)[:B * Cn]
         top_frac = self._buf("top_frac" + sfx, B * Cn)[:B * Cn]
@@ -133,6 +143,31 @@ class HieRecEngine(NRMSEngine):
                                mask=mask, pools=pools, p=p, seed=seed, gen=self._gen)
         self.last_interest = (u1, u2, ug)
         return scores
+
+    def recommend(self, flat, browsed, cat, k, exclude_history=True):
+        """browsed [B, H] int64 news ids inside the catalogue (0 = padding slot), cat: a Catalogue -> (scores [B, k], ids [B, k]).
+        Per chunk of users: the interests from catalogue rows and tables (the code path of forward), the query of every
+        catalogue group (nrms_hier_query), then the grouped top-k."""
+        B, H = browsed.shape
+        d, G = self.dims.word_embed_size, cat.group_topic.shape[0]
+        scores = torch.empty(B, int(k), dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, int(k), dtype=torch.int64, device=self.device)
+        step = self.grouped_chunk_users(B, cat.items.shape[0], d, int(k), G)
+        for b0 in range(0, B, step):
+            br = browsed[b0:b0 + step]
+            b, slots = br.shape[0], br.reshape(-1)
+            valid = (br != 0).to(torch.uint8)
+            t, u1, u2, ug, _ = self._interests(flat, cat.vectors.index_select(0, slots), valid, cat.categ.index_select(0, slots),
+                                               cat.subcateg.index_select(0, slots), b, H, "_rec")
+            query = self._buf("hier_query", b * G * d)[:b * G * d].view(b, G, d)
+            rc = self.lib.nrms_hier_query(b, H, G, d, _lib.ptr(cat.group_topic), _lib.ptr(cat.group_sub), _lib.ptr(t["l1_sub"]),
+                                          _lib.ptr(t["l1_cnt"]), _lib.ptr(t["l2_top"]), _lib.ptr(t["l2_cnt"]), _lib.ptr(t["n_valid"]),
+                                          _lib.ptr(u1), _lib.ptr(u2), _lib.ptr(ug), C.c_float(self.lambda_sub),
+                                          C.c_float(self.lambda_top), _lib.ptr(query), _stream())
+            _lib.check(rc, "nrms_hier_query")
+            s_, i_ = self.top_k_grouped(query, cat.items, cat.item_ids, cat.group_ptr, k, br if exclude_history else None)
+            scores[b0:b0 + b], ids[b0:b0 + b] = s_, i_
+        return scores, ids
 
     def backward(self, flat, gflat, dscores, gen=None, table_grad_ready=None):
         sv = self._saved
@@ -193,6 +228,28 @@ class HieRecEngine(NRMSEngine):
             table_grad_ready()
 
 
+class Catalogue:
+    """What HieRec retrieval reads of a news catalogue (Model.encode_catalogue): row r = news id r throughout.
+    vectors [N, d]: the evaluation-precision news vectors in id order; categ / subcateg int64 [N]: validated category ids;
+    items [N - 1, d]: rows 1.. (the padding title is never a candidate) grouped by (topic, sub-topic), ids ascending inside a
+    group; item_ids int32 [N - 1]: their news ids; group_ptr int64 [G + 1]; group_topic / group_sub int64 [G]: each group's ids."""
+
+    def __init__(self, vectors, categ, subcateg, n_sub):
+        N, dev = vectors.shape[0], vectors.device
+        self.vectors, self.categ, self.subcateg = vectors, categ, subcateg
+        key = categ[1:] * n_sub + subcateg[1:]
+        uniq, inv = torch.unique(key, sorted=True, return_inverse=True)
+        order = torch.sort(inv, stable=True).indices + 1
+        self.items = vectors.index_select(0, order)
+        self.item_ids = order.to(torch.int32)
+        counts = torch.bincount(inv, minlength=uniq.shape[0])
+        if uniq.shape[0] == 0:                       # no news besides the padding title: one empty group
+            uniq, counts = torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+        self.group_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), counts.cumsum(0)])
+        self.group_topic, self.group_sub = (uniq // n_sub).contiguous(), (uniq % n_sub).contiguous()
+        assert N - 1 == self.items.shape[0]
+
+
 class Model(FlatHipModel):
     """HieRec-style hierarchical interest model: ``Model(config)``, ``forward(batch) -> scores [B, C]`` (the reference's plugin
     contract, ``model/__init__.py:22-23,38``)."""
@@ -217,6 +274,64 @@ class Model(FlatHipModel):
     def _make_engine(self, device, precision):
         return HieRecEngine(self._dims, self._layout, device, precision, self.config.subcategory_nums, self.config.category_nums,
                             getattr(self.config, "hierec_lambda_sub", 0.7), getattr(self.config, "hierec_lambda_top", 0.15))
+
+    # ---- retrieval over the whole catalogue ----------------------------------------------------
+    @torch.no_grad()
+    def encode_catalogue(self, titles, categ=None, subcateg=None, absts=None):
+        """titles [N, L] word ids, categ / subcateg [N] category and sub-category ids, row r = news id r (``DeviceFeed.titles``
+        and ``DeviceFeed.news_info()``; absts is accepted with them and not read) -> a Catalogue: the evaluation-precision
+        news vectors, grouped by (topic, sub-topic) for nrms_topk_grouped_dot.  Category ids outside their tables are read
+        as 0 and counted (engine.check_ids raises)."""
+        if categ is None or subcateg is None:
+            raise NotImplementedError("hierec: catalogue retrieval needs the category and sub-category of every news item: "
+                                      "encode_catalogue(titles, categ, subcateg), e.g. with DeviceFeed.news_info()")
+        dev = self._prepare()
+        eng = self._engine
+        vectors = eng.encode_titles(self._flat, nrms_hip._ids_on(dev, titles), tag="news_eval")
+        N = vectors.shape[0]
+        tables = []
+        for src, vocab in ((categ, eng.n_top), (subcateg, eng.n_sub)):
+            src = torch.as_tensor(src).to(dev, dtype=torch.int64).reshape(-1).contiguous()
+            if src.shape[0] != N:
+                raise _lib.NrmsError("encode_catalogue: %d category ids for %d titles" % (src.shape[0], N))
+            dst = torch.empty_like(src)
+            _lib.check(eng.lib.nrms_sanitize_ids(_lib.ptr(src), _lib.ptr(dst), C.c_int64(N), int(vocab), _lib.ptr(eng._bad_ids),
+                                                 _stream()), "nrms_sanitize_ids")
+            tables.append(dst)
+        eng.note_bad_ids()
+        return Catalogue(vectors, tables[0], tables[1], eng.n_sub)
+
+    @torch.no_grad()
+    def recommend(self, batch, k, catalogue, exclude_history=True):
+        """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores [B, k]
+        fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_grouped_dot).
+
+        catalogue: encode_catalogue(titles, categ, subcateg).  Only ``browsed_ids`` [B, H] is read: the history vectors and
+        categories are catalogue rows, a slot is valid where its id is not 0, and the interests are those forward builds;
+        a news item's score is its forward score as that user's candidate.  Ids outside the catalogue are read as padding
+        and counted (check_recommend_ids raises).  News id 0 is never returned, with exclude_history neither is a browsed
+        id; missing slots get id -1 / score -inf."""
+        get = batch.get if hasattr(batch, "get") else batch.__getitem__
+        browsed = get("browsed_ids")
+        if browsed is None:
+            raise KeyError("recommend: the batch dict lacks 'browsed_ids' (the news ids of the clicked history)")
+        if not isinstance(catalogue, Catalogue):
+            raise NotImplementedError("hierec: recommend needs a catalogue with the category tables, from "
+                                      "encode_catalogue(titles, categ, subcateg)")
+        dev = self._prepare()
+        browsed = torch.as_tensor(browsed).to(dev, dtype=torch.int64).contiguous()
+        if browsed.dim() != 2 or browsed.shape[1] > 64:
+            raise _lib.NrmsError("recommend: browsed_ids must be [B, H] with H <= 64 (got %s)" % (tuple(browsed.shape),))
+        bad = (browsed < 0) | (browsed >= catalogue.vectors.shape[0])
+        browsed = browsed.masked_fill(bad, 0)
+        if self._bad_browsed is None or self._bad_browsed.device != dev:
+            self._bad_browsed = torch.zeros((), dtype=torch.int64, device=dev)
+        self._bad_browsed += bad.sum()
+        scores, ids = self._engine.recommend(self._flat, browsed, catalogue, k, exclude_history)
+        return ids, scores
+
+    _bad_browsed = None
+    check_recommend_ids = nrms_hip.Model.check_recommend_ids
 
     def _zero_frozen_rows(self, gflat):
         # padding_idx = 0 of the two embedding tables: row 0 takes no gradient (nn.Embedding semantics)

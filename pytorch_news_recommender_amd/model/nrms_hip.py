@@ -184,7 +184,7 @@ class Model(FlatHipModel):
             raise KeyError("recommend: the batch dict lacks 'browsed_ids' (the news ids of the clicked history)")
         dev = self._prepare()
         cat = torch.as_tensor(catalogue)
-        d = self._dims.word_embed_size
+        d = self._catalogue_width()
         if cat.dim() != 2 or cat.shape[1] != d or cat.dtype != torch.float32 or cat.device != dev:
             raise _lib.NrmsError("recommend: catalogue must be [N, %d] float32 on %s (encode_catalogue), got %s %s on %s"
                                  % (d, dev, tuple(cat.shape), cat.dtype, cat.device))
@@ -199,12 +199,19 @@ class Model(FlatHipModel):
         if self._bad_browsed is None or self._bad_browsed.device != dev:
             self._bad_browsed = torch.zeros((), dtype=torch.int64, device=dev)
         self._bad_browsed += bad.sum()
-        user = self._engine.encode_users(self._flat, cat.index_select(0, browsed.view(-1)).view(B, H, d), tag="user_eval")
+        user = self._catalogue_users(cat.index_select(0, browsed.view(-1)).view(B, H, d))
         # the kernel runs on rows 1.. (the padding title is never a candidate); history ids shift with them, which sends
         # the padding slots (id 0) out of range, where the kernel ignores them
         exclude = browsed - 1 if exclude_history else None
         scores, ids = self._engine.top_k(user, cat[1:], k, exclude)
         return torch.where(ids >= 0, ids + 1, ids), scores
+
+    def _catalogue_width(self):
+        return self._dims.word_embed_size
+
+    def _catalogue_users(self, hist):
+        """Catalogue rows of the history [B, H, width] -> user vectors [B, width]."""
+        return self._engine.encode_users(self._flat, hist, tag="user_eval")
 
     _bad_browsed = None
     CATALOGUE_RETRIEVAL = True          # recommend / encode_catalogue are available (run_v0 --recommend checks this)

@@ -8,11 +8,13 @@ and ``state_dict()`` order are the reference's, so checkpoints interchange with 
 are the reference's (nrms_naml.py:217-228,245): ``browsed_titles / _absts / _categ_ids / _subcateg_ids``, the four
 ``candidate_*`` counterparts and ``candidate_mask`` -- all emitted by data_handler.MyDataset.
 """
+import ctypes as C
+
 import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import FlatLayout
+from ..engine import FlatLayout, _stream
 from ..naml_engine import NamlDims, NamlEngine, naml_entries
 from . import nrms_hip
 
@@ -99,10 +101,54 @@ class Model(nrms_hip.Model):
 
     get_user_vector = get_prediction = get_news_vector
 
-    def recommend(self, *a, **k):
-        raise NotImplementedError("nrms_naml: catalogue retrieval needs a category and sub-category per news item, and "
-                                  "there is no per-news category table (DeviceFeed carries them per sample)")
+    # ---- retrieval over the whole catalogue (recommend itself is nrms_hip.Model's, with the two hooks below) ------------
+    @torch.no_grad()
+    def encode_catalogue(self, titles, absts=None, categ=None, subcateg=None):
+        """titles [N, Lt], absts [N, La] word ids (None: empty abstracts), categ / subcateg [N] category and sub-category ids,
+        row r = news id r (``DeviceFeed.titles`` and ``DeviceFeed.news_info()``) -> news feature rows [N, F]
+        (NewsEncoder.forward, nrms_naml.py:121-177, no dropout), in chunks of 32 768.  Ids outside their tables are read as
+        padding and counted (engine.check_ids raises)."""
+        if categ is None or subcateg is None:
+            raise NotImplementedError("nrms_naml: catalogue retrieval needs the category and sub-category of every news item: "
+                                      "encode_catalogue(titles, absts, categ, subcateg), e.g. with DeviceFeed.news_info()")
+        dev = self._prepare()
+        eng, d = self._engine, self._dims
+        titles = torch.as_tensor(titles).to(dev, dtype=torch.int64)
+        N = titles.shape[0]
+        if absts is None:
+            absts = torch.zeros(N, int(self.config.n_words_abst), dtype=torch.int64, device=dev)
+        ids = []
+        for src, vocab in ((titles, d.n_words), (absts, d.n_words), (categ, d.category_nums), (subcateg, d.subcategory_nums)):
+            src = torch.as_tensor(src).to(dev, dtype=torch.int64).contiguous()
+            if src.shape[0] != N:
+                raise _lib.NrmsError("encode_catalogue: %d rows of ids for %d titles" % (src.shape[0], N))
+            dst = torch.empty_like(src)
+            _lib.check(eng.lib.nrms_sanitize_ids(_lib.ptr(src), _lib.ptr(dst), C.c_int64(src.numel()), int(vocab),
+                                                 _lib.ptr(eng._bad_ids), _stream()), "nrms_sanitize_ids")
+            ids.append(dst)
+        eng.note_bad_ids()
+        ids_t, ids_a, cat, sub = ids[0], ids[1], ids[2].view(N), ids[3].view(N)
+        out = torch.empty(N, d.news_feature_size, dtype=torch.float32, device=dev)
+        for c0 in range(0, N, 32768):
+            c1 = min(N, c0 + 32768)
+            eng.news_features(self._flat, ids_t[c0:c1], ids_a[c0:c1], cat[c0:c1], sub[c0:c1], 0.0, 0, "_cat", out=out[c0:c1])
+        return out
 
-    encode_catalogue = recommend
+    def recommend(self, batch, k, catalogue, exclude_history=True):
+        """nrms_hip.Model.recommend over encode_catalogue's feature rows: the user vector is the LayerNorm of the history's
+        catalogue rows through the user encoder (_forward_dedup's path), the score a plain dot product (click_scores)."""
+        if catalogue is None:
+            raise NotImplementedError("nrms_naml: recommend needs a catalogue built with the per-news category tables: "
+                                      "encode_catalogue(titles, absts, categ, subcateg)")
+        return super().recommend(batch, k, catalogue, exclude_history)
+
+    def _catalogue_width(self):
+        return self._dims.news_feature_size
+
+    def _catalogue_users(self, hist):
+        B, H, F = hist.shape
+        normed = self._engine.layernorm(self._flat, hist.reshape(B * H, F))
+        return self._engine.encode_users(self._flat, normed.view(B, H, F), 0.0, 0, "user_eval")
+
     CATALOGUE_RETRIEVAL = False
 

@@ -320,13 +320,15 @@ def test(config, model, data_iter, test_list_nums=None, ckpt_file=None, out_file
     return file_name
 
 
-def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True):
+def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
-    (``DeviceFeed.titles``); it is encoded once.  With exclude_history the user's browsed news are left out.  Should the
-    catalogue hold fewer than k eligible news for a user, the line is shorter.  Returns the file name."""
+    (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
+    (``DeviceFeed.news_info()``), passed to encode_catalogue as keyword arguments.  With exclude_history the user's
+    browsed news are left out.  Should the catalogue hold fewer than k eligible news for a user, the line is shorter.
+    Returns the file name."""
     net = _inner(model)
-    catalogue = net.encode_catalogue(titles)
+    catalogue = net.encode_catalogue(titles, **(news_info or {}))
     lines = []
     for datas in data_iter:
         ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history)
