@@ -8,16 +8,21 @@ MIND shapes hist=50 cand=5 title_len=30 d=300 V=45800, 512 users per GPU).
 
 One step = forward + CE(label 0) + backward + [RCCL all-reduce of the flat gradient] + fused
 Adam over all 14.4 M parameters, dropout 0.2 on, synthetic batch already resident in HBM.
-Rank 0 prints ONE JSON line; `roofline` describes the dominant kernel (HIP events on the launch
-stream, a separate pass over the same K steps, run before the warm-up and the timed region), `roofline.step_frac` the whole step against the dense
-fp16/bf16 MFMA peak by BASELINE.md's formula, `cpu_baseline` the oracle's reference-shaped train
-step timed on this box's host cores (N=1 only, bounded sample), `modes` the other precision modes
-and the drop-in autograd + torch.optim.Adam loop on the same batch.
+Rank 0 prints ONE JSON line: `value` users/s over the K timed steps, `ms_per_step`, `loss`, the workload.
+
+A plain run does only what that figure needs (set-up, 1 + 2K + W untimed steps, the K timed steps,
+--dump-outputs).  With --full the line also carries: `roofline` for the dominant kernel (HIP events on
+the launch stream, a separate pass over the same K steps, run before the warm-up and the timed region),
+`roofline.step_frac` the whole step against the dense fp16/bf16 MFMA peak by BASELINE.md's formula,
+`config.score_parity_vs_reference`, `data_parallel` (N > 1), and for N = 1 `modes` (the other precision
+modes and the drop-in autograd + torch.optim.Adam loop on the same batch), `variants`, `eval_path` and
+`cpu_baseline`, the oracle's reference-shaped train step timed on the host's cores (bounded sample).
 """
 import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -454,7 +459,102 @@ def v1_leg(dev, B):
     return out
 
 
-def main():
+def kernel_report(eng, args, shape, world, live_frac, compact, allpad_frac, dt_instr, per_gpu):
+    """--full: `roofline`, `kernels` and `top_mfma_kernel` from the per-kernel HIP-event timers of the instrumented pass
+    (args.steps recorded steps), plus the measured HBM traffic of the dominant kernel and of the whole step."""
+    B = args.users_per_gpu
+    fp16_news = args.precision == "fp16"
+    work = kernel_work(shape, B, live_frac, compact, allpad_frac, fp16_news, bool(args.fp16_user_encoder))
+    # which arithmetic each timer's kernels run in (fp16 mode: the user encoder's kernels are bf16x3)
+    kprec = {k: args.precision for k in work}
+    if fp16_news and not args.fp16_user_encoder:
+        for k in ("user64_fwd", "user64_bwd", "qkv_proj_fwd", "addattn_fwd", "dctx_bwd", "attn_fwd", "attn_bwd", "addattn_bwd_rows"):
+            kprec[k] = "bf16x3"
+    kernels = {}
+    for name, (bound, fl, by) in work.items():
+        ms, n = eng.timing_read(name)
+        if n == 0:
+            continue
+        sec = ms / args.steps * 1e-3
+        kernels[name] = {"ms_per_step": ms / args.steps, "launches_per_step": n / args.steps, "bound": bound,
+                         "tflops": fl / sec / 1e12, "gbps": by / sec / 1e9}
+        if bound == "mfma":
+            kernels[name]["frac_of_mfma_peak"] = fl / sec / 1e12 / PEAKS[kprec[name]]
+        else:
+            kernels[name]["frac_of_hbm_peak"] = by / sec / 1e9 / PEAK_HBM_GBPS
+    for name in OTHER_TIMERS:
+        ms, n = eng.timing_read(name)
+        if n:
+            kernels[name] = {"ms_per_step": ms / args.steps, "launches_per_step": n / args.steps}
+    dom = max((k for k in kernels if "bound" in kernels[k]), key=lambda k: kernels[k]["ms_per_step"])
+    dom_ms, dom_n = eng.timing_read(dom)
+    bound, fl, by = work[dom]
+    peak = PEAKS[kprec[dom]] if bound == "mfma" else PEAK_HBM_GBPS
+    achieved = (fl / 1e12 if bound == "mfma" else by / 1e9) / (dom_ms / args.steps * 1e-3)
+    # measured HBM bytes per step of that kernel and of the whole step: rocprofv3 PMC FETCH_SIZE x 2 + WRITE_SIZE in separate
+    # passes (tools/hbm_traffic.py).  A committed profile is used only if it was measured on EXACTLY this kernel source
+    # (hash of csrc/ + include/); otherwise the two passes run now, as child processes, on the code that was just timed.
+    traffic, step_traffic, traffic_src = None, None, "unavailable"
+    if B == 512 and world == 1:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import hbm_traffic
+        sha = hbm_traffic.csrc_sha16()
+        tfile = os.path.join(ROOT, "profiles", "r04_%s_hbm_traffic.json" % args.precision)
+        prof = None
+        if os.path.exists(tfile) and not args.fp16_user_encoder:
+            try:
+                cand = json.load(open(tfile))
+                if cand.get("csrc_sha16") == sha:
+                    prof, traffic_src = cand, "profiles/%s (same kernel source: csrc sha %s)" % (os.path.basename(tfile), sha)
+                else:
+                    traffic_src = "profiles/%s is stale (csrc sha %s != %s)" % (os.path.basename(tfile), cand.get("csrc_sha16"), sha)
+            except Exception as e:
+                traffic_src = "unreadable profile: %r" % (e,)
+        if prof is None and not args.no_live_traffic:
+            try:
+                log("measuring HBM traffic live (two rocprofv3 --pmc passes as child processes)")
+                torch.cuda.synchronize()
+                prof = hbm_traffic.collect(os.path.join(tempfile.gettempdir(), "nrms_traffic_%d" % os.getpid()), steps=3,
+                                           precision=args.precision, extra=["--fp16-user-encoder"] if args.fp16_user_encoder else [])
+                traffic_src = "measured in this run (tools/hbm_traffic.py, 3 steps per pass)"
+            except Exception as e:
+                traffic_src += "; live measurement failed: %r" % (e,)
+        if prof is not None:
+            traffic = prof["by_timer"].get(dom, {}).get("hbm_bytes_per_step")
+            step_traffic = prof.get("step_bytes")
+    out = {
+        "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": peak,
+                     "unit": "TFLOP/s" if bound == "mfma" else "GB/s", "frac": achieved / peak, "traffic": traffic,
+                     "traffic_note": "HBM bytes per step of that kernel, rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE (separate passes); "
+                                     "source: " + traffic_src,
+                     "step_traffic": step_traffic,
+                     "step_traffic_note": "HBM bytes of ALL kernels of one train step, same measurement; algorithmic: 4.87 MB/user x %d = "
+                                          "%.2f GB (SURVEY 8d)" % (B, 4.87e6 * B / 1e9),
+                     "peak_note": ("HBM3E spec 8 TB/s (6.3 TB/s measured achievable)" if bound == "hbm" else
+                                   {"fp32": "f32-input MFMA dense peak", "bf16": "bf16 MFMA dense peak", "fp16": "fp16 MFMA dense peak",
+                                    "bf16x3": "bf16 dense peak / 3 (3 bf16 MFMAs per fp32-equivalent step by construction)"}[kprec[dom]]),
+                     "avg_launch_ms": dom_ms / max(dom_n, 1),
+                     "timing_note": "kernel durations: HIP events on the launch stream, recorded in a separate pass of the "
+                                    "same %d steps (after as many unrecorded settling steps) before the warm-up and the (un-instrumented) timed region, with the helper streams off "
+                                    "(NRMS_NO_SIDE_STREAMS) so that no two kernels share the GPU; that pass ran at "
+                                    "%.2f ms/step" % (args.steps, dt_instr / args.steps * 1e3),
+                     "algorithmic_per_step": by if bound == "hbm" else fl,
+                     # the WHOLE step by BASELINE.md section 2: users/s x 3.558309e9 flop / peak (per GPU)
+                     "step_frac": per_gpu * FLOP_PER_USER_TRAIN / (PEAK_16_MFMA_TFLOPS * 1e12),
+                     "step_frac_note": "users/s per GPU x 3 558 309 000 flop (reference algorithm, padding included) / 2.5e15 "
+                                       "(dense fp16/bf16 MFMA peak, undivided)",
+                     "step_tflops_equiv": per_gpu * FLOP_PER_USER_TRAIN / 1e12},
+        "kernels": kernels,
+    }
+    mf = [k for k in kernels if kernels[k].get("bound") == "mfma"]
+    if mf:
+        k = max(mf, key=lambda kk: kernels[kk]["ms_per_step"])
+        out["top_mfma_kernel"] = {"kernel": k, "tflops": kernels[k]["tflops"], "peak": PEAKS[kprec[k]],
+                                  "frac": kernels[k]["tflops"] / PEAKS[kprec[k]]}
+    return out
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: steady state -- with 5 warm-up + 20 timed steps (0.09 s in all) the same box reads 2.5 ... 3.5 % lower (clocks, caches
@@ -464,12 +564,16 @@ def main():
     ap.add_argument("--users-per-gpu", type=int, default=512)
     ap.add_argument("--resident-batches", type=int, default=32,
                     help="distinct synthetic batches resident in HBM that the steps cycle over (1 = replay one batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the secondary legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel timers and roofline, HBM "
+                         "traffic, score parity against the exact fp32 mode, the data-parallel facts (N > 1) and, N = 1, the "
+                         "secondary legs (other precision modes, model variants, evaluation path) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the secondary legs")
     ap.add_argument("--dense-padding", action="store_true",
                     help="diagnostics: process padding tokens densely (as if embedding row 0 were not zero)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the two rocprofv3 --pmc child passes when the committed traffic profile is stale")
-    ap.add_argument("--cpu-budget-s", type=float, default=60.0, help="wall-clock budget of the larger CPU-baseline batch")
+                    help="with --full: do not run the two rocprofv3 --pmc child passes when the committed traffic profile is stale")
+    ap.add_argument("--cpu-budget-s", type=float, default=60.0, help="with --full: wall-clock budget of the larger CPU-baseline batch")
     ap.add_argument("--grad-sync", default="allreduce", choices=["allreduce", "sharded"],
                     help="N > 1: one all-reduce of the flat gradient + full Adam on every rank (default), or reduce-scatter -> "
                          "Adam on the owned 1/N of the parameters -> all-gather (parallel.ShardedGradSync)")
@@ -480,20 +584,24 @@ def main():
                          "bf16x3 -- faster, but the scores then sit AT the 1e-4 bar on 512-user batches")
     ap.add_argument("--precision", default="fp16", choices=["fp32", "bf16x3", "bf16", "fp16"],
                     help="fp16 (default): fused one-wave-per-title kernels, scores inside 1e-4 of the oracle at 512 users "
-                         "(the measured maximum is in the JSON line); bf16x3: split-bf16 projections (2e-6); fp32 = exact f32 MFMA; "
+                         "(the --full JSON line has the measured maximum); bf16x3: split-bf16 projections (2e-6); fp32 = exact f32 MFMA; "
                          "bf16 misses the bar (3e-4)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write what its last step computed (loss sum, click scores, updated "
                          "parameters; a fixed sample of the embedding table) as DIR/<name>.npy (rank 0)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     # the dropout seeds derive from torch.initial_seed(), which torch otherwise draws afresh per process: fixed here so that
     # the same arguments give the same inputs, dropout masks included, from run to run
     torch.manual_seed(0)
 
-    # N > 1: have RCCL write its topology / algorithm choices (rings, trees, channels, transports) to a per-rank file so
-    # the first multi-GPU record says what it ran on (parsed into data_parallel.rccl_info below)
+    # N > 1 with --full: have RCCL write its topology / algorithm choices (rings, trees, channels, transports) to a per-rank
+    # file so the multi-GPU record says what it ran on (parsed into data_parallel.rccl_info below)
     nccl_log = None
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and "NCCL_DEBUG" not in os.environ:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) > 1 and "NCCL_DEBUG" not in os.environ:
         nccl_log = "/tmp/nrms_rccl_%s_rank%s.log" % (os.environ.get("MASTER_PORT", "0"), os.environ.get("RANK", "0"))
         os.environ["NCCL_DEBUG"] = "INFO"
         os.environ["NCCL_DEBUG_SUBSYS"] = "INIT,GRAPH,ENV,TUNING"
@@ -546,7 +654,7 @@ def main():
         counter[0] += 1
         return model.train_step(b, world_size=world, all_reduce=reduce)
 
-    # ---- score parity of the timed mode, measured here (outside every timed region): the training forward of the timed
+    # ---- --full: score parity of the timed mode, measured here (outside every timed region): the training forward of the timed
     # precision against the library's exact fp32 mode (itself pinned to the oracle at this size by
     # tests/test_hip_fullsize.py::test_every_mode_against_the_oracle_at_full_size) on timed batch 0, dropout off, initial weights
     def score_gap():
@@ -565,23 +673,25 @@ def main():
             cfg.dropout, cfg.precision = p_keep, prec_keep
             model.engine        # re-applies config.precision
 
-    parity_init = score_gap() if rank == 0 else None
+    parity_init = score_gap() if rank == 0 and args.full else None
 
     log("model ready on %s (rank %d/%d), %d users/GPU, precision %s" % (dev, rank, world, B, args.precision))
-    # ---- the instrumented pass FIRST: K steps with the per-kernel HIP-event timers on (two events created and recorded
-    # around each launch slow a step by a few %, so they are NOT on during the timed region) and the helper streams off (a
-    # kernel's duration under the timed region's overlap is not its own); `kernels` / `roofline` come from this pass, on every
-    # rank so collectives stay aligned.  It runs before the W warm-up steps and the timed region, not after them: a process
-    # that has stepped for only W = 5 steps is still 2.5 ... 3.5 % below its steady state (clocks, caches; same box: 150.4 ...
-    # 152.5 k users/s after 5 steps, 155.8 ... 156.0 k after 30 or 50), and sustained training is what `value` stands for.
+    # ---- the instrumented pass FIRST: K steps with the helper streams off (a kernel's duration under the timed region's
+    # overlap is not its own) and, with --full, the per-kernel HIP-event timers on (two events created and recorded around
+    # each launch slow a step by a few %, so they are NOT on during the timed region); `kernels` / `roofline` come from this
+    # pass, on every rank so collectives stay aligned.  It runs before the W warm-up steps and the timed region, not after
+    # them, and in a plain run too: a process that has stepped for only W = 5 steps is still 2.5 ... 3.5 % below its steady
+    # state (clocks, caches; same box: 150.4 ... 152.5 k users/s after 5 steps, 155.8 ... 156.0 k after 30 or 50), sustained
+    # training is what `value` stands for, and these steps are part of the training that the dumped outputs record.
     step()
     torch.cuda.synchronize()
     log("first step done")
     os.environ["NRMS_NO_SIDE_STREAMS"] = "1"
     for _ in range(args.steps):            # K settling steps in the same configuration, not recorded (the kernels' durations
         step()                             # are also 5 % longer in a process that has only just started stepping)
-    eng.timing_reset()
-    eng.timing(True)
+    if args.full:
+        eng.timing_reset()
+        eng.timing(True)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     for _ in range(args.steps):
@@ -591,7 +701,8 @@ def main():
     dt_instr = time.perf_counter() - t1
     eng.timing(False)
     os.environ.pop("NRMS_NO_SIDE_STREAMS", None)
-    log("instrumented pass: %d settling + %d recorded steps, the recorded ones in %.3f s" % (args.steps, args.steps, dt_instr))
+    log("instrumented pass: %d settling + %d %s steps, the latter in %.3f s" % (
+        args.steps, args.steps, "recorded" if args.full else "unrecorded", dt_instr))
     for i in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -611,11 +722,11 @@ def main():
     log("timed region: %d steps in %.3f s" % (args.steps, dt))
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, model, loss_sum)      # before any later step changes the model
-    eng.check_ids()
+    eng.check_ids()             # the timed steps' word ids were all inside the vocabulary (one event wait)
 
-    # ---- data-parallel facts (every rank takes part; rank 0 reports)
+    # ---- --full: data-parallel facts (every rank takes part; rank 0 reports)
     dp = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         ref = model._flat.clone()
         dist.broadcast(ref, src=0)
@@ -687,65 +798,6 @@ def main():
         compact = bool(eng.pad_row_zero)
         titles = np.concatenate([b[k].reshape(-1, shape.n_words_title) for b in batches_np for k in ("browsed_titles", "candidate_titles")])
         allpad_frac = 1.0 - float((titles != 0).any(axis=1).mean())
-        fp16_news = args.precision == "fp16"
-        work = kernel_work(shape, B, live_frac, compact, allpad_frac, fp16_news, bool(args.fp16_user_encoder))
-        # which arithmetic each timer's kernels run in (fp16 mode: the user encoder's kernels are bf16x3)
-        kprec = {k: args.precision for k in work}
-        if fp16_news and not args.fp16_user_encoder:
-            for k in ("user64_fwd", "user64_bwd", "qkv_proj_fwd", "addattn_fwd", "dctx_bwd", "attn_fwd", "attn_bwd", "addattn_bwd_rows"):
-                kprec[k] = "bf16x3"
-        kernels = {}
-        for name, (bound, fl, by) in work.items():
-            ms, n = eng.timing_read(name)
-            if n == 0:
-                continue
-            sec = ms / args.steps * 1e-3
-            kernels[name] = {"ms_per_step": ms / args.steps, "launches_per_step": n / args.steps, "bound": bound,
-                             "tflops": fl / sec / 1e12, "gbps": by / sec / 1e9}
-            if bound == "mfma":
-                kernels[name]["frac_of_mfma_peak"] = fl / sec / 1e12 / PEAKS[kprec[name]]
-            else:
-                kernels[name]["frac_of_hbm_peak"] = by / sec / 1e9 / PEAK_HBM_GBPS
-        for name in OTHER_TIMERS:
-            ms, n = eng.timing_read(name)
-            if n:
-                kernels[name] = {"ms_per_step": ms / args.steps, "launches_per_step": n / args.steps}
-        dom = max((k for k in kernels if "bound" in kernels[k]), key=lambda k: kernels[k]["ms_per_step"])
-        dom_ms, dom_n = eng.timing_read(dom)
-        bound, fl, by = work[dom]
-        peak = PEAKS[kprec[dom]] if bound == "mfma" else PEAK_HBM_GBPS
-        achieved = (fl / 1e12 if bound == "mfma" else by / 1e9) / (dom_ms / args.steps * 1e-3)
-        # measured HBM bytes per step of that kernel and of the whole step: rocprofv3 PMC FETCH_SIZE x 2 + WRITE_SIZE in separate
-        # passes (tools/hbm_traffic.py).  A committed profile is used only if it was measured on EXACTLY this kernel source
-        # (hash of csrc/ + include/); otherwise the two passes run now, as child processes, on the code that was just timed.
-        traffic, step_traffic, traffic_src = None, None, "unavailable"
-        if B == 512 and world == 1:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import hbm_traffic
-            sha = hbm_traffic.csrc_sha16()
-            tfile = os.path.join(ROOT, "profiles", "r04_%s_hbm_traffic.json" % args.precision)
-            prof = None
-            if os.path.exists(tfile) and not args.fp16_user_encoder:
-                try:
-                    cand = json.load(open(tfile))
-                    if cand.get("csrc_sha16") == sha:
-                        prof, traffic_src = cand, "profiles/%s (same kernel source: csrc sha %s)" % (os.path.basename(tfile), sha)
-                    else:
-                        traffic_src = "profiles/%s is stale (csrc sha %s != %s)" % (os.path.basename(tfile), cand.get("csrc_sha16"), sha)
-                except Exception as e:
-                    traffic_src = "unreadable profile: %r" % (e,)
-            if prof is None and not args.no_live_traffic:
-                try:
-                    log("measuring HBM traffic live (two rocprofv3 --pmc passes as child processes)")
-                    torch.cuda.synchronize()
-                    prof = hbm_traffic.collect(os.path.join("/tmp", "nrms_traffic_%d" % os.getpid()), steps=3, precision=args.precision,
-                                               extra=["--fp16-user-encoder"] if args.fp16_user_encoder else [])
-                    traffic_src = "measured in this run (tools/hbm_traffic.py, 3 steps per pass)"
-                except Exception as e:
-                    traffic_src += "; live measurement failed: %r" % (e,)
-            if prof is not None:
-                traffic = prof["by_timer"].get(dom, {}).get("hbm_bytes_per_step")
-                step_traffic = prof.get("step_bytes")
         total_users = B * world * args.steps
         users_per_s = total_users / dt
         per_gpu = users_per_s / world
@@ -754,8 +806,8 @@ def main():
             "value": users_per_s, "unit": "users/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "warmup_effective": 1 + 2 * args.steps + args.warmup,
             "warmup_note": "steps this process had run when the timed region started: 1 first step + K settling + K instrumented "
-                           "(per-kernel timers, helper streams off) + W warm-up; steady state is what `value` reports -- a process "
-                           "that has stepped only W = 5 times reads 2.5 ... 3.5 % lower (DESIGN 6)",
+                           "(helper streams off; per-kernel timers with --full) + W warm-up; steady state is what `value` reports -- a "
+                           "process that has stepped only W = 5 times reads 2.5 ... 3.5 % lower (DESIGN 6)",
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": DTYPES[args.precision], "data": "synthetic",
             "config": {"workload": "configs[1] shapes: NRMS(nrms_v0) train step, %d users/GPU, hist=50, "
@@ -767,45 +819,20 @@ def main():
                                                   "embedding row 0 is zero" if compact else
                                                   "dX + embedding scatter (dead values)"),
                        "parallelism": "dp%d" % world, "precision": args.precision,
-                       "resident_batches": N_BATCHES,
-                       "score_parity_vs_reference": (
-                           "max |score - exact fp32 mode| = %.2e over the valid scores of timed batch 0 (max |score| %.3f), training "
-                           "forward, dropout off, initial weights, measured in this run; the fp32 mode is pinned to the oracle at this "
-                           "size to 1e-5 and this mode to 1e-4 by tests/test_hip_fullsize.py" % parity_init),
-                       "score_parity_max_abs": parity_init[0]},
+                       "resident_batches": N_BATCHES},
             "loss": loss,
-            "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": peak,
-                         "unit": "TFLOP/s" if bound == "mfma" else "GB/s", "frac": achieved / peak, "traffic": traffic,
-                         "traffic_note": "HBM bytes per step of that kernel, rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE (separate passes); "
-                                         "source: " + traffic_src,
-                         "step_traffic": step_traffic,
-                         "step_traffic_note": "HBM bytes of ALL kernels of one train step, same measurement; algorithmic: 4.87 MB/user x %d = "
-                                              "%.2f GB (SURVEY 8d)" % (B, 4.87e6 * B / 1e9),
-                         "peak_note": ("HBM3E spec 8 TB/s (6.3 TB/s measured achievable)" if bound == "hbm" else
-                                       {"fp32": "f32-input MFMA dense peak", "bf16": "bf16 MFMA dense peak", "fp16": "fp16 MFMA dense peak",
-                                        "bf16x3": "bf16 dense peak / 3 (3 bf16 MFMAs per fp32-equivalent step by construction)"}[kprec[dom]]),
-                         "avg_launch_ms": dom_ms / max(dom_n, 1),
-                         "timing_note": "kernel durations: HIP events on the launch stream, recorded in a separate pass of the "
-                                        "same %d steps (after as many unrecorded settling steps) before the warm-up and the (un-instrumented) timed region, with the helper streams off "
-                                        "(NRMS_NO_SIDE_STREAMS) so that no two kernels share the GPU; that pass ran at "
-                                        "%.2f ms/step" % (args.steps, dt_instr / args.steps * 1e3),
-                         "algorithmic_per_step": by if bound == "hbm" else fl,
-                         # the WHOLE step by BASELINE.md section 2: users/s x 3.558309e9 flop / peak (per GPU)
-                         "step_frac": per_gpu * FLOP_PER_USER_TRAIN / (PEAK_16_MFMA_TFLOPS * 1e12),
-                         "step_frac_note": "users/s per GPU x 3 558 309 000 flop (reference algorithm, padding included) / 2.5e15 "
-                                           "(dense fp16/bf16 MFMA peak, undivided)",
-                         "step_tflops_equiv": per_gpu * FLOP_PER_USER_TRAIN / 1e12},
-            "kernels": kernels,
         }
-        mf = [k for k in kernels if kernels[k].get("bound") == "mfma"]
-        if mf:
-            k = max(mf, key=lambda kk: kernels[kk]["ms_per_step"])
-            out["top_mfma_kernel"] = {"kernel": k, "tflops": kernels[k]["tflops"], "peak": PEAKS[kprec[k]],
-                                      "frac": kernels[k]["tflops"] / PEAKS[kprec[k]]}
+        if args.full:
+            out["config"]["score_parity_vs_reference"] = (
+                "max |score - exact fp32 mode| = %.2e over the valid scores of timed batch 0 (max |score| %.3f), training "
+                "forward, dropout off, initial weights, measured in this run; the fp32 mode is pinned to the oracle at this "
+                "size to 1e-5 and this mode to 1e-4 by tests/test_hip_fullsize.py" % parity_init)
+            out["config"]["score_parity_max_abs"] = parity_init[0]
+            out.update(kernel_report(eng, args, shape, world, live_frac, compact, allpad_frac, dt_instr, per_gpu))
         if dp is not None:
             out["data_parallel"] = dp
-    # secondary (N = 1, outside the timed region of `value`): the other modes on the same batch
-    if world == 1 and not args.no_cpu_baseline and rank == 0:
+    # --full, secondary (N = 1, outside the timed region of `value`): the other modes on the same batch
+    if world == 1 and args.full and not args.no_cpu_baseline and rank == 0:
         modes = {}
         n = max(3, args.steps // 2)
         log("secondary legs: modes")
@@ -853,7 +880,7 @@ def main():
             out["eval_path"] = {"error": repr(e)}
     # the CPU baseline LAST: its OpenMP worker threads keep spinning for a while after each parallel region, which starves the
     # host thread that launches the GPU legs above (the ~50-launch bf16x3 step measured 58 k instead of 72 k users/s behind it)
-    if world == 1 and not args.no_cpu_baseline and rank == 0:
+    if world == 1 and args.full and not args.no_cpu_baseline and rank == 0:
         torch.cuda.synchronize()
         log("cpu baseline")
         out["cpu_baseline"] = cpu_baseline(shape, budget_s=args.cpu_budget_s)

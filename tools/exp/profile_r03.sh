@@ -13,7 +13,7 @@ rm -rf "$OUT"; mkdir -p "$SUM"
 step() { echo "[profile] $1" >&2; shift; "$@"; rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "[profile] timed out / killed (rc=$rc): stopping" >&2; exit $rc; fi; return 0; }
 export TMPDIR=/tmp
 cd /tmp
-step "kernel stats" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" \
+step "kernel stats" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --full \
     --no-cpu-baseline --no-live-traffic > "$OUT/bench_under_profiler.json" 2> "$OUT/stats.err"
 cd "$ROOT"
 cp $(find "$OUT/stats" -name "*kernel_stats.csv" | head -1) "$SUM/r03_fp16_kernel_stats.csv" 2>/dev/null
@@ -29,9 +29,9 @@ step "v1 kernel stats" timeout -k 10 300 rocprofv3 --kernel-trace --stats --outp
 cd "$ROOT"
 cp $(find "$OUT/stats_v1" -name "*kernel_stats.csv" | head -1) "$SUM/r03_v1_fp16_kernel_stats.csv" 2>/dev/null
 step "v1 step" timeout -k 10 300 python3 tools/bench_v1.py fp16 > "$SUM/r03_v1_step_kernels.txt" 2> "$OUT/v1_step.err"
-step "bench" timeout -k 10 500 python3 bench.py --no-live-traffic > "$SUM/r03_bench_fp16.json" 2> "$OUT/bench.err"
+step "bench" timeout -k 10 500 python3 bench.py --full --no-live-traffic > "$SUM/r03_bench_fp16.json" 2> "$OUT/bench.err"
 step "bench 2 ranks (gloo, one GPU)" env NRMS_DIST_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 > "$SUM/r03_bench_2rank_gloo.json" 2> "$OUT/bench2.err"
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 > "$SUM/r03_bench_2rank_gloo.json" 2> "$OUT/bench2.err"
 step "bench 2 ranks sharded (gloo, one GPU)" env NRMS_DIST_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 2 --steps 5 --warmup 2 --grad-sync sharded > "$SUM/r03_bench_2rank_gloo_sharded.json" 2> "$OUT/bench2s.err"
+    --master-addr 127.0.0.1 --master-port 29518 bench.py --full --gpus 2 --steps 5 --warmup 2 --grad-sync sharded > "$SUM/r03_bench_2rank_gloo_sharded.json" 2> "$OUT/bench2s.err"
 ls -la "$SUM" >&2

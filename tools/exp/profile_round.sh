@@ -12,7 +12,7 @@ ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 echo "[profile] kernel stats" >&2
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --full \
     --precision $PREC --no-cpu-baseline > "$OUT/bench_under_profiler.json" 2> "$OUT/stats.err"
 for C in FETCH_SIZE WRITE_SIZE; do
   echo "[profile] pmc $C" >&2
