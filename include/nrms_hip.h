@@ -499,6 +499,44 @@ int nrms_hier_score_bwd(int32_t B, int32_t C, int32_t d, const float* cand, cons
 int nrms_dropout_keep_mask(uint64_t seed, int32_t site, int64_t n_rows, int32_t d, float p_drop,
                            uint8_t* keep, void* stream);
 
+/* nrms_bert's news-vector layer (BertNewsEncoder, model/nrms.py:216-256): slot s of a batch (B*H history slots, then B*C
+ * candidate slots) holds news id ids[s]; its vector is dropout(table[ids[s]] W^T + b), table [n_rows, d] the fine-tuned
+ * pretrained vectors (no padding row: id 0 is an ordinary row), W [d, d], b [d] (news_dense.0).  Dropout site 4 over the
+ * [n_slots, d] output (nrms_dropout_keep_mask(seed, NRMS_DROPOUT_SITE_NEWSVEC, n_slots, d, p_drop) replays it). */
+#define NRMS_DROPOUT_SITE_NEWSVEC 4
+typedef struct nrms_newsvec_desc {
+    int64_t  n_slots;      /* B * (H + C) */
+    int32_t  n_rows;       /* rows of the table (news ids 0 .. n_rows - 1) */
+    int32_t  d;            /* width E, a multiple of 4, <= 1024 */
+    int32_t  precision;    /* NRMS_PRECISION_FP32, _BF16X3 or _BF16 (the dense products) */
+    float    p_drop;       /* dropout on the slot vectors (model/nrms.py:254); 0 in eval */
+    uint64_t seed;         /* counter-based RNG key of the step */
+} nrms_newsvec_desc;
+/* `saved`: caller-owned bytes the forward writes and the backward of the same batch reads (the distinct ids, ascending, and
+ * the slot -> id-group maps); `workspace`: scratch of either direction.  Both 256-byte aligned. */
+size_t nrms_newsvec_saved_bytes(const nrms_newsvec_desc* desc);
+size_t nrms_newsvec_workspace_bytes(const nrms_newsvec_desc* desc);
+/* Forward.  Ids outside [0, n_rows) are read as 0 and counted into *n_bad (device int32; may be NULL), as nrms_sanitize_ids
+ * does.  The batch's distinct ids are grouped on the device (stable sort), each goes through the dense layer once, the slots
+ * then receive their group's row through the dropout.  No host synchronisation.  out: [n_slots, d]. */
+int nrms_newsvec_fwd(const nrms_newsvec_desc* desc, const int64_t* ids, const float* table, const float* w, const float* b,
+                     float* out, void* saved, size_t saved_bytes, int32_t* n_bad, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* Backward of the forward that filled `saved`: the slot gradients dout [n_slots, d] are undone through the dropout and summed
+ * per distinct id in slot order (no atomics; bit-reproducible); d_w, d_b are ACCUMULATED from the distinct rows; the rows of
+ * d_table [n_rows, d] of the batch's distinct ids are OVERWRITTEN with their gradient (plain stores), every other row is left
+ * as it is (the caller zeroes the buffer: rows outside the batch have gradient 0). */
+int nrms_newsvec_bwd(const nrms_newsvec_desc* desc, const float* table, const float* w, const float* dout, const void* saved,
+                     size_t saved_bytes, float* d_table, float* d_w, float* d_b, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* Device copies of what a forward left in `saved`: *n_unique (int32) and, if ids is not NULL, the distinct ids in ascending
+ * order (ids [n_slots] int32, the first *n_unique valid). */
+int nrms_newsvec_distinct(const nrms_newsvec_desc* desc, const void* saved, int32_t* n_unique, int32_t* ids, void* stream);
+/* Every row of the table through the dense layer, no dropout (catalogue retrieval, evaluation): out [n_rows, d]. */
+size_t nrms_newsvec_rows_workspace_bytes(int64_t n_rows, int32_t d, int32_t precision);
+int nrms_newsvec_rows_fwd(int64_t n_rows, int32_t d, int32_t precision, const float* table, const float* w, const float* b,
+                          float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * nrms_timing_read synchronises the recorded events; returns 0 and the accumulated
  * milliseconds / launch count of kernels whose name starts with `prefix`. */

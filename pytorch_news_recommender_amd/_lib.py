@@ -20,6 +20,7 @@ NRMS_PRECISION_BF16X3 = 1
 NRMS_PRECISION_BF16 = 2
 NRMS_PRECISION_FP16 = 3
 NRMS_DROPOUT_FIELDS16 = 0x100
+NRMS_DROPOUT_SITE_NEWSVEC = 4
 NRMS_FP16_KP, NRMS_FP16_DP, NRMS_FP16_QP = 320, 320, 224     # fixed activation pitches of the fp16 mode (include/nrms_hip.h)
 PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2, "fp16": 3}
 
@@ -63,6 +64,11 @@ class NewsFeatures(C.Structure):
     _fields_ = [("n", C.c_int64), ("d_text", C.c_int32), ("d_cat", C.c_int32), ("n_cat", C.c_int32), ("n_sub", C.c_int32),
                 ("p_drop", C.c_float), ("seed", C.c_uint64), ("title_vec", C.c_void_p), ("abst_vec", C.c_void_p),
                 ("cat_table", C.c_void_p), ("sub_table", C.c_void_p), ("categ", C.c_void_p), ("subcateg", C.c_void_p)]
+
+
+class NewsvecDesc(C.Structure):
+    _fields_ = [("n_slots", C.c_int64), ("n_rows", C.c_int32), ("d", C.c_int32), ("precision", C.c_int32),
+                ("p_drop", C.c_float), ("seed", C.c_uint64)]
 
 
 # name -> (restype, argtypes).  Every symbol include/nrms_hip.h declares.
@@ -136,6 +142,15 @@ SIGNATURES = {
     "nrms_news_features_fwd": (C.c_int, [C.POINTER(NewsFeatures), C.c_void_p, C.c_void_p]),
     "nrms_news_features_bwd": (C.c_int, [C.POINTER(NewsFeatures), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "nrms_newsvec_saved_bytes": (C.c_size_t, [C.POINTER(NewsvecDesc)]),
+    "nrms_newsvec_workspace_bytes": (C.c_size_t, [C.POINTER(NewsvecDesc)]),
+    "nrms_newsvec_fwd": (C.c_int, [C.POINTER(NewsvecDesc)] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                                                C.c_void_p]),
+    "nrms_newsvec_bwd": (C.c_int, [C.POINTER(NewsvecDesc)] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 4
+                         + [C.c_size_t, C.c_void_p]),
+    "nrms_newsvec_distinct": (C.c_int, [C.POINTER(NewsvecDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrms_newsvec_rows_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "nrms_newsvec_rows_fwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "nrms_timing_enable": (None, [C.c_int]),
     "nrms_timing_reset": (None, []),
     "nrms_timing_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -16,6 +16,7 @@ class Config(object):
         self.small_dev_path = dataset + '/small_dev/'
 
         self.word_embedding_pretrained = 'all_word_embedding_v3.npz'
+        self.bert_embedding_pretrained = 'news_embeds_512.npz'    # nrms_bert: pretrained vector per news id (config.py:18)
         self.mode = 'large'                      # 'large' / 'demo' / 'synthetic'
 
         self.save_path = './save_model/'
@@ -72,7 +73,8 @@ class Config(object):
 
     def __nrms__(self):
         self.news_feature_size = 800             # nrms_naml: 2 * word_embed_size + 2 * cate_embed_size (config.py:68)
-        self.query_vector_dim_large = 400        # nrms_naml user encoder (config.py:72)
+        self.bert_embed_size = 512               # nrms_bert: width of the news-vector table (config.py:69)
+        self.query_vector_dim_large = 400        # nrms_naml / nrms_bert user encoder (config.py:72)
         self.query_vector_dim = 200
         self.title_heads_num = 6
         self.num_attention_heads = 10

@@ -232,6 +232,16 @@ class SyntheticMind:
         t[0] = 0
         return t
 
+    def news_vectors(self, E, seed=0, noise=1.0):
+        """Pretrained-style news vectors for nrms_bert: [n_news + 1, E] float32, row r = news id r (ids are 1-based; row 0,
+        the padding slot's id, is noise only).  A news item's row is its topic's centroid (N(0, 1) per component) plus noise
+        (N(0, noise^2)), so that ids of one topic are correlated and synthetic training can learn."""
+        rng = np.random.default_rng(seed + 7919)
+        centroids = rng.normal(0.0, 1.0, size=(self.n_topics, E))
+        out = rng.normal(0.0, noise, size=(self.n_news + 1, E))
+        out[1:] += centroids[self.topic]
+        return out.astype(np.float32)
+
     def _pick(self, topic, n, p_in=0.8):
         out = []
         for _ in range(n):

@@ -199,7 +199,7 @@ class Model(FlatHipModel):
         if self._bad_browsed is None or self._bad_browsed.device != dev:
             self._bad_browsed = torch.zeros((), dtype=torch.int64, device=dev)
         self._bad_browsed += bad.sum()
-        user = self._catalogue_users(cat.index_select(0, browsed.view(-1)).view(B, H, d))
+        user = self._catalogue_users(cat.index_select(0, browsed.view(-1)).view(B, H, d), browsed)
         # the kernel runs on rows 1.. (the padding title is never a candidate); history ids shift with them, which sends
         # the padding slots (id 0) out of range, where the kernel ignores them
         exclude = browsed - 1 if exclude_history else None
@@ -209,8 +209,8 @@ class Model(FlatHipModel):
     def _catalogue_width(self):
         return self._dims.word_embed_size
 
-    def _catalogue_users(self, hist):
-        """Catalogue rows of the history [B, H, width] -> user vectors [B, width]."""
+    def _catalogue_users(self, hist, browsed=None):
+        """Catalogue rows of the history [B, H, width] (browsed: their ids, 0 = padding slot) -> user vectors [B, width]."""
         return self._engine.encode_users(self._flat, hist, tag="user_eval")
 
     _bad_browsed = None

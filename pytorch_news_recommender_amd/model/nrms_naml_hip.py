@@ -145,7 +145,7 @@ class Model(nrms_hip.Model):
     def _catalogue_width(self):
         return self._dims.news_feature_size
 
-    def _catalogue_users(self, hist):
+    def _catalogue_users(self, hist, browsed=None):
         B, H, F = hist.shape
         normed = self._engine.layernorm(self._flat, hist.reshape(B * H, F))
         return self._engine.encode_users(self._flat, normed.view(B, H, F), 0.0, 0, "user_eval")

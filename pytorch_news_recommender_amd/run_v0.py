@@ -3,6 +3,8 @@
     python -m pytorch_news_recommender_amd.run_v0 --model nrms_hip --dataset synthetic
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m pytorch_news_recommender_amd.run_v0 ...
 
+``--model nrms_bert`` (the reference's ``model/nrms.py``, NRMS over pretrained per-news vectors) also reads
+config.data_path + config.bert_embedding_pretrained; ``--dataset synthetic`` writes topic-correlated vectors there.
 ``--dataset large|demo`` reads what the reference's preprocessing leaves under config.data_path
 (idx_train_datas.pkl / idx_dev_datas.pkl, news_title.pkl or news_words.csv, dev_behaviors.csv:
 data_handler.py:43-135, train_eval.py:36-39); ``--dataset synthetic`` fabricates a MIND-shaped corpus (no
@@ -92,6 +94,11 @@ def main(argv=None):
         emb = os.path.join(config.data_path, config.word_embedding_pretrained)
         if rank == 0 and not os.path.exists(emb):
             np.savez(emb, embeddings=corpus.embedding_table(config.word_embed_size))
+        if args.model.lower() == 'nrms_bert':
+            # nrms_bert reads one pretrained vector per news id (row r = news id r) from the file beside the word table
+            vec = os.path.join(config.data_path, config.bert_embedding_pretrained)
+            if rank == 0 and not os.path.exists(vec):
+                np.savez(vec, embeddings=corpus.news_vectors(config.bert_embed_size))
         parallel.barrier()
         titles, absts = corpus.id2title_dict, corpus.id2abst_dict
         train_samples = corpus.train_samples(args.synthetic_users)

@@ -418,3 +418,85 @@ def make_batch_graph(shape: Shape, n_neighbors: int = 8, seed: int = 1, batch_si
         nbr[3, :] = [5 % N, -1] + [7 % N] * (n_neighbors - 2)
     b["neighbor_rows"] = nbr
     return b
+
+
+# ---- nrms_bert: NRMS over pretrained per-news vectors (model/nrms_bert_hip.py; /root/reference/MIND_2020/model/nrms.py) ---------
+@dataclass(frozen=True)
+class BertShape:
+    """Names follow config.py:69,72,77 (bert_embed_size, query_vector_dim_large, user_heads_num)."""
+    n_news: int = 130000          # rows of the news-vector table (row r = news id r)
+    bert_embed_size: int = 512    # E
+    user_heads_num: int = 8
+    query_vector_dim_large: int = 400
+    batch_size: int = 512
+    history_len: int = 50
+    n_candidates: int = 5
+
+
+G9_SMALL = BertShape(n_news=23, bert_embed_size=64, user_heads_num=8, query_vector_dim_large=16, batch_size=3, history_len=7,
+                     n_candidates=4)
+G9_E512 = BertShape(n_news=300, bert_embed_size=512, batch_size=2)
+G9_E1024 = BertShape(n_news=300, bert_embed_size=1024, batch_size=2)
+
+
+def bert_param_shapes(s: BertShape):
+    """The 14 tensors of nrms.Model.state_dict(), in registration order (nrms.py:219-229,261-265,64-66,90-96)."""
+    E, Q = s.bert_embed_size, s.query_vector_dim_large
+    out = {"news_encoder.news_embedding.weight": (s.n_news, E),
+           "news_encoder.news_dense.0.weight": (E, E), "news_encoder.news_dense.0.bias": (E,)}
+    a = "user_encoder.multi_head_self_attention."
+    for i in range(3):
+        out[a + "linear_layers.%d.weight" % i] = (E, E)
+        out[a + "linear_layers.%d.bias" % i] = (E,)
+    out[a + "output_linear.weight"] = (E, E)
+    out[a + "output_linear.bias"] = (E,)
+    out["user_encoder.additive_attention.query_vector"] = (Q,)     # a module's own parameters precede its children's
+    out["user_encoder.additive_attention.linear.weight"] = (Q, E)
+    out["user_encoder.additive_attention.linear.bias"] = (Q,)
+    return out
+
+
+def make_params_bert(s: BertShape, seed: int = 0):
+    """torch's initial distributions (Linear: U(+-1/sqrt fan_in)); the news table N(0, 0.4) with an ordinary row 0 (the
+    reference's news_embedding has no padding_idx); query vector U(-0.1, 0.1) (nrms.py:96)."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for name, shp in bert_param_shapes(s).items():
+        if name.endswith("news_embedding.weight"):
+            t = rng.normal(0.0, 0.4, size=shp)
+        elif name.endswith("query_vector"):
+            t = rng.uniform(-0.1, 0.1, size=shp)
+        elif name.endswith(".weight"):
+            bound = 1.0 / np.sqrt(shp[1])
+            t = rng.uniform(-bound, bound, size=shp)
+        else:
+            t = rng.uniform(-1.0, 1.0, size=shp) / np.sqrt(s.bert_embed_size)
+        out[name] = np.ascontiguousarray(t, dtype=np.float32)
+    return out
+
+
+def make_batch_bert(s: BertShape, seed: int = 1, batch_size: int | None = None, edge_cases: bool = True):
+    """The batch-dict keys nrms.Model.forward reads (nrms.py:317-346): ``browsed_ids`` [B, H] / ``candidate_ids`` [B, C] int64
+    (0 = padding slot), ``browsed_mask`` [B, H] and ``candidate_mask`` [B, C] uint8, left-aligned histories (data_handler.py).
+    edge_cases: user 1 has an empty history, user 0 repeats a news item within its history and shares one with user 2's
+    candidates, candidate (0, C-1) is masked, ids 0 (as a candidate) and n_news - 1 are in use."""
+    B = s.batch_size if batch_size is None else batch_size
+    H, C, N = s.history_len, s.n_candidates, s.n_news
+    rng = np.random.default_rng(seed)
+    hist = rng.integers(1, N, size=(B, H), dtype=np.int64)
+    cand = rng.integers(1, N, size=(B, C), dtype=np.int64)
+    hist_len = rng.integers(1, H + 1, size=(B,))
+    cmask = np.ones((B, C), dtype=np.uint8)
+    if edge_cases and B > 2 and H > 2 and C > 1:
+        hist_len[0] = H
+        hist_len[1] = 0
+        hist[0, 1] = hist[0, 0]
+        hist[0, 2] = N - 1
+        cand[2, 0] = hist[0, 0]
+        cand[1, 1] = 0
+        cmask[0, C - 1] = 0
+    live = np.arange(H)[None, :] < hist_len[:, None]
+    hist = np.where(live, hist, 0)
+    c64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+    return {"browsed_ids": c64(hist), "candidate_ids": c64(cand), "browsed_mask": live.astype(np.uint8), "candidate_mask": cmask,
+            "browsed_lens": hist_len.astype(np.int64)}
