@@ -20,6 +20,16 @@ __device__ __forceinline__ h8 acc_frag(const f32x16& x, int s) {
     return r;
 }
 
+// One element of an all-padding title's context after the context dropout: the product rounded to fp32, THEN to fp16, as the
+// source of the live classes reads.  Left to the compiler, a multiply followed by a conversion becomes one v_fma_mixlo_f16 -- a
+// single rounding -- in some places and two instructions in others (whatever the contraction setting); the empty asm makes the
+// fp32 product a value of its own, so the stored bits do not depend on where the compiler saw the pair.
+__device__ __forceinline__ _Float16 closed_ctx16(float b_v, float scale) {
+    float p = b_v * scale;
+    __asm__ volatile("" : "+v"(p));
+    return (_Float16)p;
+}
+
 // padded feature index held by register r of lane-half hh (accumulator row), and the P16 memory position of it
 __device__ __forceinline__ int p16_pos(int fpad) {           // natural padded feature -> position inside its row
     const int b = fpad >> 4, t = fpad & 15;

@@ -346,6 +346,140 @@ __global__ __launch_bounds__(F16_THREADS, SB == 1 ? F16_FWD_WGS : 1) void fused_
     }
 }
 
+// The additive attention and the pooling of one title of fused_fwd16p_kernel, from its 20 context fragments cf (the lane's token,
+// zeros beyond the sequence): walks the ring's next seven steps (see fused_fwd16_kernel for the commentary).
+template <bool TRAIN, class Ring, class TileAt>
+__device__ __forceinline__ void fwd16p_additive_pool(const Fwd16Args& a, Ring& ring, int& n, int n_steps, TileAt tile_at, const float* addv,
+                                                     const h8 (&cf)[F16_CS], bool valid, bool tok, int sq, long t0, int l32, int hh) {
+    constexpr int AH = Ring::AHEAD;
+    constexpr float NEG = -3.0e38f;
+    const int S = a.S;
+    float score = 0.f;
+#pragma unroll 1
+    for (int t = 0; t < F16_QT; ++t) {
+        const f32x16 ba = rows_of(addv + 32 * t, hh), qq = rows_of(addv + F16_QP + 32 * t, hh);
+        __builtin_amdgcn_sched_barrier(0);
+        auto pre2 = [&](int g) { if (n + AH < n_steps) ring.load_piece_at(n + AH, tile_at(n + AH), g); };
+        if (!valid && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
+        f32x16 tt = zero16();
+        if (valid) tile_mma<true>(tt, ring, n, cf, pre2);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            h4 th;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float ex = __builtin_amdgcn_exp2f(fmaf(tt[4 * g + e], 2.885390082f, ba[4 * g + e]));
+                const float v = fmaf(-2.0f, __builtin_amdgcn_rcpf(ex + 1.0f), 1.0f);
+                score += qq[4 * g + e] * v;
+                th[e] = (_Float16)v;
+            }
+            if (TRAIN && valid) {
+                if (!tok) th = h4{0, 0, 0, 0};
+                *reinterpret_cast<h4*>(a.t16 + (((long)sq * (F16_QP / 16) + 2 * t + (g >> 1)) * 32 + l32) * 16 + 8 * (g & 1) + 4 * hh) = th;
+            }
+        }
+        ring.step_barrier(n);
+        ++n;
+    }
+    score += __shfl_xor(score, 32, 64);
+    score = l32 < S ? score : NEG;
+    float mx = score;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float wgt = l32 < S ? __expf(score - mx) : 0.f;
+    float es = wgt;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) es += __shfl_xor(es, o, 64);
+    wgt /= es;
+    if (TRAIN && a.w != nullptr && tok && hh == 0) a.w[t0 + l32] = wgt;
+    if (valid) {
+        h8 sel[2];
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sel[s2][j] = (_Float16)(l32 == 16 * s2 + 8 * hh + j ? 1.0f : 0.0f);
+        float wrow[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) wrow[r] = __shfl(wgt, crow32(r, hh), 64);
+#pragma unroll
+        for (int p = 0; p < F16_CS / 2; ++p) {
+            f32x16 dd = mfma32h(cf[2 * p], sel[0], zero16());
+            dd = mfma32h(cf[2 * p + 1], sel[1], dd);
+            float acc = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc += wrow[r] * dd[r];
+            acc += __shfl_xor(acc, 32, 64);
+            const int nn = l32, f = 16 * (nn >> 4) + 8 * ((nn & 7) >> 2) + 4 * ((nn >> 3) & 1) + (nn & 3);
+            if (hh == 0 && f < a.dk && p < a.h) a.out[(long)sq * a.d + p * a.dk + f] = acc;
+        }
+    }
+}
+
+// The all-padding class of fused_fwd16p_kernel (one wave per title, the whole workgroup of this class).  Such a title's context
+// is b_v in every row, so the 20 fragments of its context after the dropout come from b_v and the mask alone: they are built
+// once, in front of the additive stage, and stay in registers through it and the pooling -- the live classes store theirs head
+// by head, wait for the stores and load all twenty back.  The ctx16 block the backward reads is written LAST, from the same
+// registers, where nothing waits for it.  The head loop is unrolled (cf is indexed statically: a run-time index would put it
+// into scratch memory).
+template <bool TRAIN>
+__device__ __forceinline__ void fwd16p_closed(const Fwd16Args& a, char* smem, int first_slot, int n_e) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l32 = lane & 31, hh = lane >> 5;
+    constexpr int DP = F16_DP;
+    const int sl = first_slot + wave;
+    const bool valid = sl < n_e;
+    const int sq = valid ? a.order[(long)a.n_seq + sl] : 0;
+    const long t0 = (long)sq * a.S;
+    const bool tok = valid && l32 < a.S;
+
+    // tile steps: the 7 additive tiles
+    const int first_tile = 3 * a.h;
+    auto tile_at = [&](int step) { return first_tile + step; };
+    using Ring = TileRingDMA<F16_FWD_SLOTS>;
+    constexpr int AH = Ring::AHEAD;
+    Ring ring;
+    ring.smem = smem; ring.src = a.wtiles; ring.n_tiles = F16_QT; ring.wave = wave; ring.lane = lane; ring.l32 = l32; ring.hh = hh;
+#pragma unroll
+    for (int i = 0; i < AH; ++i) ring.load_at(i, tile_at(i));
+    float* addv = reinterpret_cast<float*>(smem + F16_FWD_SLOTS * F16_SLOT_DMA);          // [2][F16_QP]
+    for (int i = tid; i < 2 * F16_QP; i += F16_THREADS) addv[i] = i < F16_QP ? a.badd32[i] : a.qv32[i - F16_QP];
+
+    // the context fragments: the same values and Philox calls as the live classes' dropout + ctx16 store; heads the model does
+    // not have are zero columns
+    h8 cf[F16_CS];
+#pragma unroll
+    for (int head = 0; head < F16_CS / 2; ++head) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            h8 fr = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (head < a.h && tok) {
+                const float* bv = a.bqkv32 + (3 * head + 2) * 32 + 16 * c + 4 * hh;     // ctx = b_v: registers 8 c .. 8 c + 7 of rows_of
+                const f32x4 b0 = *reinterpret_cast<const f32x4*>(bv), b1 = *reinterpret_cast<const f32x4*>(bv + 8);
+                float sc[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sc[e] = 1.0f;
+                if (a.drop.thresh != 0u) {
+                    const uint64_t e0 = (uint64_t)(t0 + l32) * (uint64_t)DP + (uint64_t)(head * 32 + 16 * c + 8 * hh);
+                    dropout_scale8(a.drop.seed, 1u, e0 >> 3, a.drop.thresh16, a.drop.inv_keep, sc);
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) fr[e] = closed_ctx16(e < 4 ? b0[e & 3] : b1[e & 3], sc[e]);
+            }
+            cf[2 * head + c] = fr;
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);                             // vmcnt(0): the first tiles have landed (see fused_fwd16_kernel)
+    __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    int n = 0;
+    fwd16p_additive_pool<TRAIN>(a, ring, n, F16_QT, tile_at, addv, cf, valid, tok, sq, t0, l32, hh);
+    if (valid) {                                                    // (rows beyond the sequence and absent heads: zeros, as everywhere)
+        _Float16* dst = a.ctx16 + frag_off((long)sq, F16_CS, 0, l32, hh);
+#pragma unroll
+        for (int s = 0; s < F16_CS; ++s) *reinterpret_cast<h8*>(dst + 512 * s) = cf[s];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The news encoder's forward on the padding-skipping path (NRMS_FLAG_PAD_ROW_ZERO: pos / ids / a 3-class order list):
 // the same products as fused_fwd16_kernel<., 1>, with the 32-row tile of the ATTENTION stage used twice as well.
@@ -379,7 +513,11 @@ __global__ __launch_bounds__(F16_THREADS, F16_FWD_WGS) void fused_fwd16p_kernel(
     const int g_long = (n_long + F16_WAVES - 1) / F16_WAVES, g_e = (n_e + F16_WAVES - 1) / F16_WAVES;
     const int blk = blockIdx.x;
     if (blk >= g_pair + g_long + g_e) return;                       // surplus workgroup (the grid is an upper bound)
-    const bool pair = blk < g_pair, skip_heads = blk >= g_pair + g_long;      // uniform over the workgroup
+    if (blk >= g_pair + g_long) {                                   // uniform over the workgroup: four all-padding titles
+        fwd16p_closed<TRAIN>(a, smem, (blk - g_pair - g_long) * F16_WAVES, n_e);
+        return;
+    }
+    const bool pair = blk < g_pair;                                 // uniform over the workgroup
     const int NT = pair ? 2 : 1;                                    // titles per wave
     int seq[2] = {0, 0};
     bool val[2] = {false, false};
@@ -387,12 +525,9 @@ __global__ __launch_bounds__(F16_THREADS, F16_FWD_WGS) void fused_fwd16p_kernel(
         const int p0 = 2 * (blk * F16_WAVES + wave);
 #pragma unroll
         for (int i = 0; i < 2; ++i) { val[i] = p0 + i < n_short; seq[i] = val[i] ? a.order[2 * (long)a.n_seq + p0 + i] : 0; }
-    } else if (!skip_heads) {
+    } else {
         const int sl = (blk - g_pair) * F16_WAVES + wave;
         val[0] = sl < n_long; seq[0] = val[0] ? a.order[sl] : 0;
-    } else {
-        const int sl = (blk - g_pair - g_long) * F16_WAVES + wave;
-        val[0] = sl < n_e; seq[0] = val[0] ? a.order[(long)a.n_seq + sl] : 0;
     }
     long tok0[2];
     int nlive[2];                                                   // real tokens of a short title (a prefix by classification)
@@ -408,7 +543,7 @@ __global__ __launch_bounds__(F16_THREADS, F16_FWD_WGS) void fused_fwd16p_kernel(
     const int myn = myp ? nlive[1] : nlive[0];
     const bool myval = myp ? val[1] : val[0];
     long xrow = -1;                                                 // -1: a row of zeros (rows the tile does not use)
-    if (!skip_heads && myval) {
+    if (myval) {
         const long t0 = myp ? tok0[1] : tok0[0];
         if (pair) {
             if (myr < myn) xrow = a.pos[t0 + myr];                  // a real token (pos >= 0 by classification)
@@ -440,10 +575,9 @@ __global__ __launch_bounds__(F16_THREADS, F16_FWD_WGS) void fused_fwd16p_kernel(
 #pragma unroll
     for (int i = 0; i < 2; ++i) tok_ok[i] = val[i] && l32 < S;
 
-    // ---- tile steps: the 3 h head tiles (not for all-padding titles), then the 7 additive tiles once per title
-    const int n_head_steps = skip_heads ? 0 : n_head_tiles;
-    const int n_steps = n_head_steps + F16_QT * NT;
-    auto tile_at = [&](int step) { return step < n_head_steps ? step : n_head_tiles + (step - n_head_steps) % F16_QT; };
+    // ---- tile steps: the 3 h head tiles, then the 7 additive tiles once per title
+    const int n_steps = n_head_tiles + F16_QT * NT;
+    auto tile_at = [&](int step) { return step < n_head_tiles ? step : n_head_tiles + (step - n_head_tiles) % F16_QT; };
     using Ring = TileRingDMA<F16_FWD_SLOTS>;
     constexpr int AH = Ring::AHEAD;
     Ring ring;
@@ -473,41 +607,37 @@ __global__ __launch_bounds__(F16_THREADS, F16_FWD_WGS) void fused_fwd16p_kernel(
 #pragma unroll 1
     for (int head = 0; head < a.h; ++head) {
         f32x16 ct;                                                  // ctx^T[f][tile column] of this head
-        if (!skip_heads) {
-            f32x16 qt = zero16(), kt = zero16(), vv = zero16();
-            auto pre = [&](int g) { if (n + AH < n_steps) ring.load_piece_at(n + AH, tile_at(n + AH), g); };
-            if (!any_live && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
-            if (any_live) tile_mma<true>(qt, ring, n, xf, pre);
-            ring.step_barrier(n);
-            ++n;
-            if (!any_live && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
-            if (any_live) tile_mma<true>(kt, ring, n, xf, pre);
-            ring.step_barrier(n);
-            ++n;
-            if (!any_live && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
-            if (any_live) tile_mma<false>(vv, ring, n, xf, pre);
-            if (any_live) {
-                // S^T[j][i] (rows j = keys in registers, columns i = queries), masked / weighted by the additive bias
-                f32x16 st = mfma32h(acc_frag(kt, 0), acc_frag(qt, 0), zero16());
-                st = mfma32h(acc_frag(kt, 1), acc_frag(qt, 1), st);
-                float m = NEG;
+        f32x16 qt = zero16(), kt = zero16(), vv = zero16();
+        auto pre = [&](int g) { if (n + AH < n_steps) ring.load_piece_at(n + AH, tile_at(n + AH), g); };
+        if (!any_live && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
+        if (any_live) tile_mma<true>(qt, ring, n, xf, pre);
+        ring.step_barrier(n);
+        ++n;
+        if (!any_live && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
+        if (any_live) tile_mma<true>(kt, ring, n, xf, pre);
+        ring.step_barrier(n);
+        ++n;
+        if (!any_live && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
+        if (any_live) tile_mma<false>(vv, ring, n, xf, pre);
+        if (any_live) {
+            // S^T[j][i] (rows j = keys in registers, columns i = queries), masked / weighted by the additive bias
+            f32x16 st = mfma32h(acc_frag(kt, 0), acc_frag(qt, 0), zero16());
+            st = mfma32h(acc_frag(kt, 1), acc_frag(qt, 1), st);
+            float m = NEG;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { st[r] += kbias[r]; m = fmaxf(m, st[r]); }
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-                float sum = 0.f;
+            for (int r = 0; r < 16; ++r) { st[r] += kbias[r]; m = fmaxf(m, st[r]); }
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            float sum = 0.f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { st[r] = __expf(st[r] - m); sum += st[r]; }
-                sum += __shfl_xor(sum, 32, 64);
-                const float inv = 1.0f / sum;
+            for (int r = 0; r < 16; ++r) { st[r] = __expf(st[r] - m); sum += st[r]; }
+            sum += __shfl_xor(sum, 32, 64);
+            const float inv = 1.0f / sum;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) st[r] *= inv;
-                ct = mfma32h(acc_frag(vv, 0), acc_frag(st, 0), zero16());
-                ct = mfma32h(acc_frag(vv, 1), acc_frag(st, 1), ct);
-            } else {
-                ct = zero16();
-            }
+            for (int r = 0; r < 16; ++r) st[r] *= inv;
+            ct = mfma32h(acc_frag(vv, 0), acc_frag(st, 0), zero16());
+            ct = mfma32h(acc_frag(vv, 1), acc_frag(st, 1), ct);
         } else {
-            ct = rows_of(a.bqkv32 + (3 * head + 2) * 32, hh);       // all-padding title: ctx = b_v
+            ct = zero16();
         }
         // ---- per title: its L rows of the context, dropout, ctx16
 #pragma unroll
@@ -537,10 +667,8 @@ __global__ __launch_bounds__(F16_THREADS, F16_FWD_WGS) void fused_fwd16p_kernel(
                 }
             }
         }
-        if (!skip_heads) {
-            ring.step_barrier(n);
-            ++n;
-        }
+        ring.step_barrier(n);
+        ++n;
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -567,65 +695,7 @@ __global__ __launch_bounds__(F16_THREADS, F16_FWD_WGS) void fused_fwd16p_kernel(
 #pragma unroll
             for (int s = 0; s < F16_CS; ++s) cf[s] = *reinterpret_cast<const h8*>(src + 512 * s);
         }
-        float score = 0.f;
-#pragma unroll 1
-        for (int t = 0; t < F16_QT; ++t) {
-            const f32x16 ba = rows_of(addv + 32 * t, hh), qq = rows_of(addv + F16_QP + 32 * t, hh);
-            __builtin_amdgcn_sched_barrier(0);
-            auto pre2 = [&](int g) { if (n + AH < n_steps) ring.load_piece_at(n + AH, tile_at(n + AH), g); };
-            if (!valid && n + AH < n_steps) ring.load_at(n + AH, tile_at(n + AH));
-            f32x16 tt = zero16();
-            if (valid) tile_mma<true>(tt, ring, n, cf, pre2);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h4 th;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float ex = __builtin_amdgcn_exp2f(fmaf(tt[4 * g + e], 2.885390082f, ba[4 * g + e]));
-                    const float v = fmaf(-2.0f, __builtin_amdgcn_rcpf(ex + 1.0f), 1.0f);
-                    score += qq[4 * g + e] * v;
-                    th[e] = (_Float16)v;
-                }
-                if (TRAIN && valid) {
-                    if (!tok) th = h4{0, 0, 0, 0};
-                    *reinterpret_cast<h4*>(a.t16 + (((long)sq * (F16_QP / 16) + 2 * t + (g >> 1)) * 32 + l32) * 16 + 8 * (g & 1) + 4 * hh) = th;
-                }
-            }
-            ring.step_barrier(n);
-            ++n;
-        }
-        score += __shfl_xor(score, 32, 64);
-        score = l32 < S ? score : NEG;
-        float mx = score;
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        float wgt = l32 < S ? __expf(score - mx) : 0.f;
-        float es = wgt;
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) es += __shfl_xor(es, o, 64);
-        wgt /= es;
-        if (TRAIN && a.w != nullptr && tok && hh == 0) a.w[t0 + l32] = wgt;
-        if (valid) {
-            h8 sel[2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sel[s2][j] = (_Float16)(l32 == 16 * s2 + 8 * hh + j ? 1.0f : 0.0f);
-            float wrow[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) wrow[r] = __shfl(wgt, crow32(r, hh), 64);
-#pragma unroll
-            for (int p = 0; p < F16_CS / 2; ++p) {
-                f32x16 dd = mfma32h(cf[2 * p], sel[0], zero16());
-                dd = mfma32h(cf[2 * p + 1], sel[1], dd);
-                float acc = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc += wrow[r] * dd[r];
-                acc += __shfl_xor(acc, 32, 64);
-                const int nn = l32, f = 16 * (nn >> 4) + 8 * ((nn & 7) >> 2) + 4 * ((nn >> 3) & 1) + (nn & 3);
-                if (hh == 0 && f < a.dk && p < a.h) a.out[(long)sq * a.d + p * a.dk + f] = acc;
-            }
-        }
+        fwd16p_additive_pool<TRAIN>(a, ring, n, n_steps, tile_at, addv, cf, valid, tok, sq, t0, l32, hh);
     }
 }
 
