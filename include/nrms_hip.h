@@ -104,7 +104,10 @@ extern "C" {
  * vocab == 0 : user encoder -- input is `x` [n_seq, seq_len, d_model]
  *              (UserEncoder.forward, model/nrms_v0.py:188-199). */
 typedef struct nrms_encoder_desc {
-    int32_t  n_seq;        /* titles (B*(H+C)) or users (B) */
+    int32_t  n_seq;        /* titles (B*(H+C)) or users (B); n_seq * seq_len < 2^31 rows.  Every row index of the fp32 / bf16x3 /
+                              bf16 chain is exact over that whole range (csrc/rowdiv.h), and every width up to d_model = 1024 at
+                              every seq_len is addressed exactly (the 32 x 32 attention tiles pack their offsets only where they
+                              fit): tests/test_hip_extents.py runs 9 M rows and d_model 672 ... 1024 against float64 */
     int32_t  seq_len;      /* L or H, 1..64 */
     int32_t  d_model;      /* config.word_embed_size (nrms_naml user encoder: news_feature_size); multiple of 4, <= 1024 */
     int32_t  n_heads;      /* config.num_attention_heads (v1 / naml news encoder: title_heads_num; naml user encoder:

@@ -96,14 +96,16 @@ struct Prefetch {
 // (these kernels are bound by the line-touch rate of the vector memory path, not by bytes).
 struct BlockPos { uint32_t goff, inimg, which, row; bool ok; };   // float2 units; which: 0 Q, 1 K, 2 V
 
-template <int NS, int ND>
+template <int NS, int ND, bool PK = true>
 struct PrefetchQKV {
     static constexpr int IT = 24 * NS * ND;         // >= 32 NS * 48 ND / 64
     // Where the registers allow (32x32 tiles) each iteration's block position is computed ONCE per wave
     // and kept packed in one register: bits 0-14 global offset in float2 (row * ld/2 + c), 15-24 offset
     // inside the operand image in float2 (row * RS/2 + c'), 25-26 operand (0 Q, 1 K, 2 V; 3 = out of
     // range), 27-31 row.  Recomputing it per unit costs ~20 VALU per iteration -- a fifth of the forward.
-    static constexpr bool PACKED = NS * ND == 1;
+    // The 15-bit field holds the largest offset, (S - 1) * 3 d / 2 + 3 d_k / 2 - 1, up to d = 672 at S = 32 (packed_offsets_fit,
+    // decided by the launcher): wider models take PK = false, the positions recomputed per unit as for the big tiles.
+    static constexpr bool PACKED = PK && NS * ND == 1;
     float2 v[IT];
     uint32_t pos[PACKED ? IT : 1];
 
@@ -627,7 +629,7 @@ __device__ __forceinline__ void stage_out_col(float* dstq, int RS, const f32x16 
 }
 
 // ---------------------------------------------------------------------------------------
-template <int NS, int ND, int WPB, bool MASKED, bool APAD, bool SPLIT>
+template <int NS, int ND, int WPB, bool MASKED, bool APAD, bool SPLIT, bool PK = true>
 __global__ __launch_bounds__(64 * WPB) void attn_fwd_kernel(AttnArgs a) {
     constexpr int SP = 32 * NS, DKP = 32 * ND, RS = DKP + 4, WF = 3 * SP * RS + 64;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -643,7 +645,7 @@ __global__ __launch_bounds__(64 * WPB) void attn_fwd_kernel(AttnArgs a) {
     const long total = (long)a.n_seq * a.h;
     const long ld = 3L * a.d;
     const long ustride = (long)gridDim.x * WPB;
-    PrefetchQKV<NS, ND> pf;
+    PrefetchQKV<NS, ND, PK> pf;
     const int blk = a.S * a.w2;                 // float2 in one head block
     long u = (long)blockIdx.x * WPB + wave;
     // APAD: all-padding units neither load nor compute.  `ap_cur` / `ap_next` = this / the next unit is all
@@ -776,7 +778,7 @@ __global__ __launch_bounds__(64 * WPB) void attn_fwd_kernel(AttnArgs a) {
 // 32x32 transpose through a wave-private LDS image each.
 // (second launch bound: the 32x32 instantiations must stay at two waves per SIMD, i.e. <= 256 registers; the
 // COMPACT variants would otherwise settle at 260 and lose half their occupancy)
-template <int NS, int ND, int WPB, bool MASKED, bool COMPACT, bool SPLIT>
+template <int NS, int ND, int WPB, bool MASKED, bool COMPACT, bool SPLIT, bool PK = true>
 __global__ __launch_bounds__(64 * WPB, NS * ND == 1 ? 2 : 1) void attn_bwd_kernel(AttnArgs a) {
     constexpr bool PF = NS == 1;      // prefetch across the compute only where registers allow
     constexpr int SP = 32 * NS, DKP = 32 * ND, RS = DKP + 4, TS = TSH;
@@ -823,7 +825,7 @@ __global__ __launch_bounds__(64 * WPB, NS * ND == 1 ? 2 : 1) void attn_bwd_kerne
     const long total = (long)a.n_seq * a.h;
     const long ld = 3L * a.d;
     const long ustride = (long)gridDim.x * WPB;
-    PrefetchQKV<NS, ND> pf;
+    PrefetchQKV<NS, ND, PK> pf;
     Prefetch<NS, ND> pg;
     const int blk = a.S * a.w2;
     long u = (long)blockIdx.x * WPB + wave;
@@ -1466,10 +1468,19 @@ static int launch_attn_fwd_coop(const AttnArgs& a, hipStream_t stream) {
     return a.ids != nullptr ? launch_attn_fwd_coop2<false, true>(a, stream) : launch_attn_fwd_coop2<false, false>(a, stream);
 }
 
-size_t attention_padsum_floats() { return (size_t)(256 * 16 + 256) * 4 * PADSUM_STRIDE; }   // grid cap + up to n_heads - 1 extra blocks, 4 waves each
+// grid cap + up to n_heads - 1 extra blocks (launch_attn_inst4 rounds the wave count up to a multiple of n_heads; n_heads <= 512:
+// d_model <= 1024, even d_k), 4 waves each
+size_t attention_padsum_floats() { return (size_t)(256 * 16 + 512) * 4 * PADSUM_STRIDE; }
 
-template <int NS, int ND, int WPB, bool BWD, bool MASKED, bool COMPACT, bool SPLIT>
+// PrefetchQKV keeps a position's global offset (float2 units inside one sequence's head block) in 15 bits: true when the
+// largest one fits.  Only the 32 x 32 tiles pack; at S = 32, d_k = 32 the limit is d = 672 (31 295; d = 704 gives 32 783).
+static bool packed_offsets_fit(const AttnArgs& a) { return (long)(a.S - 1) * (3L * a.d / 2) + a.w2 - 1 <= 0x7fffL; }
+
+template <int NS, int ND, int WPB, bool BWD, bool MASKED, bool COMPACT, bool SPLIT, bool PK = true>
 static int launch_attn_inst4(const AttnArgs& a, float* dbias, hipStream_t stream) {
+    if constexpr (PK && NS * ND == 1) {
+        if (!packed_offsets_fit(a)) return launch_attn_inst4<NS, ND, WPB, BWD, MASKED, COMPACT, SPLIT, false>(a, dbias, stream);
+    }
     constexpr int SP = 32 * NS, RS = 32 * ND + 4;
     constexpr bool ALIAS = NS == 1;                     // 32-row units: the transpose image lives over the dead V tile
     constexpr size_t wf = BWD ? (4 * SP * RS + (ALIAS ? 0 : 32 * 33) + 64 + (COMPACT ? 64 + 3 * 32 * ND : 0)) : (3 * SP * RS + 64);
@@ -1482,15 +1493,15 @@ static int launch_attn_inst4(const AttnArgs& a, float* dbias, hipStream_t stream
         while ((blocks * WPB) % a.h != 0) ++blocks;
     const char* name = BWD ? "attn_bwd" : "attn_fwd";
     hipError_t e;
-    if (BWD) e = hipFuncSetAttribute((const void*)attn_bwd_kernel<NS, ND, WPB, MASKED, COMPACT, SPLIT>,
+    if (BWD) e = hipFuncSetAttribute((const void*)attn_bwd_kernel<NS, ND, WPB, MASKED, COMPACT, SPLIT, PK>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    else e = hipFuncSetAttribute((const void*)attn_fwd_kernel<NS, ND, WPB, MASKED, COMPACT && !MASKED, SPLIT>,
+    else e = hipFuncSetAttribute((const void*)attn_fwd_kernel<NS, ND, WPB, MASKED, COMPACT && !MASKED, SPLIT, PK>,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e)); return NRMS_ELAUNCH; }
     {
         TimingScope ts(name, stream);
-        if (BWD) hipLaunchKernelGGL((attn_bwd_kernel<NS, ND, WPB, MASKED, COMPACT, SPLIT>), dim3(blocks), dim3(64 * WPB), bytes, stream, a);
-        else hipLaunchKernelGGL((attn_fwd_kernel<NS, ND, WPB, MASKED, COMPACT && !MASKED, SPLIT>), dim3(blocks), dim3(64 * WPB), bytes, stream, a);
+        if (BWD) hipLaunchKernelGGL((attn_bwd_kernel<NS, ND, WPB, MASKED, COMPACT, SPLIT, PK>), dim3(blocks), dim3(64 * WPB), bytes, stream, a);
+        else hipLaunchKernelGGL((attn_fwd_kernel<NS, ND, WPB, MASKED, COMPACT && !MASKED, SPLIT, PK>), dim3(blocks), dim3(64 * WPB), bytes, stream, a);
         const int rc = check_launch(name);
         if (rc) return rc;
     }

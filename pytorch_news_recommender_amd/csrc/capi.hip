@@ -788,7 +788,7 @@ extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encode
             g.M = M; g.N = d; g.K = q; g.rows_per_tile = NT_BM;
             g.ds = ds; g.qv = w->q_vec; g.T = acts->t;
             g.W = wadd_t; g.C = dctx; g.ldc = d;
-            g.wrow = acts->w; g.dout = dout; g.S = S;
+            g.wrow = acts->w; g.dout = dout; g.seq_of_row = make_row_div((uint32_t)S);
             g.drop = drop_c;
             rc = nt_gemm(desc, A_DZ, E_DCTX, g, wplanes, s, "dctx_bwd");
             if (rc) return rc;

@@ -52,8 +52,9 @@ int launch_gather_dropout_compact(long M, int d, const int64_t* ids, const int* 
 
 // qkv[m, :] = bias for padding tokens: with an all-zero embedding row 0 their x row is exactly zero
 // (also under dropout), so the projection of a padding token IS the bias and the GEMM skips them.
-constexpr int FILL_SLICES = 6;          // 64 lanes x 6 float4 = 1536 floats >= 3 d_model (d_model <= 512)
-template <bool SKIP_ALL_PAD>
+// FILL_SLICES float4 per lane: 6 (64 x 6 x 4 = 1536 floats >= 3 d_model for d_model <= 512) or 12 (3072: d_model <= 1024, the
+// widest the C ABI accepts; until tests/test_hip_extents.py the wide models with NRMS_FLAG_PAD_ROW_ZERO were refused here)
+template <bool SKIP_ALL_PAD, int FILL_SLICES>
 __global__ __launch_bounds__(256) void fill_pad_rows_kernel_t(long n_seq, int S, int n4, const int64_t* ids, const float* row,
                                                               float* out) {
     // one wave per sequence: its padding rows get the bias; a sequence that is ALL padding is skipped (with
@@ -83,12 +84,14 @@ __global__ __launch_bounds__(256) void fill_pad_rows_kernel_t(long n_seq, int S,
 int launch_fill_pad_rows(long n_seq, int S, int n, const int64_t* ids, const float* row, float* out, bool skip_all_pad,
                          hipStream_t stream) {
     if (n_seq <= 0) return NRMS_OK;
-    if ((n & 3) != 0 || n > 256 * FILL_SLICES || S > 64) { set_error("fill_pad_rows: n=%d S=%d unsupported", n, S); return NRMS_EINVAL; }
+    if ((n & 3) != 0 || n > 256 * 12 || S > 64) { set_error("fill_pad_rows: n=%d S=%d unsupported", n, S); return NRMS_EINVAL; }
     int blocks = cdiv(n_seq, 4);
     if (blocks > 256 * 32) blocks = 256 * 32;
     TimingScope ts("fill_pad_rows", stream);
-    if (skip_all_pad) hipLaunchKernelGGL(fill_pad_rows_kernel_t<true>, dim3(blocks), dim3(256), 0, stream, n_seq, S, n / 4, ids, row, out);
-    else hipLaunchKernelGGL(fill_pad_rows_kernel_t<false>, dim3(blocks), dim3(256), 0, stream, n_seq, S, n / 4, ids, row, out);
+    const bool wide = n > 256 * 6;
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, n_seq, S, n / 4, ids, row, out); };
+    if (skip_all_pad) { if (wide) go(fill_pad_rows_kernel_t<true, 12>); else go(fill_pad_rows_kernel_t<true, 6>); }
+    else { if (wide) go(fill_pad_rows_kernel_t<false, 12>); else go(fill_pad_rows_kernel_t<false, 6>); }
     return check_launch("fill_pad_rows");
 }
 
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(256) void tok_place_kernel(const int64_t* ids, cons
 // H16: dX rows are fp16 [rows][ldx] still multiplied by the fp16 backward's loss scale (half the bytes of the dX GEMM's
 // store and of this kernel's reads); the sum is taken in fp32 and divided by the scale (sc[1], device) once per table row.
 typedef _Float16 sg_h4 __attribute__((ext_vector_type(4)));
-template <bool H16>
+template <bool H16, int SL = 2>
 __global__ __launch_bounds__(256) void scatter_grouped_kernel(int V, int d4, const int* live, const int* offs,
                                                               const int* total, const int* order, const void* dxv, int ldx,
                                                               const float* sc, Dropout drop, float* dtable) {
@@ -309,7 +312,8 @@ __global__ __launch_bounds__(256) void scatter_grouped_kernel(int V, int d4, con
     if (beg == end) return;
     // a lane owns float4 columns lane, lane + 64, ... (SL slices): ONE pass over the bucket, all slices of a
     // token's row loaded together (a pass per slice doubled the dependent order -> row load chain)
-    constexpr int SL = 2;                          // d_model <= 512 -> d4 <= 128
+    // SL = 2: d_model <= 512 (d4 <= 128); SL = 4: up to the 1024 the C ABI accepts (chosen by the launcher -- with two
+    // slices only, columns 512.. of a wider table gradient were silently left out)
     f32x4 s[SL];
 #pragma unroll
     for (int j = 0; j < SL; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -387,6 +391,7 @@ int launch_scatter_grouped(long M, int V, int d, const int64_t* ids, const int* 
                            const Dropout& drop, float* dtable, int* scratch, hipStream_t stream, bool dx_fp16, int ldx,
                            const float* sc, bool prepared) {
     if (M <= 0) return NRMS_OK;
+    if ((d & 3) != 0 || d > 1024 || (dx_fp16 && d > 512)) { set_error("scatter_grouped: d=%d unsupported", d); return NRMS_EINVAL; }
     if (!prepared) {
         const int rc = launch_scatter_prepare(M, V, ids, live, n_live, scratch, stream);
         if (rc) return rc;
@@ -399,9 +404,12 @@ int launch_scatter_grouped(long M, int V, int d, const int64_t* ids, const int* 
     if (dx_fp16)
         hipLaunchKernelGGL(scatter_grouped_kernel<true>, dim3(cdiv(V, 4)), dim3(256), 0, stream, V, d / 4, live, cnt, total, order, dx,
                            ldx, sc, drop, dtable);
-    else
+    else if (d <= 512)
         hipLaunchKernelGGL(scatter_grouped_kernel<false>, dim3(cdiv(V, 4)), dim3(256), 0, stream, V, d / 4, live, cnt, total, order, dx,
                            d, nullptr, drop, dtable);
+    else
+        hipLaunchKernelGGL((scatter_grouped_kernel<false, 4>), dim3(cdiv(V, 4)), dim3(256), 0, stream, V, d / 4, live, cnt, total, order,
+                           dx, d, nullptr, drop, dtable);
     return check_launch("scatter_grouped");
 }
 

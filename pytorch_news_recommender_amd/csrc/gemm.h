@@ -14,6 +14,7 @@
 // left is the additive-attention dZ = ds*q*(1-T^2) (three VALU ops per element).
 #pragma once
 #include "common.h"
+#include "rowdiv.h"
 
 namespace nrms {
 
@@ -36,7 +37,7 @@ struct NTArgs {
     float* C; int ldc;        // output
     const float* wrow;        // E_DCTX: [M] pooling weights
     const float* dout;        // E_DCTX: [n_seq, N]
-    int S;                    // E_DCTX: rows per sequence
+    RowDiv seq_of_row;        // E_DCTX: make_row_div(rows per sequence), rowdiv.h
     Dropout drop;             // optional epilogue dropout (thresh != 0), Philox site 1, element index
                               // g*N + n -- only the output-projection topology (nrms_v1) needs it here
     // Row compaction (A_PLAIN only; both null = dense): row r of the product is row a_rows[r] of A, and
@@ -178,12 +179,13 @@ __device__ __forceinline__ void nt_epilogue(const NTArgs& g, const f32x4 (&acc)[
     const bool ok_a = c4a < F4_ROW && sub < RPI && na < g.N;
     f32x4 bias_a = {0.f, 0.f, 0.f, 0.f};
     if (EMODE == E_STORE && g.bias != nullptr && ok_a) bias_a = *reinterpret_cast<const f32x4*>(g.bias + na);
-    const float inv_S = EMODE == E_STORE ? 0.f : 1.0f / (float)g.S;
 
     // bias / w_s * dout of one float4 of row gr at column n
     auto fix = [&](f32x4 v, long gr, int n, const f32x4& bias4) {
         if (EMODE == E_STORE) return v + bias4;
-        const long seq = (long)(((float)gr + 0.5f) * inv_S);               // exact for gr < 2^22
+        // exact for every row of the accepted domain (M < 2^31); a multiply-high and a shift on a row index that is
+        // wave-uniform per store instruction (a float reciprocal here went wrong from row 4 397 273 on: rowdiv.h)
+        const long seq = (long)row_div((uint32_t)gr, g.seq_of_row);
         return v + g.wrow[gr] * *reinterpret_cast<const f32x4*>(g.dout + seq * (long)g.N + n);
     };
     const bool dropped = g.drop.thresh != 0u;                              // uniform

@@ -92,7 +92,8 @@ __global__ __launch_bounds__(64 * HIER_WPB) void hier_tree_kernel(HierTreeArgs a
     (void)my_g;
 }
 
-// exclusive scans of the three per-user member counts (one block; B <= 2^20)
+// exclusive scans of the three per-user member counts (one block: each thread walks ceil(B / 1024) users, so it is right for any B and
+// merely serial -- a thousand users per thread -- beyond B = 2^20)
 __global__ __launch_bounds__(1024) void hier_scan_kernel(int B, const int* counts, int* base) {
     __shared__ int part[1024];
     for (int level = 0; level < 3; ++level) {
