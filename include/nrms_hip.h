@@ -419,6 +419,44 @@ int nrms_segment_pool_bwd(const nrms_segpool_desc* desc, const float* x, const f
  * ascending list position: no atomics, the same bits on every run. */
 int nrms_csr_from_padded(int64_t n_seg, int32_t K, const int64_t* lists, int64_t n_rows, int32_t* seg_ptr, int32_t* idx, void* stream);
 
+/* ---- Click graph: neighbour sampling for the user-news graph encoder (csrc/graphsample.hip; click_graph.py; PARITY UNPINNED,
+ * the reference has no graph model).  The bipartite user-news click graph of the WHOLE data set as two CSRs in HBM; every edge is
+ * in both, a user's news and a news's users in ascending id, no duplicates; news id 0 (the padding slot) is never an edge. */
+typedef struct nrms_click_graph {
+    int64_t n_users, n_news, n_edges;     /* n_news = rows of the catalogue (ids 0 .. n_news - 1), < 2^31; n_users < 2^31 */
+    const int64_t* user_ptr;              /* [n_users + 1] */
+    const int32_t* user_news;             /* [n_edges] */
+    const int64_t* news_ptr;              /* [n_news + 1] */
+    const int32_t* news_users;            /* [n_edges] */
+} nrms_click_graph;
+/* neighbor_ids [n_slots, K] int32, 1 <= K <= 64, n_slots < 0x7f7f7f7f, n_slots * K < 2^31.  Draw t of a slot that shows news j = slot_ids[r]:
+ *   r4 = philox4x32_7(seed, group = j * K + t, site 5)          (the counter layout of the dropout sites, csrc/common.h)
+ *   deg = news_ptr[j + 1] - news_ptr[j];  -1 if deg == 0, j == 0 or j outside [0, n_news)
+ *   u = news_users[news_ptr[j] + ((uint64) r4[0] * deg >> 32)]
+ *   m = user_news[user_ptr[u] + ((uint64) r4[1] * deg(u) >> 32)]
+ *   -1 if m == j, else m.
+ * Repeated neighbours among the K draws are kept.  The result is a function of (graph, j, t, seed) alone: not of the slot, the
+ * batch or the call.  Slot ids outside [0, n_news) are counted into *n_bad (device int32, as nrms_sanitize_ids counts).  One
+ * kernel, no atomics on the results.  The call needs no workspace today (the query returns 0; workspace may be NULL). */
+size_t nrms_graph_sample_workspace_bytes(int64_t n_slots, int32_t K);
+int nrms_graph_sample_neighbors(const nrms_click_graph* graph, int64_t n_slots, int32_t K, const int64_t* slot_ids, uint64_t seed,
+                                int32_t* neighbor_ids, int32_t* n_bad, void* workspace, size_t workspace_bytes, void* stream);
+/* Neighbour news ids -> rows of the batch's numbering, neighbor_rows [n_slots, K] int64 (the input of nrms_csr_from_padded):
+ *   a neighbour some slot of the batch shows -> the smallest such slot r (slot_ids[r] == id);
+ *   any other neighbour                      -> n_slots + e, e = its rank among the batch's distinct out-of-batch neighbour ids in
+ *                                               ascending order, while e < cap; -1 for e >= cap (so the largest ids go first);
+ *   -1 (or an id outside (0, n_news))        -> -1.
+ * extra_ids [cap] int32 = those distinct ids in ascending order, padded with 0; *n_extra (device int32) = how many are valid;
+ * *n_dropped (device int32) += distinct ids of rank >= cap.  No host synchronisation; integer atomicMin / atomicOr only, so two
+ * calls with the same inputs give the same bytes.  workspace: nrms_graph_resolve_workspace_bytes(n_news) bytes, 4-byte aligned
+ * (two tables over the news ids; the call initialises them).  Intended range: the ranking pass is ONE 1 024-lane workgroup that walks
+ * the n_news / 32 bitmap words (4 words per lane and 5 us at 130 000 news; about 0.2 ms at 10^7); larger catalogues stay correct but
+ * that pass, and the two tables' memsets (4.1 bytes per news id), grow linearly with n_news, whatever the batch. */
+size_t nrms_graph_resolve_workspace_bytes(int64_t n_news);
+int nrms_graph_resolve_rows(int64_t n_slots, int32_t K, int64_t n_news, const int64_t* slot_ids, const int32_t* neighbor_ids, int32_t cap,
+                            int64_t* neighbor_rows, int32_t* extra_ids, int32_t* n_extra, int32_t* n_dropped, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ---- All-padding sequences of the output-projection topology in closed form (csrc/empty_seq.hip; nrms_naml's word-level
  * encoder, model/nrms_naml.py:42-100,121-177: 41 % of a MIND-shaped batch's title / abstract slots are history padding).  With a
  * zero padding row every Q | K | V row of such a sequence is the bias, so attention row i is b_v scaled per head by

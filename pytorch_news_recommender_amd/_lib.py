@@ -60,6 +60,11 @@ class SegPoolDesc(C.Structure):
 NRMS_SEGPOOL_ROWS_UNIQUE = 1
 
 
+class ClickGraphDesc(C.Structure):
+    _fields_ = [("n_users", C.c_int64), ("n_news", C.c_int64), ("n_edges", C.c_int64), ("user_ptr", C.c_void_p),
+                ("user_news", C.c_void_p), ("news_ptr", C.c_void_p), ("news_users", C.c_void_p)]
+
+
 class NewsFeatures(C.Structure):
     _fields_ = [("n", C.c_int64), ("d_text", C.c_int32), ("d_cat", C.c_int32), ("n_cat", C.c_int32), ("n_sub", C.c_int32),
                 ("p_drop", C.c_float), ("seed", C.c_uint64), ("title_vec", C.c_void_p), ("abst_vec", C.c_void_p),
@@ -115,6 +120,12 @@ SIGNATURES = {
     "nrms_encoder_empty_bwd": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EncoderGrads),
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
     "nrms_csr_from_padded": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrms_graph_sample_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "nrms_graph_sample_neighbors": (C.c_int, [C.POINTER(ClickGraphDesc), C.c_int64, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nrms_graph_resolve_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "nrms_graph_resolve_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
+                                + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "nrms_hier_add_embedding_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "nrms_hier_add_embedding_bwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.c_void_p]),

@@ -70,6 +70,11 @@ class Config(object):
         self.hierec_lambda_top = 0.15
         # model "graph" (model/graph_hip.py; parity unpinned): neighbours sampled per news slot when the batch carries no neighbor_rows
         self.graph_neighbors = 8
+        # ... with an attached click graph (Model.attach_click_graph): rows reserved per batch for the vectors of sampled
+        # neighbours that no slot of the batch shows (a fixed size: no per-batch host read).  A 512-user MIND-shaped batch
+        # (28 160 slots x 8 draws over 130 k news) draws about twelve thousand distinct ones from a Zipf-skewed graph; beyond this many the
+        # largest ids are dropped and counted (Model.check_click_graph)
+        self.graph_extra_rows = 16384
 
     def __nrms__(self):
         self.news_feature_size = 800             # nrms_naml: 2 * word_embed_size + 2 * cate_embed_size (config.py:68)

@@ -398,6 +398,15 @@ class DeviceFeed:
             self._news_info = {"absts": self.absts, "categ": tables["categ"], "subcateg": tables["subcateg"]}
         return self._news_info
 
+    def click_graph(self):
+        """The click graph of this feed's own samples (click_graph.ClickGraph, on the feed's device) for
+        ``model.graph_hip.Model.attach_click_graph``: one user node per DISTINCT history row (a training feed repeats a user's
+        history once per positive impression), news ids = rows of ``titles``.  Built on the first call, then kept."""
+        if getattr(self, "_click_graph", None) is None:
+            from .click_graph import ClickGraph
+            self._click_graph = ClickGraph.from_histories(torch.unique(self.packed["hist"], dim=0), int(self.titles.shape[0]), self.device)
+        return self._click_graph
+
     def batch(self, rows):
         """rows: int64 device tensor of sample indices -> the batch dict (device tensors).  The dict is LAZY: a value is
         gathered when it is first read (nrms_v0 reads 3 of the 13 keys, nrms_naml 9; gathering all of them cost 0.6 ms of GPU

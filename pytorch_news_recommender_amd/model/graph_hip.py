@@ -21,6 +21,32 @@ Both aggregations are ``nrms_segment_pool_fwd / _bwd`` (csrc/segpool.hip) over i
 ``nrms_csr_from_padded``; a news row is listed by many segments, so the news layer's backward sorts the list entries by row and
 adds a row's shares in list order (no atomics: bit-reproducible, include/nrms_hip.h).  A batch without ``neighbor_rows`` (the
 reference's loader knows no graph) gets them from ``graph_sampler.induced_neighbor_rows``.  No CPU fallback.
+
+Neighbours outside the batch.  The batch may also carry
+
+  ``neighbor_vectors`` [M, d] fp32 -- CONSTANT news vectors; ``neighbor_rows`` may then index [0, N + M), N = B * (H + C): row
+  N + e is ``neighbor_vectors[e]``.  The news layer pools over the N + M rows into the N slots; the constant rows take no
+  gradient (the backward drops the last M rows of dx) but do feed the gradients of ``neighbor_attention.*``.
+
+``Model.attach_click_graph(graph, titles)`` (click_graph.ClickGraph, e.g. ``DeviceFeed.click_graph()`` with ``DeviceFeed.titles``)
+replaces the induced sampler: from then on a batch without ``neighbor_rows`` gets both keys on the device, from its
+``browsed_ids``, ``browsed_mask`` and ``candidate_ids`` (a KeyError names them when they are missing), the graph and a seed --
+``nrms_graph_sample_neighbors`` draws every slot's ``config.graph_neighbors`` neighbours from the click graph of the WHOLE data
+set as a function of (graph, news id, draw, seed), ``nrms_graph_resolve_rows`` turns them into rows (a neighbour the batch shows:
+its first slot; any other: row N + e) and ``neighbor_vectors`` = the catalogue gathered at the call's ``extra_ids``, always
+``config.graph_extra_rows`` rows (no per-batch host read; distinct out-of-batch neighbours beyond that many are dropped, largest
+ids first, and counted: ``check_click_graph``).  The training seed is the train-step counter: the number of batches trained on
+so far (``train_step`` calls and train-mode forwards with autograd enabled; a train-mode forward under ``no_grad`` draws with the
+current value and leaves it).  It is not part of ``state_dict()``: a run resumed from a checkpoint starts again at 0 (set
+``_graph_step`` to continue the sequence).  The evaluation seed is the constant ``EVAL_SEED``, so an evaluation is a function of
+weights and data alone.
+
+Staleness rule (part of this specification).  The catalogue is ``encode_catalogue(titles)``: the dropout-free,
+evaluation-precision news vectors n_r of every news.  It is recomputed on attach, by ``refresh_neighbor_vectors()``
+(``train_eval.train`` calls it at every epoch start) and lazily on the first eval-mode forward after the parameters changed, so
+evaluation always sees current vectors, while TRAINING sees out-of-batch neighbour vectors at most one epoch stale -- on purpose:
+historical embeddings for out-of-batch neighbours, which carry no gradient.  "Changed" = a ``train_step``, a forward that autograd
+will differentiate, or a ``load_state_dict``; after writing into parameters by hand call ``refresh_neighbor_vectors()``.
 """
 from __future__ import annotations
 
@@ -62,11 +88,21 @@ class GraphEngine(NRMSEngine):
         ids = self._buf("ids" + sfx, N * L, torch.int64)[:N * L].view(N, L)
         self.sanitize_ids(bt.reshape(B * H, L).contiguous(), ids[:B * H])
         self.sanitize_ids(ct.reshape(B * Cn, L).contiguous(), ids[B * H:])
-        nv = self._buf("news_vec" + sfx, N * d)[:N * d].view(N, d)
+        ext = batch.get("neighbor_vectors")
+        M = 0
+        if ext is not None:
+            if ext.dim() != 2 or ext.shape[1] != d or ext.dtype != torch.float32:
+                raise _lib.NrmsError("graph: neighbor_vectors must be [M, %d] float32, got %s %s" % (d, tuple(ext.shape), ext.dtype))
+            M = ext.shape[0]
+        # rows [0, N): the slots' own vectors; rows [N, N + M): the constant vectors of out-of-batch neighbours
+        x = self._buf("news_vec" + sfx, (N + M) * d)[:(N + M) * d].view(N + M, d)
+        nv = x[:N]
+        if M:
+            x[N:].copy_(ext)
         p = float(p_drop)
         self.encode_titles(flat, ids, out=nv, p_embed=p, p_ctx=p, seed=seed, save=training, tag="news" + sfx, trusted_ids=True)
         # ---- index lists: every slot's neighbours; every user's clicked slots (history rows with browsed_mask = 1)
-        n_ptr, n_idx = self._csr("nbr" + sfx, nbr, N)
+        n_ptr, n_idx = self._csr("nbr" + sfx, nbr, N + M)
         slots = torch.arange(B * H, device=self.device, dtype=torch.int64).view(B, H)
         hist = torch.where(batch["browsed_mask"].to(torch.bool), slots, torch.full_like(slots, -1)).contiguous()
         u_ptr, u_idx = self._csr("hist" + sfx, hist, B * H)
@@ -76,7 +112,7 @@ class GraphEngine(NRMSEngine):
         prec = "fp32" if self.precision == "fp32" else "bf16x3"
         pool_n = SegmentPool(d, q, prec, rows_unique=False)
         pool_u = SegmentPool(d, q, prec, rows_unique=True)
-        g = pool_n.forward(nv, *W[LEVELS[0]], n_ptr, n_idx)          # [N, d]: the neighbour aggregate ...
+        g = pool_n.forward(x, *W[LEVELS[0]], n_ptr, n_idx)           # [N, d]: the neighbour aggregate ...
         g += nv                                                      # ... + the slot's own vector
         h = pool_u.forward(g, *W[LEVELS[1]], u_ptr, u_idx)           # [B, d]
         mask = batch.get("candidate_mask")
@@ -118,7 +154,7 @@ class GraphEngine(NRMSEngine):
 
         dg = level(pool_u, LEVELS[1], dh)                            # [N, d] (rows outside every history list: 0)
         dg[n:] += dcand
-        dnv = level(pool_n, LEVELS[0], dg)                           # through the neighbour aggregate ...
+        dnv = level(pool_n, LEVELS[0], dg)[:N]                       # through the neighbour aggregate (constant rows dropped) ...
         dnv += dg                                                    # ... and the slot's own vector
         desc_n = self._desc("news_encoder", N, L, sv["p"], sv["p"], sv["seed"], training=True)
         ws = self._bwd_workspace(desc_n)
@@ -135,7 +171,9 @@ class GraphEngine(NRMSEngine):
 
 class Model(FlatHipModel):
     """User-news graph encoder: ``Model(config)``, ``forward(batch) -> scores [B, C]`` (``model/__init__.py:22-23,38``)."""
-    KEYS = ("browsed_titles", "browsed_mask", "candidate_titles", "candidate_mask", "neighbor_rows")
+    KEYS = ("browsed_titles", "browsed_mask", "candidate_titles", "candidate_mask", "neighbor_rows", "neighbor_vectors")
+    OPTIONAL = ("candidate_mask", "neighbor_vectors")
+    EVAL_SEED = 0x6A09E667F3BCC908          # the sampler's seed of every eval-mode forward (any constant would do)
 
     def __init__(self, config, pretrained_word_embedding=None):
         super().__init__()
@@ -150,13 +188,109 @@ class Model(FlatHipModel):
         extra = []
         for lv in LEVELS:
             extra += additive_entries(lv, q, d)
+        self._graph = self._graph_titles = self._catalogue = None
+        self._catalogue_stale = False
+        self._graph_step = 0
         self._finish(FlatLayout(self._dims, news_encoder_entries(self._dims, extra)), table.device)
+        self.register_load_state_dict_post_hook(Model._mark_catalogue_stale)
 
     def _make_engine(self, device, precision):
         return GraphEngine(self._dims, device, precision=precision, layout=self._layout)
 
+    # ---- the global click graph ------------------------------------------------------------------------
+    @staticmethod
+    def _mark_catalogue_stale(module, incompatible_keys=None):
+        module._catalogue_stale = True
+
+    @torch.no_grad()
+    def encode_catalogue(self, titles):
+        """titles [N, L] word ids, row r = news id r (``DeviceFeed.titles``) -> news vectors n_r [N, d]: dropout-free, in the
+        precision evaluation runs in, whatever the module's train / eval mode (as ``nrms_hip.Model.encode_catalogue``)."""
+        dev = self._prepare()
+        return self._engine.encode_titles(self._flat, nrms_hip._ids_on(dev, titles), tag="news_eval")
+
+    def attach_click_graph(self, graph, titles):
+        """From now on a batch without ``neighbor_rows`` takes its neighbours from ``graph`` (click_graph.ClickGraph on the
+        model's device) instead of the batch-induced host sampler; titles [graph.n_news, L]: the word ids of every news, row r =
+        news id r.  The catalogue is encoded here (module docstring: staleness rule)."""
+        dev = self._prepare()
+        titles = nrms_hip._ids_on(dev, titles)
+        if graph.device != dev:
+            raise _lib.NrmsError("attach_click_graph: the graph is on %s, the model on %s" % (graph.device, dev))
+        if titles.dim() != 2 or titles.shape[0] != graph.n_news:
+            raise _lib.NrmsError("attach_click_graph: titles must be [n_news = %d, L], got %s" % (graph.n_news, tuple(titles.shape)))
+        K, cap = int(getattr(self.config, "graph_neighbors", 8)), int(getattr(self.config, "graph_extra_rows", 16384))
+        if not 1 <= K <= 64 or cap < 0:
+            raise _lib.NrmsError("attach_click_graph: config.graph_neighbors = %d must be in [1, 64], config.graph_extra_rows = %d >= 0" % (K, cap))
+        self._graph, self._graph_titles = graph, titles
+        self._graph_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._graph_dropped = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.refresh_neighbor_vectors()
+
+    def refresh_neighbor_vectors(self):
+        """Re-encode the catalogue the out-of-batch neighbour vectors are gathered from (no-op without an attached graph)."""
+        if self._graph is None:
+            return None
+        self._catalogue = self.encode_catalogue(self._graph_titles)
+        self._catalogue_stale = False
+        return self._catalogue
+
+    def check_click_graph(self):
+        """One host synchronisation.  Raises if a batch since the last check held browsed_ids / candidate_ids outside the graph's
+        [0, n_news) (their slots got no neighbours); returns how many distinct out-of-batch neighbours were dropped since the
+        last check because a batch had more than config.graph_extra_rows of them (0: none; raise the field otherwise)."""
+        if self._graph is None:
+            return 0
+        bad, dropped = int(self._graph_bad.item()), int(self._graph_dropped.item())
+        self._graph_bad.zero_()
+        self._graph_dropped.zero_()
+        if bad:
+            raise _lib.NrmsError("graph: %d news id(s) outside the click graph's [0, %d) among browsed_ids / candidate_ids" % (bad, self._graph.n_news))
+        return dropped
+
+    def _global_neighbors(self, batch, dev):
+        get = batch.get if hasattr(batch, "get") else (lambda k: batch[k])
+        missing = [k for k in ("browsed_ids", "candidate_ids") if get(k) is None]
+        if missing:
+            raise KeyError("%s: with an attached click graph the batch dict needs %s (the news ids of its slots)"
+                           % (type(self).__module__, " and ".join(repr(k) for k in missing)))
+        ids = lambda k: torch.as_tensor(get(k)).to(dev, dtype=torch.int64)
+        bi, ci = ids("browsed_ids"), ids("candidate_ids")
+        valid = torch.as_tensor(batch["browsed_mask"]).to(dev) != 0
+        slot_ids = torch.cat([torch.where(valid, bi, torch.zeros_like(bi)).reshape(-1), ci.reshape(-1)])
+        if self.training:
+            # the train-step counter: it advances with the batches that are trained on (train_step, or a forward that
+            # autograd will differentiate), not with a train-mode forward under no_grad
+            seed = self._graph_step
+            if torch.is_grad_enabled():
+                self._graph_step += 1
+        else:
+            seed = self.EVAL_SEED
+            if self._catalogue_stale:
+                self.refresh_neighbor_vectors()
+        g = self._graph
+        nbr = g.sample_neighbors(slot_ids, int(getattr(self.config, "graph_neighbors", 8)), seed, n_bad=self._graph_bad)
+        rows, extra_ids, _ = g.resolve_rows(slot_ids, nbr, int(getattr(self.config, "graph_extra_rows", 16384)), n_dropped=self._graph_dropped)
+        out = {k: get(k) for k in self.KEYS if k not in ("neighbor_rows", "neighbor_vectors") and get(k) is not None}
+        out["neighbor_rows"] = rows
+        out["neighbor_vectors"] = self._catalogue.index_select(0, extra_ids.to(torch.int64))
+        return out
+
+    def train_step(self, batch, **kw):
+        out = super().train_step(batch, **kw)
+        self._catalogue_stale = True
+        return out
+
+    def forward(self, batch):
+        out = super().forward(batch)
+        if out.requires_grad:
+            self._catalogue_stale = True            # an optimizer step follows
+        return out
+
     def _engine_args(self, batch, dev):
         if (batch.get("neighbor_rows") if hasattr(batch, "get") else None) is None:
+            if self._graph is not None:
+                return super()._engine_args(self._global_neighbors(batch, dev), dev)
             # a loader that knows no graph (data_handler.MyDataset): sample the neighbours from the click graph induced on this batch
             from ..graph_sampler import induced_neighbor_rows
             self._sampled = getattr(self, "_sampled", 0) + 1

@@ -49,6 +49,9 @@ def build_parser():
     parser.add_argument('--recommend', type=int, default=None, metavar='K', help='finally write the top K news of the whole '
                         'catalogue per impression: dev split with the trained weights, or with --test the test split with '
                         'the checkpoint --test loaded (nrms_v0 / nrms_v1 models)')
+    parser.add_argument('--graph', type=str, default='induced', choices=('induced', 'global'), help="--model graph: where a news "
+                        "slot's neighbours come from.  induced: the click graph of the batch itself (host sampler); global: the "
+                        "click graph of the whole training feed, resident in HBM, sampled by the HIP sampler (needs --feed device)")
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     return parser
 
@@ -66,9 +69,21 @@ def check_recommend_args(args):
         raise SystemExit('--recommend: model %r cannot recommend from the whole catalogue (nrms_v0 / nrms_v1 only)' % args.model)
 
 
+def check_graph_args(args):
+    """--graph global fails before any data is read: the graph model on the device feed only."""
+    if args.graph != 'global':
+        return
+    from .model import ALIASES
+    if ALIASES.get(args.model.lower(), args.model.lower()) != 'graph_hip':
+        raise SystemExit('--graph global: only --model graph samples from a click graph (got %r)' % args.model)
+    if args.feed != 'device':
+        raise SystemExit('--graph global: the click graph is built from the device feed (--feed device)')
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_recommend_args(args)
+    check_graph_args(args)
     rank, local_rank, world = parallel.init_process_group()
     torch.manual_seed(422)
     torch.cuda.manual_seed_all(422)
@@ -113,6 +128,7 @@ def main(argv=None):
         dev_labels = read_dev_labels(config)
 
     recommender = Model(config, args)
+    all_train_samples = train_samples
     if world > 1:
         recommender.model._rank_salt = rank * 0x632BE59BD9B4E019
         recommender.model.engine
@@ -138,9 +154,27 @@ def main(argv=None):
                           device=config.device)
         return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out)
 
+    def attach_graph(feed, samples=None):
+        # the click graph is replicated: every rank builds it from ALL training samples (users shard, the graph does not)
+        src = feed if samples is None else DeviceFeed(config, samples, type=0, id2title_dict=titles, id2abst_dict=absts,
+                                                      batch_size=config.batch_size, device=config.device)
+        graph = src.click_graph()
+        recommender.model.attach_click_graph(graph, feed.titles)
+        if rank == 0:
+            print('click graph: {} users, {} news, {} edges, {:.1f} MB in HBM'.format(graph.n_users, graph.n_news, graph.n_edges,
+                                                                                    graph.nbytes() / 1e6))
+
     if not args.test:
-        hist = train(config, recommender, loader(train_samples, 0, True), loader(dev_samples, 1, False), dev_labels,
+        train_feed = loader(train_samples, 0, True)
+        if args.graph == 'global':
+            attach_graph(train_feed, all_train_samples if world > 1 else None)
+        hist = train(config, recommender, train_feed, loader(dev_samples, 1, False), dev_labels,
                      max_batches=args.max_batches, verbose=rank == 0)
+        if args.graph == 'global' and rank == 0:
+            dropped = recommender.model.check_click_graph()
+            if dropped:
+                print('click graph: {} out-of-batch neighbours dropped (raise config.graph_extra_rows = {})'.format(
+                    dropped, config.graph_extra_rows))
         if rank == 0:
             print('final dev AUC:', hist['aucs'][-1] if hist['aucs'] else None)
             if hist['metrics']:
@@ -156,7 +190,11 @@ def main(argv=None):
             test_samples, shown = dev_samples, [len(y) for y in dev_labels]
         else:
             test_samples, shown = load_dataset(config, config.test_data, config.data_path, _type=1), None
-        out = test(config, recommender, loader(test_samples, 1, False), shown, ckpt_file=args.load,
+        test_feed = loader(test_samples, 1, False)
+        if args.graph == 'global':
+            # the graph the checkpoint was trained with: the training samples' (all of them, as every training rank builds it)
+            attach_graph(test_feed, all_train_samples)
+        out = test(config, recommender, test_feed, shown, ckpt_file=args.load,
                    pick_best=args.load is None)
         print('saved to', out)
         if args.recommend is not None and rank == 0:

@@ -194,6 +194,10 @@ def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autogra
     for epoch in range(config.num_epochs):
         if verbose:
             print('Epoch [{}/{}]'.format(epoch + 1, config.num_epochs))
+        if hasattr(net, 'refresh_neighbor_vectors'):
+            # graph model with an attached click graph: out-of-batch neighbour vectors are at most one epoch stale
+            # (model/graph_hip.py, staleness rule); a no-op otherwise
+            net.refresh_neighbor_vectors()
         for datas in train_iter:
             B = len(datas['browsed_titles'])
             if use_autograd:
