@@ -206,7 +206,12 @@ int nrms_encoder_fwd(const nrms_encoder_desc* desc, const nrms_encoder_weights* 
 /* Backward of the above (autograd through the same lines; `loss.backward()` train_eval.py:126).
  * dout: [n_seq, d].  grads: accumulated.  dx: [M, d] gradient w.r.t. `x` (user encoder), or
  * NULL for the news encoder, whose input gradient is scatter-added into grads->table
- * (the dense embedding gradient the reference builds 55x per step). */
+ * (the dense embedding gradient the reference builds 55x per step).
+ * workspace: nrms_encoder_bwd_workspace_bytes(desc) bytes, 256-byte aligned.  Nothing is assumed about its contents on entry and
+ * nothing outside those bytes is touched (tests/test_hip_buffer_contracts.py).  News encoder: its last segment is the scratch
+ * of the table-gradient scatter, 2 (vocab + 64) + max(M, ceil(vocab / 1024)) + 64 ints -- the histogram and cursors over the
+ * vocabulary, then one region that holds the block totals of the scan over the vocabulary (one per 1024 ids) and afterwards the M
+ * token buckets -- so the query also covers a large vocabulary with a tiny batch (vocab = 300 000, M = 8). */
 size_t nrms_encoder_bwd_workspace_bytes(const nrms_encoder_desc* desc);
 int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encoder_weights* w,
                      const int64_t* ids, const float* x, const uint8_t* mask,

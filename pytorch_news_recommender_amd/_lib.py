@@ -11,6 +11,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NRMS_HIP_LIB") or os.path.join(PKG, "libnrms_hip.so")   # override: diagnostic builds only
 
+NRMS_OK, NRMS_EINVAL, NRMS_ELAUNCH, NRMS_EWORKSPACE = 0, -1, -2, -3     # return codes (include/nrms_hip.h)
 NRMS_FLAG_PAD_ROW_ZERO = 1
 NRMS_FLAG_DEFER_WQKV = 2
 NRMS_FLAG_FWD_SCRATCH_KEPT = 4

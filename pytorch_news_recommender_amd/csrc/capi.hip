@@ -336,7 +336,8 @@ static int encoder_fwd16(const nrms_encoder_desc* desc, const nrms_encoder_weigh
             int* n_live = (int*)(base + fs.n_live);
             int* order = (int*)(base + fs.order);
             int* order_cnt = (int*)(base + fs.order_cnt);
-            rc = launch_title_order(desc->n_seq, S, ids, order, order_cnt, s_prep, 3);
+            // (the title lists serve the 32-row kernels only: the 64-row ones take the titles in index order)
+            rc = S <= 32 ? launch_title_order(desc->n_seq, S, ids, order, order_cnt, s_prep, 3) : NRMS_OK;
             if (rc) { (void)join_prep(); return rc; }
             rc = launch_compact_live_rows(M, ids, live, pos, n_live, (int*)(base + fs.cscr), s);
             if (rc == NRMS_OK) rc = launch_gather16(M, d, L.KP, ids, live, n_live, w->table, drop_e, acts->x, s);
@@ -346,7 +347,7 @@ static int encoder_fwd16(const nrms_encoder_desc* desc, const nrms_encoder_weigh
             f.pos = pos;
             f.n_rows = n_live;
             f.ids = ids;
-            f.order = order; f.order_cnt = order_cnt;
+            if (S <= 32) { f.order = order; f.order_cnt = order_cnt; }
         } else {
             rc = launch_gather16(M, d, L.KP, ids, nullptr, nullptr, w->table, drop_e, acts->x, s);
             if (rc) return rc;
@@ -423,7 +424,7 @@ static int encoder_bwd16(const nrms_encoder_desc* desc, const nrms_encoder_weigh
             live = (int*)(fb + fs.live);
             n_live = (int*)(fb + fs.n_live);
             f.pos = (int*)(fb + fs.pos); f.n_rows_dev = n_live; f.ids = ids;
-            f.order = (int*)(fb + fs.order); f.order_cnt = (int*)(fb + fs.order_cnt);
+            if (S <= 32) { f.order = (int*)(fb + fs.order); f.order_cnt = (int*)(fb + fs.order_cnt); }   // (not built beyond 32 rows)
         } else {
             // the forward's scratch may have been reused by later forward calls: rebuild the lists
             int* pos = (int*)(base + L.pos);
@@ -432,9 +433,12 @@ static int encoder_bwd16(const nrms_encoder_desc* desc, const nrms_encoder_weigh
             if (skip_pad_rows(desc)) {
                 int* order = (int*)(base + L.order);
                 int* order_cnt = (int*)(base + L.order_cnt);
-                rc = launch_title_order(desc->n_seq, S, ids, order, order_cnt, s, 3);
-                if (rc) return rc;
-                f.pos = pos; f.n_rows_dev = n_live; f.ids = ids; f.order = order; f.order_cnt = order_cnt;
+                f.pos = pos; f.n_rows_dev = n_live; f.ids = ids;
+                if (S <= 32) {                      // the 64-row kernels take the titles in index order: no lists for them
+                    rc = launch_title_order(desc->n_seq, S, ids, order, order_cnt, s, 3);
+                    if (rc) return rc;
+                    f.order = order; f.order_cnt = order_cnt;
+                }
             }
         }
         f.dx = (float*)(base + L.dxc);
@@ -689,7 +693,10 @@ extern "C" int nrms_encoder_bwd_wqkv(const nrms_encoder_desc* desc, const int64_
     NRMS_REQUIRE(gather ? (ids != nullptr && acts->x != nullptr) : (x != nullptr), "encoder_bwd_wqkv: input missing");
     if (desc->n_seq == 0) return NRMS_OK;
     const BwdWorkspace L = bwd_layout(desc);
-    NRMS_REQUIRE(workspace_bytes >= L.total, "encoder_bwd_wqkv: workspace %zu < required %zu bytes", workspace_bytes, L.total);
+    if (workspace_bytes < L.total) {
+        set_error("encoder_bwd_wqkv: workspace %zu < required %zu bytes", workspace_bytes, L.total);
+        return NRMS_EWORKSPACE;
+    }
     char* base = (char*)workspace;
     return bwd_wqkv(desc, gather ? acts->x : x, (const float*)(base + L.dqkv), (const int*)(base + L.n_live), grads,
                     (float*)(base + L.tn_partial), (hipStream_t)stream);

@@ -4,6 +4,8 @@
 // reference runs 55 times per step -- SURVEY.md a-1).
 #include "gemm.h"
 
+#include <algorithm>
+
 namespace nrms {
 
 // x[m, :] = table[ids[m], :] * keep(m, :) / (1 - p).   One float4 per lane, rows walked in
@@ -358,7 +360,11 @@ __global__ __launch_bounds__(256) void scatter_grouped_kernel(int V, int d4, con
     }
 }
 
-size_t scatter_grouped_scratch_ints(long M, int V) { return (size_t)2 * (V + 64) + (size_t)M + 64; }
+// cnt [V + 64] | cursor [V + 64] | order [max(M, ceil(V / 1024)) + 64].  The last region is the bucket array of the M tokens
+// and, before the placement fills it, the block totals of the scan over the V counts (one per 1024 ids): with a large
+// vocabulary and a tiny batch (V = 300 000, M = 8: 293 totals) the totals are the longer of the two
+static size_t scan_blocks(int V) { return (size_t)cdiv(V, 1024); }
+size_t scatter_grouped_scratch_ints(long M, int V) { return (size_t)2 * (V + 64) + std::max((size_t)M, scan_blocks(V)) + 64; }
 
 // The lists the grouped scatter walks (per table row: the compact rows of its occurrences, ascending) depend on the ids only:
 // a caller may build them early, on another stream (the fp16 backward does, beside its fused kernels), and pass prepared = true.
@@ -367,7 +373,7 @@ int launch_scatter_prepare(long M, int V, const int64_t* ids, const int* live, c
     int* cnt = scratch;                       // [V] counts -> exclusive offsets (in place)
     int* cursor = cnt + V + 64;               // [V]
     int* total = cursor + V;                  // [1]
-    int* order = cursor + V + 64;             // [M]
+    int* order = cursor + V + 64;             // [max(M, scan_blocks(V))]
     if (hipMemsetAsync(cnt, 0, (size_t)(2 * (V + 64)) * sizeof(int), stream) != hipSuccess) {
         set_error("scatter_grouped: memset failed");
         return NRMS_ELAUNCH;
@@ -377,8 +383,8 @@ int launch_scatter_prepare(long M, int V, const int64_t* ids, const int* live, c
     TimingScope ts("scatter_prepare", stream);
     hipLaunchKernelGGL(tok_hist_kernel, dim3(blocks), dim3(256), 0, stream, ids, live, n_live, cnt);
     {
-        const int nb = cdiv(V, 1024);
-        int* bsum = order;                    // [nb] block totals: the bucket array is free until the placement
+        const int nb = (int)scan_blocks(V);
+        int* bsum = order;                    // [nb] block totals: the bucket array is free until the placement (and sized for both)
         hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(1024), 0, stream, V, cnt, bsum);
         hipLaunchKernelGGL(scan_add_kernel, dim3(nb), dim3(1024), 0, stream, V, nb, cnt, bsum, total);
     }

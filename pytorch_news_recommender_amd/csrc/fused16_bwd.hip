@@ -1252,9 +1252,15 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
     }
     Bwd16Args a{};
     a.n_seq = f.n_seq; a.S = f.S; a.d = f.d; a.h = f.h; a.dk = dk; a.q = f.q;
-    a.n_groups = cdiv(f.n_seq, F16_WAVES) + (f.order != nullptr ? 2 : 0);      // three lists: up to two more partial groups
-    a.n_cls = f.order != nullptr ? 3 : 2;                                       // (launch_title_order(..., 3) by the caller)
-    a.x16 = (const _Float16*)f.x16; a.pos = f.pos; a.n_rows = f.n_rows_dev; a.ids = f.ids; a.order = f.order; a.order_cnt = f.order_cnt;
+    // The three title lists serve the 32-row kernels only (two short titles per tile, all-padding titles in closed form).  The
+    // 64-row kernels take the titles in index order, as the forward does (launch_fused_fwd16): handed the lists they walked the
+    // long ones only and left the dQKV rows of every short title (a prefix of 1 .. 15 words) unwritten -- dX, the table gradient
+    // and d(W_qkv) then read whatever the workspace held (tests/test_hip_buffer_contracts.py)
+    const bool lists = f.order != nullptr && f.S <= 32;
+    a.n_groups = cdiv(f.n_seq, F16_WAVES) + (lists ? 2 : 0);                    // three lists: up to two more partial groups
+    a.n_cls = lists ? 3 : 2;                                                    // (launch_title_order(..., 3) by the caller)
+    a.x16 = (const _Float16*)f.x16; a.pos = f.pos; a.n_rows = f.n_rows_dev; a.ids = f.ids;
+    a.order = lists ? f.order : nullptr; a.order_cnt = lists ? f.order_cnt : nullptr;
     a.btiles = btiles; a.bqkv32 = bqkv32; a.qv16 = qv16;
     a.ctx16 = (const _Float16*)f.ctx16; a.t16 = (const _Float16*)f.t16; a.w = f.w; a.dout16 = dout16;
     a.dz16 = dz16; a.dctx16 = dctx16; a.dqkv16 = dqkv16; a.red = red; a.drop = f.drop;

@@ -368,7 +368,11 @@ extern "C" int nrms_hier_tree_build(int32_t B, int32_t H, const uint8_t* valid, 
     if (B == 0) return NRMS_OK;
     NRMS_REQUIRE(valid && topic && subtopic && l1_ptr && l1_idx && l1_sub && l1_top && l1_cnt && l2_ptr && l2_idx && l2_top && l2_cnt &&
                  l3_ptr && l3_idx && n_valid && scratch, "hier_tree_build: null argument");
-    NRMS_REQUIRE(scratch_bytes >= nrms_hier_tree_scratch_bytes(B, H) && ((uintptr_t)scratch & 7) == 0, "hier_tree_build: scratch too small / unaligned");
+    if (scratch_bytes < nrms_hier_tree_scratch_bytes(B, H)) {
+        set_error("hier_tree_build: scratch %zu < required %zu bytes", scratch_bytes, nrms_hier_tree_scratch_bytes(B, H));
+        return NRMS_EWORKSPACE;
+    }
+    NRMS_REQUIRE(((uintptr_t)scratch & 7) == 0, "hier_tree_build: scratch must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* m1 = (unsigned long long*)scratch;
     unsigned long long* m2 = m1 + (size_t)B * H;

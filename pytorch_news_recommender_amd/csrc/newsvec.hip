@@ -338,7 +338,11 @@ extern "C" int nrms_newsvec_rows_fwd(int64_t n_rows, int32_t d, int32_t precisio
                  "newsvec_rows_fwd: precision %d", precision);
     NRMS_REQUIRE(table && w && b && out, "newsvec_rows_fwd: null argument");
     const size_t need = nrms_newsvec_rows_workspace_bytes(n_rows, d, precision);
-    NRMS_REQUIRE(workspace_bytes >= need && workspace != nullptr, "newsvec_rows_fwd: workspace %zu < %zu bytes", workspace_bytes, need);
+    NRMS_REQUIRE(workspace != nullptr, "newsvec_rows_fwd: null workspace");
+    if (workspace_bytes < need) {
+        set_error("newsvec_rows_fwd: workspace %zu < required %zu bytes", workspace_bytes, need);
+        return NRMS_EWORKSPACE;
+    }
     if (n_rows == 0) return NRMS_OK;
     nrms_newsvec_desc dd{};
     dd.precision = precision;

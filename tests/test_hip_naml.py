@@ -150,6 +150,9 @@ def test_dropout_replay_against_oracle(mode, geom):
     assert np.abs(s2[live] - scores[live]).max() > 1e-3
 
 
+LN_TOL = dict(y=3e-6, dx=5e-6, dgb=2e-5, rtol=1e-4)      # absolute bounds of y, dx, d(gamma) | d(beta); rtol of the gradients
+
+
 def test_layernorm_alone():
     """nrms_layernorm_fwd / _bwd against torch on the GPU tensors (the feature rows are covered by g7 and the replay)."""
     import ctypes as C
@@ -167,7 +170,7 @@ def test_layernorm_alone():
     xr = x.clone().requires_grad_(True)
     wr, br = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
     yr = torch.nn.functional.layer_norm(xr, (F,), wr, br, 1e-5)
-    np.testing.assert_allclose(y.cpu().numpy(), yr.detach().cpu().numpy(), rtol=0, atol=3e-6)
+    np.testing.assert_allclose(y.cpu().numpy(), yr.detach().cpu().numpy(), rtol=0, atol=LN_TOL["y"])
     dy = torch.randn(37, F, generator=g).to(dev)
     yr.backward(dy)
     dx = torch.empty_like(x)
@@ -177,9 +180,9 @@ def test_layernorm_alone():
     rc = eng.lib.nrms_layernorm_bwd(C.c_int64(37), F, _lib.ptr(x), _lib.ptr(w.contiguous()), _lib.ptr(stats), _lib.ptr(dy),
                                     _lib.ptr(dx), _lib.ptr(dgb), _lib.ptr(ws), C.c_size_t(ws.numel() * 4), stream)
     _lib.check(rc, "nrms_layernorm_bwd")
-    np.testing.assert_allclose(dx.cpu().numpy(), xr.grad.cpu().numpy(), rtol=1e-4, atol=5e-6)
-    np.testing.assert_allclose(dgb[:F].cpu().numpy(), wr.grad.cpu().numpy(), rtol=1e-4, atol=2e-5)
-    np.testing.assert_allclose(dgb[F:].cpu().numpy(), br.grad.cpu().numpy(), rtol=1e-4, atol=2e-5)
+    np.testing.assert_allclose(dx.cpu().numpy(), xr.grad.cpu().numpy(), rtol=LN_TOL["rtol"], atol=LN_TOL["dx"])
+    np.testing.assert_allclose(dgb[:F].cpu().numpy(), wr.grad.cpu().numpy(), rtol=LN_TOL["rtol"], atol=LN_TOL["dgb"])
+    np.testing.assert_allclose(dgb[F:].cpu().numpy(), br.grad.cpu().numpy(), rtol=LN_TOL["rtol"], atol=LN_TOL["dgb"])
     # workspace too small -> NRMS_EWORKSPACE, reported as NrmsError
     rc = eng.lib.nrms_layernorm_bwd(C.c_int64(37), F, _lib.ptr(x), _lib.ptr(w.contiguous()), _lib.ptr(stats), _lib.ptr(dy),
                                     _lib.ptr(dx), _lib.ptr(dgb), _lib.ptr(ws), C.c_size_t(16), stream)

@@ -374,7 +374,14 @@ def test_padding_token_skip_equals_dense_path(precision):
     assert model.engine.pad_row_zero is False
 
 
-@pytest.mark.parametrize("precision,score_tol,grad_rtol", [("bf16", 5e-3, 6e-2)])
+# plain bf16 (never a default): score / vector bar and gradient bar relative to a tensor's scale.  BF16_CANCEL_FLOOR: for ONE encoder
+# pass (tests/test_hip_buffer_contracts.py) the tensors whose terms cancel (b_add: |gradient| ~ 3e-5 beside tensors of 1e-1) get the
+# floor the fp16 bars grant them (tests/test_hip_fuzz.py: 1e-4 of the largest tensor's scale) -- bf16 operands carry 8 significant
+# bits, fp16 ones 11, so the coarser format cannot be held to a smaller floor
+BF16_SCORE_TOL, BF16_GRAD_RTOL, BF16_CANCEL_FLOOR = 5e-3, 6e-2, 1e-4
+
+
+@pytest.mark.parametrize("precision,score_tol,grad_rtol", [("bf16", BF16_SCORE_TOL, BF16_GRAD_RTOL)])
 def test_reduced_precision_modes(golden_dir, precision, score_tol, grad_rtol):
     """Plain bf16 projections against the REFERENCE fixture: reported with a loose bound (it cannot meet
     north_star's 1e-4 score bar and is never a default).  bf16x3 is covered like fp32 by every test above."""

@@ -8,6 +8,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+OUT_TOL = {"fp32": 1e-5, "bf16x3": 2e-5}                # of max(1, max |out|)
+
+
+def grad_bound(ref):
+    """Elementwise bound of dx, dW, db, dq (ref: a torch tensor)."""
+    return 1e-3 * ref.abs() + 2e-5 * float(ref.abs().max()) + 1e-9
+
+
 def _case(R, n_seg, d, q, seed, partition, empty_some=True, max_len=40):
     rng = np.random.default_rng(seed)
     x = (rng.standard_normal((R, d)) * 0.5).astype(np.float32)
@@ -51,13 +59,13 @@ def test_segment_pool_forward_and_gradients_against_the_oracle(case, precision):
     hx, hw, hb, hq = (torch.from_numpy(a).to(dev).requires_grad_(True) for a in (x, w, b, qv))
     out = segment_pool(hx, hw, hb, hq, torch.from_numpy(ptr).to(dev), torch.from_numpy(idx).to(dev), precision=precision, rows_unique=partition)
     (out * g.to(dev)).sum().backward()
-    tol = 1e-5 if precision == "fp32" else 2e-5
+    tol = OUT_TOL[precision]
     err = float((out.detach().cpu() - o_out.detach()).abs().max())
     print("segpool %-14s %-6s out err %.2e (scale %.2f)" % (case, precision, err, float(o_out.abs().max())))
     assert err < tol * max(1.0, float(o_out.abs().max()))
     for name, h, o in (("dx", hx, ox), ("dW", hw, ow), ("db", hb, ob), ("dq", hq, oq)):
         ref = o.grad
-        bound = 1e-3 * ref.abs() + 2e-5 * float(ref.abs().max()) + 1e-9
+        bound = grad_bound(ref)
         diff = (h.grad.cpu() - ref).abs()
         print("      %-3s err %.2e scale %.2e" % (name, float(diff.max()), float(ref.abs().max())))
         assert bool((diff <= bound).all()), (case, precision, name, float(diff.max()), float(ref.abs().max()))
