@@ -348,6 +348,28 @@ int nrms_topk_grouped_dot(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G,
                           const int32_t* item_ids, const int64_t* group_ptr, const int64_t* exclude, int32_t n_exclude,
                           float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exact rank of given items in nrms_topk_dot's order over the whole catalogue (evaluation: "at which position of all N items
+ * does the model put the item user b clicked next?"), again without the [B, N] score matrix.  user [B, d], items [N, d] fp32
+ * row-major; targets [B, T] int64: the items to rank (-1 is the padding value callers use); exclude [B, n_exclude] int64,
+ * nullable, as nrms_topk_dot's; ranks [B, T] int32; target_scores [B, T] fp32, nullable.
+ * Score, eligibility and order are nrms_topk_dot's: the same fp32 chain on v_mfma_f32_32x32x2_f32 per (user row, item row),
+ *   one accumulator over all of d in the same k order, so the same bits; n is eligible if it is not in exclude[b, :] and
+ *   s(b, n) is not NaN; score descending, equal scores put the SMALLER n first, -0.0 equals +0.0.
+ * Rank.  For a valid target t = targets[b, j]:  ranks[b, j] = 1 + #{eligible n : (s(b, n), n) precedes (s(b, t), t)}, the
+ *   1-based position t would have in nrms_topk_dot's row b were k unbounded; target_scores[b, j] = s(b, t) (-0.0 as +0.0).
+ *   Targets do not remove each other: each is ranked against the whole eligible catalogue, duplicates get equal ranks.
+ * Invalid targets.  A target outside [0, N), an excluded one and one whose score is NaN get rank 0 and score -inf.
+ * Limits: 1 <= T <= 32, d >= 1, 0 <= N <= 0x7FFF0000, B >= 0, n_exclude >= 0; B = 0 is a no-op, N = 0 writes rank 0 / -inf
+ *   everywhere.
+ * Counts are integers: two runs are bit-identical, and the result does not depend on B, the user's position in the batch, T,
+ *   the other targets, the launch geometry or what the workspace held.
+ * Workspace: nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude) bytes, 8-byte aligned, O(B * (T + n_exclude))
+ *   (0 = arguments rejected).  Three kernels on `stream`, no host synchronisation, no allocation. */
+size_t nrms_rank_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude);
+int nrms_rank_dot(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const int64_t* targets,
+                  const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ---- nrms_naml pieces around the two encoder passes (model/nrms_naml.py) ----
  * LayerNorm over the last dimension (nn.LayerNorm(news_feature_size) on the history vectors, nrms_naml.py:207,238):
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance.  stats [n_rows, 2] = (mean, 1/std) is written when

@@ -1,0 +1,347 @@
+// Exact rank of given items in nrms_topk_dot's order over a whole catalogue, without a [B, N] score matrix
+// (include/nrms_hip.h: nrms_rank_dot, whose header comment states the contract).
+//
+// rank(b, t) = 1 + #{eligible n : entry(s(b, n), n) > entry(s(b, t), t)}, with the uint64 entry of topk_entry.h, so "precedes"
+// is one integer compare and the counts are integers.  Three kernels:
+// A (rank_entries_kernel): per 32-user tile the score chain over the GATHERED rows its users name, T targets and n_exclude
+//   excluded ids each, 64 rows per wave; the entry of list position m of user b goes to ent[b][m] (0: id outside [0, N) or
+//   NaN score).  The 32 x 32 MFMA tile scores every gathered row against all 32 users; only the owner's score is kept.
+// B (rank_count_kernel): the grid and MFMA loop of topk_slice_kernel (32-user tiles x catalogue slices, two 32 x 32 tiles
+//   per wave).  Every live, non-NaN score's entry is compared with its user's T target entries in LDS; a __ballot per
+//   (accumulator register, target) gives, in its two halves, the number of the 32 items above the target for the two users
+//   the register holds, and lane (j, h) keeps the running count of target j for the user of half h: 16 counters per lane.
+//   Counts go to LDS, then to counts[b][j] with one integer atomic per (block, user, target).
+// C (rank_finish_kernel): per user, the excluded ids pass B counted are taken back out: every distinct, in-range, non-NaN
+//   excluded id whose entry precedes the target's (first occurrence of an id only); targets that are excluded, out of range
+//   or NaN get rank 0 / score -inf.
+//
+// The chain is topk_slice_kernel's, restated in rk_chain (same operand staging, same k order, one accumulator):
+// tests/test_hip_rank.py pins the score bits to nrms_topk_dot's.
+#include "topk_entry.h"
+
+namespace nrms {
+
+constexpr int RK_MAX_T = 32;
+constexpr int RK_A_CHUNKS = 4096;              // grid.y bound of kernel A (longer gathered lists are walked in a loop)
+
+// One wave: acc[c] += the 32 x 32 score tile of user rows arow (lane (r, h): the row of user r) against item rows
+// row_of(32 c + 0 .. 31), c = 0, 1.  row_of(i), i in [0, 64): a valid row of `items` (callers clamp).  topk_slice_kernel's
+// chain: each whole block of 32 floats of k is staged in the wave's LDS block st through coalesced loads (lane l of load j
+// reads row 8j + l / 8, floats 4 (l % 8) .. + 3) and read back in the MFMA layout, the next block is loaded while the MFMAs
+// of this one run; MFMA t of block m sums k = 32m + t (h = 0) and 32m + 16 + t (h = 1); the rest of d goes in zero-padded
+// groups of 8.
+template <bool VEC, class RowOf>
+__device__ __forceinline__ void rk_chain(tk_f32x16 (&acc)[TK_TN], const float* arow, const float* __restrict__ items, int d,
+                                         float* st, int lane, RowOf row_of) {
+    const int r = lane & 31, h = lane >> 5;
+    const int m_full = d / 32;
+    const float* srow[8];           // rows this lane stages: 8j + lane / 8
+#pragma unroll
+    for (int j = 0; j < 8; ++j) srow[j] = items + (long)row_of(8 * j + (lane >> 3)) * d + 4 * (lane & 7);
+#define RK_GLOAD(m)                                                                                                        \
+    do {                                                                                                               \
+        const int k0_ = 32 * (m);                                                                                      \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                                \
+            if (VEC) {                                                                                                 \
+                const float4 v_ = *reinterpret_cast<const float4*>(srow[j] + k0_);                                     \
+                g[j][0] = v_.x; g[j][1] = v_.y; g[j][2] = v_.z; g[j][3] = v_.w;                                        \
+            } else {                                                                                                   \
+                _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) g[j][e_] = srow[j][k0_ + e_];                         \
+            }                                                                                                          \
+        }                                                                                                              \
+        _Pragma("unroll") for (int t = 0; t < 16; ++t) a[t] = arow[k0_ + 16 * h + t];                                  \
+    } while (0)
+    if (m_full > 0) {
+        float g[8][4];
+        float a[16];
+        RK_GLOAD(0);
+        for (int m = 0; m < m_full; ++m) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                *reinterpret_cast<float4*>(st + (8 * j + (lane >> 3)) * TK_BP + 4 * (lane & 7)) =
+                    make_float4(g[j][0], g[j][1], g[j][2], g[j][3]);
+            tk_wave_sync();
+            float b[TK_TN][16];
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float4 v = *reinterpret_cast<const float4*>(st + (32 * c + r) * TK_BP + 16 * h + 4 * t);
+                    b[c][4 * t] = v.x; b[c][4 * t + 1] = v.y; b[c][4 * t + 2] = v.z; b[c][4 * t + 3] = v.w;
+                }
+            float acur[16];
+#pragma unroll
+            for (int t = 0; t < 16; ++t) acur[t] = a[t];
+            if (m + 1 < m_full) RK_GLOAD(m + 1);
+#pragma unroll
+            for (int t = 0; t < 16; ++t)
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[t], b[c][t], acc[c], 0, 0, 0);
+            tk_wave_sync();        // this block's LDS reads stay ahead of the next block's writes
+        }
+    }
+#undef RK_GLOAD
+    for (int g8 = 4 * m_full; 8 * g8 < d; ++g8) {       // zero-padded groups of 8 past the last whole block
+        const int k0 = 8 * g8 + 4 * h;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float at = tk_ld(arow, k0 + t, d);
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) {
+                const float* brow = items + (long)row_of(32 * c + r) * d;
+                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(at, tk_ld(brow, k0 + t, d), acc[c], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// Kernel A.  One wave per block; block (x, y): user tile x, gathered positions 64 (y + i gridDim.y) .. + 63 of the tile's list
+// of 32 M ids, M = T + n_exclude: position g is list slot m = g % M of user u0 + g / M (slots [0, T): targets, then the
+// exclude ids).  ent [B, M].  Blocks y = 0 also zero the tile's counts [B, T] for kernel B.  Needs N >= 1.
+template <bool VEC>
+__global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, int T, int n_exclude,
+                                                          const float* __restrict__ user, const float* __restrict__ items,
+                                                          const int64_t* __restrict__ targets,
+                                                          const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
+                                                          uint32_t* __restrict__ counts) {
+    __shared__ int rows[64];
+    __shared__ __attribute__((aligned(16))) float stage[64 * TK_BP];
+    const int lane = threadIdx.x;
+    const int r = lane & 31, h = lane >> 5;
+    const int u0 = blockIdx.x * TK_UT;
+    const int M = T + n_exclude;
+    const long total = (long)TK_UT * M;
+    if (blockIdx.y == 0)
+        for (int i = lane; i < TK_UT * T; i += 64) {
+            const int b = u0 + i / T;
+            if (b < B) counts[(long)b * T + (i % T)] = 0;
+        }
+    const float* arow = user + (long)min(u0 + r, B - 1) * d;
+    for (long g0 = 64L * blockIdx.y; g0 < total; g0 += 64L * gridDim.y) {
+        // this lane's own list position: the id it names, and the row the wave reads for it (row 0 for an id that names none)
+        const long g = g0 + lane;
+        const int u = (int)(g / M), m = (int)(g - (long)u * M);
+        const int b = u0 + u;
+        int64_t id = -1;
+        if (g < total && b < B) id = m < T ? targets[(long)b * T + m] : exclude[(long)b * n_exclude + (m - T)];
+        const bool in_range = id >= 0 && id < N;
+        tk_wave_sync();            // the previous round's reads of rows
+        rows[lane] = in_range ? (int)id : 0;
+        tk_wave_sync();
+        tk_f32x16 acc[TK_TN];
+#pragma unroll
+        for (int c = 0; c < TK_TN; ++c) acc[c] = tk_f32x16{};
+        rk_chain<VEC>(acc, arow, items, d, stage, lane, [&](int i) { return rows[i]; });
+        // C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5): the score of
+        // position g0 + 32 c + r against its owner u sits in half (u >> 2) & 1, register (u & 3) + 4 (u >> 3)
+#pragma unroll
+        for (int c = 0; c < TK_TN; ++c) {
+            const long gc = g0 + 32 * c + r;
+            const int uc = (int)(gc / M), mc = (int)(gc - (long)uc * M);
+            const int64_t idc = __shfl(id, 32 * c + r, 64);
+            if (gc >= total || u0 + uc >= B || ((uc >> 2) & 1) != h) continue;
+            const int qw = (uc & 3) + 4 * (uc >> 3);
+            float s = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) s = q == qw ? acc[c][q] : s;
+            const bool ok = idc >= 0 && idc < N && !__builtin_isnan(s);
+            ent[(long)(u0 + uc) * M + mc] = ok ? tk_entry(s, (uint32_t)idc) : 0;
+        }
+    }
+}
+
+// Kernel B.  Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step.  ent [B, M]:
+// the first T entries of a row are the user's targets.  counts [B, T] += #{live non-NaN n in the slice : entry(n) > target}.
+template <int W, bool VEC>
+__global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d, int T, int M, int slice_len,
+                                                            const float* __restrict__ user, const float* __restrict__ items,
+                                                            const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts) {
+    __shared__ uint64_t tgt[TK_UT][RK_MAX_T];
+    __shared__ uint32_t cnts[TK_UT][RK_MAX_T];
+    __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
+    constexpr int IT = 64 * W;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int u0 = blockIdx.x * TK_UT;
+    const int n_begin = blockIdx.y * slice_len;
+    const int n_end = min(N, n_begin + slice_len);
+
+    for (int i = threadIdx.x; i < TK_UT * RK_MAX_T; i += 64 * W) {
+        const int u = i / RK_MAX_T, j = i % RK_MAX_T;
+        tgt[u][j] = (u0 + u < B && j < T) ? ent[(long)(u0 + u) * M + j] : ~0ull;
+        cnts[u][j] = 0;
+    }
+    __syncthreads();
+
+    const int r = lane & 31, h = lane >> 5;
+    const float* arow = user + (long)min(u0 + r, B - 1) * d;
+    float* st = stage[wave];
+    uint32_t cnt[16] = {};          // lane (j, h): items above target j of user (q & 3) + 8 (q >> 2) + 4 h
+    for (int n0 = n_begin; n0 < n_end; n0 += IT) {
+        const int nw = n0 + 64 * wave;
+        if (nw >= n_end) continue;
+        tk_f32x16 acc[TK_TN];
+#pragma unroll
+        for (int c = 0; c < TK_TN; ++c) acc[c] = tk_f32x16{};
+        rk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
+        // C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
+        uint64_t e[TK_TN][16];
+#pragma unroll
+        for (int c = 0; c < TK_TN; ++c) {
+            const int n = nw + 32 * c + r;
+            const bool live = n < n_end;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const float s = acc[c][q];
+                e[c][q] = (live && !__builtin_isnan(s)) ? tk_entry(s, (uint32_t)n) : 0;       // 0 precedes nothing
+            }
+        }
+        for (int j = 0; j < T; ++j) {
+            uint64_t t[16];          // target j of this half's 16 users: 16 independent LDS reads, two addresses each
+#pragma unroll
+            for (int q = 0; q < 16; ++q) t[q] = tgt[(q & 3) + 8 * (q >> 2) + 4 * h][j];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                uint32_t above = 0;
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) {
+                    const unsigned long long m = __ballot(e[c][q] > t[q]);
+                    above += __popc(h ? (uint32_t)(m >> 32) : (uint32_t)m);
+                }
+                if (r == j) cnt[q] += above;
+            }
+        }
+    }
+    if (r < T) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if (cnt[q]) atomicAdd(&cnts[(q & 3) + 8 * (q >> 2) + 4 * h][r], cnt[q]);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < TK_UT * RK_MAX_T; i += 64 * W) {
+        const int u = i / RK_MAX_T, j = i % RK_MAX_T;
+        if (u0 + u < B && j < T && cnts[u][j]) atomicAdd(&counts[(long)(u0 + u) * T + j], cnts[u][j]);
+    }
+}
+
+// Kernel C.  One wave per user.  N = 0: every target is invalid (ent and counts are not read).
+__global__ __launch_bounds__(64) void rank_finish_kernel(int B, int N, int T, int n_exclude, const int64_t* __restrict__ targets,
+                                                         const int64_t* __restrict__ exclude, uint64_t* ent,
+                                                         const uint32_t* __restrict__ counts, int32_t* __restrict__ ranks,
+                                                         float* __restrict__ target_scores) {
+    const int lane = threadIdx.x;
+    const long b = blockIdx.x;
+    if (N == 0) {
+        if (lane < T) {
+            ranks[b * T + lane] = 0;
+            if (target_scores) target_scores[b * T + lane] = -__builtin_huge_valf();
+        }
+        return;
+    }
+    const int M = T + n_exclude;
+    uint64_t* eb = ent + b * M;
+    const int64_t* xb = exclude + b * n_exclude;           // (never read when n_exclude = 0)
+    // an id listed twice is taken back out once: only its first occurrence keeps its entry
+    for (int x = lane; x < n_exclude; x += 64) {
+        if (!eb[T + x]) continue;
+        const int64_t id = xb[x];
+        bool dup = false;
+        for (int y = 0; y < x; ++y) dup |= xb[y] == id;
+        if (dup) eb[T + x] = 0;
+    }
+    __syncthreads();
+    if (lane < T) {
+        const uint64_t et = eb[lane];
+        const int64_t id = targets[b * T + lane];
+        bool out = false;
+        uint32_t sub = 0;
+        for (int x = 0; x < n_exclude; ++x) {
+            out |= xb[x] == id;
+            sub += eb[T + x] > et;
+        }
+        const bool valid = et != 0 && !out;
+        ranks[b * T + lane] = valid ? (int32_t)(1u + counts[b * T + lane] - sub) : 0;
+        if (target_scores) target_scores[b * T + lane] = valid ? tk_entry_score(et) : -__builtin_huge_valf();
+    }
+}
+
+struct RankGeom {
+    int tiles, S, slice_len;
+};
+
+// Slices so that tiles x S is about one 8-wave block per CU; whole block steps per slice.
+static RankGeom rank_geom(int32_t B, int64_t N) {
+    RankGeom g{cdiv(B, TK_UT), 0, 0};
+    if (N == 0 || B == 0) return g;
+    const int s = std::max(1, cdiv(TK_TARGET_BLOCKS, g.tiles));
+    g.slice_len = cdiv(cdiv(N, s), TK_IT) * TK_IT;
+    g.S = cdiv(N, g.slice_len);
+    return g;
+}
+
+static bool rank_args_ok(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude) {
+    return B >= 0 && N >= 0 && N <= TK_MAX_N && d >= 1 && T >= 1 && T <= RK_MAX_T && n_exclude >= 0;
+}
+
+static size_t rank_entry_bytes(int32_t B, int32_t T, int32_t n_exclude) {
+    return ((size_t)B * ((size_t)T + (size_t)n_exclude) * sizeof(uint64_t) + 255) / 256 * 256;
+}
+
+}  // namespace nrms
+
+using namespace nrms;
+
+extern "C" size_t nrms_rank_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude) {
+    if (!rank_args_ok(B, N, d, T, n_exclude)) return 0;
+    // the entries [B, T + n_exclude] and the counts [B, T]; never 0 for accepted arguments
+    return 256 + rank_entry_bytes(B, T, n_exclude) + (size_t)B * (size_t)T * sizeof(uint32_t);
+}
+
+extern "C" int nrms_rank_dot(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                             const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                             float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
+    NRMS_REQUIRE(B >= 0, "rank_dot: B must be >= 0 (B=%d)", B);
+    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "rank_dot: N must be in [0, %d] (N=%lld)", TK_MAX_N, (long long)N);
+    NRMS_REQUIRE(d >= 1, "rank_dot: d must be >= 1 (d=%d)", d);
+    NRMS_REQUIRE(T >= 1 && T <= RK_MAX_T, "rank_dot: T must be in [1, %d] (T=%d)", RK_MAX_T, T);
+    NRMS_REQUIRE(n_exclude >= 0, "rank_dot: n_exclude must be >= 0 (n_exclude=%d)", n_exclude);
+    if (B == 0) return NRMS_OK;
+    NRMS_REQUIRE(user, "rank_dot: user is null");
+    NRMS_REQUIRE(items || N == 0, "rank_dot: items is null");
+    NRMS_REQUIRE(targets, "rank_dot: targets is null");
+    NRMS_REQUIRE(ranks, "rank_dot: ranks is null");
+    NRMS_REQUIRE(workspace, "rank_dot: workspace is null");
+    if (!exclude) n_exclude = 0;
+    const size_t need = nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude);
+    if (workspace_bytes < need) {
+        set_error("rank_dot: workspace %zu < required %zu bytes", workspace_bytes, need);
+        return NRMS_EWORKSPACE;
+    }
+    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "rank_dot: workspace must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    TimingScope ts("rank_dot", s);
+    uint64_t* ent = (uint64_t*)workspace;
+    uint32_t* counts = (uint32_t*)((char*)workspace + rank_entry_bytes(B, T, n_exclude));
+    const RankGeom g = rank_geom(B, N);
+    const int n = (int)N, M = T + n_exclude;
+    if (g.S > 0) {
+        const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
+        const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64));
+        if (vec) hipLaunchKernelGGL(rank_entries_kernel<true>, grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
+                                    exclude, ent, counts);
+        else hipLaunchKernelGGL(rank_entries_kernel<false>, grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
+                                exclude, ent, counts);
+        int rc = check_launch("rank_dot(entries)");
+        if (rc != NRMS_OK) return rc;
+        const dim3 grid_b(g.tiles, g.S);
+        if (vec) hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, true>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M,
+                                    g.slice_len, user, items, ent, counts);
+        else hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, false>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M,
+                                g.slice_len, user, items, ent, counts);
+        rc = check_launch("rank_dot(count)");
+        if (rc != NRMS_OK) return rc;
+    }
+    hipLaunchKernelGGL(rank_finish_kernel, dim3(B), dim3(64), 0, s, B, n, T, n_exclude, targets, exclude, ent, counts, ranks,
+                       target_scores);
+    return check_launch("rank_dot(finish)");
+}

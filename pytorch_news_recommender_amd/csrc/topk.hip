@@ -18,48 +18,18 @@
 // group, is laid out in 32-row tiles that never straddle a group (each group padded to a whole number of tiles; the table is
 // written by topk_tiles_kernel into the workspace), so every MFMA column tile has one A operand, the tile's group's query
 // rows.  Scores keep the chain of nrms_topk_dot, and entries carry item_ids[row] instead of the row.
-#include "common.h"
+#include "topk_entry.h"      // the entry, the tile constants and the helpers rankdot.hip shares
 
 namespace nrms {
 
-constexpr int TK_UT = 32;                      // users per block (the MFMA's 32 rows)
-constexpr int TK_WAVES = 8;                    // waves per block (k <= 192; 2 for larger k, whose buffers fill the LDS)
-constexpr int TK_TN = 2;                       // 32-item column tiles per wave
-constexpr int TK_BP = 36;                      // LDS row pitch (floats) of a wave's staged 64 x 32 item block
-constexpr int TK_IT = 32 * TK_TN * TK_WAVES;   // catalogue items per block step at the largest wave count
 constexpr int TK_EX_LDS = 64;                  // exclude lists up to this long are staged in LDS, longer ones read globally
 constexpr int TK_MAX_K = 256;
-constexpr int TK_TARGET_BLOCKS = 256;          // one 8-wave block per CU on 256 CUs
 constexpr int TK_MIN_SLICE = 4 * TK_IT;        // no slice shorter than this: each slice list costs k workspace entries
-constexpr int TK_MAX_N = 0x7FFF0000;           // ids are held in 32 bits
-
-typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
 
 // One 32-row tile of a grouped catalogue: rows [row, row + len) of group grp (len 0: an unused tile past the last group).
 struct TkTile {
     int row, len, grp, pad;
 };
-
-__device__ __forceinline__ uint64_t tk_entry(float s, uint32_t id) {
-    uint32_t u = __float_as_uint(s == 0.0f ? 0.0f : s);       // -0.0 == +0.0
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)u << 32) | (uint64_t)(0xFFFFFFFFu - id);
-}
-
-__device__ __forceinline__ float tk_entry_score(uint64_t e) {
-    const uint32_t u = (uint32_t)(e >> 32);
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-
-__device__ __forceinline__ int64_t tk_entry_id(uint64_t e) { return (int64_t)(0xFFFFFFFFu - (uint32_t)e); }
-
-__device__ __forceinline__ void tk_wave_sync() {
-    // LDS operations of one wave execute in issue order; this only stops the compiler from moving LDS accesses across
-    // the passes of a sort
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // One wave sorts buf[0, P) descending (bitonic network; P a power of two).
 template <int P>
@@ -124,8 +94,6 @@ __device__ uint64_t tk_select(uint64_t* buf, int& cnt, int k, int lane) {
     cnt = base;
     return T;
 }
-
-__device__ __forceinline__ float tk_ld(const float* p, int kk, int d) { return kk < d ? p[kk] : 0.0f; }
 
 // One wave: zeroes the entries of buf[0, cnt) whose id user b excludes (ex: the block's LDS copy of its exclude ids in
 // this slice, or the global list when it is longer than TK_EX_LDS).

@@ -633,6 +633,86 @@ class NRMSEngine:
         _lib.check(rc, "nrms_topk_dot")
         return scores, ids
 
+    def rank_of(self, user_vec, items, targets, exclude=None):
+        """user_vec [B, d], items [N, d] fp32, targets [B, T] int64, exclude [B, n_exclude] int64 or None (device, contiguous)
+        -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position of every target in top_k's order over the
+        whole catalogue (the same score bits, exclude list, NaN rule and tie rule), at any depth and without a [B, N] matrix
+        (nrms_rank_dot).  A target outside [0, N) (-1 is the padding value), an excluded one and one with a NaN score come
+        back as rank 0 / score -inf; targets do not remove each other.  The kernel takes 32 targets per call: wider
+        ``targets`` go in column chunks of 32.  include/nrms_hip.h states the contract."""
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32), ("targets", targets, torch.int64)):
+            if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NrmsError("rank_of: %s must be a contiguous 2-D %s tensor on %s (got %s %s on %s%s)"
+                                     % (name, dt, self.device, tuple(t.shape), t.dtype, t.device,
+                                        "" if t.is_contiguous() else ", not contiguous"))
+        B, d = user_vec.shape
+        N = items.shape[0]
+        if items.shape[1] != d:
+            raise _lib.NrmsError("rank_of: items width %d != user_vec width %d" % (items.shape[1], d))
+        if targets.shape[0] != B:
+            raise _lib.NrmsError("rank_of: targets must be [%d, T] (got %s)" % (B, tuple(targets.shape)))
+        n_ex = 0
+        if exclude is not None:
+            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
+                    or not exclude.is_contiguous()):
+                raise _lib.NrmsError("rank_of: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
+                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
+            n_ex = exclude.shape[1]
+            if n_ex == 0:
+                exclude = None
+        T_all = targets.shape[1]
+        ranks = torch.empty(B, T_all, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, T_all, dtype=torch.float32, device=self.device)
+        for t0 in range(0, T_all, 32):
+            T = min(32, T_all - t0)
+            whole = T == T_all
+            tg = targets if whole else targets[:, t0:t0 + T].contiguous()
+            rk = ranks if whole else torch.empty(B, T, dtype=torch.int32, device=self.device)
+            sc = scores if whole else torch.empty(B, T, dtype=torch.float32, device=self.device)
+            nbytes = self.lib.nrms_rank_dot_workspace_bytes(B, N, d, T, n_ex)
+            if nbytes == 0:
+                raise _lib.NrmsError("rank_of: arguments rejected (B=%d, N=%d, d=%d, T=%d, n_exclude=%d)" % (B, N, d, T, n_ex))
+            ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+            rc = self.lib.nrms_rank_dot(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(tg), _lib.ptr(exclude),
+                                        n_ex, _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_rank_dot")
+            if not whole:
+                ranks[:, t0:t0 + T] = rk
+                scores[:, t0:t0 + T] = sc
+        return ranks, scores
+
+    @staticmethod
+    def retrieval_metrics(ranks, ks=(10, 100)):
+        """ranks [B, T] integer (rank_of: 0 = not ranked) -> dict of float64 [B] device tensors ``recall@<k>`` and
+        ``ndcg@<k>`` for every k of ``ks``, and ``mrr``, over each user's n_t = #{j : rank_j > 0} ranked targets:
+            recall@k = #{0 < rank_j <= k} / n_t,        mrr = (sum_j 1 / rank_j) / n_t,
+            ndcg@k   = sum_{0 < rank_j <= k} 1 / log2(rank_j + 1)  /  sum_{r=1}^{min(n_t, k)} 1 / log2(r + 1).
+        This is nrms_impression_metrics's MRR / nDCG with the whole catalogue in place of the impression's shown list.  Every
+        value is NaN for a user with n_t = 0.  Callers pass distinct targets (a duplicate would count twice).  Torch ops on
+        the ranks' device, no host synchronisation."""
+        r = ranks.to(torch.float64)
+        ok = ranks > 0
+        n_t = ok.sum(dim=1)
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=ranks.device)
+        none = n_t == 0
+        den = n_t.clamp(min=1).to(torch.float64)
+        safe = torch.where(ok, r, torch.ones_like(r))
+        out = {"mrr": torch.where(none, nan, torch.where(ok, 1.0 / safe, torch.zeros_like(r)).sum(dim=1) / den)}
+        gain = 1.0 / torch.log2(safe + 1.0)
+        for k in ks:
+            k = int(k)
+            if k < 1:
+                raise ValueError("retrieval_metrics: every k must be >= 1 (got %d)" % k)
+            hit = ok & (ranks <= k)
+            out["recall@%d" % k] = torch.where(none, nan, hit.sum(dim=1).to(torch.float64) / den)
+            # the ideal list puts the n_t targets first: positions 1 .. min(n_t, k); T bounds n_t
+            kk = min(k, max(1, ranks.shape[1]))
+            ideal = torch.cumsum(1.0 / torch.log2(torch.arange(1, kk + 1, dtype=torch.float64, device=ranks.device) + 1.0), 0)
+            idcg = ideal[(n_t.clamp(min=1, max=kk) - 1)]
+            out["ndcg@%d" % k] = torch.where(none, nan, torch.where(hit, gain, torch.zeros_like(r)).sum(dim=1) / idcg)
+        return out
+
     # user chunks of top_k_grouped (and of the HieRec query that feeds it) keep the query plus the workspace under this
     retrieval_chunk_bytes = 256 << 20
 

@@ -209,6 +209,12 @@ class Model(FlatHipModel):
         dev = self._prepare()
         return self._engine.encode_titles(self._flat, nrms_hip._ids_on(dev, titles), tag="news_eval")
 
+    CATALOGUE_RANKING = False
+
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True):
+        raise NotImplementedError("graph: rank_targets is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone (no recommend either)")
+
     def attach_click_graph(self, graph, titles):
         """From now on a batch without ``neighbor_rows`` takes its neighbours from ``graph`` (click_graph.ClickGraph on the
         model's device) instead of the batch-induced host sampler; titles [graph.n_news, L]: the word ids of every news, row r =

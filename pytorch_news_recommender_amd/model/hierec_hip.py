@@ -332,6 +332,11 @@ class Model(FlatHipModel):
 
     _bad_browsed = None
     check_recommend_ids = nrms_hip.Model.check_recommend_ids
+    CATALOGUE_RANKING = False
+
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True):
+        raise NotImplementedError("hierec: rank_targets is not available: HieRec scores the catalogue with a query per (topic, "
+                                  "sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot ranks plain dot products only")
 
     def _zero_frozen_rows(self, gflat):
         # padding_idx = 0 of the two embedding tables: row 0 takes no gradient (nn.Embedding semantics)

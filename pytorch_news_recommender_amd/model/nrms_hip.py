@@ -178,16 +178,41 @@ class Model(FlatHipModel):
         outside the catalogue are read as padding and counted: check_recommend_ids raises on them).  News
         id 0, the padding title, is never returned; with exclude_history neither is a browsed id.  A user with fewer
         than k eligible news gets id -1 / score -inf in the remaining slots."""
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend")
+        scores, ids = self._engine.top_k(user, cat[1:], k, exclude)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    @torch.no_grad()
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True):
+        """The exact position of given news in each user's ranking of the whole catalogue -> (ranks [B, T] int32, scores
+        [B, T] fp32): ranks[b, j] is the 1-based place news id targets[b, j] would take in recommend()'s list for user b
+        were k unbounded (the same user vector, score bits, exclusions and tie rule; include/nrms_hip.h nrms_rank_dot), so
+        the ids recommend(k) returns rank 1 .. k.
+
+        targets [B, T] news ids, any T, -1 = padding.  A target that cannot be recommended comes back as rank 0 / score
+        -inf: id 0 (the padding title), an id outside the catalogue, a NaN score and, with exclude_history, a browsed id.
+        catalogue and ``browsed_ids`` as in recommend (ids outside the catalogue are read as padding and counted:
+        check_recommend_ids raises on them)."""
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "rank_targets")
+        tg = torch.as_tensor(targets).to(user.device, dtype=torch.int64)
+        if tg.dim() != 2 or tg.shape[0] != user.shape[0]:
+            raise _lib.NrmsError("rank_targets: targets must be [%d, T] news ids (got %s)" % (user.shape[0], tuple(tg.shape)))
+        # rows 1.. as in recommend: news id n is row n - 1, so id 0 (and -1) fall out of range and get rank 0
+        return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude)
+
+    def _catalogue_query(self, batch, catalogue, exclude_history, who):
+        """What recommend and rank_targets share: (user vectors [B, width], the checked catalogue, the exclude list in
+        the kernel's row numbering or None)."""
         get = batch.get if hasattr(batch, "get") else batch.__getitem__
         browsed = get("browsed_ids")
         if browsed is None:
-            raise KeyError("recommend: the batch dict lacks 'browsed_ids' (the news ids of the clicked history)")
+            raise KeyError("%s: the batch dict lacks 'browsed_ids' (the news ids of the clicked history)" % who)
         dev = self._prepare()
         cat = torch.as_tensor(catalogue)
         d = self._catalogue_width()
         if cat.dim() != 2 or cat.shape[1] != d or cat.dtype != torch.float32 or cat.device != dev:
-            raise _lib.NrmsError("recommend: catalogue must be [N, %d] float32 on %s (encode_catalogue), got %s %s on %s"
-                                 % (d, dev, tuple(cat.shape), cat.dtype, cat.device))
+            raise _lib.NrmsError("%s: catalogue must be [N, %d] float32 on %s (encode_catalogue), got %s %s on %s"
+                                 % (who, d, dev, tuple(cat.shape), cat.dtype, cat.device))
         cat = cat.contiguous()
         browsed = torch.as_tensor(browsed).to(dev, dtype=torch.int64).contiguous()
         B, H = browsed.shape
@@ -202,9 +227,7 @@ class Model(FlatHipModel):
         user = self._catalogue_users(cat.index_select(0, browsed.view(-1)).view(B, H, d), browsed)
         # the kernel runs on rows 1.. (the padding title is never a candidate); history ids shift with them, which sends
         # the padding slots (id 0) out of range, where the kernel ignores them
-        exclude = browsed - 1 if exclude_history else None
-        scores, ids = self._engine.top_k(user, cat[1:], k, exclude)
-        return torch.where(ids >= 0, ids + 1, ids), scores
+        return user, cat, (browsed - 1 if exclude_history else None)
 
     def _catalogue_width(self):
         return self._dims.word_embed_size
@@ -215,9 +238,10 @@ class Model(FlatHipModel):
 
     _bad_browsed = None
     CATALOGUE_RETRIEVAL = True          # recommend / encode_catalogue are available (run_v0 --recommend checks this)
+    CATALOGUE_RANKING = True            # the catalogue score is a plain dot product: rank_targets (run_v0 --retrieval_metrics)
 
     def check_recommend_ids(self):
-        """Raises if a recommend() call since the last check met browsed_ids outside its catalogue (those slots were read
+        """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read
         as padding).  One host synchronisation."""
         n = 0 if self._bad_browsed is None else int(self._bad_browsed.item())
         if n:

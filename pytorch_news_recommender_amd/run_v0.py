@@ -12,6 +12,7 @@ data ships offline).  ``--batch_size`` (not a reference flag; its scripts hard-c
 run_demo.py:28) lets BASELINE config 0 (batch 32) run through the same entry.
 """
 import argparse
+import inspect
 import os
 import time
 from importlib import import_module
@@ -24,7 +25,7 @@ from . import parallel
 from .config import Config
 from .data_handler import DeviceFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
 from .model import Model
-from .train_eval import recommend, test, train
+from .train_eval import evaluate_retrieval, recommend, test, train
 
 
 def build_parser():
@@ -49,6 +50,10 @@ def build_parser():
     parser.add_argument('--recommend', type=int, default=None, metavar='K', help='finally write the top K news of the whole '
                         'catalogue per impression: dev split with the trained weights, or with --test the test split with '
                         'the checkpoint --test loaded (nrms_v0 / nrms_v1 models)')
+    parser.add_argument('--retrieval_metrics', type=str, default=None, metavar='K[,K...]', help='finally print Recall@K, nDCG@K, MRR '
+                        'and the median rank of the held-out clicks in the ranking of the whole catalogue (any K >= 1: ranks are '
+                        'exact at any depth): dev split with the trained weights, or with --test the test split (models whose '
+                        'catalogue score is a plain dot product)')
     parser.add_argument('--graph', type=str, default='induced', choices=('induced', 'global'), help="--model graph: where a news "
                         "slot's neighbours come from.  induced: the click graph of the batch itself (host sampler); global: the "
                         "click graph of the whole training feed, resident in HBM, sampled by the HIP sampler (needs --feed device)")
@@ -69,6 +74,28 @@ def check_recommend_args(args):
         raise SystemExit('--recommend: model %r cannot recommend from the whole catalogue (nrms_v0 / nrms_v1 only)' % args.model)
 
 
+def check_retrieval_args(args):
+    """--retrieval_metrics fails before any data is read or any step is trained: integers >= 1, a model that can rank the
+    catalogue.  Returns the cutoffs (None without the flag)."""
+    if args.retrieval_metrics is None:
+        return None
+    try:
+        ks = tuple(int(v) for v in args.retrieval_metrics.split(','))
+    except ValueError:
+        raise SystemExit('--retrieval_metrics K[,K...]: integers expected (got %r)' % args.retrieval_metrics)
+    if not ks or min(ks) < 1:
+        raise SystemExit('--retrieval_metrics K[,K...]: every K must be >= 1 (got %r)' % args.retrieval_metrics)
+    if args.test and args.dataset != 'synthetic':
+        raise SystemExit('--retrieval_metrics with --test: the MIND test split carries no click labels (synthetic data only)')
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_RANKING', False):
+        raise SystemExit('--retrieval_metrics: model %r cannot rank targets against the whole catalogue (its catalogue score is '
+                         'no plain dot product)' % args.model)
+    return ks
+
+
 def check_graph_args(args):
     """--graph global fails before any data is read: the graph model on the device feed only."""
     if args.graph != 'global':
@@ -83,6 +110,7 @@ def check_graph_args(args):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_recommend_args(args)
+    retrieval_ks = check_retrieval_args(args)
     check_graph_args(args)
     rank, local_rank, world = parallel.init_process_group()
     torch.manual_seed(422)
@@ -154,6 +182,15 @@ def main(argv=None):
                           device=config.device)
         return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out)
 
+    def retrieval_quality(samples, labels):
+        # as recommend_top: the catalogue is the feed's title table, so always a DeviceFeed
+        feed = DeviceFeed(config, samples, type=1, id2title_dict=titles, id2abst_dict=absts, batch_size=config.batch_size,
+                          device=config.device)
+        net = recommender.model if hasattr(recommender, 'model') else recommender
+        needs_info = 'categ' in inspect.signature(net.encode_catalogue).parameters           # nrms_naml's feature rows
+        return evaluate_retrieval(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
+                                  news_info=feed.news_info() if needs_info else None)
+
     def attach_graph(feed, samples=None):
         # the click graph is replicated: every rank builds it from ALL training samples (users shard, the graph does not)
         src = feed if samples is None else DeviceFeed(config, samples, type=0, id2title_dict=titles, id2abst_dict=absts,
@@ -183,6 +220,8 @@ def main(argv=None):
                     m['auc'], m['mrr'], m['ndcg5'], m['ndcg10']))
         if args.recommend is not None and rank == 0:
             print('recommendations saved to', recommend_top(dev_samples))
+        if retrieval_ks is not None and rank == 0:
+            retrieval_quality(dev_samples, dev_labels)
         return hist
     else:
         # run_v0.py:93-111: the test set through the checkpoint named by --load (or the best one by file-name AUC)
@@ -199,6 +238,8 @@ def main(argv=None):
         print('saved to', out)
         if args.recommend is not None and rank == 0:
             print('recommendations saved to', recommend_top(test_samples))
+        if retrieval_ks is not None and rank == 0:
+            retrieval_quality(test_samples, dev_labels)
         return out
 
 

@@ -14,6 +14,8 @@ test():     per-impression rank lists in the MIND submission format (train_eval.
             GPU batch by batch; ``_cal_test`` is the host statement of the same ranks.
 recommend(): per impression the k news ids of the WHOLE catalogue the model ranks highest (``model.recommend``, the
             fused top-k kernel nrms_topk_dot), written in test()'s line format.
+evaluate_retrieval(): how good those lists are: the exact position of every held-out click in the model's ranking of the
+            WHOLE catalogue (``model.rank_targets``, nrms_rank_dot) as Recall@K, MRR, nDCG@K and the median rank.
 """
 from __future__ import annotations
 
@@ -346,3 +348,78 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
             f.write(str([n for n in row if n >= 0]).replace(' ', '') + '\n')
     return file_name
 
+
+
+def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
+                       verbose=True):
+    """Full-catalogue retrieval quality on held-out clicks: per impression of data_iter the targets are its clicked news (the
+    ``candidate_ids`` whose label in y_true is 1) and each is ranked against the whole catalogue in recommend()'s own order
+    (``model.rank_targets``: the exact position, at any depth).  titles / news_info / exclude_history as in recommend();
+    the catalogue is encoded once.  y_true: one 0/1 label list per impression, in data_iter order.
+
+    Returns dict: ``recall@<k>`` and ``ndcg@<k>`` for every k of ks and ``mrr`` (NRMSEngine.retrieval_metrics, unweighted
+    means over the users with at least one ranked target), ``median_rank`` (over all ranked targets), ``n_users`` (users
+    with a ranked target), ``n_targets`` (ranked targets) and ``n_skipped`` (targets that came back with rank 0: a click
+    that is already in the history, a padding or unknown id).  The per-user tensors stay on the device in
+    ``last_retrieval_metrics`` (the metrics, plus ``ranks`` [n, T] int32, 0-padded to the widest batch, and ``targets``).
+    One host synchronisation, at the end."""
+    net = _inner(model)
+    ks = tuple(int(k) for k in ks)
+    catalogue = net.encode_catalogue(titles, **(news_info or {}))
+    dev = catalogue.device
+    ranks, targets, done = [], [], 0
+    for datas in data_iter:
+        cand = torch.as_tensor(datas["candidate_ids"]).to(dev, dtype=torch.int64)
+        B, S = cand.shape
+        rows = y_true[done:done + B]
+        done += B
+        if len(rows) < B:
+            raise ValueError("evaluate_retrieval: %d label rows for %d impressions" % (len(y_true), done))
+        width = max(1, max(min(len(y), S) for y in rows))
+        lab = np.zeros((B, width), dtype=bool)
+        for i, y in enumerate(rows):
+            n = min(len(y), S)
+            lab[i, :n] = np.asarray(y[:n]) == 1
+        # the clicked ids, moved to the front of each row in shown order and padded with -1 to the batch's widest
+        T = max(1, int(lab.sum(axis=1).max()))
+        lab = torch.from_numpy(lab).to(dev)
+        order = torch.argsort((~lab).to(torch.uint8), dim=1, stable=True)[:, :T]
+        tg = torch.where(lab.gather(1, order), cand[:, :width].gather(1, order), torch.full_like(order, -1))
+        rk, _ = net.rank_targets(datas, tg, catalogue, exclude_history=exclude_history)
+        ranks.append(rk)
+        targets.append(tg)
+    T = max((r.shape[1] for r in ranks), default=1)
+    pad = lambda t, v: torch.nn.functional.pad(t, (0, T - t.shape[1]), value=v)
+    ranks = torch.cat([pad(r, 0) for r in ranks]) if ranks else torch.zeros(0, T, dtype=torch.int32, device=dev)
+    targets = torch.cat([pad(t, -1) for t in targets]) if targets else torch.zeros(0, T, dtype=torch.int64, device=dev)
+    m = net.engine.retrieval_metrics(ranks, ks)
+    names = ["recall@%d" % k for k in ks] + ["ndcg@%d" % k for k in ks] + ["mrr"]
+    ranked = ranks > 0
+    have = ranked.any(dim=1)
+    n_users = have.sum()
+    flat = torch.where(ranked, ranks, torch.full_like(ranks, torch.iinfo(torch.int32).max)).reshape(-1).sort().values
+    n_targets = ranked.sum()
+    # median of the ranked ranks (the mean of the middle two when their number is even)
+    lo = flat[((n_targets - 1).clamp(min=0) // 2).clamp(max=max(0, flat.numel() - 1))] if flat.numel() else n_targets
+    hi = flat[(n_targets // 2).clamp(max=max(0, flat.numel() - 1))] if flat.numel() else n_targets
+    vals = [torch.where(have, m[k], torch.zeros_like(m[k])).sum() / n_users.clamp(min=1) for k in names]
+    vals += [(lo.double() + hi.double()) / 2, n_users.double(), n_targets.double(), ((targets >= 0) & ~ranked).sum().double()]
+    bad = getattr(net, "_bad_browsed", None)
+    vals.append(bad.double() if bad is not None else n_users.double() * 0)
+    vals = torch.stack(vals).cpu().tolist()                    # the one host synchronisation
+    net.engine.check_ids()                                     # (its count is on the host by now)
+    if vals.pop():
+        net.check_recommend_ids()                              # raises: browsed ids outside the catalogue
+    res = dict(zip(names, vals[:len(names)]))
+    res["median_rank"] = vals[-4]
+    res["n_users"], res["n_targets"], res["n_skipped"] = int(vals[-3]), int(vals[-2]), int(vals[-1])
+    if not res["n_users"]:
+        for k in names + ["median_rank"]:
+            res[k] = float("nan")
+    net.last_retrieval_metrics = dict(m, ranks=ranks, targets=targets)
+    if verbose:
+        print("retrieval over {} news: ".format(int(catalogue.shape[0]) - 1)
+              + "  ".join("{}: {:.4f}".format(k, res[k]) for k in names)
+              + "  median rank: {:.1f}  users: {}  targets: {}  skipped: {}".format(res["median_rank"], res["n_users"],
+                                                                                   res["n_targets"], res["n_skipped"]))
+    return res
