@@ -310,15 +310,25 @@ __global__ void ce_loss_kernel(int B, int C, const float* scores, float* loss_su
         const float* s = scores + (long)b * C;
         float mx = -3.0e38f;
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, s[c]);
-        float sum = 0.f;
-        for (int c = 0; c < C; ++c) sum += expf(s[c] - mx);
-        const float lse = mx + logf(sum);
-        local += lse - s[0];
+        // softmax denominator: fp32 sums over runs of 16 slots, added up in double.  One serial fp32 sum drifts with C (7 ulp at
+        // C = 300, and the error reaches every gradient of the row); a run of 16 holds it to what a training row (C <= 16) always
+        // had, and such a row still rounds as it always did: its denominator is the one fp32 run
+        double sum = 0.0;
+        for (int c0 = 0; c0 < C; c0 += 16) {
+            const int c1 = c0 + 16 < C ? c0 + 16 : C;
+            float run = 0.f;
+            for (int c = c0; c < c1; ++c) run += expf(s[c] - mx);
+            sum += (double)run;
+        }
+        // -log_softmax(s)[0] = (mx - s[0]) + log(sum), as torch forms it: mx + log(sum) first would round log(sum) to an ulp of mx
+        // (64 for a row of -1e9, whose loss log(C) came out 0).  Formed in double and rounded once (logf is 1.8 ulp off at 300)
+        local += (float)(((double)mx - (double)s[0]) + log(sum));
         if (dscores != nullptr) {
-            const float inv = 1.0f / sum;
+            const float inv = (float)(1.0 / sum);               // == 1.0f / run when C <= 16: a double quotient rounds to fp32 once
             for (int c = 0; c < C; ++c) {
-                const float p = expf(s[c] - mx) * inv;
-                dscores[(long)b * C + c] = (p - (c == 0 ? 1.0f : 0.0f)) * gscale;
+                const float e = expf(s[c] - mx);
+                const float p = (c == 0) ? __builtin_fmaf(e, inv, -1.0f) : e * inv;      // softmax - onehot(0), one rounding
+                dscores[(long)b * C + c] = p * gscale;
             }
         }
     }
@@ -335,6 +345,19 @@ __global__ void ce_loss_kernel(int B, int C, const float* scores, float* loss_su
 // the update -- p, m and v keep their values, so Adam's moments cannot be poisoned for the rest of training -- and counted into
 // *n_bad (one atomic per wavefront that saw any; none in a healthy step).  Every rank of a data-parallel job sees the same
 // reduced gradient, hence skips the same elements: replicas stay identical.
+// One element's update, with every rounding spelt out: m, v and the denominator are formed from rounded products (no fma
+// contraction), the parameter takes step_size * m / denom in one fma.  Left to the compiler, the guarded
+// and the unguarded kernel -- and the vector body and the scalar tail of each -- were contracted differently and disagreed in
+// the last bit; these are the roundings of the guarded vector body, the one the fp16 training step has always run.
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float step_size, float b1, float b2, float omb1,
+                                            float omb2, float inv_sqrt_bc2, float eps) {
+#pragma clang fp contract(off)
+    m = b1 * m + omb1 * g;
+    v = b2 * v + omb2 * g * g;
+    const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
+    p = __builtin_fmaf(-step_size, m / denom, p);
+}
+
 template <bool GUARD>
 __global__ void adam_kernel(size_t n4, size_t n, float* p, const float* g, float* m, float* v, float step_size,
                             float b1, float b2, float omb1, float omb2, float inv_sqrt_bc2, float eps, float gscale, int* n_bad) {
@@ -348,10 +371,9 @@ __global__ void adam_kernel(size_t n4, size_t n, float* p, const float* g, float
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (GUARD && (__float_as_uint(gv[e]) & 0x7F800000u) == 0x7F800000u) { ++bad; continue; }
-            mv[e] = b1 * mv[e] + omb1 * gv[e];
-            vv[e] = b2 * vv[e] + omb2 * gv[e] * gv[e];
-            const float denom = sqrtf(vv[e]) * inv_sqrt_bc2 + eps;
-            pv[e] -= step_size * (mv[e] / denom);
+            float pe = pv[e], me = mv[e], ve = vv[e];
+            adam_update(pe, me, ve, gv[e], step_size, b1, b2, omb1, omb2, inv_sqrt_bc2, eps);
+            pv[e] = pe; mv[e] = me; vv[e] = ve;
         }
         reinterpret_cast<f32x4*>(p)[i] = pv;
         reinterpret_cast<f32x4*>(m)[i] = mv;
@@ -364,10 +386,9 @@ __global__ void adam_kernel(size_t n4, size_t n, float* p, const float* g, float
         if (GUARD && (__float_as_uint(gv) & 0x7F800000u) == 0x7F800000u) {
             ++bad;
         } else {
-            const float mv = b1 * m[t] + omb1 * gv;
-            const float vv = b2 * v[t] + omb2 * gv * gv;
-            m[t] = mv; v[t] = vv;
-            p[t] -= step_size * (mv / (sqrtf(vv) * inv_sqrt_bc2 + eps));
+            float pe = p[t], me = m[t], ve = v[t];
+            adam_update(pe, me, ve, gv, step_size, b1, b2, omb1, omb2, inv_sqrt_bc2, eps);
+            p[t] = pe; m[t] = me; v[t] = ve;
         }
     }
     if (GUARD) {

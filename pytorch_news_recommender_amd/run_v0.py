@@ -27,6 +27,9 @@ from .data_handler import DeviceFeed, MyDataset, SyntheticMind, load_dataset, re
 from .model import Model
 from .train_eval import evaluate_retrieval, recommend, test, train
 
+# rank r adds r * this to its dropout seeds (FlatHipModel._next_seed), so that the ranks of a data-parallel job draw unrelated masks
+DROPOUT_RANK_SALT = 0x632BE59BD9B4E019
+
 
 def build_parser():
     parser = argparse.ArgumentParser(description='MIND')
@@ -158,7 +161,7 @@ def main(argv=None):
     recommender = Model(config, args)
     all_train_samples = train_samples
     if world > 1:
-        recommender.model._rank_salt = rank * 0x632BE59BD9B4E019
+        recommender.model._rank_salt = rank * DROPOUT_RANK_SALT
         recommender.model.engine
         parallel.broadcast_parameters(recommender.model._flat)
         # every rank: the same number of equal-sized batches (the gradient all-reduce is collective and the loss is

@@ -1,34 +1,23 @@
 """Neighbour sampling from a device-resident click graph (click_graph.py, csrc/graphsample.hip) and the graph encoder on top of it
 (model/graph_hip.py with an attached graph).  PARITY UNPINNED: the reference holds no graph model; the sampler is checked bit for
 bit against the numpy restatement below of the five steps in include/nrms_hip.h (Philox4x32-7 in uint64 arithmetic, as
-csrc/common.h), the model against oracle/nrms_oracle.py + oracle/segpool_oracle.py with the out-of-batch rows as constants."""
+csrc/common.h: tests/philox_ref.py), the model against oracle/nrms_oracle.py + oracle/segpool_oracle.py with the out-of-batch rows
+as constants."""
 import numpy as np
 import pytest
 import torch
 
 from pytorch_news_recommender_amd import _lib, synth
 
+from tests.philox_ref import philox4x32_7
+
 pytestmark = pytest.mark.gpu
 
 SITE = 5                                    # PHILOX_SITE_GRAPH_SAMPLE (csrc/common.h)
-M32 = np.uint64(0xFFFFFFFF)
 S32 = np.uint64(32)
 
 
 # ---- numpy restatement ---------------------------------------------------------------------------------------------------------
-def philox4x32_7(seed, group, site):
-    """csrc/common.h philox4x32_7: counter (group lo, group hi, site, 0x9E3779B9), key (seed lo, seed hi), 7 rounds."""
-    group = np.asarray(group, dtype=np.uint64)
-    c0, c1 = group & M32, group >> S32
-    c2, c3 = np.full_like(group, site), np.full_like(group, 0x9E3779B9)
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    for _ in range(7):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> S32) ^ c1 ^ k0, p1 & M32, (p0 >> S32) ^ c3 ^ k1, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
-
-
 def csr_ref(hist, n_news):
     """Grouping by hand: (user_ptr, user_news, news_ptr, news_users, n_padding, n_out_of_range)."""
     hist = np.asarray(hist, dtype=np.int64)
