@@ -484,6 +484,36 @@ int nrms_graph_resolve_rows(int64_t n_slots, int32_t K, int64_t n_news, const in
                             int64_t* neighbor_rows, int32_t* extra_ids, int32_t* n_extra, int32_t* n_dropped, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- Impression log: the negatives of every training row, redrawn per epoch (csrc/negsample.hip; data_handler.py ImpressionFeed).
+ * The reference shuffles an impression's non-clicked news once, offline, and gives its i-th clicked item the slice
+ * [i * sample_size, (i + 1) * sample_size) of that shuffle (MIND_2020/data_processor.py:519-528).  Here the log stays in HBM as a CSR
+ * -- impression i shows shown[imp_ptr[i] .. imp_ptr[i + 1]) with labels label[...] (non-zero = clicked) -- and the shuffle is a
+ * ranking by counter-based keys, so a call with another seed is another epoch's draw.  The impression's positives are its clicked
+ * entries in shown order, p = 0, 1, ...; sample_ptr [n_imp + 1] is the exclusive scan of the impressions' positive counts, built
+ * once by the caller: sample_ptr[i] is the first output row of impression i and n_samples = sample_ptr[n_imp].
+ *   key of the entry at log position e = imp_ptr[i] + j:
+ *     w(e) = word e & 3 of philox4x32_7(seed, group = e >> 2, site 6)      (the counter layout of the dropout sites, csrc/common.h)
+ *   rank of negative j:  r(j) = #{negatives j' of the same impression : (w(e'), j') < (w(e), j)}      (equal words: the earlier position first)
+ *   row sample_ptr[i] + p of cand [n_samples, S + 1] int64:
+ *     slot 0 = the p-th positive; slots 1 .. = the negatives with p * S <= r < (p + 1) * S in ascending r; the remaining slots 0;
+ *     clen [n_samples] int64 = 1 + the number of negatives written (a positive whose slice is empty still has its row, clen = 1).
+ * Equal words are the only departure from a uniform shuffle: two of an impression's n negatives share a word with probability
+ * below n^2 / 2^33 (5e-4 at n = 2048, 1e-5 at n = 300), and then the earlier one comes first.  The result is a function of (imp_ptr,
+ * shown, label, S, seed) alone; every byte of cand and clen is written, with plain stores by one writer each, and nothing else is
+ * (but the workspace and *n_bad): two calls with the same inputs give the same bytes.  1 <= S <= 64, 1 <= max_shown <= 2048,
+ * n_imp < 2^31.  An impression longer than max_shown gets rows that hold its positives only (clen = 1) and adds one to *n_bad (device
+ * int32, as nrms_sanitize_ids counts); so does, without writing anything, an impression whose extent leaves the log or whose rows in
+ * sample_ptr are not as many as its positives.  Bad scalar arguments, null pointers and a workspace below
+ * nrms_negative_sample_workspace_bytes(n_imp, nnz = imp_ptr[n_imp], S) bytes (4-byte aligned; the call initialises it; the query
+ * returns 0 for arguments the call would refuse) return non-zero before any launch.  No host synchronisation.  An impression of at
+ * most 64 entries is ranked by one wavefront, a longer one by one workgroup; the workspace lists the latter (an integer counter
+ * orders that list, never a result). */
+size_t nrms_negative_sample_workspace_bytes(int64_t n_imp, int64_t nnz, int32_t S);
+int nrms_negative_sample(int64_t n_imp, const int64_t* imp_ptr /* [n_imp + 1] */, const int32_t* shown /* [nnz] */,
+                         const uint8_t* label /* [nnz] */, const int64_t* sample_ptr /* [n_imp + 1] */, int32_t S, int32_t max_shown,
+                         uint64_t seed, int64_t* cand /* [n_samples, S + 1] */, int64_t* clen /* [n_samples] */, int32_t* n_bad,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- All-padding sequences of the output-projection topology in closed form (csrc/empty_seq.hip; nrms_naml's word-level
  * encoder, model/nrms_naml.py:42-100,121-177: 41 % of a MIND-shaped batch's title / abstract slots are history padding).  With a
  * zero padding row every Q | K | V row of such a sequence is the bias, so attention row i is b_v scaled per head by

@@ -41,6 +41,8 @@ struct Keep4 { bool k[4]; };
 // Sites 0 .. 4 are the dropout sites of include/nrms_hip.h (nrms_dropout_keep_mask, NRMS_DROPOUT_SITE_NEWSVEC).  Site 5 is not a
 // dropout: the neighbour draws of csrc/graphsample.hip, group = news id * K + draw, words 0 and 1 of the call.
 constexpr uint32_t PHILOX_SITE_GRAPH_SAMPLE = 5u;
+// Site 6: the shuffle keys of csrc/negsample.hip, group = (position in the impression log) >> 2, word = position & 3.
+constexpr uint32_t PHILOX_SITE_NEG_SAMPLE = 6u;
 
 __host__ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2,
                                                       uint32_t& c3, uint32_t k0, uint32_t k1) {

@@ -225,6 +225,7 @@ class SyntheticMind:
         self.subcategory = 1 + (self.topic * 7 + rng2.integers(0, 5, size=n_news)) % max(n_sub - 1, 1)
         self.n_topics = n_topics
         self.rng = rng
+        self.imp_rng = np.random.default_rng(seed + 2000003)       # train_impressions' own stream, as the abstracts have theirs
         self.by_topic = [np.flatnonzero(self.topic == t) + 1 for t in range(n_topics)]   # 1-based ids
 
     def embedding_table(self, d, seed=0):
@@ -242,11 +243,12 @@ class SyntheticMind:
         out[1:] += centroids[self.topic]
         return out.astype(np.float32)
 
-    def _pick(self, topic, n, p_in=0.8):
+    def _pick(self, topic, n, p_in=0.8, rng=None):
+        rng = self.rng if rng is None else rng
         out = []
         for _ in range(n):
-            t = topic if self.rng.random() < p_in else int(self.rng.integers(0, self.n_topics))
-            out.append(int(self.rng.choice(self.by_topic[t])))
+            t = topic if rng.random() < p_in else int(rng.integers(0, self.n_topics))
+            out.append(int(rng.choice(self.by_topic[t])))
         return out
 
     def train_samples(self, n_users):
@@ -284,6 +286,25 @@ class SyntheticMind:
             imps = [shown[i] for i in perm]
             samples.append([hist, self._cat(hist), self._sub(hist), imps, self._cat(imps), self._sub(imps)])
             labels.append([y[i] for i in perm])
+        return samples, labels
+
+    def train_impressions(self, n_imps, max_shown=40):
+        """Training data in the impression form of ``eval_samples`` -- (samples, labels), 4 .. max_shown shown news per
+        impression, at least one clicked and one not -- for ``ImpressionFeed``, which draws every clicked item's negatives from
+        the impression's own non-clicked news.  Drawn from a generator of its own: the streams of ``train_samples`` and
+        ``eval_samples`` are what they were, however often this is called."""
+        cfg, rng = self.config, self.imp_rng
+        samples, labels = [], []
+        for _ in range(n_imps):
+            t = int(rng.integers(0, self.n_topics))
+            hist = self._pick(t, int(rng.integers(3, cfg.history_len + 1)), rng=rng)
+            n = int(rng.integers(4, max(int(max_shown), 4) + 1))
+            npos = int(rng.integers(1, max(2, n // 4)))
+            shown = self._pick(t, npos, p_in=1.0, rng=rng) + [int(x) for x in rng.integers(1, self.n_news + 1, size=n - npos)]
+            perm = rng.permutation(n)
+            imps = [shown[i] for i in perm]
+            samples.append([hist, self._cat(hist), self._sub(hist), imps, self._cat(imps), self._sub(imps)])
+            labels.append([1 if i < npos else 0 for i in perm])
         return samples, labels
 
 
@@ -371,6 +392,12 @@ class DeviceFeed:
     def __len__(self):
         return self.n // self.batch_size if self.drop_last else (self.n + self.batch_size - 1) // self.batch_size
 
+    def _news_info_source(self):
+        """(news ids, {"categ": ..., "subcateg": ...}): every slot of the samples with the category pair it carries, flat."""
+        p = self.packed
+        flat = lambda a, b: torch.cat([p[a].reshape(-1), p[b].reshape(-1)])
+        return flat("hist", "cand"), {"categ": flat("hcat", "ccat"), "subcateg": flat("hsub", "csub")}
+
     def news_info(self):
         """Per-news tables for catalogue retrieval, rows aligned with ``titles`` (row r = news id r): ``{"absts": [N, A]
         word ids or None, "categ": int64 [N], "subcateg": int64 [N]}``.  The samples carry a category and sub-category per
@@ -378,13 +405,13 @@ class DeviceFeed:
         unknown: row 0, ids no sample shows and slots without categories stay 0.  In the reference the category is a function
         of the news id (MIND_2020/data_handler.py:71-77), so two different non-zero values for one id raise ValueError."""
         if getattr(self, "_news_info", None) is None:
-            p, N = self.packed, self.titles.shape[0]
-            ids = torch.cat([p["hist"].reshape(-1), p["cand"].reshape(-1)])
+            N = self.titles.shape[0]
+            ids, values = self._news_info_source()
             live = (ids > 0) & (ids < N)
             ids = ids[live]
             tables = {}
-            for name, h, c in (("categ", "hcat", "ccat"), ("subcateg", "hsub", "csub")):
-                v = torch.cat([p[h].reshape(-1), p[c].reshape(-1)])[live]
+            for name in ("categ", "subcateg"):
+                v = values[name][live]
                 known = v != 0
                 big = torch.iinfo(torch.int64).max
                 hi = torch.full((N,), -big, dtype=torch.int64, device=self.device).scatter_reduce_(0, ids[known], v[known], "amax")
@@ -450,5 +477,193 @@ class DeviceFeed:
             self.epoch += 1
         else:
             order = torch.arange(self.n, device=self.device)
+        for b in range(len(self)):
+            yield self.batch(order[b * self.batch_size:(b + 1) * self.batch_size])
+
+
+IMPRESSION_MAX_SHOWN = 2048                      # nrms_negative_sample: max_shown <= 2048 (include/nrms_hip.h)
+EPOCH_SEED_STEP = 0x9E3779B97F4A7C15
+
+
+class ImpressionFeed(DeviceFeed):
+    """A training ``DeviceFeed`` over IMPRESSIONS (shown news + 0/1 labels) whose negatives are redrawn at the start of every
+    epoch, on the device.  The reference shuffles an impression's non-clicked news once, offline, and gives the i-th clicked
+    item the slice [i * sample_size, (i + 1) * sample_size) of that shuffle (data_processor.py:519-528); every epoch then shows a
+    user the same few negatives.  Here the impression log stays in HBM as a CSR and ``nrms_negative_sample`` (include/nrms_hip.h)
+    makes the same slices of a fresh shuffle per epoch: one call, keyed by
+
+        epoch_seed = (seed + epoch * 0x9E3779B97F4A7C15) mod 2^64,
+
+    refills the candidate side (``candidate_ids``, ``candidate_mask`` and, from the per-news tables of ``news_info()``, the
+    candidate categories).  One row per clicked item, the impression's history repeated for each, as in the reference's training
+    set; a clicked item whose slice is empty keeps its row with the candidates masked out.  The draw is a function of the log, the
+    seed and the epoch only: not of the batch size, the shuffle or the rank.  There is no CPU path for the draw.
+
+    samples / labels: the ``[hist, hcat, hsub, imps, icat, isub]`` + 0/1 lists form of ``SyntheticMind.eval_samples``;
+    ``from_arrays`` takes the same as arrays.  ``min_history``: impressions whose history is shorter are left out (default 0:
+    keep all; the reference's training set uses 5, MIND_2020/data_handler.py:92).  ``resample=False`` keeps epoch 0's draw.
+    ``rank`` / ``world``: every rank of a data-parallel job builds the SAME feed from all impressions with the same seed and
+    iterates over its own contiguous share of the rows (n_samples // world each)."""
+
+    def __init__(self, config, samples, labels, id2title_dict=None, id2abst_dict=None, batch_size=None, device="cuda", shuffle=False,
+                 drop_last=False, seed=0, resample=True, min_history=0, rank=0, world=1):
+        if len(samples) != len(labels):
+            raise ValueError("ImpressionFeed: %d impressions but %d label lists" % (len(samples), len(labels)))
+        H, n = config.history_len, len(samples)
+        hist, hcat, hsub = (np.zeros((n, H), dtype=np.int64) for _ in range(3))
+        hlen = np.zeros(n, dtype=np.int64)
+        shown, label, scat, ssub = [], [], [], []
+        with_cat = n > 0 and all(len(d) > 5 and d[1] is not None and d[4] is not None for d in samples)
+        for k, (data, y) in enumerate(zip(samples, labels)):
+            h = list(data[0])[:H]
+            x = len(h)
+            hist[k, :x], hlen[k] = h, x
+            if x and with_cat:
+                hcat[k, :x] = np.asarray(data[1])[:x]
+                hsub[k, :x] = np.asarray(data[2])[:x]
+            if len(data[3]) != len(y):
+                raise ValueError("ImpressionFeed: impression %d shows %d news but has %d labels" % (k, len(data[3]), len(y)))
+            shown.append(np.asarray(data[3], dtype=np.int64).reshape(-1))
+            label.append(np.asarray(y, dtype=np.int64).reshape(-1))
+            if with_cat:
+                if len(data[4]) != len(y) or len(data[5]) != len(y):
+                    raise ValueError("ImpressionFeed: impression %d: one category pair per shown news expected" % k)
+                scat.append(np.asarray(data[4], dtype=np.int64).reshape(-1))
+                ssub.append(np.asarray(data[5], dtype=np.int64).reshape(-1))
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+        imp_ptr = np.concatenate([[0], np.cumsum([len(s) for s in shown])]).astype(np.int64)
+        self._setup(config, hist, hlen, hcat if with_cat else None, hsub if with_cat else None, imp_ptr, cat(shown), cat(label),
+                    cat(scat) if with_cat else None, cat(ssub) if with_cat else None, id2title_dict, id2abst_dict, batch_size, device,
+                    shuffle, drop_last, seed, resample, min_history, rank, world)
+
+    @classmethod
+    def from_arrays(cls, config, hist, imp_ptr, shown, label, hist_categ=None, hist_subcateg=None, shown_categ=None,
+                    shown_subcateg=None, hist_len=None, id2title_dict=None, id2abst_dict=None, batch_size=None, device="cuda",
+                    shuffle=False, drop_last=False, seed=0, resample=True, min_history=0, rank=0, world=1):
+        """hist [n_imp, history_len] news ids, left-aligned, 0 = padding (hist_len [n_imp]: the lengths, default the non-zero
+        count); imp_ptr [n_imp + 1], shown [nnz], label [nnz] (0 / 1): the impressions as a CSR; the four category arrays are
+        shaped like hist and shown and are given together or not at all."""
+        cats = (hist_categ, hist_subcateg, shown_categ, shown_subcateg)
+        if any(c is None for c in cats) and not all(c is None for c in cats):
+            raise ValueError("ImpressionFeed.from_arrays: give all four category arrays or none")
+        hist = np.asarray(hist, dtype=np.int64)
+        if hist.ndim != 2 or hist.shape[1] != config.history_len:
+            raise ValueError("ImpressionFeed.from_arrays: hist must be [n_imp, history_len = %d], got %s" % (config.history_len, hist.shape))
+        hlen = (hist != 0).sum(axis=1) if hist_len is None else np.asarray(hist_len, dtype=np.int64)
+        self = cls.__new__(cls)
+        i64 = lambda a: None if a is None else np.asarray(a, dtype=np.int64)
+        self._setup(config, hist, hlen.astype(np.int64), i64(hist_categ), i64(hist_subcateg), i64(imp_ptr), i64(shown), i64(label),
+                    i64(shown_categ), i64(shown_subcateg), id2title_dict, id2abst_dict, batch_size, device, shuffle, drop_last, seed,
+                    resample, min_history, rank, world)
+        return self
+
+    def _setup(self, config, hist, hlen, hcat, hsub, imp_ptr, shown, label, scat, ssub, id2title_dict, id2abst_dict, batch_size, device,
+               shuffle, drop_last, seed, resample, min_history, rank, world):
+        n_imp = hist.shape[0]
+        if imp_ptr.shape != (n_imp + 1,) or imp_ptr[0] != 0 or (np.diff(imp_ptr) < 0).any() or shown.shape != (int(imp_ptr[-1]),) \
+                or label.shape != shown.shape or hlen.shape != (n_imp,):
+            raise ValueError("ImpressionFeed: imp_ptr must rise from 0 over n_imp = %d impressions to len(shown) = len(label)" % n_imp)
+        if ((label != 0) & (label != 1)).any():
+            raise ValueError("ImpressionFeed: labels must be 0 or 1")
+        if shown.size and (shown.min() < 0 or shown.max() >= 2 ** 31):
+            raise ValueError("ImpressionFeed: shown news ids must be in [0, 2^31)")
+        for name, a, like in (("hist_categ", hcat, hist), ("hist_subcateg", hsub, hist), ("shown_categ", scat, shown), ("shown_subcateg", ssub, shown)):
+            if a is not None and a.shape != like.shape:
+                raise ValueError("ImpressionFeed: %s has shape %s, expected %s" % (name, a.shape, like.shape))
+        lens = np.diff(imp_ptr)
+        if n_imp and lens.max() > IMPRESSION_MAX_SHOWN:
+            k = int(lens.argmax())
+            raise ValueError("ImpressionFeed: impression %d shows %d news; negatives are sampled from at most %d shown news per "
+                             "impression (nrms_negative_sample, max_shown): split or truncate it" % (k, int(lens[k]), IMPRESSION_MAX_SHOWN))
+        if not 0 <= int(rank) < int(world):
+            raise ValueError("ImpressionFeed: rank = %r of world = %r" % (rank, world))
+        keep = hlen >= int(min_history)
+        if not keep.all():                                                   # the CSR of the impressions that stay
+            entry = np.repeat(keep, lens)
+            hist, hlen, lens = hist[keep], hlen[keep], lens[keep]
+            hcat, hsub = (None if a is None else a[keep] for a in (hcat, hsub))
+            shown, label = shown[entry], label[entry]
+            scat, ssub = (None if a is None else a[entry] for a in (scat, ssub))
+            imp_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            n_imp = hist.shape[0]
+        DeviceFeed.__init__(self, config, [], type=0, id2title_dict=id2title_dict, id2abst_dict=id2abst_dict, batch_size=batch_size,
+                            device=device, shuffle=shuffle, drop_last=drop_last, seed=seed)
+        self.resample, self.min_history, self.rank, self.world = bool(resample), int(min_history), int(rank), int(world)
+        imp_of = np.repeat(np.arange(n_imp, dtype=np.int64), lens)
+        n_pos = np.bincount(imp_of[label != 0], minlength=n_imp).astype(np.int64)
+        sample_ptr = np.concatenate([[0], np.cumsum(n_pos)]).astype(np.int64)
+        row_imp = np.repeat(np.arange(n_imp, dtype=np.int64), n_pos)          # the impression of every training row
+        n, S = int(sample_ptr[-1]), self.S
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        zeros = lambda *shape: torch.zeros(*shape, dtype=torch.int64, device=self.device)
+        rep = lambda a: dev(a[row_imp]) if a is not None else zeros(n, hist.shape[1])
+        self.packed = dict(hist=dev(hist[row_imp]), hcat=rep(hcat), hsub=rep(hsub), cand=zeros(n, S), ccat=zeros(n, S), csub=zeros(n, S),
+                           hlen=dev(np.minimum(hlen, hist.shape[1])[row_imp]), clen=zeros(n))
+        self.n_imp, self.nnz, self.n_samples = n_imp, int(imp_ptr[-1]), n
+        self.imp_ptr, self.sample_ptr = dev(imp_ptr), dev(sample_ptr)
+        self.shown, self.label = dev(shown.astype(np.int32)), dev(label.astype(np.uint8))
+        self._shown_cat = None if scat is None else (dev(hist), dev(hcat), dev(hsub), dev(scat), dev(ssub))
+        per_rank = n // self.world
+        self.row0, self.n = (self.rank * per_rank, per_rank) if self.world > 1 else (0, n)
+        self.draws, self.drawn_seed = 0, None
+        self._n_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._ws = None
+
+    def _news_info_source(self):
+        # every shown news, sampled or not, and every history slot once per impression
+        if self._shown_cat is None:
+            ids = torch.cat([self.packed["hist"].reshape(-1), self.shown.to(torch.int64)])
+            return ids, {"categ": torch.zeros_like(ids), "subcateg": torch.zeros_like(ids)}
+        hist, hcat, hsub, scat, ssub = self._shown_cat
+        flat = lambda a, b: torch.cat([a.reshape(-1), b])
+        return flat(hist, self.shown.to(torch.int64)), {"categ": flat(hcat, scat), "subcateg": flat(hsub, ssub)}
+
+    def epoch_seed(self, epoch):
+        return (self.seed + int(epoch) * EPOCH_SEED_STEP) & 0xFFFFFFFFFFFFFFFF
+
+    def draw(self, seed):
+        """Refill the candidate side with the draw of ``seed`` (one ``nrms_negative_sample`` call and two table look-ups on the
+        feed's stream); raises if the library counted an impression it could not sample."""
+        import ctypes as C
+        from . import _lib
+        if self.device.type != "cuda":
+            raise _lib.NrmsError("ImpressionFeed: the feed is on %s; negatives are sampled on a GPU (there is no CPU path)" % self.device)
+        lib = _lib.load()
+        S = self.S - 1
+        need = int(lib.nrms_negative_sample_workspace_bytes(C.c_int64(self.n_imp), C.c_int64(self.nnz), S))
+        if need == 0:
+            _lib.check(-1, "nrms_negative_sample_workspace_bytes")
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device)
+        p = self.packed
+        self._n_bad.zero_()
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            rc = lib.nrms_negative_sample(C.c_int64(self.n_imp), _lib.ptr(self.imp_ptr), _lib.ptr(self.shown), _lib.ptr(self.label),
+                                          _lib.ptr(self.sample_ptr), S, IMPRESSION_MAX_SHOWN, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                          _lib.ptr(p["cand"]), _lib.ptr(p["clen"]), _lib.ptr(self._n_bad), _lib.ptr(self._ws),
+                                          C.c_size_t(self._ws.numel() * 4), stream)
+        _lib.check(rc, "nrms_negative_sample")
+        if self._shown_cat is not None:
+            info = self.news_info()
+            flat = p["cand"].reshape(-1)
+            torch.index_select(info["categ"], 0, flat, out=p["ccat"].view(-1))
+            torch.index_select(info["subcateg"], 0, flat, out=p["csub"].view(-1))
+        bad = int(self._n_bad.item())                                         # the epoch's one host synchronisation
+        if bad:
+            raise _lib.NrmsError("ImpressionFeed: nrms_negative_sample could not sample %d impression(s) (longer than %d shown news, "
+                                 "or a damaged log)" % (bad, IMPRESSION_MAX_SHOWN))
+        self.drawn_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def __iter__(self):
+        if self.resample or self.drawn_seed is None:
+            self.draw(self.epoch_seed(self.draws))
+        self.draws += 1
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + self.epoch + 1000003 * self.rank)
+            order = torch.randperm(self.n, generator=g).to(self.device) + self.row0
+            self.epoch += 1
+        else:
+            order = torch.arange(self.row0, self.row0 + self.n, device=self.device)
         for b in range(len(self)):
             yield self.batch(order[b * self.batch_size:(b + 1) * self.batch_size])

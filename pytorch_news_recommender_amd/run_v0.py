@@ -23,7 +23,7 @@ from torch.utils.data import DataLoader
 
 from . import parallel
 from .config import Config
-from .data_handler import DeviceFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
+from .data_handler import DeviceFeed, ImpressionFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
 from .model import Model
 from .train_eval import evaluate_retrieval, recommend, test, train
 
@@ -60,6 +60,10 @@ def build_parser():
     parser.add_argument('--graph', type=str, default='induced', choices=('induced', 'global'), help="--model graph: where a news "
                         "slot's neighbours come from.  induced: the click graph of the batch itself (host sampler); global: the "
                         "click graph of the whole training feed, resident in HBM, sampled by the HIP sampler (needs --feed device)")
+    parser.add_argument('--negatives', type=str, default='fixed', choices=('fixed', 'epoch'), help="where a training row's negatives "
+                        "come from.  fixed: drawn once, with the data set (the reference's offline preprocessing); epoch: redrawn "
+                        "at the start of every epoch from the impression's own non-clicked news, on the device (ImpressionFeed; "
+                        "needs --dataset synthetic and --feed device)")
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     return parser
 
@@ -110,11 +114,26 @@ def check_graph_args(args):
         raise SystemExit('--graph global: the click graph is built from the device feed (--feed device)')
 
 
+def check_negatives_args(args):
+    """--negatives epoch fails before any data is read: impressions with labels to train on exist for the synthetic corpus only
+    (reading MIND's behaviors.tsv is out of scope), the log lives in the device feed, and --test trains nothing."""
+    if args.negatives != 'epoch':
+        return
+    if args.dataset != 'synthetic':
+        raise SystemExit('--negatives epoch: training impressions exist for --dataset synthetic only (got %r: its pickles hold '
+                         'negatives that were drawn offline)' % args.dataset)
+    if args.feed != 'device':
+        raise SystemExit('--negatives epoch: the impression log is sampled in the device feed (--feed device)')
+    if args.test:
+        raise SystemExit('--negatives epoch: --test trains nothing')
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_recommend_args(args)
     retrieval_ks = check_retrieval_args(args)
     check_graph_args(args)
+    check_negatives_args(args)
     rank, local_rank, world = parallel.init_process_group()
     torch.manual_seed(422)
     torch.cuda.manual_seed_all(422)
@@ -147,8 +166,12 @@ def main(argv=None):
                 np.savez(vec, embeddings=corpus.news_vectors(config.bert_embed_size))
         parallel.barrier()
         titles, absts = corpus.id2title_dict, corpus.id2abst_dict
+        # (drawn with --negatives epoch too, where nothing trains on them: the dev split below comes from the same generator and
+        # stays the one every other run evaluates on)
         train_samples = corpus.train_samples(args.synthetic_users)
         dev_samples, dev_labels = corpus.eval_samples(1024)
+        if args.negatives == 'epoch':
+            train_imps, train_imp_labels = corpus.train_impressions(args.synthetic_users)
     else:
         if args.dataset == 'demo':
             config.word_embedding_pretrained = 'demo_word_embedding.npz'       # run_demo.py:31
@@ -205,9 +228,15 @@ def main(argv=None):
                                                                                     graph.nbytes() / 1e6))
 
     if not args.test:
-        train_feed = loader(train_samples, 0, True)
+        if args.negatives == 'epoch':
+            # every rank holds the whole log and draws with the same seed: the negatives of a row do not depend on the rank
+            train_feed = ImpressionFeed(config, train_imps, train_imp_labels, id2title_dict=titles, id2abst_dict=absts,
+                                        batch_size=config.batch_size, device=config.device, shuffle=True, drop_last=world > 1, seed=422,
+                                        rank=rank, world=world)
+        else:
+            train_feed = loader(train_samples, 0, True)
         if args.graph == 'global':
-            attach_graph(train_feed, all_train_samples if world > 1 else None)
+            attach_graph(train_feed, all_train_samples if world > 1 and args.negatives != 'epoch' else None)
         hist = train(config, recommender, train_feed, loader(dev_samples, 1, False), dev_labels,
                      max_batches=args.max_batches, verbose=rank == 0)
         if args.graph == 'global' and rank == 0:
