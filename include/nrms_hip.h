@@ -22,7 +22,8 @@
  *     two streams train concurrently); calls on the SAME stream must be issued by one host thread at a time, as stream order
  *     demands anyway.  A pending deferred join (NRMS_FLAG_DEFER_WQKV, fp16) is flushed by the next nrms_encoder_fwd /
  *     nrms_encoder_bwd on that stream in ANY precision, so a caller that never calls nrms_encoder_bwd_wqkv still gets
- *     correct ordering.  The environment variable NRMS_NO_SIDE_STREAMS keeps everything on `stream`.
+ *     correct ordering (NRMS_FLAG_DEFER_USER_JOIN: see the flag for where its join happens).  The environment variable
+ *     NRMS_NO_SIDE_STREAMS keeps everything on `stream`.
  *   - all matrices are row-major and dense; fp32 unless stated.  M = n_seq * seq_len.
  *   - gradients are ACCUMULATED (+=) into the caller's buffers (zero them per step, as
  *     `model.zero_grad()` does at train_eval.py:115).
@@ -97,6 +98,17 @@ extern "C" {
  * layout, written by the forward, read by the backward); acts.ctx, acts.t, acts.w keep their meaning (and may all be NULL in
  * inference).  Set on both nrms_encoder_fwd and nrms_encoder_bwd of a pass, or on neither; NRMS_EINVAL for any other shape. */
 #define NRMS_FLAG_FUSED_SEQ64 8
+/* nrms_encoder_bwd, user encoder (vocab == 0) in fp32 / bf16x3 / bf16, with or without NRMS_FLAG_FUSED_SEQ64; ignored for every
+ * other pass.  The call returns WITHOUT ordering `stream` behind the helper stream that runs its weight-gradient GEMMs: dx and
+ * d(q_vec) are complete in stream order, d(w_qkv), d(b_qkv), d(w_add), d(b_add) (d(w_o), d(b_o)) are NOT -- nothing before the
+ * optimizer reads them, and the next backward on the stream (the news encoder's) can start under them.  The contract:
+ *   - until the join, the caller leaves alone everything those GEMMs read: `workspace` (dQKV, ds, the partial slabs), `x`, the
+ *     saved activations and w.q_vec.  In particular the next nrms_encoder_bwd on the stream needs ANOTHER workspace buffer.
+ *   - the join is the end of the next NRMS_PRECISION_FP16 nrms_encoder_bwd without use_output_proj on the stream (or, where that
+ *     call carries NRMS_FLAG_DEFER_WQKV, its nrms_encoder_bwd_wqkv); any other nrms_encoder_fwd / nrms_encoder_bwd /
+ *     nrms_encoder_bwd_wqkv on the stream joins when it STARTS; nrms_encoder_join does it for a caller that has neither.
+ *   - an error return has joined already.  With NRMS_NO_SIDE_STREAMS there is nothing to join. */
+#define NRMS_FLAG_DEFER_USER_JOIN 16
 
 /* One self-attention + additive-pooling encoder pass over n_seq sequences of seq_len rows.
  * vocab > 0  : news encoder -- input is `ids` [n_seq, seq_len] int64, rows gathered from
@@ -223,6 +235,9 @@ int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encoder_weights* 
 int nrms_encoder_bwd_wqkv(const nrms_encoder_desc* desc, const int64_t* ids, const float* x,
                           const nrms_encoder_acts* acts, const nrms_encoder_grads* grads,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* Orders `stream` behind whatever an earlier nrms_encoder_bwd on it left running on the helper streams (NRMS_FLAG_DEFER_WQKV in
+ * the fp16 mode, NRMS_FLAG_DEFER_USER_JOIN).  A no-op when nothing is outstanding. */
+int nrms_encoder_join(void* stream);
 
 /* Word ids must lie in [0, vocab) before they reach nrms_encoder_fwd / _bwd: the kernels index the table, the
  * token histogram and the placement lists with the raw id.  nn.Embedding raises on an out-of-range index

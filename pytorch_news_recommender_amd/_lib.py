@@ -16,6 +16,7 @@ NRMS_FLAG_PAD_ROW_ZERO = 1
 NRMS_FLAG_DEFER_WQKV = 2
 NRMS_FLAG_FWD_SCRATCH_KEPT = 4
 NRMS_FLAG_FUSED_SEQ64 = 8
+NRMS_FLAG_DEFER_USER_JOIN = 16
 NRMS_PRECISION_FP32 = 0
 NRMS_PRECISION_BF16X3 = 1
 NRMS_PRECISION_BF16 = 2
@@ -89,6 +90,7 @@ SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "nrms_encoder_bwd_wqkv": (C.c_int, [C.POINTER(EncoderDesc), C.c_void_p, C.c_void_p, C.POINTER(EncoderActs),
                                         C.POINTER(EncoderGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nrms_encoder_join": (C.c_int, [C.c_void_p]),
     "nrms_sanitize_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrms_sanitize_ids_i32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrms_title_dedup": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

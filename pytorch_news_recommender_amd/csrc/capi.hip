@@ -145,7 +145,8 @@ static int validate_desc(const nrms_encoder_desc* d, const char* who) {
                      "%s: precision fp16 supports neither masks nor p_drop_attn (use bf16x3)", who);
     }
     NRMS_REQUIRE((d->mask_mode & ~3) == 0, "%s: mask_mode=%d", who, d->mask_mode);
-    NRMS_REQUIRE((d->flags & ~(NRMS_FLAG_PAD_ROW_ZERO | NRMS_FLAG_DEFER_WQKV | NRMS_FLAG_FWD_SCRATCH_KEPT | NRMS_FLAG_FUSED_SEQ64)) == 0,
+    NRMS_REQUIRE((d->flags & ~(NRMS_FLAG_PAD_ROW_ZERO | NRMS_FLAG_DEFER_WQKV | NRMS_FLAG_FWD_SCRATCH_KEPT | NRMS_FLAG_FUSED_SEQ64 |
+                               NRMS_FLAG_DEFER_USER_JOIN)) == 0,
                  "%s: unknown flags 0x%x", who, d->flags);
     if (d->flags & NRMS_FLAG_FUSED_SEQ64) {
         const char* why = nullptr;
@@ -635,10 +636,10 @@ SideSet* side_streams_for(hipStream_t caller) {
     SideSet* ss = new SideSet();
     bool ok = true;
     for (int i = 0; i < 2 && ok; ++i) ok = hipStreamCreateWithFlags(&ss->s[i], hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 8 && ok; ++i) ok = hipEventCreateWithFlags(&ss->ev[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < SIDE_EVENTS && ok; ++i) ok = hipEventCreateWithFlags(&ss->ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {                                     // remember the failure (a null set): do not retry on every call
         for (int i = 0; i < 2; ++i) if (ss->s[i]) (void)hipStreamDestroy(ss->s[i]);
-        for (int i = 0; i < 8; ++i) if (ss->ev[i]) (void)hipEventDestroy(ss->ev[i]);
+        for (int i = 0; i < SIDE_EVENTS; ++i) if (ss->ev[i]) (void)hipEventDestroy(ss->ev[i]);
         delete ss;
         ss = nullptr;
         (void)hipGetLastError();
@@ -650,6 +651,16 @@ SideSet* side_streams_for(hipStream_t caller) {
 int side_order(SideSet* ss, int e, hipStream_t from, hipStream_t to, const char* what) {
     if (hipEventRecord(ss->ev[e], from) != hipSuccess || hipStreamWaitEvent(to, ss->ev[e], 0) != hipSuccess) {
         set_error("%s: ordering the helper stream failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return NRMS_ELAUNCH;
+    }
+    return NRMS_OK;
+}
+
+int side_join_user(SideSet* ss, hipStream_t caller, const char* what) {
+    if (ss == nullptr || !ss->pending_user) return NRMS_OK;
+    ss->pending_user = false;
+    if (hipStreamWaitEvent(caller, ss->ev[SIDE_EV_USER], 0) != hipSuccess) {
+        set_error("%s: hipStreamWaitEvent failed", what);
         return NRMS_ELAUNCH;
     }
     return NRMS_OK;
@@ -697,10 +708,15 @@ extern "C" int nrms_encoder_bwd_wqkv(const nrms_encoder_desc* desc, const int64_
         set_error("encoder_bwd_wqkv: workspace %zu < required %zu bytes", workspace_bytes, L.total);
         return NRMS_EWORKSPACE;
     }
+    // (NRMS_FLAG_DEFER_USER_JOIN: a d(W_add) GEMM still on the helper stream uses the same partial slabs)
+    rc = fused_bwd16_join((hipStream_t)stream);
+    if (rc) return rc;
     char* base = (char*)workspace;
     return bwd_wqkv(desc, gather ? acts->x : x, (const float*)(base + L.dqkv), (const int*)(base + L.n_live), grads,
                     (float*)(base + L.tn_partial), (hipStream_t)stream);
 }
+
+extern "C" int nrms_encoder_join(void* stream) { return fused_bwd16_join((hipStream_t)stream); }
 
 extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encoder_weights* w, const int64_t* ids,
                                 const float* x, const uint8_t* mask, const nrms_encoder_acts* acts, const float* dout,
@@ -746,8 +762,8 @@ extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encode
     float* dq_partial = (float*)(base + L.dq_partial);
     void* wplanes = (void*)(base + L.wplanes);
 
-    // a deferred fp16 join still pending on this stream (NRMS_FLAG_DEFER_WQKV without nrms_encoder_bwd_wqkv yet): order it
-    // first -- the events and helper streams below are the same set
+    // a deferred join still pending on this stream (NRMS_FLAG_DEFER_WQKV without nrms_encoder_bwd_wqkv yet, or an earlier
+    // NRMS_FLAG_DEFER_USER_JOIN): order it first -- the events and helper streams below are the same set
     rc = fused_bwd16_join(s);
     if (rc) return rc;
     SideSet* ss = side_streams_for(s);
@@ -882,9 +898,17 @@ extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encode
         else rc = launch_scatter_grouped((long)M, desc->vocab, d, ids, live, n_live, dctx, drop_e, grads->table,
                                          (int*)(base + L.sscr), s);
     }
-    if (side && rc == NRMS_OK) {                   // the caller's stream continues after the weight gradients too
-        rc = side_order(ss, 4, s2, s, "encoder_bwd");
-        if (rc == NRMS_OK) join_guard.disarm();
+    if (side && rc == NRMS_OK) {
+        if (!gather && (desc->flags & NRMS_FLAG_DEFER_USER_JOIN) != 0) {
+            // the weight gradients stay behind on the helper stream: the fp16 backward that follows on the caller's stream
+            // (launch_fused_bwd16) or fused_bwd16_join orders them.  An event of their own, which no fp16 call records.
+            if (hipEventRecord(ss->ev[SIDE_EV_USER], s2) != hipSuccess) { set_error("encoder_bwd: hipEventRecord failed"); return NRMS_ELAUNCH; }
+            ss->pending_user = true;
+            join_guard.disarm();
+        } else {                                   // the caller's stream continues after the weight gradients too
+            rc = side_order(ss, 4, s2, s, "encoder_bwd");
+            if (rc == NRMS_OK) join_guard.disarm();
+        }
     }
     return rc;
 }

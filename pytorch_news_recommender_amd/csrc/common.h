@@ -190,11 +190,17 @@ int check_launch(const char* what);
 // inside the same C-ABI call (or by the deferred join).  Two engines on two streams -- or on two devices -- of one process
 // get two independent sets; nothing is shared between caller streams.  nullptr = keep everything on the caller's stream
 // (NRMS_NO_SIDE_STREAMS, creation failure, or more than 32 distinct caller streams).
+constexpr int SIDE_EVENTS = 9, SIDE_EV_USER = 8;
 struct SideSet {
     hipStream_t s[2] = {nullptr, nullptr};
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[SIDE_EVENTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool pending = false;          // a deferred join is outstanding (NRMS_FLAG_DEFER_WQKV, fp16 mode)
+    // NRMS_FLAG_DEFER_USER_JOIN: the user encoder's weight-gradient GEMMs still run on s[0]; event SIDE_EV_USER (recorded behind
+    // them, and by nothing else: the fp16 calls re-record events 0 .. 7 while this join is outstanding) orders them
+    bool pending_user = false;
 };
+// Orders the caller's stream behind a pending NRMS_FLAG_DEFER_USER_JOIN (no-op without one)
+int side_join_user(SideSet* ss, hipStream_t caller, const char* what);
 SideSet* side_streams_for(hipStream_t caller);
 // `to` continues from what is enqueued on `from` so far (event e of the set); NRMS_ELAUNCH when the runtime refuses
 int side_order(SideSet* ss, int e, hipStream_t from, hipStream_t to, const char* what);

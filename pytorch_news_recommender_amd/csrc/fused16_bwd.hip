@@ -628,12 +628,12 @@ __global__ __launch_bounds__(256) void absmax_kernel(long n, const float* x, uns
 }
 
 // dout16[n][P16(padded f)] = fp16(dout[n][f] * scale), zero in the padding columns
-__global__ __launch_bounds__(256) void dout16_kernel(long n_seq, int d, int h, int dk, float fixed_scale, const unsigned* max_bits,
-                                                     float* sc, const float* dout, _Float16* dout16) {
-    const float scale = loss_scale_from_max(*max_bits, fixed_scale);
+// (n_blocks: the blocks that share the rows -- dout16_maps_kernel appends blocks with other work)
+__device__ __forceinline__ void dout16_rows(long n_seq, int d, int h, int dk, float scale, float* sc, const float* dout, _Float16* dout16,
+                                            int n_blocks) {
     if (blockIdx.x == 0 && threadIdx.x == 0) { sc[0] = scale; sc[1] = 1.0f / scale; }
     const long total = n_seq * F16_DP;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)n_blocks * blockDim.x) {
         const long r = i / F16_DP;
         const int p = (int)(i - r * F16_DP);
         const int b16 = p >> 4, t = p & 15, hh = t >> 3, jj = t & 7;
@@ -643,6 +643,11 @@ __global__ __launch_bounds__(256) void dout16_kernel(long n_seq, int d, int h, i
         if (head < h && f < dk) v = dout[r * d + head * dk + f] * scale;
         dout16[i] = (_Float16)v;
     }
+}
+
+__global__ __launch_bounds__(256) void dout16_kernel(long n_seq, int d, int h, int dk, float fixed_scale, const unsigned* max_bits,
+                                                     float* sc, const float* dout, _Float16* dout16) {
+    dout16_rows(n_seq, d, h, dk, loss_scale_from_max(*max_bits, fixed_scale), sc, dout, dout16, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -659,9 +664,11 @@ struct Prep16bArgs {
                           // fragments of W' (rows = dqkv16 columns, 64 per slab; columns = input features) in the order a
                           // wave reads them -- one contiguous KiB per (k-step, n-tile), filled by LDS-DMA
     _Float16* qv16;       // [QP]
+    unsigned* max_bits;   // cleared for the absmax_kernel that follows in stream order (or null)
 };
 
 __global__ __launch_bounds__(256) void prep16b_kernel(Prep16bArgs a) {
+    if (a.max_bits != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *a.max_bits = 0u;
     const float qscale = 1.0f / sqrtf((float)a.dk);
     constexpr int KP = F16_KP;
     const long n1 = (long)4 * a.h * 32 * KP, n2 = (long)30 * 32 * KP, n3 = F16_QP, n4 = (long)3 * a.h * 32;
@@ -1071,10 +1078,10 @@ __global__ __launch_bounds__(1024) void red16_kernel(const float* red, int n_wg,
 }
 
 // index maps of the reduce: rows of d(W_qkv) (dqkv16 column order), columns of d(W_add) (ctx16 column order)
-__global__ void maps16_kernel(int d, int h, int dk, int q, const float* sc, float qscale, int* nmap_qkv, float* nscale_qkv,
-                              int* kmap_x, int* nmap_add, float* nscale_add, int* kmap_ctx) {
-    const float inv_scale = sc[1];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+struct Maps16 { int *nmap_qkv, *kmap_x, *nmap_add, *kmap_ctx; float *nscale_qkv, *nscale_add; };
+__device__ __forceinline__ void maps16_entry(int i, int d, int h, int dk, int q, float inv_scale, float qscale, const Maps16& m) {
+    int* const nmap_qkv = m.nmap_qkv; int* const kmap_x = m.kmap_x; int* const nmap_add = m.nmap_add; int* const kmap_ctx = m.kmap_ctx;
+    float* const nscale_qkv = m.nscale_qkv; float* const nscale_add = m.nscale_add;
     if (i < B16_DQ) {
         const int head = i / 96, rem = i - head * 96, which = rem >> 5, p = rem & 31;
         const int s = p >> 4, t = p & 15, hh = t >> 3, jj = t & 7;
@@ -1090,6 +1097,22 @@ __global__ void maps16_kernel(int d, int h, int dk, int q, const float* sc, floa
         const int head = fpad >> 5, f = fpad & 31;
         kmap_ctx[i] = (head < h && f < dk) ? head * dk + f : -1;
     }
+}
+
+// dout16_kernel and the index maps in one launch: both need nothing but the loss scale (max |dout| is complete in stream order).
+// The last MAPS16_BLOCKS blocks write the maps, with 1 / scale computed as block 0 computes sc[1]; the others share the rows.
+constexpr int MAPS16_BLOCKS = (B16_DQ + 255) / 256;
+static_assert(B16_DQ >= F16_KP && B16_DQ >= F16_QP && B16_DQ >= F16_DP, "maps16_entry: one thread per entry of the longest map");
+__global__ __launch_bounds__(256) void dout16_maps_kernel(long n_seq, int d, int h, int dk, int q, float fixed_scale, float qscale,
+                                                          const unsigned* max_bits, float* sc, const float* dout, _Float16* dout16,
+                                                          Maps16 m) {
+    const float scale = loss_scale_from_max(*max_bits, fixed_scale);
+    const int n_rows_blocks = (int)gridDim.x - MAPS16_BLOCKS;
+    if ((int)blockIdx.x >= n_rows_blocks) {
+        maps16_entry(((int)blockIdx.x - n_rows_blocks) * 256 + (int)threadIdx.x, d, h, dk, q, 1.0f / scale, qscale, m);
+        return;
+    }
+    dout16_rows(n_seq, d, h, dk, scale, sc, dout, dout16, n_rows_blocks);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1204,6 +1227,20 @@ int launch_dout16(long n_seq, int d, int h, int dk, float fixed_scale, float* sc
     return check_launch("dout16");
 }
 
+// The same with max_bits cleared already (prep16b_kernel, earlier in stream order) and the index maps of the two weight-gradient
+// reduces written by the same launch: absmax + one kernel instead of memset + absmax + dout16 + maps16
+static int launch_dout16_maps(long n_seq, int d, int h, int dk, int q, float fixed_scale, float qscale, float* sc, const float* dout,
+                              _Float16* dout16, const Maps16& m, hipStream_t stream) {
+    unsigned* max_bits = (unsigned*)(sc + 2);
+    const long nd = n_seq * d;
+    if (!(fixed_scale > 0.f))
+        hipLaunchKernelGGL(absmax_kernel, dim3(nd > 512L * 1024 ? 512 : (int)cdiv(nd, 1024)), dim3(256), 0, stream, nd, dout, max_bits);
+    const int row_blocks = cdiv(n_seq * F16_DP, 256) > 4096 ? 4096 : cdiv(n_seq * F16_DP, 256);
+    hipLaunchKernelGGL(dout16_maps_kernel, dim3(row_blocks + MAPS16_BLOCKS), dim3(256), 0, stream, n_seq, d, h, dk, q, fixed_scale,
+                       qscale, max_bits, sc, dout, dout16, m);
+    return check_launch("dout16");
+}
+
 int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
     if (f.n_seq <= 0) return NRMS_OK;
     const long M = (long)f.n_seq * f.S;
@@ -1230,7 +1267,10 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
     if (f.sc_out != nullptr) *f.sc_out = sc;
     float* partial_qkv = (float*)(base + L.partial);
     float* partial_add = (float*)(base + L.partial + up256((size_t)L.tn_splits_qkv * B16_DQ * F16_KP * 4));
-    { const int jr = fused_bwd16_join(stream); if (jr) return jr; }      // an un-joined earlier call on this stream: order it first
+    // an un-joined earlier fp16 call on this stream: order it first.  A user encoder's deferred weight gradients
+    // (NRMS_FLAG_DEFER_USER_JOIN) keep running on helper stream 0 -- what this call gives that stream queues behind them, they
+    // read nothing this call writes (the caller's contract), and the caller's stream joins them at the END of this call
+    { const int jr = fused_bwd16_join(stream, false); if (jr) return jr; }
     // (NRMS_NO_SIDE_STREAMS is read per call so that a profiler pass can serialise the step: exclusive kernel durations)
     SideSet* ss = side_streams_for(stream);
     const bool side = ss != nullptr;
@@ -1241,13 +1281,15 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
         Prep16bArgs p{};
         p.d = f.d; p.h = f.h; p.dk = dk; p.q = f.q; p.w_qkv = f.w_qkv; p.b_qkv = f.b_qkv; p.w_add = f.w_add; p.q_vec = f.q_vec;
         p.btiles = btiles; p.xtiles = xtiles; p.qv16 = qv16; p.bqkv32 = bqkv32;
+        p.max_bits = (unsigned*)(sc + 2);                       // (in place of a memset in front of absmax_kernel)
         TimingScope ts("prep16", stream);
         hipLaunchKernelGGL(prep16b_kernel, dim3(2048), dim3(256), 0, stream, p);
-        int rc0 = launch_dout16((long)f.n_seq, f.d, f.h, dk, f.loss_scale, sc, f.dout, dout16, stream);
-        if (rc0) return rc0;
-        hipLaunchKernelGGL(maps16_kernel, dim3(cdiv(B16_DQ, 256)), dim3(256), 0, stream, f.d, f.h, dk, f.q, sc, qscale,
-                           nmap_qkv, nscale_qkv, kmap_x, nmap_add, nscale_add, kmap_ctx);
         int rc = check_launch("prep16b");
+        if (rc) return rc;
+        Maps16 mp;
+        mp.nmap_qkv = nmap_qkv; mp.nscale_qkv = nscale_qkv; mp.kmap_x = kmap_x; mp.nmap_add = nmap_add; mp.nscale_add = nscale_add;
+        mp.kmap_ctx = kmap_ctx;
+        rc = launch_dout16_maps((long)f.n_seq, f.d, f.h, dk, f.q, f.loss_scale, qscale, sc, f.dout, dout16, mp, stream);
         if (rc) return rc;
     }
     Bwd16Args a{};
@@ -1298,13 +1340,6 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
         int rc = check_launch("fused_bwd16");
         if (rc) return rc;
     }
-    {
-        TimingScope ts("red16", stream);
-        hipLaunchKernelGGL(red16_kernel, dim3(cdiv(B16_RED, 32)), dim3(1024), 0, stream, red, 2 * n_wg, f.h, dk, f.d, f.q, sc,
-                           qscale, f.db_qkv, f.db_add, f.dq_vec);
-        int rc = check_launch("red16");
-        if (rc) return rc;
-    }
     int rc = NRMS_OK;
     if (!side) {
         rc = launch_tn16(1, dz16, F16_QP, F16_QP, (const _Float16*)f.ctx16, F16_DP, F16_DP, Mp, nullptr, partial_add,
@@ -1327,27 +1362,40 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
         g.sc = sc; g.lda = B16_DQ; g.n_slabs = DX_SLABS;
         rc = launch_dx16(g, f.dx_fp16, stream);
     }
+    // the bias gradients and d(q_vec) from the two kernels' per-workgroup sums: nobody reads them before the optimizer, so they
+    // follow the d(W_qkv) fork and the dX GEMM instead of standing in front of both.  (red16 is the only writer of d(b_qkv),
+    // d(b_add) and d(q_vec) in this call -- the tn16 reduces on the helper streams write d(W_qkv) / d(W_add) only -- and `red`
+    // and `sc` are not written again.)
+    if (rc == NRMS_OK) {
+        TimingScope ts("red16", stream);
+        hipLaunchKernelGGL(red16_kernel, dim3(cdiv(B16_RED, 32)), dim3(1024), 0, stream, red, 2 * n_wg, f.h, dk, f.d, f.q, sc,
+                           qscale, f.db_qkv, f.db_add, f.dq_vec);
+        rc = check_launch("red16");
+    }
     if (side && rc == NRMS_OK) {                                    // join: the caller's stream continues after both GEMMs
-        if (f.defer_join) ss->pending = true;                       // ... or later, in fused_bwd16_join
+        if (f.defer_join) ss->pending = true;                       // ... or later, in fused_bwd16_join (pending_user with it)
         else if (hipStreamWaitEvent(stream, ss->ev[2], 0) != hipSuccess || hipStreamWaitEvent(stream, ss->ev[3], 0) != hipSuccess) {
             set_error("fused_bwd16: hipStreamWaitEvent failed");
             return NRMS_ELAUNCH;                                    // (the guard still joins what it can)
-        }
+        } else if ((rc = side_join_user(ss, stream, "fused_bwd16")) != NRMS_OK) return rc;
         join_guard.disarm();
     }
     return rc;
 }
 
-// The other half of Fused16Bwd::defer_join: work enqueued on `stream` after this sees d(W_qkv), d(b_qkv), d(W_add), d(b_add).
-int fused_bwd16_join(hipStream_t stream) {
+// The other half of Fused16Bwd::defer_join: work enqueued on `stream` after this sees d(W_qkv), d(b_qkv), d(W_add), d(b_add) --
+// and, with `user`, the weight gradients a user encoder's backward left behind (NRMS_FLAG_DEFER_USER_JOIN).
+int fused_bwd16_join(hipStream_t stream, bool user) {
     SideSet* ss = side_streams_for(stream);
-    if (ss == nullptr || !ss->pending) return NRMS_OK;
-    ss->pending = false;
-    if (hipStreamWaitEvent(stream, ss->ev[2], 0) != hipSuccess || hipStreamWaitEvent(stream, ss->ev[3], 0) != hipSuccess) {
-        set_error("fused_bwd16_join: hipStreamWaitEvent failed");
-        return NRMS_ELAUNCH;
+    if (ss == nullptr) return NRMS_OK;
+    if (ss->pending) {
+        ss->pending = false;
+        if (hipStreamWaitEvent(stream, ss->ev[2], 0) != hipSuccess || hipStreamWaitEvent(stream, ss->ev[3], 0) != hipSuccess) {
+            set_error("fused_bwd16_join: hipStreamWaitEvent failed");
+            return NRMS_ELAUNCH;
+        }
     }
-    return NRMS_OK;
+    return user ? side_join_user(ss, stream, "fused_bwd16_join") : NRMS_OK;
 }
 
 }  // namespace nrms

@@ -395,7 +395,7 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream);
 // fused16v1_bwd_bytes(M, n_seq, h) bytes
 size_t fused16v1_bwd_bytes(long M, int n_seq, int h);
 int launch_fused_bwd16v1(const Fused16Bwd& f, hipStream_t stream);
-int fused_bwd16_join(hipStream_t stream);
+int fused_bwd16_join(hipStream_t stream, bool user = true);
 
 // user64.hip: the split-bf16 user encoder (sequences of 33..64 rows) as one kernel per direction (NRMS_FLAG_FUSED_SEQ64)
 bool user64_supported(int S, int d, int h, int q, const char** why);

@@ -12,6 +12,8 @@
 // the GEMM waves -- see gemm.h).
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "gemm.h"
 
 namespace nrms {
@@ -290,6 +292,21 @@ static int launch_bf_inst(const BFArgs& a, hipStream_t stream, const char* name)
     return check_launch(name);
 }
 
+// hipDeviceProp_t::multiProcessorCount of the current device, asked once (every device of a process is the same part here)
+static int cu_count() {
+    static std::atomic<int> cached{0};
+    int n = cached.load(std::memory_order_relaxed);
+    if (n > 0) return n;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) {
+        (void)hipGetLastError();
+        return 256;
+    }
+    cached.store(prop.multiProcessorCount, std::memory_order_relaxed);
+    return prop.multiProcessorCount;
+}
+
 template <int AMODE, int EMODE, int NPASS>
 static int launch_bf_mode(const BFArgs& a, hipStream_t stream, const char* name) {
     const int N = a.g.N;
@@ -301,6 +318,24 @@ static int launch_bf_mode(const BFArgs& a, hipStream_t stream, const char* name)
         if (cand[i] < 8 && N > 128) continue;
         const long pad = (long)cdiv(N, cand[i] * 16) * cand[i] * 16;
         if (best < 0 || pad < best) { best = pad; nt = cand[i]; }
+    }
+    // Few rows: that choice leaves most CUs without a workgroup (the user encoder's dX GEMM: 25 600 rows, N = 300 -> 100 row
+    // tiles x 1 column block on 256 CUs).  When it fills less than half of them, take the least-padded tile that splits the
+    // columns into more blocks and still fits the CUs (N = 300: 10 tiles, two blocks).  A re-read of A costs nothing on an idle
+    // GPU; at large M the wide tile stays (narrow tiles lost there, docs/EXPERIMENTS.md).  The k order of an output element
+    // does not depend on the tile: results are bit-identical.  NRMS_NT_WIDE_TILES: tuning only, forces the first choice.
+    const long row_tiles = cdiv(a.g.M, a.g.rows_per_tile);
+    const int n_cu = cu_count();
+    if (2 * row_tiles * cdiv(N, nt * 16) <= n_cu && getenv("NRMS_NT_WIDE_TILES") == nullptr) {
+        const int blocks0 = cdiv(N, nt * 16);
+        long best2 = -1;
+        for (int i = 0; i < 6; ++i) {
+            if (cand[i] < 8) continue;
+            const int blocks = cdiv(N, cand[i] * 16);
+            if (blocks <= blocks0 || row_tiles * blocks > n_cu) continue;
+            const long pad = (long)blocks * cand[i] * 16;
+            if (best2 < 0 || pad < best2) { best2 = pad; nt = cand[i]; }
+        }
     }
     switch (nt) {
         case 19: return launch_bf_inst<19, AMODE, EMODE, NPASS>(a, stream, name);

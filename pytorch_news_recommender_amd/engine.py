@@ -446,14 +446,24 @@ class NRMSEngine:
         nbytes = max(self.lib.nrms_encoder_bwd_workspace_bytes(C.byref(d)) for d in descs)
         return self._buf("bwd_ws", (nbytes + 3) // 4)
 
-    def encode_users_backward(self, flat, gflat, news_vectors, dout, dx=None, tag="user", mask=None, mask_mode=0):
+    def encode_users_backward(self, flat, gflat, news_vectors, dout, dx=None, tag="user", mask=None, mask_mode=0,
+                              defer_join=False):
         """Backward of encode_users(save=True): accumulates the user-encoder parameter gradients into
-        gflat and returns d(news_vectors) [B, H, d]."""
+        gflat and returns d(news_vectors) [B, H, d].
+
+        defer_join (Engine.backward only): NRMS_FLAG_DEFER_USER_JOIN -- the weight-gradient GEMMs are still running on a helper
+        stream when this returns (d(news_vectors) is complete in stream order); the fp16 news-encoder backward that follows
+        joins them, or join_backward().  Their inputs then live in a workspace of this call's own, not in the shared one."""
         B, H, d = news_vectors.shape
         if dx is None:
             dx = torch.empty(B * H, d, dtype=torch.float32, device=self.device)
         desc = self._desc("user_encoder", B, H, mask_mode=mask_mode if mask is not None else 0, training=True)
-        ws = self._bwd_workspace(desc)
+        if defer_join and desc.precision != _lib.NRMS_PRECISION_FP16:
+            desc.flags |= _lib.NRMS_FLAG_DEFER_USER_JOIN
+            nbytes = self.lib.nrms_encoder_bwd_workspace_bytes(C.byref(desc))
+            ws = self._buf("bwd_ws_user", (nbytes + 3) // 4)
+        else:
+            ws = self._bwd_workspace(desc)
         w, g = self._weights(flat, "user_encoder"), self._grads(gflat, "user_encoder")
         acts = self._acts(tag, B * H, True, desc=desc)
         rc = self.lib.nrms_encoder_bwd(C.byref(desc), C.byref(w), None, _lib.ptr(news_vectors),
@@ -462,6 +472,10 @@ class NRMSEngine:
                                        C.c_size_t(ws.numel() * 4), _stream())
         _lib.check(rc, "nrms_encoder_bwd(user)")
         return dx[:B * H].view(B, H, d)
+
+    def join_backward(self):
+        """Order the current stream behind whatever an earlier backward left on the library's helper streams."""
+        _lib.check(self.lib.nrms_encoder_join(_stream()), "nrms_encoder_join")
 
     # ---- full model backward ------------------------------------------------------------
     def backward(self, flat, gflat, dscores, table_grad_ready=None, gen=None):
@@ -499,23 +513,32 @@ class NRMSEngine:
         desc_u = self._desc("user_encoder", B, H, mask_mode=sv["user_mask_mode"], training=True)
         desc_n = self._desc("news_encoder", N, L, sv["p_embed"], sv["p"], sv["seed"], training=True)
         ws = self._bwd_workspace(desc_u, desc_n)
+        # the user encoder's weight gradients feed nothing before the optimizer: where the fp16 news backward follows (it joins
+        # them at its end) they stay on their helper stream, reading a workspace of their own (the news backward overwrites `ws`)
+        defer_user = desc_n.precision == _lib.NRMS_PRECISION_FP16 and not self.dims.output_proj
         self.encode_users_backward(flat, gflat, hist.view(B, H, d), duser, dx=dnv, tag="user", mask=sv["user_mask"],
-                                   mask_mode=sv["user_mask_mode"])
+                                   mask_mode=sv["user_mask_mode"], defer_join=defer_user)
         wn, gn = self._weights(flat, "news_encoder"), self._grads(gflat, "news_encoder")
         acts_n = self._acts("news", N * L, True, gather=True, desc=desc_n)
         if desc_n.precision == _lib.NRMS_PRECISION_FP16:
             desc_n.flags |= _lib.NRMS_FLAG_FWD_SCRATCH_KEPT     # acts_n.scratch is this step's forward scratch (its own buffer)
         if table_grad_ready is not None:
             desc_n.flags |= _lib.NRMS_FLAG_DEFER_WQKV
-        rc = self.lib.nrms_encoder_bwd(C.byref(desc_n), C.byref(wn), _lib.ptr(sv["ids"]), None, None, C.byref(acts_n),
-                                       _lib.ptr(dnv), C.byref(gn), None, _lib.ptr(ws),
-                                       C.c_size_t(ws.numel() * 4), _stream())
-        _lib.check(rc, "nrms_encoder_bwd(news)")
-        if table_grad_ready is not None:
-            table_grad_ready()
-            rc = self.lib.nrms_encoder_bwd_wqkv(C.byref(desc_n), _lib.ptr(sv["ids"]), None, C.byref(acts_n), C.byref(gn),
-                                                _lib.ptr(ws), C.c_size_t(ws.numel() * 4), _stream())
-            _lib.check(rc, "nrms_encoder_bwd_wqkv(news)")
+        rc_join = 0
+        try:
+            rc = self.lib.nrms_encoder_bwd(C.byref(desc_n), C.byref(wn), _lib.ptr(sv["ids"]), None, None, C.byref(acts_n),
+                                           _lib.ptr(dnv), C.byref(gn), None, _lib.ptr(ws),
+                                           C.c_size_t(ws.numel() * 4), _stream())
+            _lib.check(rc, "nrms_encoder_bwd(news)")
+            if table_grad_ready is not None:
+                table_grad_ready()
+                rc = self.lib.nrms_encoder_bwd_wqkv(C.byref(desc_n), _lib.ptr(sv["ids"]), None, C.byref(acts_n), C.byref(gn),
+                                                    _lib.ptr(ws), C.c_size_t(ws.numel() * 4), _stream())
+                _lib.check(rc, "nrms_encoder_bwd_wqkv(news)")
+        finally:
+            if defer_user:      # joined already unless the news backward failed or had no title to run on: a no-op then
+                rc_join = self.lib.nrms_encoder_join(_stream())
+        _lib.check(rc_join, "nrms_encoder_join")
 
     def adam_step(self, flat, gflat, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                   grad_scale=1.0, guard=None):
