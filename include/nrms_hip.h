@@ -529,6 +529,39 @@ int nrms_negative_sample(int64_t n_imp, const int64_t* imp_ptr /* [n_imp + 1] */
                          uint64_t seed, int64_t* cand /* [n_samples, S + 1] */, int64_t* clen /* [n_samples] */, int32_t* n_bad,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Click log: negatives from the whole catalogue, redrawn per epoch (csrc/catneg.hip; data_handler.py ClickFeed; PARITY UNPINNED,
+ * the reference trains on impressions only).  A data set that records who clicked what, and no impressions, has no non-clicked news
+ * to draw from: row r (one click: a user, the clicked news row_pos[r], a key row_key[r] that names the click, e.g. its position in
+ * the log) takes S negatives from the catalogue by integer weights.  set_ptr [n_users + 1] / set_news hold every user's distinct
+ * clicked news in ascending id (the user side of nrms_click_graph); cum [n_news + 1] is the exclusive running sum of the
+ * non-negative weights per news id: cum[0] = cum[1] = 0 (id 0 is the padding slot), nondecreasing, W = cum[n_news] in [1, 2^62].
+ *   draw of row key k, slot s = 0 .. S - 1, attempt a = 0 .. 7:
+ *     r4 = philox4x32_7(seed, group = ((k * 64 + s) << 2) | (a >> 1), site 7)      (the counter layout of the dropout sites, csrc/common.h)
+ *     u = (uint64) r4[2 (a & 1)] << 32 | r4[2 (a & 1) + 1];   x = (u * W) >> 64      (the high half of the 128-bit product: x < W)
+ *     n(s, a) = the id with cum[n] <= x < cum[n + 1]                               (an id of weight 0 is never drawn, ties in cum included)
+ *   value of slot s = n(s, a) of the FIRST attempt a for which it is not 0, not in set_news[set_ptr[u] .. set_ptr[u + 1]) for
+ *     u = row_user[r], and not the value of a slot s' < s of the same row; no value if all eight fail.  A slot depends on lower slots
+ *     only: the values for S = 4 are the first four for S = 8.
+ *   row r of cand [n_rows, S + 1] int64: slot 0 = row_pos[r], then the valued slots in slot order, packed to the front, then zeros;
+ *     clen [n_rows] int64 = 1 + the number of valued slots; *n_short (device int32) += the slots left without a value (informational:
+ *     a user whose set covers most of the weight, or a catalogue of fewer than S eligible ids).
+ * A row whose user is outside [0, n_users) or whose positive is outside (0, n_news) writes cand = [0 ...], clen = 1, adds one to
+ * *n_bad (device int32, as nrms_sanitize_ids counts) and nothing to *n_short.  Every byte of cand and clen is written, by one plain
+ * store each; the only atomics are the two integer counters.  The result is a function of (row_key, row_user, row_pos, the sets, cum, S,
+ * seed) alone: not of the row's position, n_rows, the launch geometry or what the workspace holds -- a row drawn alone, in another
+ * order or on another rank has the same bytes.  1 <= S <= 64, 2 <= n_news < 2^31, 0 <= n_rows < 2^31 (0: nothing is launched),
+ * 0 <= n_users < 2^31, 0 <= row_key < 2^48 (the group must not wrap).  Bad scalar arguments, null pointers and a workspace below
+ * nrms_catalogue_negative_sample_workspace_bytes(n_rows, n_news, S) bytes (4-byte aligned; reserved, the call touches none of it today;
+ * the query returns 0 for arguments the call would refuse) return non-zero before any launch.  No host synchronisation, no allocation.
+ * One kernel: a row is a segment of P = next power of two >= S lanes of a wavefront; attempts 2 .. 7 are computed only by
+ * wavefronts in which a slot has used up the attempts before them. */
+size_t nrms_catalogue_negative_sample_workspace_bytes(int64_t n_rows, int64_t n_news, int32_t S);
+int nrms_catalogue_negative_sample(int64_t n_rows, const int64_t* row_key /* [n_rows] */, const int32_t* row_user /* [n_rows] */,
+                                   const int32_t* row_pos /* [n_rows] */, int64_t n_users, const int64_t* set_ptr /* [n_users + 1] */,
+                                   const int32_t* set_news /* [set_ptr[n_users]] */, int64_t n_news, const int64_t* cum /* [n_news + 1] */,
+                                   int32_t S, uint64_t seed, int64_t* cand /* [n_rows, S + 1] */, int64_t* clen /* [n_rows] */,
+                                   int32_t* n_short, int32_t* n_bad, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- All-padding sequences of the output-projection topology in closed form (csrc/empty_seq.hip; nrms_naml's word-level
  * encoder, model/nrms_naml.py:42-100,121-177: 41 % of a MIND-shaped batch's title / abstract slots are history padding).  With a
  * zero padding row every Q | K | V row of such a sequence is the bias, so attention row i is b_v scaled per head by

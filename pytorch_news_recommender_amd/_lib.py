@@ -132,6 +132,9 @@ SIGNATURES = {
     "nrms_negative_sample_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
     "nrms_negative_sample": (C.c_int, [C.c_int64] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 3
                              + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nrms_catalogue_negative_sample_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "nrms_catalogue_negative_sample": (C.c_int, [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                                 C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "nrms_hier_add_embedding_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "nrms_hier_add_embedding_bwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.c_void_p]),

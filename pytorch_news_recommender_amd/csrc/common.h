@@ -43,6 +43,9 @@ struct Keep4 { bool k[4]; };
 constexpr uint32_t PHILOX_SITE_GRAPH_SAMPLE = 5u;
 // Site 6: the shuffle keys of csrc/negsample.hip, group = (position in the impression log) >> 2, word = position & 3.
 constexpr uint32_t PHILOX_SITE_NEG_SAMPLE = 6u;
+// Site 7: the catalogue draws of csrc/catneg.hip, group = ((row key * 64 + slot) << 2) | (attempt >> 1), words 2 (attempt & 1) and
+// 2 (attempt & 1) + 1 of the call.
+constexpr uint32_t PHILOX_SITE_CATALOGUE_NEG = 7u;
 
 __host__ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2,
                                                       uint32_t& c3, uint32_t k0, uint32_t k1) {

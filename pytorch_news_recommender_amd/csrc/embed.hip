@@ -338,19 +338,26 @@ __global__ __launch_bounds__(256) void scatter_grouped_kernel(int V, int d4, con
             }
         }
     };
-    // The placement fills a bucket in whatever order its atomics resolve.  Each 64-entry chunk of the bucket is
-    // therefore consumed in ASCENDING row order (wave-wide minimum selection): a word that occurs at most 64
-    // times in the step -- all of them in practice outside a handful of stop words -- gets a bit-reproducible
-    // gradient row; longer buckets are reproducible up to the order of their chunks.
-    for (int k0 = beg; k0 < end; k0 += 64) {
-        const int n = min(64, end - k0);
-        int mine = lane < n ? order[k0 + lane] : 0x7fffffff;
+    // The placement fills a bucket in whatever order its atomics resolve.  Each 256-entry chunk of the bucket (four
+    // entries per lane, in four registers) is therefore consumed in ASCENDING row order (wave-wide minimum
+    // selection): a word that occurs at most 256 times in the step -- all of them in practice outside a handful of
+    // stop words -- gets a bit-reproducible gradient row; longer buckets are reproducible up to the order of their
+    // chunks.  (A bucket of at most 64 entries leaves three of the registers empty: the order, and the sum, it always had.)
+    constexpr int NONE = 0x7fffffff;
+    for (int k0 = beg; k0 < end; k0 += 256) {
+        const int n = min(256, end - k0);
+        int m0 = lane < n ? order[k0 + lane] : NONE, m1 = lane + 64 < n ? order[k0 + 64 + lane] : NONE;
+        int m2 = lane + 128 < n ? order[k0 + 128 + lane] : NONE, m3 = lane + 192 < n ? order[k0 + 192 + lane] : NONE;
         for (int i = 0; i < n; ++i) {
-            int m = mine;
+            int m = min(min(m0, m1), min(m2, m3));
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o, 64));
             add_row(m);
-            if (mine == m) mine = 0x7fffffff;
+            // (a row is listed once: at most one of the four matches)
+            m0 = m0 == m ? NONE : m0;
+            m1 = m1 == m ? NONE : m1;
+            m2 = m2 == m ? NONE : m2;
+            m3 = m3 == m ? NONE : m3;
         }
     }
 #pragma unroll

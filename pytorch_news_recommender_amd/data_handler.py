@@ -226,6 +226,7 @@ class SyntheticMind:
         self.n_topics = n_topics
         self.rng = rng
         self.imp_rng = np.random.default_rng(seed + 2000003)       # train_impressions' own stream, as the abstracts have theirs
+        self.click_rng = np.random.default_rng(seed + 3000003)     # click_log's own stream
         self.by_topic = [np.flatnonzero(self.topic == t) + 1 for t in range(n_topics)]   # 1-based ids
 
     def embedding_table(self, d, seed=0):
@@ -306,6 +307,19 @@ class SyntheticMind:
             samples.append([hist, self._cat(hist), self._sub(hist), imps, self._cat(imps), self._sub(imps)])
             labels.append([1 if i < npos else 0 for i in perm])
         return samples, labels
+
+    def click_log(self, n_users, min_clicks=6, max_clicks=80):
+        """A click log without impressions for ``ClickFeed``: ``(user_ptr int64 [n_users + 1], clicks int64)``, user u's clicks in
+        time order at ``clicks[user_ptr[u]:user_ptr[u + 1]]``, min_clicks .. max_clicks each; every user has a topic and clicks
+        mostly inside it (``_pick``).  Drawn from a generator of its own, as ``train_impressions`` is: no other stream moves."""
+        rng = self.click_rng
+        lens, clicks = [], []
+        for _ in range(n_users):
+            t = int(rng.integers(0, self.n_topics))
+            n = int(rng.integers(int(min_clicks), int(max_clicks) + 1))
+            clicks += self._pick(t, n, rng=rng)
+            lens.append(n)
+        return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(clicks, dtype=np.int64)
 
 
 class LazyBatch(Mapping):
@@ -445,7 +459,7 @@ class DeviceFeed:
 
         def sel(name):                                                # rows of one packed array, gathered once
             if name not in memo:
-                memo[name] = p[name].index_select(0, rows)
+                memo[name] = self._rows_of(name, rows)
             return memo[name]
 
         def text(table, slots, width):
@@ -469,6 +483,9 @@ class DeviceFeed:
                           'candidate_categ_ids': lambda: sel("ccat"),
                           'candidate_subcateg_ids': lambda: sel("csub"),
                           'candidate_mask': lambda: mask(S, "clen")})
+
+    def _rows_of(self, name, rows):
+        return self.packed[name].index_select(0, rows)
 
     def __iter__(self):
         if self.shuffle:
@@ -667,3 +684,202 @@ class ImpressionFeed(DeviceFeed):
             order = torch.arange(self.row0, self.row0 + self.n, device=self.device)
         for b in range(len(self)):
             yield self.batch(order[b * self.batch_size:(b + 1) * self.batch_size])
+
+
+CLICK_WEIGHT_ONE = 65536                         # ClickFeed: w(n) = floor(count(n) ** popularity_power * 65536)
+
+
+class ClickFeed(DeviceFeed):
+    """A training ``DeviceFeed`` over a CLICK LOG -- who clicked what, in what order, and no impressions -- whose negatives are
+    drawn from the whole catalogue at the start of every epoch, on the device (``nrms_catalogue_negative_sample``,
+    include/nrms_hip.h "Click log").  ``clicks[user_ptr[u]:user_ptr[u + 1]]`` are user u's clicks in time order, ids in (0, N),
+    N = the rows of the title table.  A user's last ``holdout`` clicks are held out (``heldout_samples()``); the rest is the
+    user's training part, and a user with fewer than ``min_history + 1`` training clicks gives no rows, no held-out targets and
+    counts for nothing.  Every training position t >= min_history is one row: positive ``clicks[t]``, history the up to
+    ``config.history_len`` clicks before t (oldest first, left-aligned), key = the click's position in the log
+    ``user_ptr[u] + t`` -- so a click's draw does not depend on which other rows exist.  Histories are not stored per row: a
+    batch gathers them from the resident log by index arithmetic (16 bytes per row instead of 8 * history_len).
+
+    Negatives: S = config.sample_size per row by weight w(n) = floor(count(n) ** popularity_power * 65536), count(n) = the
+    training users who clicked n (power 0: w = 1 for every n >= 1, a uniform draw; ``weights`` int64 [N] overrides both), never a
+    news of the user's own training part (the held-out clicks are NOT rejected: that would leak them), never twice in a row.
+    A slot whose eight attempts all fail stays empty (masked out) and is counted in ``n_short``.
+
+    ``epoch_seed``, ``draw``, ``resample``, ``rank`` / ``world`` and ``news_info()`` as in ``ImpressionFeed``: the draw is a
+    function of the log, the seed and the epoch only; one host synchronisation per epoch reads the two counters.  There is no
+    CPU path for the draw.  ``news_categ`` / ``news_subcateg``: int64 [N] per-news tables for the category keys (zeros without)."""
+
+    def __init__(self, config, user_ptr, clicks, id2title_dict=None, id2abst_dict=None, news_categ=None, news_subcateg=None, holdout=1,
+                 min_history=1, popularity_power=0.75, weights=None, batch_size=None, device="cuda", shuffle=False, drop_last=False, seed=0,
+                 resample=True, rank=0, world=1):
+        user_ptr, clicks = np.asarray(user_ptr, dtype=np.int64).reshape(-1), np.asarray(clicks, dtype=np.int64).reshape(-1)
+        if user_ptr.size < 1 or user_ptr[0] != 0 or (np.diff(user_ptr) < 0).any() or int(user_ptr[-1]) != clicks.size:
+            raise ValueError("ClickFeed: user_ptr must rise from 0 to len(clicks) = %d" % clicks.size)
+        if int(holdout) < 0 or int(min_history) < 0:
+            raise ValueError("ClickFeed: holdout = %r and min_history = %r must be >= 0" % (holdout, min_history))
+        if not 0 <= int(rank) < int(world):
+            raise ValueError("ClickFeed: rank = %r of world = %r" % (rank, world))
+        if not float(popularity_power) >= 0.0:
+            raise ValueError("ClickFeed: popularity_power = %r must be >= 0" % (popularity_power,))
+        if clicks.size >= 2 ** 48:
+            raise ValueError("ClickFeed: a row's key is its log position, below 2^48")
+        DeviceFeed.__init__(self, config, [], type=0, id2title_dict=id2title_dict, id2abst_dict=id2abst_dict, batch_size=batch_size,
+                            device=device, shuffle=shuffle, drop_last=drop_last, seed=seed)
+        N, H, S = int(self.titles.shape[0]), int(config.history_len), self.S
+        if clicks.size and (clicks.min() <= 0 or clicks.max() >= N):
+            raise ValueError("ClickFeed: clicked news ids must be in (0, N = %d)" % N)
+        if not 2 <= N < 2 ** 31:
+            raise ValueError("ClickFeed: the catalogue must have 2 <= N < 2^31 rows, got %d" % N)
+        for name, a in (("news_categ", news_categ), ("news_subcateg", news_subcateg), ("weights", weights)):
+            if a is not None and tuple(np.shape(a)) != (N,):
+                raise ValueError("ClickFeed: %s must be [N = %d], got %s" % (name, N, np.shape(a)))
+        if (news_categ is None) != (news_subcateg is None):
+            raise ValueError("ClickFeed: give news_categ and news_subcateg together or not at all")
+        self.holdout, self.min_history, self.popularity_power = int(holdout), int(min_history), float(popularity_power)
+        self.resample, self.rank, self.world = bool(resample), int(rank), int(world)
+        n_users = user_ptr.size - 1
+        train_len = np.maximum(np.diff(user_ptr) - self.holdout, 0)
+        live = train_len >= self.min_history + 1                               # the users that train
+        self.n_users, self.n_news, self.live_users = n_users, N, live
+        # rows: positions min_history .. train_len - 1 of every live user
+        per_user = np.where(live, train_len - self.min_history, 0)
+        row_user = np.repeat(np.arange(n_users, dtype=np.int64), per_user)
+        first = np.concatenate([[0], np.cumsum(per_user)])[:-1]
+        t = np.arange(int(per_user.sum()), dtype=np.int64) - np.repeat(first, per_user) + self.min_history
+        row_key = user_ptr[row_user] + t
+        # rejection sets and popularity: the distinct (user, news) pairs of the live users' training parts
+        in_train = np.arange(clicks.size, dtype=np.int64) - np.repeat(user_ptr[:-1], np.diff(user_ptr)) < np.repeat(np.where(live, train_len, 0), np.diff(user_ptr))
+        user_of = np.repeat(np.arange(n_users, dtype=np.int64), np.diff(user_ptr))
+        pairs = np.unique(user_of[in_train] * N + clicks[in_train])
+        set_user, set_news = pairs // N, pairs % N
+        set_ptr = np.concatenate([[0], np.cumsum(np.bincount(set_user, minlength=n_users))]).astype(np.int64)
+        count = np.bincount(set_news, minlength=N).astype(np.int64)
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.int64).copy()
+            if (w < 0).any() or w[0] != 0:
+                raise ValueError("ClickFeed: weights must be >= 0 and weights[0] (the padding slot) 0")
+        elif self.popularity_power == 0.0:
+            w = np.ones(N, dtype=np.int64)
+        else:
+            w = np.floor(count.astype(np.float64) ** self.popularity_power * CLICK_WEIGHT_ONE).astype(np.int64)
+        w[0] = 0
+        if float(w.astype(np.float64).sum()) > 2.0 ** 62 or int(w.sum()) < 1:
+            raise ValueError("ClickFeed: the weights must sum to a value in [1, 2^62]")
+        cum = np.concatenate([[0], np.cumsum(w)]).astype(np.int64)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        zeros = lambda *shape: torch.zeros(*shape, dtype=torch.int64, device=self.device)
+        n = int(row_key.size)
+        self.user_ptr, self.clicks = dev(user_ptr), dev(clicks)
+        self.row_key, self.row_user = dev(row_key), dev(row_user.astype(np.int32))
+        self.row_pos = dev(clicks[row_key].astype(np.int32))
+        self.row_hlen = dev(np.minimum(t, H))
+        self.set_ptr, self.set_news, self.count, self.weights, self.cum = dev(set_ptr), dev(set_news.astype(np.int32)), dev(count), dev(w), dev(cum)
+        # (the library refuses null pointers: a log in which nobody trains still hands it one element)
+        self._set_news_arg = self.set_news if self.set_news.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._train_len = train_len
+        self._categ = None if news_categ is None else (dev(np.asarray(news_categ, dtype=np.int64)), dev(np.asarray(news_subcateg, dtype=np.int64)))
+        self.packed = dict(cand=zeros(n, S), ccat=zeros(n, S), csub=zeros(n, S), clen=zeros(n))
+        self.n_samples = n
+        per_rank = n // self.world
+        self.row0, self.n = (self.rank * per_rank, per_rank) if self.world > 1 else (0, n)
+        self.draws, self.drawn_seed, self.n_short = 0, None, None
+        self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)     # n_short, n_bad
+        self._ws = None
+
+    def _rows_of(self, name, rows):
+        if name in self.packed:
+            return self.packed[name].index_select(0, rows)
+        hlen = self.row_hlen.index_select(0, rows)
+        if name == "hlen":
+            return hlen
+        # the history of a row: the hlen clicks in front of its own, gathered from the log
+        H = self.config.history_len
+        j = torch.arange(H, device=self.device)[None, :]
+        at = (self.row_key.index_select(0, rows) - hlen)[:, None] + j
+        ids = torch.where(j < hlen[:, None], self.clicks[at.clamp_(0, max(self.clicks.numel() - 1, 0))], torch.zeros_like(at)) \
+            if self.clicks.numel() else torch.zeros_like(at)
+        if name == "hist":
+            return ids
+        if self._categ is None:
+            return torch.zeros_like(ids)
+        return self._categ[0 if name == "hcat" else 1][ids]
+
+    def news_info(self):
+        if getattr(self, "_news_info", None) is None:
+            z = torch.zeros(self.n_news, dtype=torch.int64, device=self.device)
+            categ, sub = (z, z.clone()) if self._categ is None else self._categ
+            self._news_info = {"absts": self.absts, "categ": categ, "subcateg": sub}
+        return self._news_info
+
+    def click_graph(self):
+        raise NotImplementedError("ClickFeed: no click graph is built from a click log yet (click_graph.ClickGraph.from_histories takes history rows)")
+
+    def epoch_seed(self, epoch):
+        return (self.seed + int(epoch) * EPOCH_SEED_STEP) & 0xFFFFFFFFFFFFFFFF
+
+    def draw(self, seed):
+        """Refill the candidate side with the draw of ``seed`` (one ``nrms_catalogue_negative_sample`` call and two table look-ups on
+        the feed's stream); raises if the library counted a row it could not sample; ``n_short`` = the slots left empty."""
+        import ctypes as C
+        from . import _lib
+        if self.device.type != "cuda":
+            raise _lib.NrmsError("ClickFeed: the feed is on %s; negatives are sampled on a GPU (there is no CPU path)" % self.device)
+        lib = _lib.load()
+        S, n = self.S - 1, self.n_samples
+        need = int(lib.nrms_catalogue_negative_sample_workspace_bytes(C.c_int64(n), C.c_int64(self.n_news), S))
+        if need == 0:
+            _lib.check(-1, "nrms_catalogue_negative_sample_workspace_bytes")
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device)
+        p = self.packed
+        self._counters.zero_()
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            sample = lib.nrms_catalogue_negative_sample
+            rc = 0 if n == 0 else sample(C.c_int64(n), _lib.ptr(self.row_key), _lib.ptr(self.row_user), _lib.ptr(self.row_pos),
+                                         C.c_int64(self.n_users), _lib.ptr(self.set_ptr), _lib.ptr(self._set_news_arg), C.c_int64(self.n_news),
+                                         _lib.ptr(self.cum), S, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _lib.ptr(p["cand"]),
+                                         _lib.ptr(p["clen"]), _lib.ptr(self._counters[0:]), _lib.ptr(self._counters[1:]),
+                                         _lib.ptr(self._ws), C.c_size_t(self._ws.numel() * 4), stream)
+        _lib.check(rc, "nrms_catalogue_negative_sample")
+        if self._categ is not None:
+            flat = p["cand"].reshape(-1)
+            torch.index_select(self._categ[0], 0, flat, out=p["ccat"].view(-1))
+            torch.index_select(self._categ[1], 0, flat, out=p["csub"].view(-1))
+        self.n_short, bad = self._counters.tolist()                              # the epoch's one host synchronisation
+        if bad:
+            raise _lib.NrmsError("ClickFeed: nrms_catalogue_negative_sample could not sample %d row(s) (a user or a positive outside "
+                                 "its range: a damaged log)" % bad)
+        self.drawn_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def __iter__(self):
+        if self.resample or self.drawn_seed is None:
+            self.draw(self.epoch_seed(self.draws))
+        self.draws += 1
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + self.epoch + 1000003 * self.rank)
+            order = torch.randperm(self.n, generator=g).to(self.device) + self.row0
+            self.epoch += 1
+        else:
+            order = torch.arange(self.row0, self.row0 + self.n, device=self.device)
+        for b in range(len(self)):
+            yield self.batch(order[b * self.batch_size:(b + 1) * self.batch_size])
+
+    def heldout_samples(self):
+        """``(samples, labels)`` of the live users' held-out clicks in the ``[hist, hcat, hsub, imps, icat, isub]`` + 0/1 form:
+        imps = the user's last ``holdout`` clicks (every label 1), hist = the user's last ``config.history_len`` training clicks --
+        ready for ``DeviceFeed(type=1)`` and ``evaluate_retrieval``."""
+        user_ptr, clicks = self.user_ptr.cpu().numpy(), self.clicks.cpu().numpy()
+        H = self.config.history_len
+        categ = None if self._categ is None else tuple(c.cpu().numpy() for c in self._categ)
+        look = lambda k, ids: [0] * len(ids) if categ is None else [int(categ[k][i]) for i in ids]
+        samples, labels = [], []
+        for u in np.flatnonzero(self.live_users):
+            end = int(user_ptr[u] + self._train_len[u])
+            hist = clicks[max(int(user_ptr[u]), end - H):end].tolist()
+            imps = clicks[end:int(user_ptr[u + 1])].tolist()
+            if not imps:
+                continue
+            samples.append([hist, look(0, hist), look(1, hist), imps, look(0, imps), look(1, imps)])
+            labels.append([1] * len(imps))
+        return samples, labels

@@ -23,7 +23,7 @@ from torch.utils.data import DataLoader
 
 from . import parallel
 from .config import Config
-from .data_handler import DeviceFeed, ImpressionFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
+from .data_handler import ClickFeed, DeviceFeed, ImpressionFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
 from .model import Model
 from .train_eval import evaluate_retrieval, recommend, test, train
 
@@ -60,10 +60,14 @@ def build_parser():
     parser.add_argument('--graph', type=str, default='induced', choices=('induced', 'global'), help="--model graph: where a news "
                         "slot's neighbours come from.  induced: the click graph of the batch itself (host sampler); global: the "
                         "click graph of the whole training feed, resident in HBM, sampled by the HIP sampler (needs --feed device)")
-    parser.add_argument('--negatives', type=str, default='fixed', choices=('fixed', 'epoch'), help="where a training row's negatives "
-                        "come from.  fixed: drawn once, with the data set (the reference's offline preprocessing); epoch: redrawn "
-                        "at the start of every epoch from the impression's own non-clicked news, on the device (ImpressionFeed; "
-                        "needs --dataset synthetic and --feed device)")
+    parser.add_argument('--negatives', type=str, default='fixed', choices=('fixed', 'epoch', 'catalogue'), help="where a training row's "
+                        "negatives come from.  fixed: drawn once, with the data set (the reference's offline preprocessing); epoch: redrawn "
+                        "at the start of every epoch from the impression's own non-clicked news, on the device (ImpressionFeed); "
+                        "catalogue: training on a click log without impressions, the negatives redrawn every epoch from the whole "
+                        "catalogue by smoothed popularity, on the device (ClickFeed).  epoch and catalogue need --dataset synthetic "
+                        "and --feed device")
+    parser.add_argument('--negative_power', type=float, default=0.75, metavar='P', help='--negatives catalogue: a news is drawn with '
+                        'weight (number of users who clicked it) ** P; 0 = uniform over the catalogue')
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     return parser
 
@@ -115,8 +119,23 @@ def check_graph_args(args):
 
 
 def check_negatives_args(args):
-    """--negatives epoch fails before any data is read: impressions with labels to train on exist for the synthetic corpus only
-    (reading MIND's behaviors.tsv is out of scope), the log lives in the device feed, and --test trains nothing."""
+    """--negatives epoch / catalogue fail before any data is read: impressions with labels, or a click log, to train on exist for the
+    synthetic corpus only (reading MIND's behaviors.tsv is out of scope), the log lives in the device feed, and --test trains
+    nothing."""
+    if args.negatives == 'catalogue':
+        if args.dataset != 'synthetic':
+            raise SystemExit('--negatives catalogue: a click log exists for --dataset synthetic only (got %r: its pickles hold '
+                             'negatives that were drawn offline)' % args.dataset)
+        if args.feed != 'device':
+            raise SystemExit('--negatives catalogue: the click log is sampled in the device feed (--feed device)')
+        if args.test:
+            raise SystemExit('--negatives catalogue: --test trains nothing')
+        if not args.negative_power >= 0.0:
+            raise SystemExit('--negative_power P: P must be >= 0 (got %r)' % args.negative_power)
+        if args.graph == 'global':
+            raise SystemExit('--negatives catalogue: --graph global builds its click graph from history rows, which a click log does '
+                             'not keep')
+        return
     if args.negatives != 'epoch':
         return
     if args.dataset != 'synthetic':
@@ -172,6 +191,8 @@ def main(argv=None):
         dev_samples, dev_labels = corpus.eval_samples(1024)
         if args.negatives == 'epoch':
             train_imps, train_imp_labels = corpus.train_impressions(args.synthetic_users)
+        if args.negatives == 'catalogue':
+            click_ptr, click_ids = corpus.click_log(args.synthetic_users)
     else:
         if args.dataset == 'demo':
             config.word_embedding_pretrained = 'demo_word_embedding.npz'       # run_demo.py:31
@@ -233,6 +254,13 @@ def main(argv=None):
             train_feed = ImpressionFeed(config, train_imps, train_imp_labels, id2title_dict=titles, id2abst_dict=absts,
                                         batch_size=config.batch_size, device=config.device, shuffle=True, drop_last=world > 1, seed=422,
                                         rank=rank, world=world)
+        elif args.negatives == 'catalogue':
+            # as above: every rank holds the whole click log and the draw of a click depends on its position in the log only
+            train_feed = ClickFeed(config, click_ptr, click_ids, id2title_dict=titles, id2abst_dict=absts,
+                                   news_categ=np.concatenate([[0], corpus.category]), news_subcateg=np.concatenate([[0], corpus.subcategory]),
+                                   popularity_power=args.negative_power, batch_size=config.batch_size, device=config.device, shuffle=True,
+                                   drop_last=world > 1, seed=422, rank=rank, world=world)
+            held_samples, held_labels = train_feed.heldout_samples()
         else:
             train_feed = loader(train_samples, 0, True)
         if args.graph == 'global':
@@ -250,10 +278,14 @@ def main(argv=None):
                 m = hist['metrics'][-1][1]
                 print('final dev AUC: {:.4f}  MRR: {:.4f}  nDCG@5: {:.4f}  nDCG@10: {:.4f}'.format(
                     m['auc'], m['mrr'], m['ndcg5'], m['ndcg10']))
+        if args.negatives == 'catalogue' and rank == 0:
+            print('click log: {} rows, {} slots left empty in the last draw'.format(train_feed.n_samples, train_feed.n_short))
+        # a click log is evaluated on its own held-out clicks (each user's last one) against the whole catalogue
+        top_samples, top_labels = (held_samples, held_labels) if args.negatives == 'catalogue' else (dev_samples, dev_labels)
         if args.recommend is not None and rank == 0:
-            print('recommendations saved to', recommend_top(dev_samples))
+            print('recommendations saved to', recommend_top(top_samples))
         if retrieval_ks is not None and rank == 0:
-            retrieval_quality(dev_samples, dev_labels)
+            retrieval_quality(top_samples, top_labels)
         return hist
     else:
         # run_v0.py:93-111: the test set through the checkpoint named by --load (or the best one by file-name AUC)
