@@ -683,6 +683,34 @@ size_t nrms_newsvec_rows_workspace_bytes(int64_t n_rows, int32_t d, int32_t prec
 int nrms_newsvec_rows_fwd(int64_t n_rows, int32_t d, int32_t precision, const float* table, const float* w, const float* b,
                           float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* In-batch sampled softmax: every row of the batch is scored against the batch's whole candidate pool (csrc/poolce.hip).
+ * M = B * C pool columns, cand [M, d] (row b's own candidates are columns b*C .. b*C + C - 1), own(b) = b*C the column of row
+ * b's positive.  Column j is LIVE if cand_mask is NULL or cand_mask[j] != 0; row b is live if its own column is.  For a live row b,
+ * column j is IN THE SOFTMAX OF b if j == own(b), or if j is live, cand_id[j] != cand_id[own(b)] and cand_id[j] is not among
+ * reject[b, 0:R) (entries of reject that are <= 0 match nothing).  Duplicate ids in the pool count as often as they occur.
+ *   z[b, j]   = <user[b], cand[j]> + col_bias[j]          fp32 products, fp32 accumulation in ascending k; col_bias NULL = 0
+ *                                                          (the positive's column takes its bias too: the logQ correction of
+ *                                                          Yi et al. 2019 is col_bias[j] = -log q(cand_id[j]))
+ *   loss_b    = logsumexp_{j in the softmax of b} z[b, j] - z[b, own(b)]
+ *   g[b, j]   = (softmax_b[j] - [j == own(b)]) * grad_scale for the columns in the softmax of b; every other entry, and every entry
+ *               of a dead row, is exactly 0
+ *   loss_sum[0] += sum over the live rows of loss_b        (the caller divides by the batch, as for nrms_ce_loss_fwd_bwd)
+ *   duser[b]  = sum_j g[b, j] cand[j]                      written, not accumulated
+ *   dcand[j]  = sum_b g[b, j] user[b]                      written, not accumulated
+ *   n_pairs[0] += the number of pairs (b, j != own(b)) with j in the softmax of b      (device int64; may be NULL)
+ * dcand and duser both NULL: the loss only.  Vectors at dead slots must be finite (they are multiplied by 0).
+ * Domain: 1 <= B <= 4096, 1 <= C <= 64, B*C <= 32768, 1 <= d <= 1024, 0 <= R <= 256; reject is NULL exactly when R == 0.  Anything
+ * else, a workspace smaller than the query's answer (which is 0 for a refused shape), or exactly one of dcand / duser being NULL
+ * returns NRMS_EINVAL before any launch.  `workspace` holds the [B, M] fp32 matrix z, later g (materialised on purpose: 5 MB at
+ * B = 512, C = 5), the row losses and the K slabs of duser; nothing is assumed about its contents.  Every sum has a fixed order
+ * (the only atomic is the integer n_pairs), so two calls on the same inputs give the same bits.  The denominator, the log and the
+ * reciprocal of a row are formed in double and rounded once, as in nrms_ce_loss_fwd_bwd.  No allocation, no host synchronisation;
+ * up to six kernels on `stream`, each timed under a name that starts with "pooled_ce". */
+size_t nrms_pooled_ce_workspace_bytes(int32_t B, int32_t C, int32_t d, int32_t R);
+int nrms_pooled_ce_fwd_bwd(int32_t B, int32_t C, int32_t d, int32_t R, const float* cand, const float* user, const int64_t* cand_id,
+                           const uint8_t* cand_mask, const int64_t* reject, const float* col_bias, float grad_scale, float* loss_sum,
+                           float* dcand, float* duser, int64_t* n_pairs, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * nrms_timing_read synchronises the recorded events; returns 0 and the accumulated
  * milliseconds / launch count of kernels whose name starts with `prefix`. */

@@ -174,6 +174,9 @@ SIGNATURES = {
     "nrms_newsvec_distinct": (C.c_int, [C.POINTER(NewsvecDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrms_newsvec_rows_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "nrms_newsvec_rows_fwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "nrms_pooled_ce_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "nrms_pooled_ce_fwd_bwd": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 4
+                               + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "nrms_timing_enable": (None, [C.c_int]),
     "nrms_timing_reset": (None, []),
     "nrms_timing_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -206,24 +206,14 @@ class BertEngine(NRMSEngine):
                                gen=self._gen)
         return scores
 
-    def backward(self, flat, gflat, dscores, gen=None, table_grad_ready=None):
+    def backward(self, flat, gflat, dscores=None, gen=None, table_grad_ready=None):
         """Every parameter gradient of the saved training forward into gflat (same layout as flat; the table rows of the
-        batch's news are stored, the rest accumulated)."""
-        sv = self._saved
-        if sv is None:
-            raise _lib.NrmsError("backward() without a training forward")
-        if gen is not None and gen != sv["gen"]:
-            raise _lib.NrmsError("backward() of training forward #%d, but the saved activations belong to forward #%d "
-                                 "(two training forwards were run before one backward)" % (gen, sv["gen"]))
-        B, H, Cn, N, E = sv["B"], sv["H"], sv["C"], sv["N"], self.dims.width
+        batch's news are stored, the rest accumulated).  dscores None: the pooled loss's gradient (NRMSEngine.backward)."""
+        E = self.dims.width
+        sv, dnv, duser = self._head_backward(dscores, gen, E)
+        B, H, Cn, N = sv["B"], sv["H"], sv["C"], sv["N"]
         p, seed = sv["p"], sv["seed"]
         nv = sv["nv"]
-        dnv = self._buf("d_news_vec", N * E)[:N * E].view(N, E)
-        duser = self._buf("d_user_vec", B * E)[:B * E].view(B, E)
-        rc = self.lib.nrms_click_score_bwd(B, Cn, E, C.c_void_p(nv[B * H:].data_ptr()), _lib.ptr(sv["user"]), _lib.ptr(sv["mask"]),
-                                           _lib.ptr(dscores.contiguous()), C.c_void_p(dnv[B * H:].data_ptr()), _lib.ptr(duser),
-                                           _stream())
-        _lib.check(rc, "nrms_click_score_bwd")
         desc_u = self._udesc(B, H, p, seed ^ USER_SEED_SALT)
         ws = self._bwd_workspace(desc_u)
         wu, gu = self._ptrs(_lib.EncoderWeights, flat, "user_encoder"), self._ptrs(_lib.EncoderGrads, gflat, "user_encoder")

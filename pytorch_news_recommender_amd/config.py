@@ -62,6 +62,11 @@ class Config(object):
         # 512-user batches -- outside the absolute 1e-4 bar, hence opt-in); default False = bf16x3
         self.fp16_inference = False
         self.fp16_v1_news_encoder = False
+        # train_step's loss: "rowwise" = cross-entropy of each user over the user's own sample_size + 1 candidates (the reference's);
+        # "pooled" = in-batch sampled softmax over the candidates of the whole batch (nrms_pooled_ce_fwd_bwd), with the logQ
+        # correction where the feed provides ``candidate_logq`` (ClickFeed) unless logq_correction is False
+        self.train_loss = "rowwise"
+        self.logq_correction = True
         # HIP path only: when embedding row 0 (padding_idx) is all zeros, skip the padding tokens in the
         # Q|K|V projection and its weight gradient (identical results; include/nrms_hip.h NRMS_FLAG_PAD_ROW_ZERO)
         self.skip_padding_tokens = True

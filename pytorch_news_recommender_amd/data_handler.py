@@ -324,14 +324,15 @@ class SyntheticMind:
 
 class LazyBatch(Mapping):
     """A read-only batch dict whose values are produced on first access and kept (keys, order and ``len`` are those of the
-    eager dict; ``items()`` / ``values()`` materialise everything)."""
+    eager dict; ``items()`` / ``values()`` materialise everything).  ``extra``: keys beyond the reference's batch layout that a
+    consumer asks for by name (``batch["candidate_logq"]``, ``batch.get(...)``, ``in``); iteration and ``len`` do not list them."""
 
-    def __init__(self, makers):
-        self._makers, self._vals = makers, {}
+    def __init__(self, makers, extra=None):
+        self._makers, self._vals, self._extra = makers, {}, extra or {}
 
     def __getitem__(self, key):
         if key not in self._vals:
-            self._vals[key] = self._makers[key]()
+            self._vals[key] = (self._makers[key] if key in self._makers else self._extra[key])()
         return self._vals[key]
 
     def __iter__(self):
@@ -707,7 +708,17 @@ class ClickFeed(DeviceFeed):
 
     ``epoch_seed``, ``draw``, ``resample``, ``rank`` / ``world`` and ``news_info()`` as in ``ImpressionFeed``: the draw is a
     function of the log, the seed and the epoch only; one host synchronisation per epoch reads the two counters.  There is no
-    CPU path for the draw.  ``news_categ`` / ``news_subcateg``: int64 [N] per-news tables for the category keys (zeros without)."""
+    CPU path for the draw.  ``news_categ`` / ``news_subcateg``: int64 [N] per-news tables for the category keys (zeros without).
+
+    Beside DeviceFeed's 13 keys a batch answers to the lazy key ``candidate_logq`` float32 [B, S + 1] (by name: iterating the batch
+    still lists the 13): log q of every candidate slot's news, for the logQ correction of the pooled loss (config.train_loss = "pooled").  q(n) is the probability that a slot of a
+    batch's candidate pool holds n when positives and negatives are pooled together,
+        q(n) = (pos_rows(n) / n_rows + S w(n) / W) / (1 + S),
+    pos_rows(n) = the training rows whose positive is n, w / W = the sampler's weights and their sum, S = config.sample_size.  The
+    table ``logq`` [N] is built once, in float64, and kept as float32; a news with q = 0 (nobody's positive and weight 0) holds
+    -inf and cannot occur in a pool.  The rejection of a user's own clicks by the sampler is ignored in q: it renormalises a row's
+    draw over the catalogue minus a few dozen news, a relative change of about (the weight share of those news), far below what
+    the correction is for."""
 
     def __init__(self, config, user_ptr, clicks, id2title_dict=None, id2abst_dict=None, news_categ=None, news_subcateg=None, holdout=1,
                  min_history=1, popularity_power=0.75, weights=None, batch_size=None, device="cuda", shuffle=False, drop_last=False, seed=0,
@@ -767,6 +778,7 @@ class ClickFeed(DeviceFeed):
             raise ValueError("ClickFeed: the weights must sum to a value in [1, 2^62]")
         cum = np.concatenate([[0], np.cumsum(w)]).astype(np.int64)
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        self.logq = dev(self.pool_logq(np.bincount(clicks[row_key], minlength=N), w, S - 1))
         zeros = lambda *shape: torch.zeros(*shape, dtype=torch.int64, device=self.device)
         n = int(row_key.size)
         self.user_ptr, self.clicks = dev(user_ptr), dev(clicks)
@@ -785,6 +797,20 @@ class ClickFeed(DeviceFeed):
         self.draws, self.drawn_seed, self.n_short = 0, None, None
         self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)     # n_short, n_bad
         self._ws = None
+
+    @staticmethod
+    def pool_logq(pos_rows, weights, sample_size):
+        """float32 [N] log q (the class docstring's formula), from the rows per positive and the sampler's weights."""
+        pos, w = np.asarray(pos_rows, dtype=np.float64), np.asarray(weights, dtype=np.float64)
+        n_rows, S = pos.sum(), float(sample_size)
+        q = ((pos / n_rows if n_rows > 0 else np.zeros_like(pos)) + S * w / w.sum()) / (1.0 + S)
+        with np.errstate(divide="ignore"):
+            return np.log(q).astype(np.float32)
+
+    def batch(self, rows):
+        b = DeviceFeed.batch(self, rows)
+        b._extra['candidate_logq'] = lambda: self.logq.index_select(0, b['candidate_ids'].reshape(-1)).view(b['candidate_ids'].shape)
+        return b
 
     def _rows_of(self, name, rows):
         if name in self.packed:

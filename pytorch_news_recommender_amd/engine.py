@@ -477,38 +477,109 @@ class NRMSEngine:
         """Order the current stream behind whatever an earlier backward left on the library's helper streams."""
         _lib.check(self.lib.nrms_encoder_join(_stream()), "nrms_encoder_join")
 
-    # ---- full model backward ------------------------------------------------------------
-    def backward(self, flat, gflat, dscores, table_grad_ready=None, gen=None):
-        """Accumulates d(loss)/d(params) into gflat (same layout as flat) given dscores [B,C].
-        gen: the generation stamp of the training forward this backward belongs to (saved activations are one
-        slot: a later training forward replaces them, and a backward for the earlier one must not run on them).
+    # ---- the scoring head's backward, shared by every engine whose candidate vectors are the tail of a [B*(H+C), width] buffer ----
+    POOLED_VEC = ("nv", "d_news_vec")      # (key of that buffer in _saved, name of its gradient buffer); NamlEngine: feat / d_feat
 
-        table_grad_ready: optional callable invoked as soon as the embedding-table gradient (95 % of the
-        gradient bytes) is complete on the stream; the news encoder's d(W_qkv) GEMM is then deferred behind
-        it (NRMS_FLAG_DEFER_WQKV) so that a data-parallel caller can start the table all-reduce underneath."""
+    def _head_buffers(self, sv, width):
+        """(cand [B*C, width], user [B, width], d(vectors) [B*(H+C), width], d(user) [B, width]) of the saved training forward."""
+        B, H, Cn = sv["B"], sv["H"], sv["C"]
+        N = B * (H + Cn)
+        key, dkey = self.POOLED_VEC
+        dvec = self._buf(dkey, N * width)[:N * width].view(N, width)
+        duser = self._buf("d_user_vec", B * width)[:B * width].view(B, width)
+        return sv[key][B * H:], sv["user"], dvec, duser
+
+    def _head_backward(self, dscores, gen, width):
+        """The front of every backward(): the saved forward (checked against ``gen``) and d(candidate vectors) -- the tail of the
+        returned d(vectors) buffer -- and d(user vectors): from dscores [B, C] through nrms_click_score_bwd, or, with dscores None,
+        what pooled_ce_loss() left there for this forward.  -> (saved, d(vectors), d(user))."""
         sv = self._saved
         if sv is None:
             raise _lib.NrmsError("backward() without a training forward()")
         if gen is not None and gen != sv["gen"]:
             raise _lib.NrmsError("backward() for training forward #%d, but the saved activations belong to forward #%d: "
                                  "a later training forward replaced them (one forward/backward pair at a time)" % (gen, sv["gen"]))
-        B, H, Cn, L = sv["B"], sv["H"], sv["C"], sv["L"]
+        B, H, Cn = sv["B"], sv["H"], sv["C"]
+        cand, user, dvec, duser = self._head_buffers(sv, width)
+        if dscores is None:
+            if getattr(self, "_pooled_gen", None) != sv["gen"]:
+                raise _lib.NrmsError("backward(dscores=None) needs the gradients of pooled_ce_loss(), and none was computed for "
+                                     "training forward #%d" % sv["gen"])
+        else:
+            rc = self.lib.nrms_click_score_bwd(B, Cn, width, _lib.ptr(cand), _lib.ptr(user), _lib.ptr(sv["mask"]),
+                                               _lib.ptr(dscores.contiguous()), C.c_void_p(dvec[B * H:].data_ptr()), _lib.ptr(duser),
+                                               _stream())
+            _lib.check(rc, "nrms_click_score_bwd")
+        return sv, dvec, duser
+
+    def pooled_ce_loss(self, cand_ids, reject=None, col_bias=None, grad_scale=None, want_grad=True):
+        """In-batch sampled softmax of the saved training forward (nrms_pooled_ce_fwd_bwd, include/nrms_hip.h): every user against
+        the B*C candidate vectors of the whole batch.  cand_ids [B, C] int64 news ids of the candidate slots; reject [B, R] int64
+        or None: ids that are no negatives for that user (0 = padding); col_bias [B, C] fp32 or None, added to the scores of a
+        column (the logQ correction: -log q).  Returns the loss sum over the batch (device scalar).  With want_grad the gradients
+        land where backward(dscores=None) reads them; the pair count of the call is kept in ``pooled_pairs`` (device int64)."""
+        sv = self._saved
+        if sv is None:
+            raise _lib.NrmsError("pooled_ce_loss() without a training forward()")
+        B, Cn = sv["B"], sv["C"]
+        key, _ = self.POOLED_VEC
+        width = sv[key].shape[1]
+        cand, user, dvec, duser = self._head_buffers(sv, width)
+        dev = self.device
+        ids = torch.as_tensor(cand_ids).to(dev, torch.int64).contiguous()
+        if ids.numel() != B * Cn:
+            raise _lib.NrmsError("pooled_ce_loss: cand_ids must be [%d, %d] (got %s)" % (B, Cn, tuple(ids.shape)))
+        R = 0
+        if reject is not None:
+            reject = torch.as_tensor(reject).to(dev, torch.int64).contiguous()
+            if reject.dim() != 2 or reject.shape[0] != B:
+                raise _lib.NrmsError("pooled_ce_loss: reject must be [%d, R] (got %s)" % (B, tuple(reject.shape)))
+            R = reject.shape[1]
+            if R == 0:
+                reject = None
+        if col_bias is not None:
+            col_bias = torch.as_tensor(col_bias).to(dev, torch.float32).contiguous()
+            if col_bias.numel() != B * Cn:
+                raise _lib.NrmsError("pooled_ce_loss: col_bias must be [%d, %d] (got %s)" % (B, Cn, tuple(col_bias.shape)))
+        nbytes = self.lib.nrms_pooled_ce_workspace_bytes(B, Cn, width, R)
+        if nbytes == 0:
+            raise _lib.NrmsError("pooled_ce_loss: arguments rejected (B=%d, C=%d, d=%d, R=%d; B <= 4096, C <= 64, B*C <= 32768, "
+                                 "d <= 1024, R <= 256)" % (B, Cn, width, R))
+        ws = self._buf("pooled_ce_ws", (nbytes + 3) // 4)
+        loss_sum = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.pooled_pairs = torch.zeros(1, dtype=torch.int64, device=dev)
+        gs = (1.0 / B) if grad_scale is None else grad_scale
+        H = sv["H"]
+        rc = self.lib.nrms_pooled_ce_fwd_bwd(B, Cn, width, R, _lib.ptr(cand), _lib.ptr(user), _lib.ptr(ids), _lib.ptr(sv["mask"]),
+                                             _lib.ptr(reject), _lib.ptr(col_bias), C.c_float(gs), _lib.ptr(loss_sum),
+                                             C.c_void_p(dvec[B * H:].data_ptr()) if want_grad else None,
+                                             _lib.ptr(duser) if want_grad else None, _lib.ptr(self.pooled_pairs), _lib.ptr(ws),
+                                             C.c_size_t(ws.numel() * 4), _stream())
+        _lib.check(rc, "nrms_pooled_ce_fwd_bwd")
+        if want_grad:
+            self._pooled_gen = sv["gen"]
+        return loss_sum
+
+    # ---- full model backward ------------------------------------------------------------
+    def backward(self, flat, gflat, dscores=None, table_grad_ready=None, gen=None):
+        """Accumulates d(loss)/d(params) into gflat (same layout as flat) given dscores [B,C]; dscores None: the gradient of the
+        pooled loss that pooled_ce_loss() computed for this training forward (NrmsError if it did not).
+        gen: the generation stamp of the training forward this backward belongs to (saved activations are one
+        slot: a later training forward replaces them, and a backward for the earlier one must not run on them).
+
+        table_grad_ready: optional callable invoked as soon as the embedding-table gradient (95 % of the
+        gradient bytes) is complete on the stream; the news encoder's d(W_qkv) GEMM is then deferred behind
+        it (NRMS_FLAG_DEFER_WQKV) so that a data-parallel caller can start the table all-reduce underneath."""
         d = self.dims.word_embed_size
+        sv, dnv, duser = self._head_backward(dscores, gen, d)
+        B, H, Cn, L = sv["B"], sv["H"], sv["C"], sv["L"]
         N = B * (H + Cn)
         # fp16 mode: the loss scale is derived on the device from the gradient each encoder receives (any loss reduction,
         # batch size or world size); a fixed value only for experiments (tools/fp16_grad_stats.py)
         self.poll_grad_overflow()
         self.loss_scale = float(getattr(self, "loss_scale_override", None) or -float(self.loss_scale_backoff))
-        nv, user = sv["nv"], sv["user"]
+        nv = sv["nv"]
         hist = nv[:B * H]
-        cand = nv[B * H:]
-        dnv = self._buf("d_news_vec", N * d)[:N * d].view(N, d)
-        duser = self._buf("d_user_vec", B * d)[:B * d].view(B, d)
-        dscores = dscores.contiguous()
-        rc = self.lib.nrms_click_score_bwd(B, Cn, d, _lib.ptr(cand), _lib.ptr(user), _lib.ptr(sv["mask"]),
-                                           _lib.ptr(dscores), C.c_void_p(dnv[B * H:].data_ptr()), _lib.ptr(duser),
-                                           _stream())
-        _lib.check(rc, "nrms_click_score_bwd")
         # user encoder: its input gradient lands directly in the history rows of d(news vectors)
         desc_u = self._desc("user_encoder", B, H, mask_mode=sv["user_mask_mode"], training=True)
         desc_n = self._desc("news_encoder", N, L, sv["p_embed"], sv["p"], sv["seed"], training=True)

@@ -117,7 +117,8 @@ class FlatHipModel(nn.Module):
         pass
 
     def _backward(self, gflat, dscores, gen=None, table_grad_ready=None):
-        """The engine's backward into gflat, then the frozen rows' gradients zeroed (before any all-reduce sees them)."""
+        """The engine's backward into gflat, then the frozen rows' gradients zeroed (before any all-reduce sees them).  dscores
+        None: the gradient the engine's pooled_ce_loss() left for this forward."""
         self._engine.backward(self._flat, gflat, dscores, gen=gen, table_grad_ready=table_grad_ready)
         self._zero_frozen_rows(gflat)
 
@@ -166,6 +167,31 @@ class FlatHipModel(nn.Module):
     def _infer(self, batch, args, p_drop, seed):
         return self._engine.forward(self._flat, *args, training=False, p_drop=p_drop, seed=seed)
 
+    TRAIN_LOSSES = ("rowwise", "pooled")
+
+    def _train_loss(self):
+        """config.train_loss: "rowwise" (default; each user against the user's own C candidates) or "pooled" (each user against
+        the candidates of the whole batch, engine.pooled_ce_loss)."""
+        name = getattr(self.config, "train_loss", "rowwise")
+        if name not in self.TRAIN_LOSSES:
+            raise ValueError("config.train_loss must be one of %s (got %r)" % (self.TRAIN_LOSSES, name))
+        return name
+
+    def _pooled_loss(self, batch, grad_scale):
+        """The pooled loss of the training forward just run: pool ids = the batch's ``candidate_ids`` [B, C]; a user's own history
+        ``browsed_ids`` [B, H] (0 = padding; absent: nothing) is no negative for that user; ``candidate_logq`` [B, C] (log of the
+        probability that a pool slot holds that news; optional, ClickFeed provides it) is subtracted from the scores unless
+        config.logq_correction is False.  Leaves the gradients for _backward(dscores=None)."""
+        get = batch.get if hasattr(batch, "get") else (lambda k: batch[k] if k in batch else None)
+        ids = get("candidate_ids")
+        if ids is None:
+            raise KeyError("%s: config.train_loss = 'pooled' needs the batch key 'candidate_ids' (the news id of every candidate "
+                           "slot)" % type(self).__module__)
+        logq = get("candidate_logq") if getattr(self.config, "logq_correction", True) else None
+        dev = self._flat.device
+        bias = None if logq is None else -torch.as_tensor(logq).to(dev, torch.float32)
+        return self._engine.pooled_ce_loss(ids, reject=get("browsed_ids"), col_bias=bias, grad_scale=grad_scale)
+
     # ---- reference API ----------------------------------------------------------------------
     def forward(self, batch):
         """batch: the collated dict of data_handler.MyDataset (CPU or GPU tensors).  Returns click logits [B, C] on the GPU."""
@@ -183,13 +209,16 @@ class FlatHipModel(nn.Module):
     def train_step(self, batch, lr=None, betas=(0.9, 0.999), eps=1e-8, world_size=1, all_reduce=None, global_batch=None):
         """forward + CE(label 0) + backward + [gradient all-reduce] + Adam, all in HIP on flat
         buffers, no host sync.  Returns the local loss SUM over the batch as a device scalar
-        (divide by the batch size for the reference's mean loss).
+        (divide by the batch size for the reference's mean loss).  With config.train_loss = "pooled" the loss is the in-batch
+        sampled softmax over this rank's own batch (_pooled_loss) instead of the row-wise cross-entropy; the rest of the step is
+        the same.
 
         all_reduce: callable(flat_grad_tensor) that sums gradients over data-parallel ranks
         (RCCL; parallel.GradAllReduce), or a parallel.ShardedGradSync; gradients are scaled by 1/global_batch so the
         summed result is the gradient of the mean loss over the global batch."""
         dev = self._prepare()
         eng = self._engine
+        pooled = self._train_loss() == "pooled"
         args = self._engine_args(batch, dev)
         if self._opt is None:
             self._opt = dict(step=0, g=torch.zeros_like(self._flat), m=torch.zeros_like(self._flat),
@@ -199,7 +228,10 @@ class FlatHipModel(nn.Module):
         seed = self._next_seed() if p_drop > 0 else 0
         scores = eng.forward(self._flat, *args, training=True, p_drop=p_drop, seed=seed)
         gb = scores.shape[0] * world_size if global_batch is None else global_batch
-        loss_sum, dscores = eng.ce_loss(scores, grad_scale=1.0 / gb)
+        if pooled:
+            loss_sum, dscores = self._pooled_loss(batch, 1.0 / gb), None
+        else:
+            loss_sum, dscores = eng.ce_loss(scores, grad_scale=1.0 / gb)
         st["g"].zero_()
         lr_ = float(self.config.learning_rate if lr is None else lr)
         overlap = not os.environ.get("NRMS_NO_OVERLAP")

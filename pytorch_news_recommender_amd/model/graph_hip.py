@@ -126,6 +126,9 @@ class GraphEngine(NRMSEngine):
             self._saved = dict(B=B, H=H, C=Cn, L=L, ids=ids, g=g, h=h, mask=mask, pools=(pool_n, pool_u), p=p, seed=seed, gen=self._gen)
         return scores
 
+    def pooled_ce_loss(self, *args, **kwargs):
+        raise NotImplementedError("GraphEngine has no pooled loss (config.train_loss = 'pooled'): its candidate vectors are not the tail of one vector buffer")
+
     def backward(self, flat, gflat, dscores, gen=None, table_grad_ready=None):
         sv = self._saved
         if sv is None:

@@ -169,6 +169,9 @@ class HieRecEngine(NRMSEngine):
             scores[b0:b0 + b], ids[b0:b0 + b] = s_, i_
         return scores, ids
 
+    def pooled_ce_loss(self, *args, **kwargs):
+        raise NotImplementedError("HieRecEngine has no pooled loss (config.train_loss = 'pooled'): its score is a mixture over the user's interest tree, not one user vector")
+
     def backward(self, flat, gflat, dscores, gen=None, table_grad_ready=None):
         sv = self._saved
         if sv is None:

@@ -347,24 +347,16 @@ class NamlEngine(NRMSEngine):
             cand_mask = cand_mask.contiguous()
         return self.click_scores_indexed(feat, inverse[B * H:], user, B, Cn, cand_mask)
 
-    def backward(self, flat, gflat, dscores, gen=None, table_grad_ready=None):
-        """Accumulates every parameter gradient of the saved training forward into gflat (same layout as flat)."""
-        sv = self._saved
-        if sv is None:
-            raise _lib.NrmsError("backward() without a training forward")
-        if gen is not None and gen != sv["gen"]:
-            raise _lib.NrmsError("backward() of training forward #%d, but the saved activations belong to forward #%d "
-                                 "(two training forwards were run before one backward)" % (gen, sv["gen"]))
+    POOLED_VEC = ("feat", "d_feat")
+
+    def backward(self, flat, gflat, dscores=None, gen=None, table_grad_ready=None):
+        """Accumulates every parameter gradient of the saved training forward into gflat (same layout as flat).  dscores None: the
+        pooled loss's gradient (NRMSEngine.backward)."""
         d = self.dims
-        B, H, Cn, N, F, dt = sv["B"], sv["H"], sv["C"], sv["N"], d.news_feature_size, d.word_embed_size
+        F, dt = d.news_feature_size, d.word_embed_size
+        sv, dfeat, duser = self._head_backward(dscores, gen, F)
+        B, H, Cn, N = sv["B"], sv["H"], sv["C"], sv["N"]
         p, seed = sv["p"], sv["seed"]
-        dfeat = self._buf("d_feat", N * F)[:N * F].view(N, F)
-        duser = self._buf("d_user_vec", B * F)[:B * F].view(B, F)
-        cand = sv["feat"][B * H:].view(B, Cn, F)
-        rc = self.lib.nrms_click_score_bwd(B, Cn, F, _lib.ptr(cand), _lib.ptr(sv["user"]), _lib.ptr(sv["mask"]),
-                                           _lib.ptr(dscores.contiguous()), C.c_void_p(dfeat[B * H:].data_ptr()), _lib.ptr(duser),
-                                           _stream())
-        _lib.check(rc, "nrms_click_score_bwd")
         desc_u = self._desc("user_encoder", B, H, p, seed ^ 0x2545F4914F6CDD1D)
         desc_t = self._desc("news_encoder", N, sv["ids_t"].shape[1], p, seed)
         desc_a = self._desc("news_encoder", N, sv["ids_a"].shape[1], p, seed ^ 0x5DEECE66D1CE4E5B)

@@ -68,6 +68,11 @@ def build_parser():
                         "and --feed device")
     parser.add_argument('--negative_power', type=float, default=0.75, metavar='P', help='--negatives catalogue: a news is drawn with '
                         'weight (number of users who clicked it) ** P; 0 = uniform over the catalogue')
+    parser.add_argument('--loss', type=str, default='rowwise', choices=('rowwise', 'pooled'), help="the training loss.  rowwise: each user "
+                        "against the user's own sample_size + 1 candidates (the reference's cross-entropy); pooled: each user against the "
+                        "candidates of the whole batch (in-batch sampled softmax; with --negatives catalogue the scores are corrected by "
+                        "the log of each news's probability of being in the pool)")
+    parser.add_argument('--no_logq', action='store_true', help='--loss pooled: leave the log-probability correction out')
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     return parser
 
@@ -147,12 +152,24 @@ def check_negatives_args(args):
         raise SystemExit('--negatives epoch: --test trains nothing')
 
 
+def check_loss_args(args):
+    """--loss pooled fails before any data is read: a model whose engine has the pooled loss, and a run that trains."""
+    if args.loss != 'pooled':
+        return
+    from .model import ALIASES
+    if ALIASES.get(args.model.lower(), args.model.lower()) in ('hierec_hip', 'graph_hip'):
+        raise SystemExit('--loss pooled: model %r has no pooled loss (nrms_v0, nrms_v1, nrms_bert and nrms_naml have)' % args.model)
+    if args.test:
+        raise SystemExit('--loss pooled: --test trains nothing')
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_recommend_args(args)
     retrieval_ks = check_retrieval_args(args)
     check_graph_args(args)
     check_negatives_args(args)
+    check_loss_args(args)
     rank, local_rank, world = parallel.init_process_group()
     torch.manual_seed(422)
     torch.cuda.manual_seed_all(422)
@@ -164,6 +181,8 @@ def main(argv=None):
     config.num_epochs = 6 if args.epochs is None else args.epochs
     config.mode = args.dataset
     config.eval_metrics = args.metrics
+    config.train_loss = args.loss
+    config.logq_correction = not args.no_logq
     if args.data_path:
         config.data_path = os.path.join(args.data_path, '')
     if args.save_path:

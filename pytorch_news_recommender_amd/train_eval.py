@@ -143,6 +143,9 @@ def train(config, model, train_iter, dev_iter=None, dev_labels=None, use_autogra
     With config.warm_up the epochs are preceded by the reference's warm-up pass over the first
     batches of train_iter with a linearly increasing learning rate (train_eval.py:64-99)."""
     net = _inner(model)
+    if use_autograd and getattr(config, 'train_loss', 'rowwise') == 'pooled':
+        raise ValueError("train(use_autograd=True): config.train_loss = 'pooled' exists in the fused train_step only (the criterion of "
+                         "the autograd path sees one row of scores per user, not the batch's candidate pool)")
     rank, _, world = parallel.env_world()
     reduce = parallel.GradAllReduce() if world > 1 and torch.distributed.is_initialized() else None
     start = time.time()
