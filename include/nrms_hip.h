@@ -110,6 +110,20 @@ extern "C" {
  *   - an error return has joined already.  With NRMS_NO_SIDE_STREAMS there is nothing to join. */
 #define NRMS_FLAG_DEFER_USER_JOIN 16
 
+/* nrms_encoder_bwd_adam, news encoder (vocab > 0) whose table gradient is the grouped scatter (NRMS_PRECISION_FP16: with
+ * NRMS_FLAG_PAD_ROW_ZERO; fp32 / bf16x3 / bf16: always, unless the environment asks for the atomic scatter): the kernel that sums
+ * a table row's gradient applies Adam to that row at once, from the operands in nrms_table_adam.  Every row of the table is
+ * updated -- rows without a token in the batch and row 0 with the gradient +0 -- with the bits of
+ *     zeroed grads.table -> nrms_encoder_bwd -> nrms_adam_step[_guarded](vocab * d_model, table, grads.table, ...),
+ * grads.table is WRITTEN (not accumulated: it needs no zero fill and holds the gradient the optimizer consumed), and the table
+ * is modified when the call returns: the caller runs the optimizer over the remaining parameters only (nrms_adam_step_rest).
+ * For a caller whose table receives exactly this one scatter per step and whose gradient needs no reduction before the optimizer.
+ * No kernel of the library reads the table while the update runs: within a backward only the forward's gather does, and the
+ * weight-gradient GEMMs still on the helper streams read the saved activations and the workspace.
+ * NRMS_EINVAL: vocab == 0, flags that make the table gradient another kernel, together with NRMS_FLAG_DEFER_WQKV, or through
+ * nrms_encoder_bwd (which has no operands for it). */
+#define NRMS_FLAG_TABLE_ADAM 32
+
 /* One self-attention + additive-pooling encoder pass over n_seq sequences of seq_len rows.
  * vocab > 0  : news encoder -- input is `ids` [n_seq, seq_len] int64, rows gathered from
  *              `table` (NewsEncoder.forward, model/nrms_v0.py:154-176).
@@ -230,6 +244,23 @@ int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encoder_weights* 
                      const nrms_encoder_acts* acts, const float* dout,
                      const nrms_encoder_grads* grads, float* dx,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* nrms_encoder_bwd with NRMS_FLAG_TABLE_ADAM: the Adam operands of the embedding table (see nrms_adam_step for their meaning). */
+typedef struct nrms_table_adam {
+    float*   param;        /* [vocab, d] the table itself (w->table, writable) */
+    float*   exp_avg;      /* [vocab, d] */
+    float*   exp_avg_sq;   /* [vocab, d] */
+    double   lr, beta1, beta2, eps;
+    int32_t  step;         /* 1-based */
+    float    grad_scale;
+    int32_t* n_nonfinite;  /* device int32 counter: the guarded update (nrms_adam_step_guarded); NULL: nrms_adam_step */
+} nrms_table_adam;
+/* table_adam non-NULL exactly when desc->flags has NRMS_FLAG_TABLE_ADAM; with NULL this is nrms_encoder_bwd.  n_seq == 0: the
+ * table still takes its step (gradient +0). */
+int nrms_encoder_bwd_adam(const nrms_encoder_desc* desc, const nrms_encoder_weights* w,
+                          const int64_t* ids, const float* x, const uint8_t* mask,
+                          const nrms_encoder_acts* acts, const float* dout,
+                          const nrms_encoder_grads* grads, float* dx,
+                          void* workspace, size_t workspace_bytes, const nrms_table_adam* table_adam, void* stream);
 /* Step 5 of the backward on its own: d(w_qkv), d(b_qkv) += dQKV^T [X | 1] from the dQKV left in `workspace`
  * by nrms_encoder_bwd(desc with NRMS_FLAG_DEFER_WQKV) -- same desc, ids / x, acts, grads, workspace. */
 int nrms_encoder_bwd_wqkv(const nrms_encoder_desc* desc, const int64_t* ids, const float* x,
@@ -294,6 +325,12 @@ int nrms_adam_step(size_t n, float* param, const float* grad, float* exp_avg, fl
 int nrms_adam_step_guarded(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                            double lr, double beta1, double beta2, double eps, int32_t step, float grad_scale,
                            int32_t* n_nonfinite, void* stream);
+/* The optimizer step of the parameters BEHIND a table that nrms_encoder_bwd_adam updated: nrms_adam_step (n_nonfinite NULL) or
+ * nrms_adam_step_guarded (non-NULL), same kernels and bits; its launch is recorded under the timer "rest_adam" (timers are read by
+ * prefix; "adam" is the table's fused kernel on that path). */
+int nrms_adam_step_rest(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                        double lr, double beta1, double beta2, double eps, int32_t step, float grad_scale,
+                        int32_t* n_nonfinite, void* stream);
 /* For callers that run their own optimizer (torch.optim.Adam on the autograd path, train_eval.py:126-127): inf / nan elements
  * of grad [n] are replaced by 0 in place and counted into *n_nonfinite (device int32, caller-zeroed). */
 int nrms_grad_guard(size_t n, float* grad, int32_t* n_nonfinite, void* stream);

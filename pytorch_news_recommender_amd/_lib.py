@@ -17,6 +17,7 @@ NRMS_FLAG_DEFER_WQKV = 2
 NRMS_FLAG_FWD_SCRATCH_KEPT = 4
 NRMS_FLAG_FUSED_SEQ64 = 8
 NRMS_FLAG_DEFER_USER_JOIN = 16
+NRMS_FLAG_TABLE_ADAM = 32
 NRMS_PRECISION_FP32 = 0
 NRMS_PRECISION_BF16X3 = 1
 NRMS_PRECISION_BF16 = 2
@@ -47,6 +48,11 @@ class EncoderWeights(C.Structure):
 class EncoderGrads(C.Structure):
     _fields_ = [("table", C.c_void_p), ("w_qkv", C.c_void_p), ("b_qkv", C.c_void_p), ("w_o", C.c_void_p),
                 ("b_o", C.c_void_p), ("w_add", C.c_void_p), ("b_add", C.c_void_p), ("q_vec", C.c_void_p)]
+
+
+class TableAdam(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("step", C.c_int32), ("grad_scale", C.c_float), ("n_nonfinite", C.c_void_p)]
 
 
 class EncoderActs(C.Structure):
@@ -88,6 +94,9 @@ SIGNATURES = {
     "nrms_encoder_bwd": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.POINTER(EncoderActs), C.c_void_p, C.POINTER(EncoderGrads), C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nrms_encoder_bwd_adam": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(EncoderActs), C.c_void_p, C.POINTER(EncoderGrads), C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.POINTER(TableAdam), C.c_void_p]),
     "nrms_encoder_bwd_wqkv": (C.c_int, [C.POINTER(EncoderDesc), C.c_void_p, C.c_void_p, C.POINTER(EncoderActs),
                                         C.POINTER(EncoderGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "nrms_encoder_join": (C.c_int, [C.c_void_p]),
@@ -107,6 +116,8 @@ SIGNATURES = {
                                  C.c_double, C.c_double, C.c_double, C.c_int32, C.c_float, C.c_void_p]),
     "nrms_adam_step_guarded": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                          C.c_double, C.c_double, C.c_double, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "nrms_adam_step_rest": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                      C.c_double, C.c_double, C.c_double, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "nrms_grad_guard": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrms_segment_pool_workspace_bytes": (C.c_size_t, [C.POINTER(SegPoolDesc)]),
     "nrms_segment_pool_fwd": (C.c_int, [C.POINTER(SegPoolDesc)] + [C.c_void_p] * 10 + [C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -146,8 +146,14 @@ static int validate_desc(const nrms_encoder_desc* d, const char* who) {
     }
     NRMS_REQUIRE((d->mask_mode & ~3) == 0, "%s: mask_mode=%d", who, d->mask_mode);
     NRMS_REQUIRE((d->flags & ~(NRMS_FLAG_PAD_ROW_ZERO | NRMS_FLAG_DEFER_WQKV | NRMS_FLAG_FWD_SCRATCH_KEPT | NRMS_FLAG_FUSED_SEQ64 |
-                               NRMS_FLAG_DEFER_USER_JOIN)) == 0,
+                               NRMS_FLAG_DEFER_USER_JOIN | NRMS_FLAG_TABLE_ADAM)) == 0,
                  "%s: unknown flags 0x%x", who, d->flags);
+    if (d->flags & NRMS_FLAG_TABLE_ADAM)
+        // the fused table update rides on the grouped scatter of a news encoder whose table gradient is complete inside the call
+        NRMS_REQUIRE(d->vocab > 0 && (d->flags & NRMS_FLAG_DEFER_WQKV) == 0 &&
+                     (d->precision != NRMS_PRECISION_FP16 || (d->flags & NRMS_FLAG_PAD_ROW_ZERO) != 0),
+                     "%s: flags 0x%x: NRMS_FLAG_TABLE_ADAM needs the news encoder (vocab > 0) with the grouped table scatter (fp16: "
+                     "NRMS_FLAG_PAD_ROW_ZERO) and no NRMS_FLAG_DEFER_WQKV", who, d->flags);
     if (d->flags & NRMS_FLAG_FUSED_SEQ64) {
         const char* why = nullptr;
         NRMS_REQUIRE(d->vocab == 0 && d->precision == NRMS_PRECISION_BF16X3 && !d->use_output_proj && d->mask_mode == 0 &&
@@ -384,9 +390,24 @@ static Bwd16Layout bwd16_layout(const nrms_encoder_desc* d) {
     return L;
 }
 
+// NRMS_FLAG_TABLE_ADAM: the operands as the kernel takes them (the constants from the host code of nrms_adam_step)
+static int table_adam_args(const nrms_encoder_desc* desc, const nrms_encoder_weights* w, const nrms_encoder_grads* grads,
+                           const nrms_table_adam* ta, TableAdam* out) {
+    NRMS_REQUIRE(ta->param && ta->exp_avg && ta->exp_avg_sq && ta->step >= 1, "encoder_bwd: NRMS_FLAG_TABLE_ADAM: bad operands");
+    NRMS_REQUIRE(w != nullptr && ta->param == w->table, "encoder_bwd: NRMS_FLAG_TABLE_ADAM: param must be the table the encoder reads");
+    NRMS_REQUIRE(grads != nullptr && grads->table != nullptr, "encoder_bwd: NRMS_FLAG_TABLE_ADAM: grads.table missing");
+    NRMS_REQUIRE((((uintptr_t)ta->param | (uintptr_t)grads->table | (uintptr_t)ta->exp_avg | (uintptr_t)ta->exp_avg_sq) & 15) == 0,
+                 "encoder_bwd: NRMS_FLAG_TABLE_ADAM: buffers must be 16-byte aligned");
+    out->p = ta->param; out->m = ta->exp_avg; out->v = ta->exp_avg_sq;
+    out->c = adam_consts(ta->lr, ta->beta1, ta->beta2, ta->eps, ta->step);
+    out->gscale = ta->grad_scale;
+    out->n_bad = (int*)ta->n_nonfinite;
+    return NRMS_OK;
+}
+
 static int encoder_bwd16(const nrms_encoder_desc* desc, const nrms_encoder_weights* w, const int64_t* ids, const float* x,
                          const nrms_encoder_acts* acts, const float* dout, const nrms_encoder_grads* grads, float* dx,
-                         void* workspace, size_t workspace_bytes, hipStream_t s) {
+                         void* workspace, size_t workspace_bytes, const TableAdam* tadam, hipStream_t s) {
     NRMS_REQUIRE(w && acts && dout && grads && workspace, "encoder_bwd(fp16): null argument");
     const bool v1 = desc->use_output_proj != 0;
     NRMS_REQUIRE(!v1 || (w->w_o && acts->attn && grads->w_o && grads->b_o),
@@ -479,7 +500,10 @@ static int encoder_bwd16(const nrms_encoder_desc* desc, const nrms_encoder_weigh
     }
     if (gather) {
         const Dropout drop_e = make_dropout(desc->seed, desc->p_drop_embed);
-        if (skip_pad_rows(desc))
+        if (tadam != nullptr)     // (validate_desc: the compact path) -- scatter and the table's Adam step in one kernel
+            rc = launch_scatter_grouped_adam(M, desc->vocab, d, ids, live, n_live, f.dx, drop_e, grads->table, (int*)(base + L.sscr), s,
+                                             f.dx_fp16, NRMS_FP16_KP, sc_dev, prepared, *tadam);
+        else if (skip_pad_rows(desc))
             rc = launch_scatter_grouped(M, desc->vocab, d, ids, live, n_live, f.dx, drop_e, grads->table, (int*)(base + L.sscr), s,
                                         f.dx_fp16, NRMS_FP16_KP, sc_dev, prepared);
         else       // dense rows (one per token): the atomic scatter walks the live list over the dense rows
@@ -493,6 +517,7 @@ extern "C" int nrms_encoder_fwd(const nrms_encoder_desc* desc, const nrms_encode
                                 void* stream) {
     int rc = validate_desc(desc, "encoder_fwd");
     if (rc) return rc;
+    NRMS_REQUIRE((desc->flags & NRMS_FLAG_TABLE_ADAM) == 0, "encoder_fwd: flags 0x%x: NRMS_FLAG_TABLE_ADAM belongs to nrms_encoder_bwd_adam", desc->flags);
     if (acts != nullptr) kept_forget(acts->scratch);          // whatever lists an earlier forward left in this scratch are gone
     if (desc->precision == NRMS_PRECISION_FP16) {
         NRMS_REQUIRE(w && acts && out, "encoder_fwd: null argument");
@@ -697,6 +722,7 @@ extern "C" int nrms_encoder_bwd_wqkv(const nrms_encoder_desc* desc, const int64_
                                      size_t workspace_bytes, void* stream) {
     int rc = validate_desc(desc, "encoder_bwd_wqkv");
     if (rc) return rc;
+    NRMS_REQUIRE((desc->flags & NRMS_FLAG_TABLE_ADAM) == 0, "encoder_bwd_wqkv: flags 0x%x: NRMS_FLAG_TABLE_ADAM belongs to nrms_encoder_bwd_adam", desc->flags);
     if (desc->precision == NRMS_PRECISION_FP16) return fused_bwd16_join((hipStream_t)stream);   // the GEMMs run already: order them
     NRMS_REQUIRE(acts && grads && workspace, "encoder_bwd_wqkv: null argument");
     NRMS_REQUIRE(grads->w_qkv && grads->b_qkv, "encoder_bwd_wqkv: null gradient buffer");
@@ -718,14 +744,12 @@ extern "C" int nrms_encoder_bwd_wqkv(const nrms_encoder_desc* desc, const int64_
 
 extern "C" int nrms_encoder_join(void* stream) { return fused_bwd16_join((hipStream_t)stream); }
 
-extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encoder_weights* w, const int64_t* ids,
-                                const float* x, const uint8_t* mask, const nrms_encoder_acts* acts, const float* dout,
-                                const nrms_encoder_grads* grads, float* dx, void* workspace, size_t workspace_bytes,
-                                void* stream) {
-    int rc = validate_desc(desc, "encoder_bwd");
-    if (rc) return rc;
-    if (desc->precision == NRMS_PRECISION_FP16)
-        return encoder_bwd16(desc, w, ids, x, acts, dout, grads, dx, workspace, workspace_bytes, (hipStream_t)stream);
+// the fp32 / bf16x3 / bf16 backward (desc validated by the caller)
+static int encoder_bwd_chain(const nrms_encoder_desc* desc, const nrms_encoder_weights* w, const int64_t* ids,
+                             const float* x, const uint8_t* mask, const nrms_encoder_acts* acts, const float* dout,
+                             const nrms_encoder_grads* grads, float* dx, void* workspace, size_t workspace_bytes,
+                             const TableAdam* tadam, hipStream_t s) {
+    int rc;
     NRMS_REQUIRE(w && acts && dout && grads && workspace, "encoder_bwd: null argument");
     NRMS_REQUIRE(acts->qkv && acts->ctx && acts->t && acts->w, "encoder_bwd: all saved activations are required");
     NRMS_REQUIRE(grads->w_qkv && grads->b_qkv && grads->w_add && grads->b_add && grads->q_vec,
@@ -743,7 +767,6 @@ extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encode
     }
     NRMS_REQUIRE(((uintptr_t)workspace & 255) == 0, "encoder_bwd: workspace must be 256-byte aligned");
     if (desc->n_seq == 0) return NRMS_OK;
-    hipStream_t s = (hipStream_t)stream;
     const int S = desc->seq_len, d = desc->d_model, q = desc->q_dim, M = desc->n_seq * S;
     const Dropout drop_e = make_dropout(desc->seed, desc->p_drop_embed);
     const Dropout drop_c = make_dropout(desc->seed, desc->p_drop_ctx);
@@ -894,7 +917,10 @@ extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encode
     }
     if (gather) {
         const bool atomic_scatter = getenv("NRMS_ATOMIC_SCATTER") != nullptr;      // A/B switch, read per call (no latched state)
-        if (atomic_scatter) rc = launch_scatter_dropout_compact((long)M, d, ids, live, n_live, dctx, drop_e, grads->table, s);
+        if (tadam != nullptr)      // NRMS_FLAG_TABLE_ADAM (refused with the atomic scatter): scatter + the table's Adam step
+            rc = launch_scatter_grouped_adam((long)M, desc->vocab, d, ids, live, n_live, dctx, drop_e, grads->table,
+                                             (int*)(base + L.sscr), s, false, 0, nullptr, false, *tadam);
+        else if (atomic_scatter) rc = launch_scatter_dropout_compact((long)M, d, ids, live, n_live, dctx, drop_e, grads->table, s);
         else rc = launch_scatter_grouped((long)M, desc->vocab, d, ids, live, n_live, dctx, drop_e, grads->table,
                                          (int*)(base + L.sscr), s);
     }
@@ -909,6 +935,51 @@ extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encode
             rc = side_order(ss, 4, s2, s, "encoder_bwd");
             if (rc == NRMS_OK) join_guard.disarm();
         }
+    }
+    return rc;
+}
+
+extern "C" int nrms_encoder_bwd(const nrms_encoder_desc* desc, const nrms_encoder_weights* w, const int64_t* ids,
+                                const float* x, const uint8_t* mask, const nrms_encoder_acts* acts, const float* dout,
+                                const nrms_encoder_grads* grads, float* dx, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    return nrms_encoder_bwd_adam(desc, w, ids, x, mask, acts, dout, grads, dx, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int nrms_encoder_bwd_adam(const nrms_encoder_desc* desc, const nrms_encoder_weights* w, const int64_t* ids,
+                                     const float* x, const uint8_t* mask, const nrms_encoder_acts* acts, const float* dout,
+                                     const nrms_encoder_grads* grads, float* dx, void* workspace, size_t workspace_bytes,
+                                     const nrms_table_adam* table_adam, void* stream) {
+    int rc = validate_desc(desc, "encoder_bwd");
+    if (rc) return rc;
+    NRMS_REQUIRE(((desc->flags & NRMS_FLAG_TABLE_ADAM) != 0) == (table_adam != nullptr),
+                 "encoder_bwd: NRMS_FLAG_TABLE_ADAM and the nrms_table_adam operands (nrms_encoder_bwd_adam) go together");
+    TableAdam tadam_v{};
+    const TableAdam* tadam = nullptr;
+    if (table_adam != nullptr) {
+        rc = table_adam_args(desc, w, grads, table_adam, &tadam_v);
+        if (rc) return rc;
+        tadam = &tadam_v;
+        NRMS_REQUIRE(desc->precision == NRMS_PRECISION_FP16 || getenv("NRMS_ATOMIC_SCATTER") == nullptr,
+                     "encoder_bwd: NRMS_FLAG_TABLE_ADAM needs the grouped scatter (NRMS_ATOMIC_SCATTER is set)");
+    }
+    if (desc->precision == NRMS_PRECISION_FP16)
+        rc = encoder_bwd16(desc, w, ids, x, acts, dout, grads, dx, workspace, workspace_bytes, tadam, (hipStream_t)stream);
+    else
+        rc = encoder_bwd_chain(desc, w, ids, x, mask, acts, dout, grads, dx, workspace, workspace_bytes, tadam, (hipStream_t)stream);
+    if (rc == NRMS_OK && tadam != nullptr && desc->n_seq == 0) {
+        // no title, no scatter: the table still takes its step, with the gradient +0 (stored, as the fused kernel stores it)
+        const size_t n = (size_t)desc->vocab * desc->d_model;
+        if (hipMemsetAsync(grads->table, 0, n * sizeof(float), (hipStream_t)stream) != hipSuccess) {
+            set_error("encoder_bwd: memset failed");
+            return NRMS_ELAUNCH;
+        }
+        rc = table_adam->n_nonfinite != nullptr
+                 ? nrms_adam_step_guarded(n, table_adam->param, grads->table, table_adam->exp_avg, table_adam->exp_avg_sq, table_adam->lr,
+                                          table_adam->beta1, table_adam->beta2, table_adam->eps, table_adam->step, table_adam->grad_scale,
+                                          table_adam->n_nonfinite, stream)
+                 : nrms_adam_step(n, table_adam->param, grads->table, table_adam->exp_avg, table_adam->exp_avg_sq, table_adam->lr,
+                                  table_adam->beta1, table_adam->beta2, table_adam->eps, table_adam->step, table_adam->grad_scale, stream);
     }
     return rc;
 }

@@ -182,6 +182,23 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// One element's Adam update, with every rounding spelt out: m, v and the denominator are formed from rounded products (no fma
+// contraction), the parameter takes step_size * m / denom in one fma.  Left to the compiler, the guarded
+// and the unguarded kernel -- and the vector body and the scalar tail of each -- were contracted differently and disagreed in
+// the last bit; these are the roundings of the guarded vector body, the one the fp16 training step has always run.
+// (pool.hip adam_kernel and embed.hip scatter_grouped_adam_kernel: one definition, so the fused table update has the same bits.)
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float step_size, float b1, float b2, float omb1,
+                                            float omb2, float inv_sqrt_bc2, float eps) {
+#pragma clang fp contract(off)
+    m = b1 * m + omb1 * g;
+    v = b2 * v + omb2 * g * g;
+    const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
+    p = __builtin_fmaf(-step_size, m / denom, p);
+}
+// the scalars of one Adam step, formed on the host (pool.hip adam_consts)
+struct AdamConsts { float step_size, b1, b2, omb1, omb2, inv_sqrt_bc2, eps; };
+AdamConsts adam_consts(double lr, double beta1, double beta2, double eps, int32_t step);
+
 // ---------------------------------------------------------------------------------------
 // host side: error text + optional per-kernel event timing
 // ---------------------------------------------------------------------------------------

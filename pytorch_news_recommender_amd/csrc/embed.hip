@@ -301,24 +301,17 @@ __global__ __launch_bounds__(256) void tok_place_kernel(const int64_t* ids, cons
 // H16: dX rows are fp16 [rows][ldx] still multiplied by the fp16 backward's loss scale (half the bytes of the dX GEMM's
 // store and of this kernel's reads); the sum is taken in fp32 and divided by the scale (sc[1], device) once per table row.
 typedef _Float16 sg_h4 __attribute__((ext_vector_type(4)));
-template <bool H16, int SL = 2>
-__global__ __launch_bounds__(256) void scatter_grouped_kernel(int V, int d4, const int* live, const int* offs,
-                                                              const int* total, const int* order, const void* dxv, int ldx,
-                                                              const float* sc, Dropout drop, float* dtable) {
+// The sum of one table row's bucket [beg, end) of `order`, shared by the scatter and by the fused scatter + Adam kernel (one
+// body: the two have the same bits).
+template <bool H16, int SL>
+__device__ __forceinline__ void bucket_sum(f32x4 (&s)[SL], int lane, int d4, int beg, int end, const int* live, const int* order,
+                                           const void* dxv, int ldx, const Dropout& drop) {
     const float* dx = reinterpret_cast<const float*>(dxv);
     const _Float16* dx16 = reinterpret_cast<const _Float16*>(dxv);
-    const int lane = threadIdx.x & 63;
-    const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (v >= V || v == 0) return;                                   // id 0 = padding: no gradient
-    const int beg = offs[v], end = v + 1 < V ? offs[v + 1] : *total;
-    if (beg == end) return;
     // a lane owns float4 columns lane, lane + 64, ... (SL slices): ONE pass over the bucket, all slices of a
     // token's row loaded together (a pass per slice doubled the dependent order -> row load chain)
     // SL = 2: d_model <= 512 (d4 <= 128); SL = 4: up to the 1024 the C ABI accepts (chosen by the launcher -- with two
     // slices only, columns 512.. of a wider table gradient were silently left out)
-    f32x4 s[SL];
-#pragma unroll
-    for (int j = 0; j < SL; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto add_row = [&](int r) {
         const long t = live[r];
 #pragma unroll
@@ -360,10 +353,82 @@ __global__ __launch_bounds__(256) void scatter_grouped_kernel(int V, int d4, con
             m3 = m3 == m ? NONE : m3;
         }
     }
+}
+
+template <bool H16, int SL = 2>
+__global__ __launch_bounds__(256) void scatter_grouped_kernel(int V, int d4, const int* live, const int* offs,
+                                                              const int* total, const int* order, const void* dxv, int ldx,
+                                                              const float* sc, Dropout drop, float* dtable) {
+    const int lane = threadIdx.x & 63;
+    const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= V || v == 0) return;                                   // id 0 = padding: no gradient
+    const int beg = offs[v], end = v + 1 < V ? offs[v + 1] : *total;
+    if (beg == end) return;
+    f32x4 s[SL];
+#pragma unroll
+    for (int j = 0; j < SL; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bucket_sum<H16, SL>(s, lane, d4, beg, end, live, order, dxv, ldx, drop);
 #pragma unroll
     for (int j = 0; j < SL; ++j) {
         const int c4 = lane + 64 * j;
         if (c4 < d4) *reinterpret_cast<f32x4*>(dtable + ((long)v * d4 + c4) * 4) += H16 ? s[j] * sc[1] : s[j];
+    }
+}
+
+// NRMS_FLAG_TABLE_ADAM: the wave of table row v ends the bucket walk with the row's complete gradient in registers and applies Adam
+// to the row at once -- the gradient is stored for the caller (plain stores into a buffer that needs no zero fill) but never read
+// back, and the three launches zero fill -> scatter -> Adam become one.  EVERY row is visited: a row without a token in the
+// batch, and the padding row 0, take the gradient +0 (Adam still moves their m, v and p).  g = +0 + sum, as the += onto the
+// zeroed buffer gave; then adam_kernel's own element code (the same adam_update, the same guard, one atomic per wave that saw a
+// non-finite element; branch-free here: a skipped element computes its update and keeps its old values).
+// Registers decide this kernel: the bucket walk is a chain of dependent loads (order -> live -> dX row), so its rate is the
+// number of waves in flight, eight per SIMD at <= 64 VGPRs like the plain scatter.  p, m, v are therefore loaded AFTER the walk,
+// one slice at a time (held across it, with a branch per guarded element, the kernel took 154 VGPRs -- three waves per SIMD --
+// and the step was 3.5 % SLOWER than three separate kernels: docs/EXPERIMENTS.md).
+template <bool H16, int SL, bool GUARD>
+__global__ __launch_bounds__(256) void scatter_grouped_adam_kernel(int V, int d4, const int* live, const int* offs,
+                                                                   const int* total, const int* order, const void* dxv, int ldx,
+                                                                   const float* sc, Dropout drop, float* dtable, TableAdam a) {
+    const int lane = threadIdx.x & 63;
+    const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= V) return;
+    f32x4 s[SL];
+#pragma unroll
+    for (int j = 0; j < SL; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (v != 0) {                                                   // id 0 = padding: no gradient
+        const int beg = offs[v], end = v + 1 < V ? offs[v + 1] : *total;
+        bucket_sum<H16, SL>(s, lane, d4, beg, end, live, order, dxv, ldx, drop);
+    }
+    const long row4 = (long)v * d4;
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        const int c4 = lane + 64 * j;
+        if (c4 < d4) {
+            f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
+            g += H16 ? s[j] * sc[1] : s[j];
+            f32x4 pv = reinterpret_cast<const f32x4*>(a.p)[row4 + c4];
+            f32x4 mv = reinterpret_cast<const f32x4*>(a.m)[row4 + c4];
+            f32x4 vv = reinterpret_cast<const f32x4*>(a.v)[row4 + c4];
+            reinterpret_cast<f32x4*>(dtable)[row4 + c4] = g;
+            const f32x4 gv = g * a.gscale;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool skip = GUARD && (__float_as_uint(gv[e]) & 0x7F800000u) == 0x7F800000u;
+                float pe = pv[e], me = mv[e], ve = vv[e];
+                adam_update(pe, me, ve, gv[e], a.c.step_size, a.c.b1, a.c.b2, a.c.omb1, a.c.omb2, a.c.inv_sqrt_bc2, a.c.eps);
+                pv[e] = skip ? pv[e] : pe; mv[e] = skip ? mv[e] : me; vv[e] = skip ? vv[e] : ve;
+                bad += skip ? 1 : 0;
+            }
+            reinterpret_cast<f32x4*>(a.p)[row4 + c4] = pv;
+            reinterpret_cast<f32x4*>(a.m)[row4 + c4] = mv;
+            reinterpret_cast<f32x4*>(a.v)[row4 + c4] = vv;
+        }
+    }
+    if (GUARD) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+        if (bad != 0 && lane == 0) atomicAdd(a.n_bad, bad);
     }
 }
 
@@ -424,6 +489,30 @@ int launch_scatter_grouped(long M, int V, int d, const int64_t* ids, const int* 
         hipLaunchKernelGGL((scatter_grouped_kernel<false, 4>), dim3(cdiv(V, 4)), dim3(256), 0, stream, V, d / 4, live, cnt, total, order,
                            dx, d, nullptr, drop, dtable);
     return check_launch("scatter_grouped");
+}
+
+int launch_scatter_grouped_adam(long M, int V, int d, const int64_t* ids, const int* live, const int* n_live, const void* dx,
+                                const Dropout& drop, float* dtable, int* scratch, hipStream_t stream, bool dx_fp16, int ldx,
+                                const float* sc, bool prepared, const TableAdam& a) {
+    if (M <= 0 || V <= 0) { set_error("scatter_grouped_adam: nothing to scatter (the caller runs the plain Adam step)"); return NRMS_EINVAL; }
+    if ((d & 3) != 0 || d > 1024 || (dx_fp16 && d > 512)) { set_error("scatter_grouped_adam: d=%d unsupported", d); return NRMS_EINVAL; }
+    if (!prepared) {
+        const int rc = launch_scatter_prepare(M, V, ids, live, n_live, scratch, stream);
+        if (rc) return rc;
+    }
+    int* cnt = scratch;
+    int* cursor = cnt + V + 64;
+    int* total = cursor + V;
+    int* order = cursor + V + 64;
+    const bool guard = a.n_bad != nullptr;
+    TimingScope ts("adam", stream);
+    auto go = [&](auto kernel, int ld, const float* scp) {
+        hipLaunchKernelGGL(kernel, dim3(cdiv(V, 4)), dim3(256), 0, stream, V, d / 4, live, cnt, total, order, dx, ld, scp, drop, dtable, a);
+    };
+    if (dx_fp16) { if (guard) go(scatter_grouped_adam_kernel<true, 2, true>, ldx, sc); else go(scatter_grouped_adam_kernel<true, 2, false>, ldx, sc); }
+    else if (d <= 512) { if (guard) go(scatter_grouped_adam_kernel<false, 2, true>, d, nullptr); else go(scatter_grouped_adam_kernel<false, 2, false>, d, nullptr); }
+    else { if (guard) go(scatter_grouped_adam_kernel<false, 4, true>, d, nullptr); else go(scatter_grouped_adam_kernel<false, 4, false>, d, nullptr); }
+    return check_launch("scatter_grouped_adam");
 }
 
 // dst[i] = src[i] if 0 <= src[i] < vocab else 0 (the padding id); *n_bad += number of ids replaced.  The encoder

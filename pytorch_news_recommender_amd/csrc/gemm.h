@@ -437,6 +437,18 @@ size_t scatter_grouped_scratch_ints(long M, int V);
 int launch_scatter_grouped(long M, int V, int d, const int64_t* ids, const int* live, const int* n_live, const void* dx,
                            const Dropout& drop, float* dtable, int* scratch, hipStream_t stream, bool dx_fp16 = false, int ldx = 0,
                            const float* sc = nullptr, bool prepared = false);
+// NRMS_FLAG_TABLE_ADAM: the same bucket sums, and the wave that holds a table row's complete gradient applies Adam to that row
+// at once (every row, also those without a token in the batch: gradient +0).  dtable receives the gradient (plain stores: it needs
+// no zero fill); a.n_bad null = unguarded.  Timer name "adam".
+struct TableAdam {
+    float *p, *m, *v;         // [V, d] parameter rows, exp_avg, exp_avg_sq
+    AdamConsts c;
+    float gscale;
+    int* n_bad;
+};
+int launch_scatter_grouped_adam(long M, int V, int d, const int64_t* ids, const int* live, const int* n_live, const void* dx,
+                                const Dropout& drop, float* dtable, int* scratch, hipStream_t stream, bool dx_fp16, int ldx,
+                                const float* sc, bool prepared, const TableAdam& a);
 // the id-only part of the above (histogram of the live tokens' ids, offsets, placement): `prepared` = it has run on `scratch`
 int launch_scatter_prepare(long M, int V, const int64_t* ids, const int* live, const int* n_live, int* scratch, hipStream_t stream);
 // dx has one row per token; the live tokens' rows are scatter-added (float atomics)

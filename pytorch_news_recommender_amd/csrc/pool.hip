@@ -345,19 +345,7 @@ __global__ void ce_loss_kernel(int B, int C, const float* scores, float* loss_su
 // the update -- p, m and v keep their values, so Adam's moments cannot be poisoned for the rest of training -- and counted into
 // *n_bad (one atomic per wavefront that saw any; none in a healthy step).  Every rank of a data-parallel job sees the same
 // reduced gradient, hence skips the same elements: replicas stay identical.
-// One element's update, with every rounding spelt out: m, v and the denominator are formed from rounded products (no fma
-// contraction), the parameter takes step_size * m / denom in one fma.  Left to the compiler, the guarded
-// and the unguarded kernel -- and the vector body and the scalar tail of each -- were contracted differently and disagreed in
-// the last bit; these are the roundings of the guarded vector body, the one the fp16 training step has always run.
-__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float step_size, float b1, float b2, float omb1,
-                                            float omb2, float inv_sqrt_bc2, float eps) {
-#pragma clang fp contract(off)
-    m = b1 * m + omb1 * g;
-    v = b2 * v + omb2 * g * g;
-    const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
-    p = __builtin_fmaf(-step_size, m / denom, p);
-}
-
+// One element's update: adam_update (common.h), shared with the fused table update of embed.hip.
 template <bool GUARD>
 __global__ void adam_kernel(size_t n4, size_t n, float* p, const float* g, float* m, float* v, float step_size,
                             float b1, float b2, float omb1, float omb2, float inv_sqrt_bc2, float eps, float gscale, int* n_bad) {
@@ -533,34 +521,52 @@ extern "C" int nrms_ce_loss_fwd_bwd(int32_t B, int32_t C, const float* scores, f
     return check_launch("ce_loss");
 }
 
+// torch.optim.Adam: step_size = lr / (1 - b1^t); denom = sqrt(v)/sqrt(1 - b2^t) + eps
+// hyper-parameters arrive as doubles, as torch holds them: 1 - beta is formed in double and rounded once
+// (float(1 - 0.999) != 1 - float(0.999): 1.3e-5 relative in exp_avg_sq)
+namespace nrms {
+AdamConsts adam_consts(double lr, double beta1, double beta2, double eps, int32_t step) {
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    AdamConsts c;
+    c.step_size = (float)(lr / bc1);
+    c.b1 = (float)beta1; c.b2 = (float)beta2; c.omb1 = (float)(1.0 - beta1); c.omb2 = (float)(1.0 - beta2);
+    c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    c.eps = (float)eps;
+    return c;
+}
+}  // namespace nrms
+
 static int adam_step(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, double lr, double beta1,
-                     double beta2, double eps, int32_t step, float grad_scale, int32_t* n_nonfinite, void* stream) {
+                     double beta2, double eps, int32_t step, float grad_scale, int32_t* n_nonfinite, void* stream,
+                     const char* timer = "adam") {
     NRMS_REQUIRE(param && grad && exp_avg && exp_avg_sq && step >= 1, "adam_step: bad arguments");
     NRMS_REQUIRE((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
                  "adam_step: buffers must be 16-byte aligned");
     if (n == 0) return NRMS_OK;
-    // torch.optim.Adam: step_size = lr / (1 - b1^t); denom = sqrt(v)/sqrt(1 - b2^t) + eps
-    // hyper-parameters arrive as doubles, as torch holds them: 1 - beta is formed in double and rounded once
-    // (float(1 - 0.999) != 1 - float(0.999): 1.3e-5 relative in exp_avg_sq)
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    const float step_size = (float)(lr / bc1);
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    const AdamConsts c = adam_consts(lr, beta1, beta2, eps, step);
     hipStream_t s = (hipStream_t)stream;
     const size_t n4 = n / 4;
     int blocks = (int)((n4 + 255) / 256);
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
-    TimingScope ts("adam", s);
+    TimingScope ts(timer, s);
     if (n_nonfinite != nullptr)
-        hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, s, n4, n, param, grad, exp_avg, exp_avg_sq, step_size,
-                           (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), inv_sqrt_bc2, (float)eps, grad_scale,
-                           (int*)n_nonfinite);
+        hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, s, n4, n, param, grad, exp_avg, exp_avg_sq, c.step_size,
+                           c.b1, c.b2, c.omb1, c.omb2, c.inv_sqrt_bc2, c.eps, grad_scale, (int*)n_nonfinite);
     else
-        hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, s, n4, n, param, grad, exp_avg, exp_avg_sq, step_size,
-                           (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), inv_sqrt_bc2, (float)eps, grad_scale,
-                           (int*)nullptr);
+        hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, s, n4, n, param, grad, exp_avg, exp_avg_sq, c.step_size,
+                           c.b1, c.b2, c.omb1, c.omb2, c.inv_sqrt_bc2, c.eps, grad_scale, (int*)nullptr);
     return check_launch("adam");
+}
+
+// The parameters behind a table that NRMS_FLAG_TABLE_ADAM updated inside the backward: the same kernels as nrms_adam_step /
+// nrms_adam_step_guarded (n_nonfinite null: unguarded), recorded under a timer of its own ("rest_adam": the timers are read by
+// prefix, and "adam" is the table's fused kernel on that path)
+extern "C" int nrms_adam_step_rest(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, double lr,
+                                   double beta1, double beta2, double eps, int32_t step, float grad_scale, int32_t* n_nonfinite,
+                                   void* stream) {
+    return adam_step(n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale, n_nonfinite, stream, "rest_adam");
 }
 
 extern "C" int nrms_adam_step(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, double lr,

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from dataclasses import dataclass
 
 import torch
@@ -142,6 +143,7 @@ class NRMSEngine:
             raise _lib.NrmsError("the NRMS HIP engine needs a GPU device (got %s); there is no CPU path" % device)
         self._bufs = {}
         self._saved = None
+        self._fuse_table_adam = os.environ.get("NRMS_NO_FUSED_TABLE_ADAM", "0") in ("", "0")
         self.fp16_user_encoder = False     # precision "fp16": the user encoder runs in bf16x3 unless this is set
         self.fp16_backward = True          # training in fp16 mode runs the fused fp16 backward (csrc/fused16_bwd.hip)
         self.loss_scale = 0.0              # fp16 backward: 0 = chosen on the device from max |dout| per call (nrms_hip.h)
@@ -561,7 +563,30 @@ class NRMSEngine:
         return loss_sum
 
     # ---- full model backward ------------------------------------------------------------
-    def backward(self, flat, gflat, dscores=None, table_grad_ready=None, gen=None):
+    # Exactly one table scatter feeds the word-embedding table in a step of THIS class's backward().  A subclass does not inherit
+    # the claim: it is False there unless the subclass states it itself.
+    single_table_scatter = True
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        if "single_table_scatter" not in cls.__dict__:
+            cls.single_table_scatter = False
+
+    def fuses_table_adam(self):
+        """True when the saved training forward's backward can update the word-embedding table inside its scatter kernel
+        (NRMS_FLAG_TABLE_ADAM, include/nrms_hip.h): exactly ONE table scatter feeds the table in a step -- the class says so
+        (single_table_scatter; subclasses such as nrms_naml's engine, with its title and abstract passes, default to False and keep
+        the separate optimizer) -- and that scatter is the grouped one.  NRMS_NO_FUSED_TABLE_ADAM=1 (read when the engine is
+        built) forces the separate path."""
+        sv = self._saved
+        if (sv is None or not type(self).single_table_scatter or type(self).backward is not NRMSEngine.backward
+                or not self._fuse_table_adam or os.environ.get("NRMS_ATOMIC_SCATTER") is not None):
+            return False
+        # (the fp16 news encoder scatters dense rows with atomics unless the padding row is zero; every other precision groups)
+        return (self.pad_row_zero or self.precision != "fp16"
+                or not self._fp16_ok("news_encoder", sv["L"], 0, True))
+
+    def backward(self, flat, gflat, dscores=None, table_grad_ready=None, gen=None, table_adam=None):
         """Accumulates d(loss)/d(params) into gflat (same layout as flat) given dscores [B,C]; dscores None: the gradient of the
         pooled loss that pooled_ce_loss() computed for this training forward (NrmsError if it did not).
         gen: the generation stamp of the training forward this backward belongs to (saved activations are one
@@ -569,7 +594,12 @@ class NRMSEngine:
 
         table_grad_ready: optional callable invoked as soon as the embedding-table gradient (95 % of the
         gradient bytes) is complete on the stream; the news encoder's d(W_qkv) GEMM is then deferred behind
-        it (NRMS_FLAG_DEFER_WQKV) so that a data-parallel caller can start the table all-reduce underneath."""
+        it (NRMS_FLAG_DEFER_WQKV) so that a data-parallel caller can start the table all-reduce underneath.
+
+        table_adam: dict(m, v, step, lr, betas, eps[, guard]) -- only where fuses_table_adam() holds and without
+        table_grad_ready: the news encoder's scatter kernel applies this Adam step to the table rows (NRMS_FLAG_TABLE_ADAM);
+        the table region of gflat is then written, not accumulated, and the caller steps the other parameters with
+        adam_step(..., rest=True)."""
         d = self.dims.word_embed_size
         sv, dnv, duser = self._head_backward(dscores, gen, d)
         B, H, Cn, L = sv["B"], sv["H"], sv["C"], sv["L"]
@@ -595,11 +625,28 @@ class NRMSEngine:
             desc_n.flags |= _lib.NRMS_FLAG_FWD_SCRATCH_KEPT     # acts_n.scratch is this step's forward scratch (its own buffer)
         if table_grad_ready is not None:
             desc_n.flags |= _lib.NRMS_FLAG_DEFER_WQKV
+        ta = None
+        if table_adam is not None:
+            if (table_grad_ready is not None or type(self).backward is not NRMSEngine.backward
+                    or (desc_n.precision == _lib.NRMS_PRECISION_FP16 and not desc_n.flags & _lib.NRMS_FLAG_PAD_ROW_ZERO)):
+                raise _lib.NrmsError("backward(table_adam=...) needs fuses_table_adam() and no table_grad_ready")
+            lo, _, n_table = self.layout.entries[self.layout.names[0]]
+            if lo != 0 or wn.table != flat.data_ptr():
+                raise _lib.NrmsError("backward(table_adam=...): the word-embedding table must open the flat buffer")
+            guard = table_adam.get("guard")
+            guard = self.precision == "fp16" if guard is None else guard
+            betas = table_adam.get("betas", (0.9, 0.999))
+            ta = _lib.TableAdam(param=flat.data_ptr(), exp_avg=table_adam["m"].data_ptr(), exp_avg_sq=table_adam["v"].data_ptr(),
+                                lr=float(table_adam["lr"]), beta1=float(betas[0]), beta2=float(betas[1]),
+                                eps=float(table_adam.get("eps", 1e-8)), step=int(table_adam["step"]),
+                                grad_scale=float(table_adam.get("grad_scale", 1.0)),
+                                n_nonfinite=self._grad_bad.data_ptr() if guard else None)
+            desc_n.flags |= _lib.NRMS_FLAG_TABLE_ADAM
         rc_join = 0
         try:
-            rc = self.lib.nrms_encoder_bwd(C.byref(desc_n), C.byref(wn), _lib.ptr(sv["ids"]), None, None, C.byref(acts_n),
-                                           _lib.ptr(dnv), C.byref(gn), None, _lib.ptr(ws),
-                                           C.c_size_t(ws.numel() * 4), _stream())
+            rc = self.lib.nrms_encoder_bwd_adam(C.byref(desc_n), C.byref(wn), _lib.ptr(sv["ids"]), None, None, C.byref(acts_n),
+                                                _lib.ptr(dnv), C.byref(gn), None, _lib.ptr(ws),
+                                                C.c_size_t(ws.numel() * 4), None if ta is None else C.byref(ta), _stream())
             _lib.check(rc, "nrms_encoder_bwd(news)")
             if table_grad_ready is not None:
                 table_grad_ready()
@@ -612,12 +659,20 @@ class NRMSEngine:
         _lib.check(rc_join, "nrms_encoder_join")
 
     def adam_step(self, flat, gflat, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                  grad_scale=1.0, guard=None):
+                  grad_scale=1.0, guard=None, rest=False):
         """torch.optim.Adam's update on flat buffers.  guard (default: on in the fp16 mode): elements with a non-finite
         gradient are left out of the update and counted (nrms_adam_step_guarded); note_grad_check() afterwards lets the
-        count reach the host without a sync."""
+        count reach the host without a sync.  rest: the parameters behind a table that backward(table_adam=...) stepped
+        (nrms_adam_step_rest: the same kernels under a timer of their own)."""
         if guard is None:
             guard = self.precision == "fp16"
+        if rest:
+            rc = self.lib.nrms_adam_step_rest(C.c_size_t(flat.numel()), _lib.ptr(flat), _lib.ptr(gflat), _lib.ptr(exp_avg),
+                                              _lib.ptr(exp_avg_sq), C.c_double(lr), C.c_double(betas[0]), C.c_double(betas[1]),
+                                              C.c_double(eps), int(step), C.c_float(grad_scale),
+                                              _lib.ptr(self._grad_bad) if guard else None, _stream())
+            _lib.check(rc, "nrms_adam_step_rest")
+            return
         if guard:
             rc = self.lib.nrms_adam_step_guarded(C.c_size_t(flat.numel()), _lib.ptr(flat), _lib.ptr(gflat), _lib.ptr(exp_avg),
                                                  _lib.ptr(exp_avg_sq), C.c_double(lr), C.c_double(betas[0]), C.c_double(betas[1]),

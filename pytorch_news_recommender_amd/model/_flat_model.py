@@ -116,11 +116,23 @@ class FlatHipModel(nn.Module):
     def _zero_frozen_rows(self, gflat):
         pass
 
-    def _backward(self, gflat, dscores, gen=None, table_grad_ready=None):
+    def _backward(self, gflat, dscores, gen=None, table_grad_ready=None, table_adam=None):
         """The engine's backward into gflat, then the frozen rows' gradients zeroed (before any all-reduce sees them).  dscores
-        None: the gradient the engine's pooled_ce_loss() left for this forward."""
-        self._engine.backward(self._flat, gflat, dscores, gen=gen, table_grad_ready=table_grad_ready)
+        None: the gradient the engine's pooled_ce_loss() left for this forward.  table_adam: see _fuses_table_adam."""
+        if table_adam is not None:
+            self._engine.backward(self._flat, gflat, dscores, gen=gen, table_adam=table_adam)
+        else:
+            self._engine.backward(self._flat, gflat, dscores, gen=gen, table_grad_ready=table_grad_ready)
         self._zero_frozen_rows(gflat)
+
+    def _fuses_table_adam(self, world_size, all_reduce):
+        """The word-embedding table (the layout's first entry, 95 % of the parameters) takes its Adam step inside the news
+        encoder's scatter kernel (NRMS_FLAG_TABLE_ADAM) when nothing has to happen to its gradient between the backward and the
+        optimizer -- one rank, no all-reduce, no frozen rows to zero -- and the engine says that exactly one table scatter
+        feeds the table in a step (engine.fuses_table_adam)."""
+        fuses = getattr(self._engine, "fuses_table_adam", None)
+        return (world_size == 1 and all_reduce is None and type(self)._zero_frozen_rows is FlatHipModel._zero_frozen_rows
+                and fuses is not None and fuses() and self._layout.entries[self._names[0]][0] == 0)
 
     def _prepare(self):
         """Make sure parameters live in one flat GPU buffer (``.to(device)`` replaces tensors) and the engine is current."""
@@ -232,8 +244,20 @@ class FlatHipModel(nn.Module):
             loss_sum, dscores = self._pooled_loss(batch, 1.0 / gb), None
         else:
             loss_sum, dscores = eng.ce_loss(scores, grad_scale=1.0 / gb)
-        st["g"].zero_()
         lr_ = float(self.config.learning_rate if lr is None else lr)
+        if self._fuses_table_adam(world_size, all_reduce):
+            # the table region of g is written by the fused kernel (every row): no zero fill, no second pass over it
+            n_table = self._layout.entries[self._names[0]][2]
+            st["g"][n_table:].zero_()
+            self._backward(st["g"], dscores, table_adam=dict(m=st["m"], v=st["v"], step=st["step"] + 1, lr=lr_, betas=betas, eps=eps))
+            st["step"] += 1
+            eng.adam_step(self._flat[n_table:], st["g"][n_table:], st["m"][n_table:], st["v"][n_table:], st["step"], lr=lr_,
+                          betas=betas, eps=eps, rest=True)
+            if eng.precision == "fp16":
+                eng.note_grad_check()
+            self._last_scores = scores
+            return loss_sum
+        st["g"].zero_()
         overlap = not os.environ.get("NRMS_NO_OVERLAP")
         if all_reduce is not None and hasattr(all_reduce, "owned"):
             # parallel.ShardedGradSync: reduce-scatter (the table region underneath the deferred weight-gradient GEMMs),
