@@ -422,6 +422,47 @@ int nrms_rank_dot(int32_t B, int64_t N, int32_t d, int32_t T, const float* user,
                   const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ---- Negatives from the model's own softmax over the whole catalogue (csrc/softmaxsample.hip; training: "which S news does the
+ * model itself confuse with the positive right now?"; PARITY UNPINNED, the reference draws its negatives offline) ----
+ * For each user b < B: S items drawn WITHOUT replacement from softmax(s(b, .) * inv_temperature) over the eligible items, never
+ * forming the [B, N] score matrix, as a pure function of the inputs.  By the Gumbel-top-S identity these are the S largest perturbed
+ * keys s(b, n) * inv_temperature + g(b, n), g i.i.d. standard Gumbel: nrms_topk_dot with a keyed perturbation in its epilogue.
+ * user [B, d], items [N, d] fp32 row-major; row_key [B] int64: what names row b's draw (e.g. a click's position in the log);
+ * exclude [B, n_exclude] int64, nullable, as nrms_topk_dot's; ids [B, S] int64; keys [B, S] fp32, nullable.
+ * Score.  s(b, n) is nrms_topk_dot's chain for (user row, item row): one fp32 accumulator over all of d on
+ *   v_mfma_f32_32x32x2_f32 in the same k order, so the same bits (the kernels are the same code).
+ * Noise.  An exact integer function of (seed, row_key[b], n), independent of B, N, the row's position and the launch geometry.  A
+ *   48-bit row key and a 31-bit item id do not fit one 64-bit Philox counter, so the draw has two levels (philox4x32_7 and the
+ *   counter layout of the dropout sites, csrc/common.h):
+ *     r = philox4x32_7(seed, group = row_key[b], site 8);   row_seed = r[0] | (uint64) r[1] << 32
+ *     w(b, n) = word n & 3 of philox4x32_7(row_seed, group = n >> 2, site 9)
+ *   (four neighbouring items share one call on purpose: adjacent lanes of an MFMA column tile hold adjacent items, so the generator
+ *   work can be quartered later without changing a draw).  m = w >> 9;  u = (2 m + 1) * 2^-24, exact in fp32 and strictly inside
+ *   (0, 1);  g = -logf(-logf(u)) in fp32, below 17.4 for every u.
+ * Key.  key(b, n) = fmaf(s(b, n), inv_temperature, g(b, n)) in fp32, inv_temperature = 1 / temperature finite and >= 0.  0 gives a
+ *   uniform draw over the eligible items with finite scores (an infinite score times 0 is NaN); large values approach "the S
+ *   hardest".
+ * Eligible: n is not in exclude[b, :] and key(b, n) is not NaN.
+ * Order.  Key descending; equal keys put the SMALLER n first; -0.0 equals +0.0 (returned as +0.0): nrms_topk_dot's order.
+ * Output.  Row b holds the first min(S, #eligible) items in that order, which is the Plackett-Luce order: slot 0 is a draw from the
+ *   softmax, slot 1 a draw from the rest, and so on; the remaining slots hold id -1 and key -inf.  keys carries the perturbed keys,
+ *   not the plain scores.
+ * Limits: 1 <= S <= 256, d >= 1, 0 <= N <= 0x7FFF0000, B >= 0, n_exclude >= 0, 0 <= row_key < 2^48; B = 0 is a no-op, N = 0
+ *   writes all-padding rows.  Arguments outside the limits return NRMS_EINVAL (row keys are device data and are not inspected).
+ * Workspace: nrms_softmax_sample_dot_workspace_bytes(B, N, d, S, n_exclude) bytes, 8-byte aligned, O(B * slices * S) (0 =
+ *   arguments rejected).
+ * Two kernels on `stream`, no host synchronisation, no allocation; plain vector stores only, no float atomics (the integer LDS
+ *   counters of the slice buffers order insertions, never a result): two runs are bit-identical whatever the workspace held. */
+size_t nrms_softmax_sample_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t S, int32_t n_exclude);
+int nrms_softmax_sample_dot(int32_t B, int64_t N, int32_t d, int32_t S, const float* user, const float* items,
+                            const int64_t* row_key /* [B] */, float inv_temperature, uint64_t seed,
+                            const int64_t* exclude /* [B, n_exclude], nullable */, int32_t n_exclude, int64_t* ids /* [B, S] */,
+                            float* keys /* [B, S], nullable */, void* workspace, size_t workspace_bytes, void* stream);
+/* Test hook, like nrms_dropout_keep_mask: the whole [B, N] perturbation of nrms_softmax_sample_dot for small shapes, w(b, n) into
+ * words and g(b, n) into gumbel (each nullable, not both; the same device function as the fused kernel's). */
+int nrms_softmax_sample_noise(int32_t B, int64_t N, const int64_t* row_key /* [B] */, uint64_t seed,
+                              uint32_t* words /* [B, N], nullable */, float* gumbel /* [B, N], nullable */, void* stream);
+
 /* ---- nrms_naml pieces around the two encoder passes (model/nrms_naml.py) ----
  * LayerNorm over the last dimension (nn.LayerNorm(news_feature_size) on the history vectors, nrms_naml.py:207,238):
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance.  stats [n_rows, 2] = (mean, 1/std) is written when

@@ -46,6 +46,11 @@ constexpr uint32_t PHILOX_SITE_NEG_SAMPLE = 6u;
 // Site 7: the catalogue draws of csrc/catneg.hip, group = ((row key * 64 + slot) << 2) | (attempt >> 1), words 2 (attempt & 1) and
 // 2 (attempt & 1) + 1 of the call.
 constexpr uint32_t PHILOX_SITE_CATALOGUE_NEG = 7u;
+// Sites 8 and 9: the Gumbel perturbation of csrc/softmaxsample.hip, in two levels because a 48-bit row key and a 31-bit item id do
+// not fit one counter.  Site 8: group = the row key, words 0 and 1 of the call are the row's 64-bit seed.  Site 9, keyed by that
+// seed: group = item id >> 2, word = item id & 3.
+constexpr uint32_t PHILOX_SITE_SOFTMAX_ROW = 8u;
+constexpr uint32_t PHILOX_SITE_SOFTMAX_ITEM = 9u;
 
 __host__ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2,
                                                       uint32_t& c3, uint32_t k0, uint32_t k1) {

@@ -718,12 +718,32 @@ class ClickFeed(DeviceFeed):
     table ``logq`` [N] is built once, in float64, and kept as float32; a news with q = 0 (nobody's positive and weight 0) holds
     -inf and cannot occur in a pool.  The rejection of a user's own clicks by the sampler is ignored in q: it renormalises a row's
     draw over the catalogue minus a few dozen news, a relative change of about (the weight share of those news), far below what
-    the correction is for."""
+    the correction is for.
+
+    ``negatives="adaptive"`` (default ``"popularity"``, everything above) draws a row's S negatives from the MODEL's own softmax
+    over the catalogue instead, softmax(score / ``temperature``) without replacement (``Model.sample_negatives``,
+    ``nrms_softmax_sample_dot``), with the weights of the model named by ``attach_scorer(model)`` as they are when the epoch
+    starts: the catalogue is encoded once per draw (dropout-free, in the evaluation precision), then this rank's rows go
+    through the user encoder and the sampler in chunks of ``draw_chunk`` rows.  ``packed`` has the layout of the popularity draw.
+      * A row's negatives are a function of (the model's weights, the log, seed, epoch, the row's key) only: not of the batch
+        size, the chunk size, the order of the rows or the rank.
+      * A negative is never a news of the user's own training part (which contains the positive) and never repeated in a row.
+      * Held-out clicks are not rejected, for the same reason as above.
+      * The negatives are as stale as one epoch, on purpose: the weights move during the epoch and the draw does not follow
+        (the staleness rule of the graph model's neighbour vectors).
+    A slot is left empty (masked out, counted in ``n_short``) only when fewer than S news are eligible.  ``candidate_logq`` is
+    the log-probability of the popularity sampler and an adaptive draw has no fixed q: with ``negatives="adaptive"`` the key
+    raises ``KeyError``.  Still one host synchronisation per epoch."""
 
     def __init__(self, config, user_ptr, clicks, id2title_dict=None, id2abst_dict=None, news_categ=None, news_subcateg=None, holdout=1,
                  min_history=1, popularity_power=0.75, weights=None, batch_size=None, device="cuda", shuffle=False, drop_last=False, seed=0,
-                 resample=True, rank=0, world=1):
+                 resample=True, rank=0, world=1, negatives="popularity", temperature=1.0):
         user_ptr, clicks = np.asarray(user_ptr, dtype=np.int64).reshape(-1), np.asarray(clicks, dtype=np.int64).reshape(-1)
+        if negatives not in ("popularity", "adaptive"):
+            raise ValueError("ClickFeed: negatives = %r must be 'popularity' or 'adaptive'" % (negatives,))
+        if not (float(temperature) > 0.0 and np.isfinite(float(temperature))):
+            raise ValueError("ClickFeed: temperature = %r must be finite and > 0" % (temperature,))
+        self.negatives, self.temperature, self.draw_chunk, self._scorer = negatives, float(temperature), 8192, None
         if user_ptr.size < 1 or user_ptr[0] != 0 or (np.diff(user_ptr) < 0).any() or int(user_ptr[-1]) != clicks.size:
             raise ValueError("ClickFeed: user_ptr must rise from 0 to len(clicks) = %d" % clicks.size)
         if int(holdout) < 0 or int(min_history) < 0:
@@ -789,6 +809,7 @@ class ClickFeed(DeviceFeed):
         # (the library refuses null pointers: a log in which nobody trains still hands it one element)
         self._set_news_arg = self.set_news if self.set_news.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
         self._train_len = train_len
+        self._row_set_len = np.diff(set_ptr)[row_user]             # host copy: the adaptive draw sizes its exclude matrices with it
         self._categ = None if news_categ is None else (dev(np.asarray(news_categ, dtype=np.int64)), dev(np.asarray(news_subcateg, dtype=np.int64)))
         self.packed = dict(cand=zeros(n, S), ccat=zeros(n, S), csub=zeros(n, S), clen=zeros(n))
         self.n_samples = n
@@ -809,7 +830,13 @@ class ClickFeed(DeviceFeed):
 
     def batch(self, rows):
         b = DeviceFeed.batch(self, rows)
-        b._extra['candidate_logq'] = lambda: self.logq.index_select(0, b['candidate_ids'].reshape(-1)).view(b['candidate_ids'].shape)
+        if self.negatives == "adaptive":
+            def no_logq():
+                raise KeyError("candidate_logq: an adaptive draw follows the model and has no fixed q (the table is the popularity "
+                               "sampler's log-probability); train without the logQ correction")
+            b._extra['candidate_logq'] = no_logq
+        else:
+            b._extra['candidate_logq'] = lambda: self.logq.index_select(0, b['candidate_ids'].reshape(-1)).view(b['candidate_ids'].shape)
         return b
 
     def _rows_of(self, name, rows):
@@ -843,13 +870,62 @@ class ClickFeed(DeviceFeed):
     def epoch_seed(self, epoch):
         return (self.seed + int(epoch) * EPOCH_SEED_STEP) & 0xFFFFFFFFFFFFFFFF
 
+    def attach_scorer(self, model):
+        """Names the model whose softmax ``negatives="adaptive"`` draws from (a model with ``CATALOGUE_SAMPLING``, or the
+        ``model.Model`` wrapper around one)."""
+        net = model.model if hasattr(model, "model") and not hasattr(model, "sample_negatives") else model
+        if not getattr(type(net), "CATALOGUE_SAMPLING", False):
+            raise ValueError("ClickFeed.attach_scorer: %s cannot sample negatives from its catalogue scores (no CATALOGUE_SAMPLING)"
+                             % type(net).__module__)
+        self._scorer = net
+
+    def _draw_adaptive(self, seed):
+        """The adaptive draw of this rank's rows [row0, row0 + n) into ``packed``; returns the device count of empty slots."""
+        import inspect
+        net = self._scorer
+        if net is None:
+            raise RuntimeError("ClickFeed: negatives='adaptive' needs attach_scorer(model) before the first epoch")
+        needs_info = 'categ' in inspect.signature(net.encode_catalogue).parameters           # nrms_naml's feature rows
+        catalogue = net.encode_catalogue(self.titles, **(self.news_info() if needs_info else {}))
+        p, S = self.packed, self.S - 1
+        short = torch.zeros((), dtype=torch.int64, device=self.device)
+        for c0 in range(self.row0, self.row0 + self.n, self.draw_chunk):
+            c1 = min(self.row0 + self.n, c0 + self.draw_chunk)
+            rows = torch.arange(c0, c1, device=self.device)
+            # the user's training-part clicks (they contain the positive), padded with -1 to the chunk's longest set
+            width = max(int(self._row_set_len[c0:c1].max()), 1)
+            user = self.row_user[c0:c1].long()
+            first, count = self.set_ptr[user], self.set_ptr[user + 1] - self.set_ptr[user]
+            j = torch.arange(width, device=self.device)[None, :]
+            at = (first[:, None] + j).clamp_(max=max(self.set_news.numel() - 1, 0))
+            exclude = torch.where(j < count[:, None], self._set_news_arg[at].long(), torch.full_like(at, -1))
+            ids = net.sample_negatives({"browsed_ids": self._rows_of("hist", rows)}, self.row_key[c0:c1], S, catalogue, self.temperature,
+                                       seed, exclude=exclude)
+            got = ids >= 0                                   # the valued slots come first: the kernel pads at the end
+            p["cand"][c0:c1, 0] = self.row_pos[c0:c1].long()
+            p["cand"][c0:c1, 1:] = torch.where(got, ids, torch.zeros_like(ids))
+            p["clen"][c0:c1] = 1 + got.sum(1)
+            short += (~got).sum()
+        return short
+
     def draw(self, seed):
         """Refill the candidate side with the draw of ``seed`` (one ``nrms_catalogue_negative_sample`` call and two table look-ups on
-        the feed's stream); raises if the library counted a row it could not sample; ``n_short`` = the slots left empty."""
+        the feed's stream); raises if the library counted a row it could not sample; ``n_short`` = the slots left empty.
+        ``negatives="adaptive"``: the catalogue encode and, per chunk of rows, the user encoder and ``nrms_softmax_sample_dot``."""
         import ctypes as C
         from . import _lib
         if self.device.type != "cuda":
             raise _lib.NrmsError("ClickFeed: the feed is on %s; negatives are sampled on a GPU (there is no CPU path)" % self.device)
+        if self.negatives == "adaptive":
+            short = self._draw_adaptive(seed)
+            if self._categ is not None:
+                flat = self.packed["cand"].reshape(-1)
+                torch.index_select(self._categ[0], 0, flat, out=self.packed["ccat"].view(-1))
+                torch.index_select(self._categ[1], 0, flat, out=self.packed["csub"].view(-1))
+            # (the histories are the feed's own checked clicks, so the model's count of ids outside the catalogue stays untouched)
+            self.n_short = int(short.item())                                         # the epoch's one host synchronisation
+            self.drawn_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            return
         lib = _lib.load()
         S, n = self.S - 1, self.n_samples
         need = int(lib.nrms_catalogue_negative_sample_workspace_bytes(C.c_int64(n), C.c_int64(self.n_news), S))

@@ -782,6 +782,48 @@ class NRMSEngine:
         _lib.check(rc, "nrms_topk_dot")
         return scores, ids
 
+    def softmax_sample(self, user_vec, items, row_key, S, inv_temperature, seed, exclude=None, return_keys=False):
+        """user_vec [B, d], items [N, d] fp32, row_key [B] int64 in [0, 2^48), exclude [B, n_exclude] int64 or None (device,
+        contiguous) -> ids [B, S] int64 (with return_keys also the perturbed keys [B, S] fp32): per user S items drawn without
+        replacement from softmax(user . item * inv_temperature) over the eligible items, in Plackett-Luce order, no [B, N]
+        matrix (nrms_softmax_sample_dot: Gumbel-top-S on top_k's kernels).  The draw of a row is a function of (its user
+        vector, items, row key, inv_temperature, seed, its exclude list) only; rows with fewer than S eligible items end in
+        id -1 / key -inf.  inv_temperature 0 is the uniform draw.  include/nrms_hip.h states the contract."""
+        S = int(S)
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        for name, t, dt, nd in (("user_vec", user_vec, torch.float32, 2), ("items", items, torch.float32, 2), ("row_key", row_key, torch.int64, 1)):
+            if t.dim() != nd or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NrmsError("softmax_sample: %s must be a contiguous %d-D %s tensor on %s (got %s %s on %s%s)"
+                                     % (name, nd, dt, self.device, tuple(t.shape), t.dtype, t.device,
+                                        "" if t.is_contiguous() else ", not contiguous"))
+        B, d = user_vec.shape
+        N = items.shape[0]
+        if items.shape[1] != d:
+            raise _lib.NrmsError("softmax_sample: items width %d != user_vec width %d" % (items.shape[1], d))
+        if row_key.shape[0] != B:
+            raise _lib.NrmsError("softmax_sample: row_key must be [%d] (got %s)" % (B, tuple(row_key.shape)))
+        n_ex = 0
+        if exclude is not None:
+            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
+                    or not exclude.is_contiguous()):
+                raise _lib.NrmsError("softmax_sample: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
+                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
+            n_ex = exclude.shape[1]
+            if n_ex == 0:
+                exclude = None
+        nbytes = self.lib.nrms_softmax_sample_dot_workspace_bytes(B, N, d, S, n_ex)
+        if nbytes == 0:
+            raise _lib.NrmsError("softmax_sample: arguments rejected (B=%d, N=%d, d=%d, S=%d; 1 <= S <= 256)" % (B, N, d, S))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        ids = torch.empty(B, S, dtype=torch.int64, device=self.device)
+        keys = torch.empty(B, S, dtype=torch.float32, device=self.device) if return_keys else None
+        rc = self.lib.nrms_softmax_sample_dot(B, C.c_int64(N), d, S, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(row_key),
+                                              C.c_float(float(inv_temperature)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                              _lib.ptr(exclude), n_ex, _lib.ptr(ids), _lib.ptr(keys), _lib.ptr(ws),
+                                              C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_softmax_sample_dot")
+        return (ids, keys) if return_keys else ids
+
     def rank_of(self, user_vec, items, targets, exclude=None):
         """user_vec [B, d], items [N, d] fp32, targets [B, T] int64, exclude [B, n_exclude] int64 or None (device, contiguous)
         -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position of every target in top_k's order over the

@@ -213,6 +213,7 @@ class Model(FlatHipModel):
         return self._engine.encode_titles(self._flat, nrms_hip._ids_on(dev, titles), tag="news_eval")
 
     CATALOGUE_RANKING = False
+    CATALOGUE_SAMPLING = False          # the catalogue score is not one dot product per user: no sample_negatives
 
     def rank_targets(self, batch, targets, catalogue, exclude_history=True):
         raise NotImplementedError("graph: rank_targets is not available: a candidate's score depends on its neighbours in the "

@@ -336,6 +336,7 @@ class Model(FlatHipModel):
     _bad_browsed = None
     check_recommend_ids = nrms_hip.Model.check_recommend_ids
     CATALOGUE_RANKING = False
+    CATALOGUE_SAMPLING = False          # the catalogue score is not one dot product per user: no sample_negatives
 
     def rank_targets(self, batch, targets, catalogue, exclude_history=True):
         raise NotImplementedError("hierec: rank_targets is not available: HieRec scores the catalogue with a query per (topic, "

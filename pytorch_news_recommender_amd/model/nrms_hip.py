@@ -200,6 +200,31 @@ class Model(FlatHipModel):
         # rows 1.. as in recommend: news id n is row n - 1, so id 0 (and -1) fall out of range and get rank 0
         return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude)
 
+    @torch.no_grad()
+    def sample_negatives(self, batch, row_key, S, catalogue, temperature, seed, exclude=None):
+        """S negatives per user of ``batch`` drawn from the model's own softmax over the whole catalogue -> news ids [B, S]
+        int64, -1 in an empty slot: a draw without replacement from softmax(score / temperature) over the eligible news, in
+        Plackett-Luce order (slot 0 a draw from the softmax, slot 1 a draw from the rest, ...; include/nrms_hip.h
+        nrms_softmax_sample_dot).  temperature > 0: large values approach the uniform draw, small ones "the S hardest".
+
+        The user vector, the catalogue (encode_catalogue), the id-0 convention and the counting of bad ``browsed_ids`` are
+        recommend's.  row_key [B] int64 in [0, 2^48) names each row's draw (e.g. the click's position in its log): a row's
+        negatives are a function of (the weights, its history, its key, temperature, seed, its exclude list) only, whatever
+        else is in the batch.  exclude [B, n] news ids padded with -1: news the user must not get (ClickFeed: the user's own
+        clicks, which contain the positive); None: the browsed ids.  News id 0, the padding title, is never drawn."""
+        if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
+            raise _lib.NrmsError("sample_negatives: temperature must be finite and > 0 (got %r)" % (temperature,))
+        user, cat, browsed_rows = self._catalogue_query(batch, catalogue, exclude is None, "sample_negatives")
+        dev = user.device
+        if exclude is not None:
+            ex = torch.as_tensor(exclude).to(dev, dtype=torch.int64)
+            if ex.dim() != 2 or ex.shape[0] != user.shape[0]:
+                raise _lib.NrmsError("sample_negatives: exclude must be [%d, n] news ids (got %s)" % (user.shape[0], tuple(ex.shape)))
+            browsed_rows = (ex - 1).contiguous()          # rows 1.. as in recommend: -1 and id 0 fall out of range
+        key = torch.as_tensor(row_key).to(dev, dtype=torch.int64).contiguous()
+        ids = self._engine.softmax_sample(user, cat[1:], key, S, 1.0 / float(temperature), seed, browsed_rows)
+        return torch.where(ids >= 0, ids + 1, ids)
+
     def _catalogue_query(self, batch, catalogue, exclude_history, who):
         """What recommend and rank_targets share: (user vectors [B, width], the checked catalogue, the exclude list in
         the kernel's row numbering or None)."""
@@ -239,6 +264,7 @@ class Model(FlatHipModel):
     _bad_browsed = None
     CATALOGUE_RETRIEVAL = True          # recommend / encode_catalogue are available (run_v0 --recommend checks this)
     CATALOGUE_RANKING = True            # the catalogue score is a plain dot product: rank_targets (run_v0 --retrieval_metrics)
+    CATALOGUE_SAMPLING = True           # ... so negatives can be drawn from its softmax: sample_negatives (run_v0 --negatives adaptive)
 
     def check_recommend_ids(self):
         """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read

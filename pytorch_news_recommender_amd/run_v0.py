@@ -60,12 +60,15 @@ def build_parser():
     parser.add_argument('--graph', type=str, default='induced', choices=('induced', 'global'), help="--model graph: where a news "
                         "slot's neighbours come from.  induced: the click graph of the batch itself (host sampler); global: the "
                         "click graph of the whole training feed, resident in HBM, sampled by the HIP sampler (needs --feed device)")
-    parser.add_argument('--negatives', type=str, default='fixed', choices=('fixed', 'epoch', 'catalogue'), help="where a training row's "
+    parser.add_argument('--negatives', type=str, default='fixed', choices=('fixed', 'epoch', 'catalogue', 'adaptive'), help="where a training row's "
                         "negatives come from.  fixed: drawn once, with the data set (the reference's offline preprocessing); epoch: redrawn "
                         "at the start of every epoch from the impression's own non-clicked news, on the device (ImpressionFeed); "
                         "catalogue: training on a click log without impressions, the negatives redrawn every epoch from the whole "
-                        "catalogue by smoothed popularity, on the device (ClickFeed).  epoch and catalogue need --dataset synthetic "
-                        "and --feed device")
+                        "catalogue by smoothed popularity, on the device (ClickFeed); adaptive: the same click log, the negatives redrawn "
+                        "every epoch from the model's own softmax over the catalogue (hard negatives; models whose catalogue score is a "
+                        "plain dot product).  epoch, catalogue and adaptive need --dataset synthetic and --feed device")
+    parser.add_argument('--negative_temperature', type=float, default=1.0, metavar='T', help='--negatives adaptive: a news is drawn with '
+                        'probability softmax(score / T); T > 0, large T approaches the uniform draw, small T the hardest negatives')
     parser.add_argument('--negative_power', type=float, default=0.75, metavar='P', help='--negatives catalogue: a news is drawn with '
                         'weight (number of users who clicked it) ** P; 0 = uniform over the catalogue')
     parser.add_argument('--loss', type=str, default='rowwise', choices=('rowwise', 'pooled'), help="the training loss.  rowwise: each user "
@@ -124,22 +127,35 @@ def check_graph_args(args):
 
 
 def check_negatives_args(args):
-    """--negatives epoch / catalogue fail before any data is read: impressions with labels, or a click log, to train on exist for the
-    synthetic corpus only (reading MIND's behaviors.tsv is out of scope), the log lives in the device feed, and --test trains
-    nothing."""
-    if args.negatives == 'catalogue':
+    """--negatives epoch / catalogue / adaptive fail before any data is read: impressions with labels, or a click log, to train on
+    exist for the synthetic corpus only (reading MIND's behaviors.tsv is out of scope), the log lives in the device feed, and --test
+    trains nothing.  adaptive also needs a model that can sample from its catalogue scores, and no logQ correction."""
+    if args.negatives in ('catalogue', 'adaptive'):
+        flag = '--negatives ' + args.negatives
         if args.dataset != 'synthetic':
-            raise SystemExit('--negatives catalogue: a click log exists for --dataset synthetic only (got %r: its pickles hold '
-                             'negatives that were drawn offline)' % args.dataset)
+            raise SystemExit('%s: a click log exists for --dataset synthetic only (got %r: its pickles hold '
+                             'negatives that were drawn offline)' % (flag, args.dataset))
         if args.feed != 'device':
-            raise SystemExit('--negatives catalogue: the click log is sampled in the device feed (--feed device)')
+            raise SystemExit('%s: the click log is sampled in the device feed (--feed device)' % flag)
         if args.test:
-            raise SystemExit('--negatives catalogue: --test trains nothing')
+            raise SystemExit('%s: --test trains nothing' % flag)
         if not args.negative_power >= 0.0:
             raise SystemExit('--negative_power P: P must be >= 0 (got %r)' % args.negative_power)
         if args.graph == 'global':
-            raise SystemExit('--negatives catalogue: --graph global builds its click graph from history rows, which a click log does '
-                             'not keep')
+            raise SystemExit('%s: --graph global builds its click graph from history rows, which a click log does '
+                             'not keep' % flag)
+        if args.negatives == 'adaptive':
+            if not (args.negative_temperature > 0.0 and np.isfinite(args.negative_temperature)):
+                raise SystemExit('--negative_temperature T: T must be finite and > 0 (got %r)' % args.negative_temperature)
+            from .model import ALIASES
+            name = args.model.lower()
+            module = import_module('.model.' + ALIASES.get(name, name), __package__)
+            if not getattr(module.Model, 'CATALOGUE_SAMPLING', False):
+                raise SystemExit('--negatives adaptive: model %r cannot sample negatives from its catalogue scores (its catalogue '
+                                 'score is no plain dot product)' % args.model)
+            if args.loss == 'pooled' and not args.no_logq:
+                raise SystemExit('--negatives adaptive with --loss pooled: an adaptive draw has no fixed log q to correct by '
+                                 '(give --no_logq)')
         return
     if args.negatives != 'epoch':
         return
@@ -210,7 +226,7 @@ def main(argv=None):
         dev_samples, dev_labels = corpus.eval_samples(1024)
         if args.negatives == 'epoch':
             train_imps, train_imp_labels = corpus.train_impressions(args.synthetic_users)
-        if args.negatives == 'catalogue':
+        if args.negatives in ('catalogue', 'adaptive'):
             click_ptr, click_ids = corpus.click_log(args.synthetic_users)
     else:
         if args.dataset == 'demo':
@@ -273,12 +289,17 @@ def main(argv=None):
             train_feed = ImpressionFeed(config, train_imps, train_imp_labels, id2title_dict=titles, id2abst_dict=absts,
                                         batch_size=config.batch_size, device=config.device, shuffle=True, drop_last=world > 1, seed=422,
                                         rank=rank, world=world)
-        elif args.negatives == 'catalogue':
+        elif args.negatives in ('catalogue', 'adaptive'):
             # as above: every rank holds the whole click log and the draw of a click depends on its position in the log only
+            # (adaptive: and on the weights, which the ranks share)
             train_feed = ClickFeed(config, click_ptr, click_ids, id2title_dict=titles, id2abst_dict=absts,
                                    news_categ=np.concatenate([[0], corpus.category]), news_subcateg=np.concatenate([[0], corpus.subcategory]),
                                    popularity_power=args.negative_power, batch_size=config.batch_size, device=config.device, shuffle=True,
-                                   drop_last=world > 1, seed=422, rank=rank, world=world)
+                                   drop_last=world > 1, seed=422, rank=rank, world=world,
+                                   negatives='adaptive' if args.negatives == 'adaptive' else 'popularity',
+                                   temperature=args.negative_temperature)
+            if args.negatives == 'adaptive':
+                train_feed.attach_scorer(recommender)
             held_samples, held_labels = train_feed.heldout_samples()
         else:
             train_feed = loader(train_samples, 0, True)
@@ -297,10 +318,10 @@ def main(argv=None):
                 m = hist['metrics'][-1][1]
                 print('final dev AUC: {:.4f}  MRR: {:.4f}  nDCG@5: {:.4f}  nDCG@10: {:.4f}'.format(
                     m['auc'], m['mrr'], m['ndcg5'], m['ndcg10']))
-        if args.negatives == 'catalogue' and rank == 0:
+        if args.negatives in ('catalogue', 'adaptive') and rank == 0:
             print('click log: {} rows, {} slots left empty in the last draw'.format(train_feed.n_samples, train_feed.n_short))
         # a click log is evaluated on its own held-out clicks (each user's last one) against the whole catalogue
-        top_samples, top_labels = (held_samples, held_labels) if args.negatives == 'catalogue' else (dev_samples, dev_labels)
+        top_samples, top_labels = (held_samples, held_labels) if args.negatives in ('catalogue', 'adaptive') else (dev_samples, dev_labels)
         if args.recommend is not None and rank == 0:
             print('recommendations saved to', recommend_top(top_samples))
         if retrieval_ks is not None and rank == 0:
