@@ -129,6 +129,18 @@ CASES = {
 }
 
 
+def score_bar(fp16, scale):
+    """Scores against the oracle (scale = max |oracle score| over the live candidates); tests/history.py imports it."""
+    return (2e-4 if fp16 else 2e-5) * max(1.0, scale)
+
+
+def grad_bound(ref, fp16, gscale):
+    """Element-wise bound of |gradient - oracle| for one tensor (gscale: the largest oracle gradient outside the word table)."""
+    rel = 2e-2 if fp16 else 1e-3
+    # (d(W_K.bias) is identically zero in exact arithmetic -- softmax is shift-invariant -- so its bound is the noise term)
+    return rel * np.abs(ref) + (rel * 0.5) * float(np.abs(ref).max()) + (1e-4 if fp16 else 2e-6) * gscale + 1e-9
+
+
 def _oracle(params, batch, heads, dscores):
     from oracle import nrms_oracle as orc
     from oracle import segpool_oracle as so
@@ -161,7 +173,7 @@ def test_scores_and_every_gradient_against_the_oracle(case, precision):
     scale = float(np.abs(o_scores[live]).max())
     fp16 = precision == "fp16"
     print("hierec %-24s %-6s scores err %.2e (scale %.2f)" % (case, precision, err, scale))
-    assert err <= (2e-4 if fp16 else 2e-5) * max(1.0, scale)
+    assert err <= score_bar(fp16, scale)
     named = dict(model.named_parameters())
     gscale = max(float(np.abs(g).max()) for k, g in o_grads.items() if not k.endswith("word_embedding.0.weight"))
     for n, ref in o_grads.items():
@@ -171,9 +183,7 @@ def test_scores_and_every_gradient_against_the_oracle(case, precision):
             g = g.copy()
             ref[0] = 0
             g[0] = 0
-        rel = 2e-2 if fp16 else 1e-3
-        # (d(W_K.bias) is identically zero in exact arithmetic -- softmax is shift-invariant -- so its bound is the noise term)
-        bound = rel * np.abs(ref) + (rel * 0.5) * float(np.abs(ref).max()) + (1e-4 if fp16 else 2e-6) * gscale + 1e-9
+        bound = grad_bound(ref, fp16, gscale)
         bad = float((np.abs(g - ref) - bound).max())
         print("      %-58s err %.2e  scale %.2e" % (n, float(np.abs(g - ref).max()), float(np.abs(ref).max())))
         assert bad <= 0.0, (case, precision, n, float(np.abs(g - ref).max()), float(np.abs(ref).max()))
