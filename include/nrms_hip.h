@@ -463,6 +463,53 @@ int nrms_softmax_sample_dot(int32_t B, int64_t N, int32_t d, int32_t S, const fl
 int nrms_softmax_sample_noise(int32_t B, int64_t N, const int64_t* row_key /* [B] */, uint64_t seed,
                               uint32_t* words /* [B, N], nullable */, float* gumbel /* [B, N], nullable */, void* stream);
 
+/* ---- Diversified re-ranking of a shortlist (csrc/mmr.hip; serving: "which k of these M candidates, so that the list is not k
+ * articles about one story?"; PARITY UNPINNED, the reference has no such step) ----
+ * For each user b < B: k entries of the row's shortlist, picked greedily by maximal marginal relevance (Carbonell & Goldstein),
+ * and the intra-list diversity of the picks.  items [N, d] fp32 row-major (the catalogue); short_ids [B, M] int64 and
+ * short_scores [B, M] fp32: the shortlist, e.g. nrms_topk_dot's output at k = M; out_ids [B, k] int64, out_scores [B, k] fp32,
+ * out_value [B, k] fp32 (nullable), ild [B] fp32 (nullable).
+ * Entries.  Entry i of row b is VALID if 0 <= short_ids[b, i] < N and short_scores[b, i] is finite.  Everything else is padding
+ *   and is never selected: nrms_topk_dot's -1 / -inf tail, NaN and +-inf scores, ids outside the catalogue.  No id outside
+ *   [0, N) is dereferenced.  An id that occurs twice makes two separate entries (their similarity is that of a row with itself).
+ * Relevance, over the row's valid entries, in fp32: s_min and s_max are their smallest and largest score;
+ *   rel_i = (s_i - s_min) / (s_max - s_min): one subtraction each and one IEEE division; rel_i = 0 for every i when
+ *   s_max == s_min (-0.0 equals +0.0).
+ * Similarity.  dot(i, j) is one fp32 accumulator over all of d on v_mfma_f32_32x32x2_f32 (k order 32m, 32m+16, 32m+1, 32m+17, ...
+ *   in each whole block of 32, then 8g, 8g+4, 8g+1, ... in zero-padded groups of 8 for the rest), the same chain for every pair;
+ *   r_i = 1 / sqrt(dot(i, i)), a correctly rounded square root and division, or 0 when dot(i, i) is 0 or not finite;
+ *   cos(i, j) = dot(i, j) * (r_i * r_j), two roundings.  cos(i, j) and cos(j, i) have the same bits, and the value depends on the
+ *   contents of the two item rows only (a zero row has cosine 0 with everything, itself included).
+ * Greedy selection, for t = 0 .. k - 1: among the valid entries not picked yet, the one of largest
+ *     v_i = (lambda * rel_i) - (c * maxsim_i),   c = 1 - lambda:
+ *   one fp32 subtraction for c, two multiplications and one subtraction for v_i, nothing fused.  maxsim_i is 0 at t = 0 and
+ *   afterwards the maximum of cos(i, p) over the entries p picked so far, formed in pick order by fmaxf (which skips a NaN
+ *   cosine; only non-finite item rows or an overflowing dot make one).
+ *   Order: v descending, -0.0 equals +0.0; equal v puts the SMALLER shortlist position first; a NaN v orders after every number.
+ * Output.  Row b holds the min(k, #valid) picks in pick order: out_ids the id, out_scores the entry's short_scores bits,
+ *   out_value v at the moment of the pick; the remaining slots hold -1 / -inf / -inf.
+ * ILD.  ild[b] = 1 - (sum of cos over the unordered pairs of picks) / (number of pairs), NaN with fewer than two picks: one fp32
+ *   accumulator from 0 over the pairs (p_u, p_t), t = 1, 2, ... and within t u = 0 .. t - 1 (pick order), one division, one
+ *   subtraction.
+ * Consequences.  lambda = 1 returns the valid entries in the order (score descending, then position): for a shortlist whose
+ *   valid scores do not increase (nrms_topk_dot's) that is its first k valid entries in shortlist order, ids and score bits.
+ *   Row b's result is a function of (its shortlist, the item rows it names, lambda, k) only: not of B, the row's position, N,
+ *   what the workspace held, or the run.
+ * Limits: 1 <= k <= M <= 256, d >= 1, 0 <= lambda <= 1, B >= 0, N >= 0; B = 0 is a no-op, N = 0 writes all-padding rows.
+ *   Arguments outside the limits return NRMS_EINVAL with a message naming the argument.
+ * Workspace: nrms_mmr_rerank_workspace_bytes(B, M, d, k) bytes, 16-byte aligned (0 = arguments rejected): the dot products
+ *   [B, Mp, Mp] fp32, Mp = M rounded up to 64, so 256 KiB per user at M = 256; callers that must bound it split B (a row does
+ *   not depend on B).
+ * Two kernels on `stream` (the first once per 32 768 users), no host synchronisation, no allocation; plain vector stores only, no
+ *   atomics: two runs are bit-identical whatever the workspace held. */
+size_t nrms_mmr_rerank_workspace_bytes(int32_t B, int32_t M, int32_t d, int32_t k);
+int nrms_mmr_rerank(int32_t B, int32_t M, int32_t d, int32_t k, int64_t N, float lambda,
+                    const float* items /* [N, d] */, const int64_t* short_ids /* [B, M] */,
+                    const float* short_scores /* [B, M] */,
+                    int64_t* out_ids /* [B, k] */, float* out_scores /* [B, k] */,
+                    float* out_value /* [B, k], nullable */, float* ild /* [B], nullable */,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- nrms_naml pieces around the two encoder passes (model/nrms_naml.py) ----
  * LayerNorm over the last dimension (nn.LayerNorm(news_feature_size) on the history vectors, nrms_naml.py:207,238):
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance.  stats [n_rows, 2] = (mean, 1/std) is written when

@@ -824,6 +824,55 @@ class NRMSEngine:
         _lib.check(rc, "nrms_softmax_sample_dot")
         return (ids, keys) if return_keys else ids
 
+    MMR_WORKSPACE_CAP = 256 << 20       # bytes of Gram workspace per nrms_mmr_rerank call: larger batches go in row chunks
+
+    def mmr_rerank(self, items, short_ids, short_scores, k, lam, return_value=False, return_ild=False):
+        """items [N, d] fp32, short_ids [B, M] int64, short_scores [B, M] fp32 (device, contiguous; e.g. top_k's output at
+        k = M) -> (ids [B, k] int64, scores [B, k] fp32), then with return_value the value v of every pick [B, k] fp32 and with
+        return_ild the intra-list diversity [B] fp32: per user k entries of the shortlist picked greedily by maximal marginal
+        relevance, v = lam * rel - (1 - lam) * (largest cosine to the picks so far) (nrms_mmr_rerank).  Entries whose id is
+        outside [0, N) or whose score is not finite are padding and are never picked; rows with fewer than k valid entries
+        end in id -1 / score -inf / value -inf; the ILD of fewer than two picks is NaN.  lam = 1 keeps a sorted shortlist's
+        order.  A row's result does not depend on the rest of the batch, so batches whose workspace would pass
+        MMR_WORKSPACE_CAP go in row chunks.  include/nrms_hip.h states the contract."""
+        k, lam = int(k), float(lam)
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        for name, t, dt in (("items", items, torch.float32), ("short_ids", short_ids, torch.int64),
+                            ("short_scores", short_scores, torch.float32)):
+            if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NrmsError("mmr_rerank: %s must be a contiguous 2-D %s tensor on %s (got %s %s on %s%s)"
+                                     % (name, dt, self.device, tuple(t.shape), t.dtype, t.device,
+                                        "" if t.is_contiguous() else ", not contiguous"))
+        N, d = items.shape
+        B, M = short_ids.shape
+        if short_scores.shape != short_ids.shape:
+            raise _lib.NrmsError("mmr_rerank: short_scores must be [%d, %d] like short_ids (got %s)" % (B, M, tuple(short_scores.shape)))
+        if not 0.0 <= lam <= 1.0:
+            raise _lib.NrmsError("mmr_rerank: lam must be in [0, 1] (got %r)" % (lam,))
+        per_row = self.lib.nrms_mmr_rerank_workspace_bytes(1, M, d, k)
+        if per_row == 0:
+            raise _lib.NrmsError("mmr_rerank: arguments rejected (B=%d, M=%d, d=%d, k=%d; 1 <= k <= M <= 256, d >= 1)" % (B, M, d, k))
+        chunk = max(1, self.MMR_WORKSPACE_CAP // per_row)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        value = torch.empty(B, k, dtype=torch.float32, device=self.device) if return_value else None
+        ild = torch.empty(B, dtype=torch.float32, device=self.device) if return_ild else None
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            nbytes = self.lib.nrms_mmr_rerank_workspace_bytes(nb, M, d, k)
+            ws = self._buf("mmr_ws", (nbytes + 7) // 8, torch.int64)
+            part = lambda t: None if t is None else t[b0:b0 + nb]
+            rc = self.lib.nrms_mmr_rerank(nb, M, d, k, C.c_int64(N), C.c_float(lam), _lib.ptr(items), _lib.ptr(short_ids[b0:b0 + nb]),
+                                          _lib.ptr(short_scores[b0:b0 + nb]), _lib.ptr(ids[b0:b0 + nb]), _lib.ptr(scores[b0:b0 + nb]),
+                                          _lib.ptr(part(value)), _lib.ptr(part(ild)), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_mmr_rerank")
+        out = (ids, scores)
+        if return_value:
+            out += (value,)
+        if return_ild:
+            out += (ild,)
+        return out
+
     def rank_of(self, user_vec, items, targets, exclude=None):
         """user_vec [B, d], items [N, d] fp32, targets [B, T] int64, exclude [B, n_exclude] int64 or None (device, contiguous)
         -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position of every target in top_k's order over the

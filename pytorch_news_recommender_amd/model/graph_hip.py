@@ -219,6 +219,14 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: rank_targets is not available: a candidate's score depends on its neighbours in the "
                                   "click graph, not on a catalogue row alone (no recommend either)")
 
+    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False):
+        if diversity is not None or shortlist is not None or return_ild:
+            raise _lib.NrmsError("graph: recommend has no diversity re-ranking (diversity / shortlist / return_ild): the model "
+                                 "cannot recommend from a catalogue at all, a candidate's score depends on its neighbours in the "
+                                 "click graph")
+        raise NotImplementedError("graph: recommend is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone")
+
     def attach_click_graph(self, graph, titles):
         """From now on a batch without ``neighbor_rows`` takes its neighbours from ``graph`` (click_graph.ClickGraph on the
         model's device) instead of the batch-induced host sampler; titles [graph.n_news, L]: the word ids of every news, row r =

@@ -169,7 +169,7 @@ class Model(FlatHipModel):
         return self._engine.encode_titles(self._flat, _ids_on(dev, titles), tag="news_eval")
 
     @torch.no_grad()
-    def recommend(self, batch, k, catalogue, exclude_history=True):
+    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False):
         """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores
         [B, k] fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_dot).
 
@@ -177,10 +177,34 @@ class Model(FlatHipModel):
         the user vector is encode_users over catalogue rows browsed_ids, the vectors forward_cached scores with (ids
         outside the catalogue are read as padding and counted: check_recommend_ids raises on them).  News
         id 0, the padding title, is never returned; with exclude_history neither is a browsed id.  A user with fewer
-        than k eligible news gets id -1 / score -inf in the remaining slots."""
+        than k eligible news gets id -1 / score -inf in the remaining slots.
+
+        diversity = lambda in [0, 1]: the list is re-ranked for diversity instead (include/nrms_hip.h nrms_mmr_rerank): the
+        ``shortlist`` best news (default min(256, 4 k); k <= shortlist <= 256) are retrieved as above and k of them are
+        picked greedily by maximal marginal relevance, lambda * (score scaled to [0, 1] over the shortlist) - (1 - lambda) *
+        (largest cosine between catalogue rows to the news picked so far), in pick order; the scores returned are still the
+        dot products.  lambda = 1 is the plain list, bit for bit.  return_ild appends the intra-list diversity [B] fp32 of the
+        returned list (1 - mean pairwise cosine of its catalogue rows, NaN with fewer than two news), from the same kernel
+        with or without ``diversity``."""
+        if diversity is None and shortlist is not None:
+            raise _lib.NrmsError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
+        if diversity is not None:
+            k, lam = int(k), float(diversity)
+            if not 0.0 <= lam <= 1.0:
+                raise _lib.NrmsError("recommend: diversity must be in [0, 1] (got %r)" % (diversity,))
+            M = min(256, 4 * k) if shortlist is None else int(shortlist)
+            if not 1 <= k <= M <= 256:
+                raise _lib.NrmsError("recommend: with diversity, 1 <= k <= shortlist <= 256 (k=%d, shortlist=%d)" % (k, M))
         user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend")
-        scores, ids = self._engine.top_k(user, cat[1:], k, exclude)
-        return torch.where(ids >= 0, ids + 1, ids), scores
+        if diversity is None:
+            scores, ids = self._engine.top_k(user, cat[1:], k, exclude)
+            out = (torch.where(ids >= 0, ids + 1, ids), scores)
+            if return_ild:      # the plain list's ILD is the re-ranker's at lambda = 1, which keeps the list as it is
+                out += (self._engine.mmr_rerank(cat[1:], ids, scores, ids.shape[1], 1.0, return_ild=True)[2],)
+            return out
+        s_scores, s_ids = self._engine.top_k(user, cat[1:], M, exclude)
+        res = self._engine.mmr_rerank(cat[1:], s_ids, s_scores, k, lam, return_ild=return_ild)
+        return (torch.where(res[0] >= 0, res[0] + 1, res[0]), res[1]) + tuple(res[2:])
 
     @torch.no_grad()
     def rank_targets(self, batch, targets, catalogue, exclude_history=True):

@@ -76,12 +76,33 @@ def build_parser():
                         "candidates of the whole batch (in-batch sampled softmax; with --negatives catalogue the scores are corrected by "
                         "the log of each news's probability of being in the pool)")
     parser.add_argument('--no_logq', action='store_true', help='--loss pooled: leave the log-probability correction out')
+    parser.add_argument('--diversity', type=float, default=None, metavar='LAMBDA', help='--recommend: re-rank the list for diversity by '
+                        'maximal marginal relevance over a shortlist, LAMBDA * relevance - (1 - LAMBDA) * largest cosine to the news '
+                        'picked so far (0 <= LAMBDA <= 1; 1 = the plain list), and print ILD@K and catalogue coverage of the plain '
+                        'and of the re-ranked list')
+    parser.add_argument('--shortlist', type=int, default=None, metavar='M', help='--diversity: the number of best news the re-ranking '
+                        'picks from (K <= M <= 256; default min(256, 4 K))')
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     return parser
 
 
 def check_recommend_args(args):
-    """--recommend fails before any data is read or any step is trained: K in [1, 256], a model that can recommend."""
+    """--recommend fails before any data is read or any step is trained: K in [1, 256], a model that can recommend; so do
+    --diversity (needs --recommend, 0 <= LAMBDA <= 1, a model that re-ranks) and --shortlist (needs --diversity, K <= M <= 256)."""
+    if args.diversity is not None:
+        if args.recommend is None:
+            raise SystemExit('--diversity LAMBDA: re-ranks the list of --recommend K (give --recommend)')
+        if not 0.0 <= args.diversity <= 1.0:
+            raise SystemExit('--diversity LAMBDA: LAMBDA must be in [0, 1] (got %r)' % args.diversity)
+        from .model import ALIASES
+        if ALIASES.get(args.model.lower(), args.model.lower()) in ('hierec_hip', 'graph_hip'):
+            raise SystemExit('--diversity: model %r has no diversity re-ranking (its catalogue score is no plain dot product over a '
+                             'row-ordered catalogue)' % args.model)
+    if args.shortlist is not None:
+        if args.diversity is None:
+            raise SystemExit('--shortlist M: the candidate count of --diversity (give --diversity)')
+        if not args.recommend <= args.shortlist <= 256:
+            raise SystemExit('--shortlist M: M must be in [K, 256] (got M=%d, K=%d)' % (args.shortlist, args.recommend))
     if args.recommend is None:
         return
     if not 1 <= args.recommend <= 256:
@@ -262,7 +283,18 @@ def main(argv=None):
         # the catalogue is the feed's title table (row r = news id r), so this step always runs on a DeviceFeed
         feed = DeviceFeed(config, samples, type=1, id2title_dict=titles, id2abst_dict=absts, batch_size=config.batch_size,
                           device=config.device)
-        return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out)
+        if args.diversity is None:
+            return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out)
+        # the plain list is the re-ranker's at lambda = 1 (bit for bit), which measures it with the same kernel
+        net = recommender.model if hasattr(recommender, 'model') else recommender
+        out = None
+        for name, lam, dst in (('plain', 1.0, os.devnull), ('diversity %g' % args.diversity, args.diversity, args.recommend_out)):
+            out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=dst, diversity=lam,
+                            shortlist=args.shortlist)
+            st = net.last_recommend_stats
+            print('{}: ILD@{}: {:.4f}  coverage: {:.4f}  users: {}'.format(name, args.recommend, st['ild'], st['coverage'],
+                                                                            st['n_users']))
+        return out
 
     def retrieval_quality(samples, labels):
         # as recommend_top: the catalogue is the feed's title table, so always a DeviceFeed

@@ -329,19 +329,49 @@ def test(config, model, data_iter, test_list_nums=None, ckpt_file=None, out_file
     return file_name
 
 
-def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None):
+def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
+              shortlist=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
     (``DeviceFeed.news_info()``), passed to encode_catalogue as keyword arguments.  With exclude_history the user's
     browsed news are left out.  Should the catalogue hold fewer than k eligible news for a user, the line is shorter.
-    Returns the file name."""
+    Returns the file name.
+
+    diversity / shortlist: ``model.recommend``'s re-ranking by maximal marginal relevance (the file format is the same, the
+    lines are in pick order).  With ``diversity`` given (models that re-rank) the call leaves
+    ``net.last_recommend_stats = {"ild": mean intra-list diversity over the users with at least two news, "coverage":
+    distinct recommended news / (N - 1), "n_users": those users}`` (NaN / 0 without such users), with one host
+    synchronisation at the end; without it the attribute is set to None and the model is called exactly as before."""
     net = _inner(model)
+    if diversity is None and shortlist is not None:
+        raise ValueError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
     lines = []
-    for datas in data_iter:
-        ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history)
-        lines.extend(ids.cpu().tolist())
+    if diversity is None:
+        net.last_recommend_stats = None
+        for datas in data_iter:
+            ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history)
+            lines.extend(ids.cpu().tolist())
+    else:
+        rows, ilds = [], []
+        for datas in data_iter:
+            ids, _, ild = net.recommend(datas, k, catalogue, exclude_history=exclude_history, diversity=diversity,
+                                        shortlist=shortlist, return_ild=True)
+            rows.append(ids)
+            ilds.append(ild)
+        n_news = int(catalogue.shape[0])
+        dev = catalogue.device
+        ids = torch.cat(rows) if rows else torch.zeros(0, int(k), dtype=torch.int64, device=dev)
+        ild = torch.cat(ilds).double() if ilds else torch.zeros(0, dtype=torch.float64, device=dev)
+        seen = torch.zeros(n_news + 1, dtype=torch.bool, device=dev)           # slot n_news takes the -1 padding
+        seen[torch.where(ids >= 0, ids, torch.full_like(ids, n_news)).reshape(-1)] = True
+        have = ~torch.isnan(ild)
+        stats = torch.stack([torch.where(have, ild, torch.zeros_like(ild)).sum() / have.sum().clamp(min=1),
+                             seen[1:n_news].sum().double() / max(1, n_news - 1), have.sum().double()]).cpu().tolist()
+        n_users = int(stats[2])                                                # (the one host synchronisation is above)
+        net.last_recommend_stats = {"ild": stats[0] if n_users else float("nan"), "coverage": stats[1], "n_users": n_users}
+        lines = ids.cpu().tolist()
     net.engine.check_ids()
     net.check_recommend_ids()
     file_name = out_file or 'recommend_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
