@@ -422,6 +422,41 @@ int nrms_rank_dot(int32_t B, int64_t N, int32_t d, int32_t T, const float* user,
                   const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ---- A per-item additive prior in retrieval and ranking (serving: popularity, freshness, editorial boosts, a global block-list;
+ * PARITY UNPINNED, the reference scores shown candidates only) ----
+ * nrms_topk_dot and nrms_rank_dot over s'(b, n) = s(b, n) + bias[n].  bias [N] fp32, 4-byte aligned, NULLABLE; every other
+ * argument is the unbiased call's.
+ * Score.  s(b, n) is nrms_topk_dot's chain, the same code and the same bits.  s'(b, n) is ONE fp32 addition, round to nearest,
+ *   of bias[n] to the finished accumulator; it is never folded into the chain.  top_scores and target_scores carry s'.
+ * Eligible: n is not in exclude[b, :] and s'(b, n) is not NaN.  A NaN bias[n] therefore removes item n for every user: this is
+ *   the global block-list, and it is part of the contract.  In ranking such a target gets rank 0 / score -inf, and such an
+ *   excluded id is taken out of nothing.  +inf + -inf is NaN and falls under the same rule.  A -inf bias leaves the item
+ *   eligible (unless s is +inf or NaN): it comes last, its score -inf, ties among such items by the smaller n.
+ * Everything else is the unbiased call's: order (s' descending, +inf first, equal s' put the SMALLER n first), -0.0 equals
+ *   +0.0 and is returned as +0.0 (the sum is not inspected before the entry is formed), padding (-1 / -inf), invalid targets,
+ *   limits, workspace alignment, and independence of B, the row's position, k, T, the launch geometry, what the workspace held
+ *   and the run.
+ * Consequences.  bias == NULL is the unbiased call, bit for bit (the same kernels are launched).  An all-zero bias gives the
+ *   same ids, ranks and score bits: s + 0.0 differs from s only for s = -0.0, which is returned as +0.0 anyway.  A bias that is
+ *   constant over n leaves ids and ranks as they are whenever the addition maps distinct scores to distinct sums and equal
+ *   scores to equal sums (always, when scores and the constant are exact in fp32 with an exact sum); rounding may otherwise
+ *   merge neighbouring scores into ties, which the id rule then decides.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_biased: ...", "rank_dot_biased: ...");
+ *   a bias that is not 4-byte aligned is one of them.
+ * Workspace: the _biased_workspace_bytes queries return exactly nrms_topk_dot_workspace_bytes(B, N, d, k) and
+ *   nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude) (0 = arguments rejected); 8-byte aligned.
+ * The same kernel counts as the unbiased calls, on `stream`, no host synchronisation, no allocation; plain vector loads and
+ *   stores, no atomics beyond the integer counters of the unbiased kernels. */
+size_t nrms_topk_dot_biased_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_biased(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                         const float* bias /* [N], nullable */, const int64_t* exclude, int32_t n_exclude, float* top_scores,
+                         int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+size_t nrms_rank_dot_biased_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude);
+int nrms_rank_dot_biased(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                         const float* bias /* [N], nullable */, const int64_t* targets, const int64_t* exclude,
+                         int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ---- Negatives from the model's own softmax over the whole catalogue (csrc/softmaxsample.hip; training: "which S news does the
  * model itself confuse with the positive right now?"; PARITY UNPINNED, the reference draws its negatives offline) ----
  * For each user b < B: S items drawn WITHOUT replacement from softmax(s(b, .) * inv_temperature) over the eligible items, never

@@ -15,6 +15,9 @@
 //   excluded id whose entry precedes the target's (first occurrence of an id only); targets that are excluded, out of range
 //   or NaN get rank 0 / score -inf.
 //
+// nrms_rank_dot_biased ranks by s'(b, n) = s(b, n) + bias[n] (one fp32 add on the finished accumulator): the BIAS instantiations
+// of A and B add bias[id] / bias[n] to the score just before tk_entry; C works on entries and is the same kernel.
+//
 // The chain is topk_slice_kernel's, restated in rk_chain (same operand staging, same k order, one accumulator):
 // tests/test_hip_rank.py pins the score bits to nrms_topk_dot's.
 #include "topk_entry.h"
@@ -98,12 +101,12 @@ __device__ __forceinline__ void rk_chain(tk_f32x16 (&acc)[TK_TN], const float* a
 // Kernel A.  One wave per block; block (x, y): user tile x, gathered positions 64 (y + i gridDim.y) .. + 63 of the tile's list
 // of 32 M ids, M = T + n_exclude: position g is list slot m = g % M of user u0 + g / M (slots [0, T): targets, then the
 // exclude ids).  ent [B, M].  Blocks y = 0 also zero the tile's counts [B, T] for kernel B.  Needs N >= 1.
-template <bool VEC>
+template <bool VEC, bool BIAS>
 __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, int T, int n_exclude,
                                                           const float* __restrict__ user, const float* __restrict__ items,
                                                           const int64_t* __restrict__ targets,
                                                           const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
-                                                          uint32_t* __restrict__ counts) {
+                                                          uint32_t* __restrict__ counts, const float* __restrict__ bias) {
     __shared__ int rows[64];
     __shared__ __attribute__((aligned(16))) float stage[64 * TK_BP];
     const int lane = threadIdx.x;
@@ -144,6 +147,9 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
             float s = 0.0f;
 #pragma unroll
             for (int q = 0; q < 16; ++q) s = q == qw ? acc[c][q] : s;
+            if constexpr (BIAS) {
+                if (idc >= 0 && idc < N) s = s + bias[idc];
+            }
             const bool ok = idc >= 0 && idc < N && !__builtin_isnan(s);
             ent[(long)(u0 + uc) * M + mc] = ok ? tk_entry(s, (uint32_t)idc) : 0;
         }
@@ -152,10 +158,11 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
 
 // Kernel B.  Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step.  ent [B, M]:
 // the first T entries of a row are the user's targets.  counts [B, T] += #{live non-NaN n in the slice : entry(n) > target}.
-template <int W, bool VEC>
+template <int W, bool VEC, bool BIAS>
 __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d, int T, int M, int slice_len,
                                                             const float* __restrict__ user, const float* __restrict__ items,
-                                                            const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts) {
+                                                            const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts,
+                                                            const float* __restrict__ bias) {
     __shared__ uint64_t tgt[TK_UT][RK_MAX_T];
     __shared__ uint32_t cnts[TK_UT][RK_MAX_T];
     __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
@@ -183,6 +190,11 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
         tk_f32x16 acc[TK_TN];
 #pragma unroll
         for (int c = 0; c < TK_TN; ++c) acc[c] = tk_f32x16{};
+        float bv[BIAS ? TK_TN : 1] = {};          // BIAS: loaded ahead of the chain, which hides the latency; added after it
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) bv[c] = bias[min(nw + 32 * c + r, N - 1)];
+        }
         rk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
         // C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
         uint64_t e[TK_TN][16];
@@ -192,7 +204,8 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
             const bool live = n < n_end;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const float s = acc[c][q];
+                float s = acc[c][q];
+                if constexpr (BIAS) s = s + bv[c];
                 e[c][q] = (live && !__builtin_isnan(s)) ? tk_entry(s, (uint32_t)n) : 0;       // 0 precedes nothing
             }
         }
@@ -297,51 +310,90 @@ extern "C" size_t nrms_rank_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
     return 256 + rank_entry_bytes(B, T, n_exclude) + (size_t)B * (size_t)T * sizeof(uint32_t);
 }
 
-extern "C" int nrms_rank_dot(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
-                             const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
-                             float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
-    NRMS_REQUIRE(B >= 0, "rank_dot: B must be >= 0 (B=%d)", B);
-    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "rank_dot: N must be in [0, %d] (N=%lld)", TK_MAX_N, (long long)N);
-    NRMS_REQUIRE(d >= 1, "rank_dot: d must be >= 1 (d=%d)", d);
-    NRMS_REQUIRE(T >= 1 && T <= RK_MAX_T, "rank_dot: T must be in [1, %d] (T=%d)", RK_MAX_T, T);
-    NRMS_REQUIRE(n_exclude >= 0, "rank_dot: n_exclude must be >= 0 (n_exclude=%d)", n_exclude);
+// nrms_rank_dot (bias null, who "rank_dot") and nrms_rank_dot_biased: one body.
+static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                         const float* bias, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                         float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
+    NRMS_REQUIRE(B >= 0, "%s: B must be >= 0 (B=%d)", who, B);
+    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "%s: N must be in [0, %d] (N=%lld)", who, TK_MAX_N, (long long)N);
+    NRMS_REQUIRE(d >= 1, "%s: d must be >= 1 (d=%d)", who, d);
+    NRMS_REQUIRE(T >= 1 && T <= RK_MAX_T, "%s: T must be in [1, %d] (T=%d)", who, RK_MAX_T, T);
+    NRMS_REQUIRE(n_exclude >= 0, "%s: n_exclude must be >= 0 (n_exclude=%d)", who, n_exclude);
     if (B == 0) return NRMS_OK;
-    NRMS_REQUIRE(user, "rank_dot: user is null");
-    NRMS_REQUIRE(items || N == 0, "rank_dot: items is null");
-    NRMS_REQUIRE(targets, "rank_dot: targets is null");
-    NRMS_REQUIRE(ranks, "rank_dot: ranks is null");
-    NRMS_REQUIRE(workspace, "rank_dot: workspace is null");
+    NRMS_REQUIRE(user, "%s: user is null", who);
+    NRMS_REQUIRE(items || N == 0, "%s: items is null", who);
+    NRMS_REQUIRE(((uintptr_t)bias & 3) == 0, "%s: bias must be 4-byte aligned", who);
+    NRMS_REQUIRE(targets, "%s: targets is null", who);
+    NRMS_REQUIRE(ranks, "%s: ranks is null", who);
+    NRMS_REQUIRE(workspace, "%s: workspace is null", who);
     if (!exclude) n_exclude = 0;
     const size_t need = nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude);
     if (workspace_bytes < need) {
-        set_error("rank_dot: workspace %zu < required %zu bytes", workspace_bytes, need);
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
         return NRMS_EWORKSPACE;
     }
-    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "rank_dot: workspace must be 8-byte aligned");
+    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
-    TimingScope ts("rank_dot", s);
+    TimingScope ts(who, s);
     uint64_t* ent = (uint64_t*)workspace;
     uint32_t* counts = (uint32_t*)((char*)workspace + rank_entry_bytes(B, T, n_exclude));
     const RankGeom g = rank_geom(B, N);
     const int n = (int)N, M = T + n_exclude;
+    char what[64];
     if (g.S > 0) {
         const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
         const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64));
-        if (vec) hipLaunchKernelGGL(rank_entries_kernel<true>, grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
-                                    exclude, ent, counts);
-        else hipLaunchKernelGGL(rank_entries_kernel<false>, grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
-                                exclude, ent, counts);
-        int rc = check_launch("rank_dot(entries)");
+#define RK_LAUNCH_A(V, BI)                                                                                                 \
+    hipLaunchKernelGGL((rank_entries_kernel<V, BI>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets, exclude, \
+                       ent, counts, bias)
+        if (bias) {
+            if (vec) RK_LAUNCH_A(true, true);
+            else RK_LAUNCH_A(false, true);
+        } else {
+            if (vec) RK_LAUNCH_A(true, false);
+            else RK_LAUNCH_A(false, false);
+        }
+#undef RK_LAUNCH_A
+        snprintf(what, sizeof what, "%s(entries)", who);
+        int rc = check_launch(what);
         if (rc != NRMS_OK) return rc;
         const dim3 grid_b(g.tiles, g.S);
-        if (vec) hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, true>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M,
-                                    g.slice_len, user, items, ent, counts);
-        else hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, false>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M,
-                                g.slice_len, user, items, ent, counts);
-        rc = check_launch("rank_dot(count)");
+#define RK_LAUNCH_B(V, BI)                                                                                                 \
+    hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, V, BI>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M, g.slice_len, user, \
+                       items, ent, counts, bias)
+        if (bias) {
+            if (vec) RK_LAUNCH_B(true, true);
+            else RK_LAUNCH_B(false, true);
+        } else {
+            if (vec) RK_LAUNCH_B(true, false);
+            else RK_LAUNCH_B(false, false);
+        }
+#undef RK_LAUNCH_B
+        snprintf(what, sizeof what, "%s(count)", who);
+        rc = check_launch(what);
         if (rc != NRMS_OK) return rc;
     }
     hipLaunchKernelGGL(rank_finish_kernel, dim3(B), dim3(64), 0, s, B, n, T, n_exclude, targets, exclude, ent, counts, ranks,
                        target_scores);
-    return check_launch("rank_dot(finish)");
+    snprintf(what, sizeof what, "%s(finish)", who);
+    return check_launch(what);
+}
+
+extern "C" int nrms_rank_dot(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                             const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                             float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
+    return rank_dot_call("rank_dot", B, N, d, T, user, items, nullptr, targets, exclude, n_exclude, ranks, target_scores, workspace,
+                         workspace_bytes, stream);
+}
+
+// The biased call's workspace is the unbiased call's: the same entries and counts.
+extern "C" size_t nrms_rank_dot_biased_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude) {
+    return nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude);
+}
+
+extern "C" int nrms_rank_dot_biased(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                                    const float* bias, const int64_t* targets, const int64_t* exclude, int32_t n_exclude,
+                                    int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
+    return rank_dot_call("rank_dot_biased", B, N, d, T, user, items, bias, targets, exclude, n_exclude, ranks, target_scores,
+                         workspace, workspace_bytes, stream);
 }

@@ -18,6 +18,9 @@
 // group, is laid out in 32-row tiles that never straddle a group (each group padded to a whole number of tiles; the table is
 // written by topk_tiles_kernel into the workspace), so every MFMA column tile has one A operand, the tile's group's query
 // rows.  Scores keep the chain of nrms_topk_dot, and entries carry item_ids[row] instead of the row.
+//
+// nrms_topk_dot_biased runs the two kernels of nrms_topk_dot with a per-item prior added to every finished score (the BIAS
+// instantiations of topk_slice_kernel): entries carry s' = s + bias[n], everything after the add is the same code.
 #include "topk_kernels.h"    // the kernels and their launcher, shared with softmaxsample.hip
 
 namespace nrms {
@@ -79,31 +82,52 @@ extern "C" size_t nrms_topk_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
     return 256 + (size_t)B * (size_t)g.S * (size_t)k * sizeof(uint64_t);     // never 0 for accepted arguments
 }
 
+// nrms_topk_dot (bias null, who "topk_dot") and nrms_topk_dot_biased: one body, so the checks and the launch cannot drift apart.
+static int topk_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                         const float* bias, const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    NRMS_REQUIRE(B >= 0, "%s: B must be >= 0 (B=%d)", who, B);
+    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "%s: N must be in [0, %d] (N=%lld)", who, TK_MAX_N, (long long)N);
+    NRMS_REQUIRE(d >= 1, "%s: d must be >= 1 (d=%d)", who, d);
+    NRMS_REQUIRE(k >= 1 && k <= TK_MAX_K, "%s: k must be in [1, %d] (k=%d)", who, TK_MAX_K, k);
+    NRMS_REQUIRE(n_exclude >= 0, "%s: n_exclude must be >= 0 (n_exclude=%d)", who, n_exclude);
+    if (B == 0) return NRMS_OK;
+    NRMS_REQUIRE(user, "%s: user is null", who);
+    NRMS_REQUIRE(items || N == 0, "%s: items is null", who);
+    NRMS_REQUIRE(((uintptr_t)bias & 3) == 0, "%s: bias must be 4-byte aligned", who);
+    NRMS_REQUIRE(top_scores, "%s: top_scores is null", who);
+    NRMS_REQUIRE(top_ids, "%s: top_ids is null", who);
+    NRMS_REQUIRE(workspace, "%s: workspace is null", who);
+    const size_t need = nrms_topk_dot_workspace_bytes(B, N, d, k);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
+        return NRMS_EWORKSPACE;
+    }
+    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+    if (!exclude) n_exclude = 0;
+    hipStream_t s = (hipStream_t)stream;
+    TimingScope ts(who, s);
+    return topk_launch(false, B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids,
+                       (uint64_t*)workspace, s, who, TkNoise{nullptr, 0.0f, 0}, bias);
+}
+
 extern "C" int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
                              const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    NRMS_REQUIRE(B >= 0, "topk_dot: B must be >= 0 (B=%d)", B);
-    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "topk_dot: N must be in [0, %d] (N=%lld)", TK_MAX_N, (long long)N);
-    NRMS_REQUIRE(d >= 1, "topk_dot: d must be >= 1 (d=%d)", d);
-    NRMS_REQUIRE(k >= 1 && k <= TK_MAX_K, "topk_dot: k must be in [1, %d] (k=%d)", TK_MAX_K, k);
-    NRMS_REQUIRE(n_exclude >= 0, "topk_dot: n_exclude must be >= 0 (n_exclude=%d)", n_exclude);
-    if (B == 0) return NRMS_OK;
-    NRMS_REQUIRE(user, "topk_dot: user is null");
-    NRMS_REQUIRE(items || N == 0, "topk_dot: items is null");
-    NRMS_REQUIRE(top_scores, "topk_dot: top_scores is null");
-    NRMS_REQUIRE(top_ids, "topk_dot: top_ids is null");
-    NRMS_REQUIRE(workspace, "topk_dot: workspace is null");
-    const size_t need = nrms_topk_dot_workspace_bytes(B, N, d, k);
-    if (workspace_bytes < need) {
-        set_error("topk_dot: workspace %zu < required %zu bytes", workspace_bytes, need);
-        return NRMS_EWORKSPACE;
-    }
-    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "topk_dot: workspace must be 8-byte aligned");
-    if (!exclude) n_exclude = 0;
-    hipStream_t s = (hipStream_t)stream;
-    TimingScope ts("topk_dot", s);
-    return topk_launch(false, B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids,
-                       (uint64_t*)workspace, s, "topk_dot");
+    return topk_dot_call("topk_dot", B, N, d, k, user, items, nullptr, exclude, n_exclude, top_scores, top_ids, workspace,
+                         workspace_bytes, stream);
+}
+
+// The biased call's workspace is the unbiased call's: entries carry s' in the same slice lists.
+extern "C" size_t nrms_topk_dot_biased_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k) {
+    return nrms_topk_dot_workspace_bytes(B, N, d, k);
+}
+
+extern "C" int nrms_topk_dot_biased(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                                    const float* bias, const int64_t* exclude, int32_t n_exclude, float* top_scores,
+                                    int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    return topk_dot_call("topk_dot_biased", B, N, d, k, user, items, bias, exclude, n_exclude, top_scores, top_ids, workspace,
+                         workspace_bytes, stream);
 }
 
 extern "C" size_t nrms_topk_grouped_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G) {

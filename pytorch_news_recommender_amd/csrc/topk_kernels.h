@@ -142,14 +142,21 @@ __device__ inline void tk_drop_excluded(uint64_t* buf, int cnt, const int32_t* e
 //
 // NOISE (nrms_softmax_sample_dot): before the filter every accumulator element becomes its perturbed key
 // fmaf(score, inv_temperature, g(row key, item)); the block's 32 row seeds are formed once, in LDS.
-template <int P, int W, bool VEC, bool GROUPED, bool NOISE>
+//
+// BIAS (nrms_topk_dot_biased): lane (r, h) loads bias[n] of its item in each of its two column tiles (one coalesced 128-byte
+// read per tile, issued before the MFMA loop so that the loop hides its latency) and, before the filter, adds it to the tile's 16
+// finished accumulator registers: one fp32 add per score, after the chain, never folded into it.  A NaN sum fails the filter's
+// NaN test like a NaN score; entries simply carry s'.
+template <int P, int W, bool VEC, bool GROUPED, bool NOISE, bool BIAS>
 __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d, int k, int slice_len, int S,
                                                             const float* __restrict__ user, const float* __restrict__ items,
                                                             const int64_t* __restrict__ exclude, int n_exclude,
                                                             uint64_t* __restrict__ ws, int G, int n_tiles,
                                                             const TkTile* __restrict__ tiles,
-                                                            const int32_t* __restrict__ item_ids, TkNoise noise) {
+                                                            const int32_t* __restrict__ item_ids, TkNoise noise,
+                                                            const float* __restrict__ bias) {
     static_assert(!(NOISE && GROUPED), "the perturbation is keyed by the item's row");
+    static_assert(!(BIAS && (GROUPED || NOISE)), "the prior is for the plain top-k only");
     __shared__ uint64_t buf[TK_UT][P];
     __shared__ uint64_t rseed[NOISE ? TK_UT : 1];
     __shared__ uint64_t thr[TK_UT];
@@ -207,6 +214,13 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 trow[c] = __builtin_amdgcn_readfirstlane(tl.row);
                 tlen[c] = __builtin_amdgcn_readfirstlane(tl.len);
                 arow[c] = user + ((long)min(u0 + r, B - 1) * G + __builtin_amdgcn_readfirstlane(tl.grp)) * d;
+            }
+        }
+        float bv[BIAS ? TK_TN : 1] = {};          // BIAS: loaded here so that the MFMA loop hides the latency, added after it
+        if constexpr (BIAS) {
+            if (nw < n_end) {
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) bv[c] = bias[min(nw + 32 * c + r, N - 1)];
             }
         }
         if (nw < n_end && (!GROUPED || tlen[0] + tlen[1] > 0)) {
@@ -286,6 +300,14 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                     for (int c = 0; c < TK_TN; ++c)
                         acc[c][q] = __builtin_fmaf(acc[c][q], noise.inv_temperature, tk_gumbel(tk_noise_word(rs, (uint32_t)(nw + 32 * c + r))));
                 }
+            }
+        }
+        if constexpr (BIAS) {
+            if (nw < n_end) {
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c)
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) acc[c][q] = acc[c][q] + bv[c];
             }
         }
         // filter.  C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5).
@@ -405,30 +427,34 @@ static bool topk_args_ok(int32_t B, int64_t N, int32_t d, int32_t k) {
 }
 
 // Both kernels of one call.  grouped: `user` is the query [B, G, d], the slices run over the tile rows of `tiles`.
+// bias (plain top-k only, [N] fp32): non-null selects the BIAS instantiations.
 static int topk_launch(bool grouped, int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int64_t n_tiles, const float* user,
                        const float* items, const int32_t* item_ids, const TkTile* tiles, const int64_t* exclude, int32_t n_exclude,
                        float* top_scores, int64_t* top_ids, uint64_t* ws, hipStream_t s, const char* who,
-                       TkNoise noise = TkNoise{nullptr, 0.0f, 0}) {
+                       TkNoise noise = TkNoise{nullptr, 0.0f, 0}, const float* bias = nullptr) {
     const TopkGeom g = topk_geom(B, grouped ? 32 * n_tiles : N);
     char what[64];
     if (g.S > 0) {
         const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
         const dim3 grid(g.tiles, g.S);
         const int n = (int)N, nt = (int)n_tiles;
-#define TK_LAUNCH_G(P, W, V, GR, NS)                                                                                       \
-    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, GR, NS>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S, user, items, \
-                       exclude, n_exclude, ws, G, nt, tiles, item_ids, noise)
+#define TK_LAUNCH_G(P, W, V, GR, NS, BI)                                                                                   \
+    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, GR, NS, BI>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S, user, \
+                       items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias)
 #define TK_LAUNCH(P, W)                                                                                                    \
     do {                                                                                                                   \
         if (grouped) {                                                                                                     \
-            if (vec) TK_LAUNCH_G(P, W, true, true, false);                                                                 \
-            else TK_LAUNCH_G(P, W, false, true, false);                                                                    \
+            if (vec) TK_LAUNCH_G(P, W, true, true, false, false);                                                          \
+            else TK_LAUNCH_G(P, W, false, true, false, false);                                                             \
         } else if (noise.row_key) {                                                                                        \
-            if (vec) TK_LAUNCH_G(P, W, true, false, true);                                                                 \
-            else TK_LAUNCH_G(P, W, false, false, true);                                                                    \
+            if (vec) TK_LAUNCH_G(P, W, true, false, true, false);                                                          \
+            else TK_LAUNCH_G(P, W, false, false, true, false);                                                             \
+        } else if (bias) {                                                                                                 \
+            if (vec) TK_LAUNCH_G(P, W, true, false, false, true);                                                          \
+            else TK_LAUNCH_G(P, W, false, false, false, true);                                                             \
         } else {                                                                                                           \
-            if (vec) TK_LAUNCH_G(P, W, true, false, false);                                                                \
-            else TK_LAUNCH_G(P, W, false, false, false);                                                                   \
+            if (vec) TK_LAUNCH_G(P, W, true, false, false, false);                                                         \
+            else TK_LAUNCH_G(P, W, false, false, false, false);                                                            \
         }                                                                                                                  \
     } while (0)
         if (k + 64 <= 128) TK_LAUNCH(128, TK_WAVES);

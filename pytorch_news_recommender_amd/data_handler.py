@@ -828,6 +828,19 @@ class ClickFeed(DeviceFeed):
         with np.errstate(divide="ignore"):
             return np.log(q).astype(np.float32)
 
+    def popularity_prior(self, alpha):
+        """float32 [N] on the feed's device: prior[n] = float32(alpha * log1p(count[n])), formed in float64 from the resident
+        ``count`` (the number of training users who clicked n; held-out clicks are not counted, so the prior cannot leak them),
+        prior[0] = 0.  The per-news prior ``Model.recommend(item_bias=...)`` and ``rank_targets(item_bias=...)`` take: what
+        ``--loss pooled``'s logQ correction trains out of the scores, put back at serving time in a tunable amount.  alpha must
+        be finite (ValueError); alpha = 0 gives zeros."""
+        alpha = float(alpha)
+        if not np.isfinite(alpha):
+            raise ValueError("ClickFeed.popularity_prior: alpha = %r must be finite" % (alpha,))
+        prior = (alpha * np.log1p(self.count.cpu().numpy().astype(np.float64))).astype(np.float32)
+        prior[0] = 0.0
+        return torch.from_numpy(prior).to(self.device)
+
     def batch(self, rows):
         b = DeviceFeed.batch(self, rows)
         if self.negatives == "adaptive":

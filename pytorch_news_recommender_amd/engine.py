@@ -746,11 +746,21 @@ class NRMSEngine:
         return impression_metrics(self.lib, self.device, scores, labels, lens, ks, ranks)
 
     # ---- retrieval over a whole catalogue ---------------------------------------------------------
-    def top_k(self, user_vec, items, k, exclude=None):
+    def _item_bias(self, who, bias, N, dev):
+        """The checked per-item prior of top_k / rank_of: a contiguous float32 [N] tensor on the device."""
+        if (not torch.is_tensor(bias) or bias.dim() != 1 or bias.shape[0] != N or bias.dtype != torch.float32 or bias.device != dev
+                or not bias.is_contiguous()):
+            got = ("%s %s on %s" % (tuple(bias.shape), bias.dtype, bias.device)) if torch.is_tensor(bias) else type(bias).__name__
+            raise _lib.NrmsError("%s: bias must be a contiguous [%d] float32 tensor on %s (got %s)" % (who, N, self.device, got))
+        return bias
+
+    def top_k(self, user_vec, items, k, exclude=None, bias=None):
         """user_vec [B, d], items [N, d] fp32, exclude [B, n_exclude] int64 or None (device, contiguous) -> (scores [B, k]
         fp32, ids [B, k] int64): per user the k items of largest user . item, no [B, N] matrix (nrms_topk_dot).  Order:
         score descending, then the smaller id; rows with fewer than k eligible items end in id -1 / score -inf; excluded
-        ids and NaN scores are never returned.  include/nrms_hip.h states the contract."""
+        ids and NaN scores are never returned.  bias [N] fp32 (device, contiguous) or None: a per-item prior, the order and
+        the returned scores are those of user . item + bias[n] (one fp32 add; a NaN bias removes the item for every user;
+        nrms_topk_dot_biased).  None calls nrms_topk_dot as before.  include/nrms_hip.h states the contract."""
         k = int(k)
         dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32)):
@@ -771,12 +781,20 @@ class NRMSEngine:
             n_ex = exclude.shape[1]
             if n_ex == 0:
                 exclude = None
+        if bias is not None:
+            self._item_bias("top_k", bias, N, dev)
         nbytes = self.lib.nrms_topk_dot_workspace_bytes(B, N, d, k)
         if nbytes == 0:
             raise _lib.NrmsError("top_k: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (B, N, d, k))
         ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
         scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
         ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        if bias is not None:
+            rc = self.lib.nrms_topk_dot_biased(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                               _lib.ptr(exclude), n_ex, _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws),
+                                               C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_topk_dot_biased")
+            return scores, ids
         rc = self.lib.nrms_topk_dot(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(exclude), n_ex,
                                     _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
         _lib.check(rc, "nrms_topk_dot")
@@ -873,13 +891,15 @@ class NRMSEngine:
             out += (ild,)
         return out
 
-    def rank_of(self, user_vec, items, targets, exclude=None):
+    def rank_of(self, user_vec, items, targets, exclude=None, bias=None):
         """user_vec [B, d], items [N, d] fp32, targets [B, T] int64, exclude [B, n_exclude] int64 or None (device, contiguous)
         -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position of every target in top_k's order over the
         whole catalogue (the same score bits, exclude list, NaN rule and tie rule), at any depth and without a [B, N] matrix
         (nrms_rank_dot).  A target outside [0, N) (-1 is the padding value), an excluded one and one with a NaN score come
         back as rank 0 / score -inf; targets do not remove each other.  The kernel takes 32 targets per call: wider
-        ``targets`` go in column chunks of 32.  include/nrms_hip.h states the contract."""
+        ``targets`` go in column chunks of 32.  bias [N] fp32 (device, contiguous) or None: top_k's per-item prior, ranks and
+        scores are those of user . item + bias[n] (a target whose bias is NaN gets rank 0 / -inf; nrms_rank_dot_biased).  None
+        calls nrms_rank_dot as before.  include/nrms_hip.h states the contract."""
         dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32), ("targets", targets, torch.int64)):
             if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
@@ -901,6 +921,8 @@ class NRMSEngine:
             n_ex = exclude.shape[1]
             if n_ex == 0:
                 exclude = None
+        if bias is not None:
+            self._item_bias("rank_of", bias, N, dev)
         T_all = targets.shape[1]
         ranks = torch.empty(B, T_all, dtype=torch.int32, device=self.device)
         scores = torch.empty(B, T_all, dtype=torch.float32, device=self.device)
@@ -914,9 +936,15 @@ class NRMSEngine:
             if nbytes == 0:
                 raise _lib.NrmsError("rank_of: arguments rejected (B=%d, N=%d, d=%d, T=%d, n_exclude=%d)" % (B, N, d, T, n_ex))
             ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
-            rc = self.lib.nrms_rank_dot(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(tg), _lib.ptr(exclude),
-                                        n_ex, _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
-            _lib.check(rc, "nrms_rank_dot")
+            if bias is not None:
+                rc = self.lib.nrms_rank_dot_biased(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                                   _lib.ptr(tg), _lib.ptr(exclude), n_ex, _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws),
+                                                   C.c_size_t(ws.numel() * 8), _stream())
+                _lib.check(rc, "nrms_rank_dot_biased")
+            else:
+                rc = self.lib.nrms_rank_dot(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(tg), _lib.ptr(exclude),
+                                            n_ex, _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+                _lib.check(rc, "nrms_rank_dot")
             if not whole:
                 ranks[:, t0:t0 + T] = rk
                 scores[:, t0:t0 + T] = sc

@@ -215,11 +215,18 @@ class Model(FlatHipModel):
     CATALOGUE_RANKING = False
     CATALOGUE_SAMPLING = False          # the catalogue score is not one dot product per user: no sample_negatives
 
-    def rank_targets(self, batch, targets, catalogue, exclude_history=True):
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None):
+        if item_bias is not None:
+            raise _lib.NrmsError("graph: rank_targets takes no item_bias: the model cannot rank a catalogue at all, a candidate's "
+                                 "score depends on its neighbours in the click graph")
         raise NotImplementedError("graph: rank_targets is not available: a candidate's score depends on its neighbours in the "
                                   "click graph, not on a catalogue row alone (no recommend either)")
 
-    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False):
+    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
+                  item_bias=None):
+        if item_bias is not None:
+            raise _lib.NrmsError("graph: recommend takes no item_bias: the model cannot recommend from a catalogue at all, a "
+                                 "candidate's score depends on its neighbours in the click graph")
         if diversity is not None or shortlist is not None or return_ild:
             raise _lib.NrmsError("graph: recommend has no diversity re-ranking (diversity / shortlist / return_ild): the model "
                                  "cannot recommend from a catalogue at all, a candidate's score depends on its neighbours in the "

@@ -305,16 +305,21 @@ class Model(FlatHipModel):
         return Catalogue(vectors, tables[0], tables[1], eng.n_sub)
 
     @torch.no_grad()
-    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False):
+    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
+                  item_bias=None):
         """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores [B, k]
         fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_grouped_dot).  The diversity
-        re-ranking of nrms_hip.Model.recommend is refused (NrmsError): it works on a row-ordered catalogue.
+        re-ranking of nrms_hip.Model.recommend is refused (NrmsError): it works on a row-ordered catalogue.  So is its
+        per-news prior ``item_bias``: the grouped top-k has no bias term.
 
         catalogue: encode_catalogue(titles, categ, subcateg).  Only ``browsed_ids`` [B, H] is read: the history vectors and
         categories are catalogue rows, a slot is valid where its id is not 0, and the interests are those forward builds;
         a news item's score is its forward score as that user's candidate.  Ids outside the catalogue are read as padding
         and counted (check_recommend_ids raises).  News id 0 is never returned, with exclude_history neither is a browsed
         id; missing slots get id -1 / score -inf."""
+        if item_bias is not None:
+            raise _lib.NrmsError("hierec: recommend takes no item_bias: its catalogue is scored with a query per (topic, "
+                                 "sub-topic) group (nrms_topk_grouped_dot), which has no per-item prior")
         if diversity is not None or shortlist is not None or return_ild:
             raise _lib.NrmsError("hierec: recommend has no diversity re-ranking (diversity / shortlist / return_ild): its "
                                  "catalogue is stored group after group and scored with a query per (topic, sub-topic) group, "
@@ -343,7 +348,10 @@ class Model(FlatHipModel):
     CATALOGUE_RANKING = False
     CATALOGUE_SAMPLING = False          # the catalogue score is not one dot product per user: no sample_negatives
 
-    def rank_targets(self, batch, targets, catalogue, exclude_history=True):
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None):
+        if item_bias is not None:
+            raise _lib.NrmsError("hierec: rank_targets takes no item_bias: HieRec scores the catalogue with a query per (topic, "
+                                 "sub-topic) group (nrms_topk_grouped_dot), which has no per-item prior and no exact rank")
         raise NotImplementedError("hierec: rank_targets is not available: HieRec scores the catalogue with a query per (topic, "
                                   "sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot ranks plain dot products only")
 

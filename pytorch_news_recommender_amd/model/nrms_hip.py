@@ -169,7 +169,8 @@ class Model(FlatHipModel):
         return self._engine.encode_titles(self._flat, _ids_on(dev, titles), tag="news_eval")
 
     @torch.no_grad()
-    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False):
+    def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
+                  item_bias=None):
         """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores
         [B, k] fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_dot).
 
@@ -185,7 +186,14 @@ class Model(FlatHipModel):
         (largest cosine between catalogue rows to the news picked so far), in pick order; the scores returned are still the
         dot products.  lambda = 1 is the plain list, bit for bit.  return_ild appends the intra-list diversity [B] fp32 of the
         returned list (1 - mean pairwise cosine of its catalogue rows, NaN with fewer than two news), from the same kernel
-        with or without ``diversity``."""
+        with or without ``diversity``.
+
+        item_bias: float32 [N] on the model's device, indexed by news id like the catalogue (row 0, the padding title's, is
+        never read), or None.  A per-news prior: the list is ordered by, and the scores returned are, dot product +
+        item_bias[id] (one fp32 add; include/nrms_hip.h nrms_topk_dot_biased), e.g. ``ClickFeed.popularity_prior``, a
+        freshness decay or an editorial boost.  A NaN entry removes that news for every user (a global block-list); -inf
+        puts it last.  With ``diversity`` the shortlist comes from the biased top-k and the re-ranker scales the biased
+        scores to relevance; diversity = 1 with a bias is the biased plain list, bit for bit.  None is the call as it was."""
         if diversity is None and shortlist is not None:
             raise _lib.NrmsError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
         if diversity is not None:
@@ -196,18 +204,19 @@ class Model(FlatHipModel):
             if not 1 <= k <= M <= 256:
                 raise _lib.NrmsError("recommend: with diversity, 1 <= k <= shortlist <= 256 (k=%d, shortlist=%d)" % (k, M))
         user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend")
+        bias = self._item_bias_rows(item_bias, cat, "recommend")
         if diversity is None:
-            scores, ids = self._engine.top_k(user, cat[1:], k, exclude)
+            scores, ids = self._engine.top_k(user, cat[1:], k, exclude, bias=bias)
             out = (torch.where(ids >= 0, ids + 1, ids), scores)
             if return_ild:      # the plain list's ILD is the re-ranker's at lambda = 1, which keeps the list as it is
                 out += (self._engine.mmr_rerank(cat[1:], ids, scores, ids.shape[1], 1.0, return_ild=True)[2],)
             return out
-        s_scores, s_ids = self._engine.top_k(user, cat[1:], M, exclude)
+        s_scores, s_ids = self._engine.top_k(user, cat[1:], M, exclude, bias=bias)
         res = self._engine.mmr_rerank(cat[1:], s_ids, s_scores, k, lam, return_ild=return_ild)
         return (torch.where(res[0] >= 0, res[0] + 1, res[0]), res[1]) + tuple(res[2:])
 
     @torch.no_grad()
-    def rank_targets(self, batch, targets, catalogue, exclude_history=True):
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None):
         """The exact position of given news in each user's ranking of the whole catalogue -> (ranks [B, T] int32, scores
         [B, T] fp32): ranks[b, j] is the 1-based place news id targets[b, j] would take in recommend()'s list for user b
         were k unbounded (the same user vector, score bits, exclusions and tie rule; include/nrms_hip.h nrms_rank_dot), so
@@ -216,13 +225,18 @@ class Model(FlatHipModel):
         targets [B, T] news ids, any T, -1 = padding.  A target that cannot be recommended comes back as rank 0 / score
         -inf: id 0 (the padding title), an id outside the catalogue, a NaN score and, with exclude_history, a browsed id.
         catalogue and ``browsed_ids`` as in recommend (ids outside the catalogue are read as padding and counted:
-        check_recommend_ids raises on them)."""
+        check_recommend_ids raises on them).
+
+        item_bias: recommend's per-news prior (float32 [N] by news id, or None).  Ranks and scores are then those of dot
+        product + item_bias[id] (include/nrms_hip.h nrms_rank_dot_biased), so with the same ``item_bias`` the ids
+        recommend(k) returns still rank 1 .. k; a target whose prior is NaN is rank 0 / score -inf."""
         user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "rank_targets")
+        bias = self._item_bias_rows(item_bias, cat, "rank_targets")
         tg = torch.as_tensor(targets).to(user.device, dtype=torch.int64)
         if tg.dim() != 2 or tg.shape[0] != user.shape[0]:
             raise _lib.NrmsError("rank_targets: targets must be [%d, T] news ids (got %s)" % (user.shape[0], tuple(tg.shape)))
         # rows 1.. as in recommend: news id n is row n - 1, so id 0 (and -1) fall out of range and get rank 0
-        return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude)
+        return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude, bias=bias)
 
     @torch.no_grad()
     def sample_negatives(self, batch, row_key, S, catalogue, temperature, seed, exclude=None):
@@ -248,6 +262,20 @@ class Model(FlatHipModel):
         key = torch.as_tensor(row_key).to(dev, dtype=torch.int64).contiguous()
         ids = self._engine.softmax_sample(user, cat[1:], key, S, 1.0 / float(temperature), seed, browsed_rows)
         return torch.where(ids >= 0, ids + 1, ids)
+
+    @staticmethod
+    def _item_bias_rows(item_bias, cat, who):
+        """The kernels' view of a per-news prior: rows 1.. like the catalogue's (None stays None)."""
+        if item_bias is None:
+            return None
+        N = cat.shape[0]
+        if (not torch.is_tensor(item_bias) or item_bias.dim() != 1 or item_bias.shape[0] != N or item_bias.dtype != torch.float32
+                or item_bias.device != cat.device):
+            got = ("%s %s on %s" % (tuple(item_bias.shape), item_bias.dtype, item_bias.device)) if torch.is_tensor(item_bias) \
+                else type(item_bias).__name__
+            raise _lib.NrmsError("%s: item_bias must be [%d] float32 on %s, indexed by news id like the catalogue (got %s)"
+                                 % (who, N, cat.device, got))
+        return item_bias.contiguous()[1:]
 
     def _catalogue_query(self, batch, catalogue, exclude_history, who):
         """What recommend and rank_targets share: (user vectors [B, width], the checked catalogue, the exclude list in

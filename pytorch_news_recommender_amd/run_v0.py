@@ -82,6 +82,9 @@ def build_parser():
                         'and of the re-ranked list')
     parser.add_argument('--shortlist', type=int, default=None, metavar='M', help='--diversity: the number of best news the re-ranking '
                         'picks from (K <= M <= 256; default min(256, 4 K))')
+    parser.add_argument('--popularity_prior', type=float, default=None, metavar='ALPHA', help='--negatives catalogue / adaptive: add the '
+                        "per-news prior ALPHA * log(1 + the number of training users who clicked the news) to every catalogue score of "
+                        '--recommend (with or without --diversity) and --retrieval_metrics (0 = none; held-out clicks are not counted)')
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     return parser
 
@@ -134,6 +137,24 @@ def check_retrieval_args(args):
         raise SystemExit('--retrieval_metrics: model %r cannot rank targets against the whole catalogue (its catalogue score is '
                          'no plain dot product)' % args.model)
     return ks
+
+
+def check_prior_args(args):
+    """--popularity_prior fails before any data is read or any step is trained: a finite ALPHA, a list or a metric to apply it to,
+    a click log to count popularity in, and a model that takes a per-news prior."""
+    if args.popularity_prior is None:
+        return
+    if not np.isfinite(args.popularity_prior):
+        raise SystemExit('--popularity_prior ALPHA: ALPHA must be finite (got %r)' % args.popularity_prior)
+    if args.recommend is None and args.retrieval_metrics is None:
+        raise SystemExit('--popularity_prior ALPHA: the prior of --recommend K and --retrieval_metrics K (give one of them)')
+    if args.negatives not in ('catalogue', 'adaptive'):
+        raise SystemExit('--popularity_prior: popularity is counted in a click log (--negatives catalogue or adaptive, got %r)'
+                         % args.negatives)
+    from .model import ALIASES
+    if ALIASES.get(args.model.lower(), args.model.lower()) in ('hierec_hip', 'graph_hip'):
+        raise SystemExit('--popularity_prior: model %r takes no per-news prior (its catalogue score is no plain dot product over a '
+                         'row-ordered catalogue)' % args.model)
 
 
 def check_graph_args(args):
@@ -204,6 +225,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     check_recommend_args(args)
     retrieval_ks = check_retrieval_args(args)
+    check_prior_args(args)
     check_graph_args(args)
     check_negatives_args(args)
     check_loss_args(args)
@@ -279,18 +301,20 @@ def main(argv=None):
                           num_workers=args.num_workers, drop_last=(world > 1 and typ == 0), shuffle=shuffle,
                           pin_memory=True)
 
+    item_prior = {}          # item_bias = the click feed's popularity prior with --popularity_prior, otherwise no keyword at all
+
     def recommend_top(samples):
         # the catalogue is the feed's title table (row r = news id r), so this step always runs on a DeviceFeed
         feed = DeviceFeed(config, samples, type=1, id2title_dict=titles, id2abst_dict=absts, batch_size=config.batch_size,
                           device=config.device)
         if args.diversity is None:
-            return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out)
+            return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior)
         # the plain list is the re-ranker's at lambda = 1 (bit for bit), which measures it with the same kernel
         net = recommender.model if hasattr(recommender, 'model') else recommender
         out = None
         for name, lam, dst in (('plain', 1.0, os.devnull), ('diversity %g' % args.diversity, args.diversity, args.recommend_out)):
             out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=dst, diversity=lam,
-                            shortlist=args.shortlist)
+                            shortlist=args.shortlist, **item_prior)
             st = net.last_recommend_stats
             print('{}: ILD@{}: {:.4f}  coverage: {:.4f}  users: {}'.format(name, args.recommend, st['ild'], st['coverage'],
                                                                             st['n_users']))
@@ -303,7 +327,7 @@ def main(argv=None):
         net = recommender.model if hasattr(recommender, 'model') else recommender
         needs_info = 'categ' in inspect.signature(net.encode_catalogue).parameters           # nrms_naml's feature rows
         return evaluate_retrieval(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
-                                  news_info=feed.news_info() if needs_info else None)
+                                  news_info=feed.news_info() if needs_info else None, **item_prior)
 
     def attach_graph(feed, samples=None):
         # the click graph is replicated: every rank builds it from ALL training samples (users shard, the graph does not)
@@ -333,6 +357,8 @@ def main(argv=None):
             if args.negatives == 'adaptive':
                 train_feed.attach_scorer(recommender)
             held_samples, held_labels = train_feed.heldout_samples()
+            if args.popularity_prior is not None:
+                item_prior['item_bias'] = train_feed.popularity_prior(args.popularity_prior)
         else:
             train_feed = loader(train_samples, 0, True)
         if args.graph == 'global':

@@ -330,7 +330,7 @@ def test(config, model, data_iter, test_list_nums=None, ckpt_file=None, out_file
 
 
 def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
-              shortlist=None):
+              shortlist=None, item_bias=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
@@ -342,8 +342,12 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     lines are in pick order).  With ``diversity`` given (models that re-rank) the call leaves
     ``net.last_recommend_stats = {"ild": mean intra-list diversity over the users with at least two news, "coverage":
     distinct recommended news / (N - 1), "n_users": those users}`` (NaN / 0 without such users), with one host
-    synchronisation at the end; without it the attribute is set to None and the model is called exactly as before."""
+    synchronisation at the end; without it the attribute is set to None and the model is called exactly as before.
+
+    item_bias: ``model.recommend``'s per-news prior (float32 [N] by news id on the model's device, e.g.
+    ``ClickFeed.popularity_prior(alpha)``), with or without ``diversity``.  None: the keyword is not passed at all."""
     net = _inner(model)
+    prior = {} if item_bias is None else {"item_bias": item_bias}
     if diversity is None and shortlist is not None:
         raise ValueError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
@@ -351,13 +355,13 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     if diversity is None:
         net.last_recommend_stats = None
         for datas in data_iter:
-            ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history)
+            ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history, **prior)
             lines.extend(ids.cpu().tolist())
     else:
         rows, ilds = [], []
         for datas in data_iter:
             ids, _, ild = net.recommend(datas, k, catalogue, exclude_history=exclude_history, diversity=diversity,
-                                        shortlist=shortlist, return_ild=True)
+                                        shortlist=shortlist, return_ild=True, **prior)
             rows.append(ids)
             ilds.append(ild)
         n_news = int(catalogue.shape[0])
@@ -384,7 +388,7 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
 
 
 def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
-                       verbose=True):
+                       verbose=True, item_bias=None):
     """Full-catalogue retrieval quality on held-out clicks: per impression of data_iter the targets are its clicked news (the
     ``candidate_ids`` whose label in y_true is 1) and each is ranked against the whole catalogue in recommend()'s own order
     (``model.rank_targets``: the exact position, at any depth).  titles / news_info / exclude_history as in recommend();
@@ -395,8 +399,12 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     with a ranked target), ``n_targets`` (ranked targets) and ``n_skipped`` (targets that came back with rank 0: a click
     that is already in the history, a padding or unknown id).  The per-user tensors stay on the device in
     ``last_retrieval_metrics`` (the metrics, plus ``ranks`` [n, T] int32, 0-padded to the widest batch, and ``targets``).
-    One host synchronisation, at the end."""
+    One host synchronisation, at the end.
+
+    item_bias: ``model.rank_targets``'s per-news prior, so that the metrics describe the order ``recommend`` serves with the
+    same prior.  None: the keyword is not passed at all."""
     net = _inner(model)
+    prior = {} if item_bias is None else {"item_bias": item_bias}
     ks = tuple(int(k) for k in ks)
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
     dev = catalogue.device
@@ -418,7 +426,7 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
         lab = torch.from_numpy(lab).to(dev)
         order = torch.argsort((~lab).to(torch.uint8), dim=1, stable=True)[:, :T]
         tg = torch.where(lab.gather(1, order), cand[:, :width].gather(1, order), torch.full_like(order, -1))
-        rk, _ = net.rank_targets(datas, tg, catalogue, exclude_history=exclude_history)
+        rk, _ = net.rank_targets(datas, tg, catalogue, exclude_history=exclude_history, **prior)
         ranks.append(rk)
         targets.append(tg)
     T = max((r.shape[1] for r in ranks), default=1)
