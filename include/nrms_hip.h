@@ -400,6 +400,46 @@ int nrms_topk_grouped_dot(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G,
                           const int32_t* item_ids, const int64_t* group_ptr, const int64_t* exclude, int32_t n_exclude,
                           float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A sectioned front page: per user the k best items of EVERY section of the catalogue in one call (serving: "the best k of sports,
+ * of finance, of health, ... for user b"; csrc/topksec.hip; PARITY UNPINNED, the reference scores shown candidates only).
+ * user [B, d], items [N, d] fp32 row-major, stored section after section: section g is rows [section_ptr[g], section_ptr[g + 1])
+ * (section_ptr int64 [G + 1], nondecreasing from 0 to N; sections may be empty or of any length, nothing is padded by the caller).
+ * item_ids int32 [N]: the id of each row, distinct, in [0, 2^31), in any order; bias [N] fp32 BY ROW (not by id), 4-byte aligned,
+ * NULLABLE; exclude [B, n_exclude] int64, nullable: ids (not rows) user b must not get (duplicates and ids that are no item's are
+ * ignored).  top_scores [B, G, k] fp32, top_ids [B, G, k] int64 (item ids).
+ * It is nrms_topk_grouped_dot's contract with these changes:
+ * One query per user.  Every section is scored with the user's own row, s(b, n) = user[b] . items[n], on the chain of
+ *   nrms_topk_dot: the same bits, whatever B, N, k, G, slice_tiles, the sections, the item's row or the run.
+ * Optional prior.  With bias the score is s' = s + bias[row]: ONE fp32 add on the finished accumulator, under the rules of
+ *   nrms_topk_dot_biased: a NaN sum removes the item, -inf puts it last, a NULL or all-zero bias gives the same ids and score bits.
+ * Selection per (user, section).  Row (b, g) of the outputs holds the first min(k, #eligible in section g) items of section g,
+ *   ordered by score descending (+inf first), equal scores by the SMALLER id, -0.0 equals +0.0 (returned as +0.0); then id -1 /
+ *   score -inf.  Eligible: the id is not in exclude[b, :] and the (biased) score is not NaN.  An empty section gives an all-padding
+ *   row.
+ * Limits: 1 <= k <= 256, d >= 1, 1 <= G <= 4096, B >= 0, 0 <= N and N + 32 G <= 0x7FFF0000, (int64) B * G * k <= 0x7FFFFFFF;
+ *   slice_tiles is 0 (the library chooses) or in [1, 1 << 20]: the 32-row tiles per slice of the launch geometry, for tests and
+ *   tuning, and ceil((N + 31 G) / 32 / slice_tiles) + G must not pass 65535 (never with 0).  B = 0 is a no-op, N = 0 writes
+ *   all-padding rows.  A section_ptr outside its contract reads no row outside [0, N) (sections are clamped), but the result is
+ *   then unspecified.
+ * Consequences.  With G = 1, item_ids[n] = n and bias NULL the result is bit-identical to nrms_topk_dot.  Row (b, g) equals
+ *   nrms_topk_dot_biased for user b over the rows of section g alone, rows renamed to ids (with ids ascending inside the section
+ *   even the tie order).  The result does not depend on slice_tiles, B, the user's position in the batch, the order of the sections,
+ *   the order of rows inside a section, what other sections hold, what the workspace held or the run.  The first k' columns of a
+ *   call with k are the call with k' <= k.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_sections_dot: ..."); an undersized workspace
+ *   returns NRMS_EWORKSPACE.
+ * Workspace: nrms_topk_sections_dot_workspace_bytes(B, N, d, k, G, slice_tiles) bytes, 16-byte aligned (0 = arguments rejected):
+ *   the tile table, the slice table, the sections' slice ranges and O(B * slices * k), all sized from bounds (at most
+ *   (N + 31 G) / 32 tiles and ceil(tiles / slice length) + G slices), since the section lengths live on the device.
+ * Three kernels on `stream`, no host synchronisation, no allocation; plain vector loads and stores, no atomics beyond the integer
+ *   LDS counters of nrms_topk_dot's slice kernel. */
+size_t nrms_topk_sections_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int32_t slice_tiles);
+int nrms_topk_sections_dot(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int32_t slice_tiles, const float* user,
+                           const float* items /* section after section */, const int32_t* item_ids, const int64_t* section_ptr,
+                           const float* bias /* [N], by row, nullable */, const int64_t* exclude, int32_t n_exclude,
+                           float* top_scores /* [B, G, k] */, int64_t* top_ids /* [B, G, k] */, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* Exact rank of given items in nrms_topk_dot's order over the whole catalogue (evaluation: "at which position of all N items
  * does the model put the item user b clicked next?"), again without the [B, N] score matrix.  user [B, d], items [N, d] fp32
  * row-major; targets [B, T] int64: the items to rank (-1 is the padding value callers use); exclude [B, n_exclude] int64,

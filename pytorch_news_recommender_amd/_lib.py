@@ -162,6 +162,9 @@ SIGNATURES = {
     "nrms_topk_grouped_dot_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "nrms_topk_grouped_dot": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32]
                               + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "nrms_topk_sections_dot_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "nrms_topk_sections_dot": (C.c_int, [C.c_int32, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 6 + [C.c_int32]
+                               + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "nrms_rank_dot_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "nrms_rank_dot": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32]
                       + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),

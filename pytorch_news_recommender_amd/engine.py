@@ -1039,6 +1039,64 @@ class NRMSEngine:
             _lib.check(rc, "nrms_topk_grouped_dot")
         return scores, ids
 
+    def top_k_sections(self, user, items, item_ids, section_ptr, k, exclude=None, bias=None, slice_tiles=0):
+        """user [B, d] fp32, items [N, d] fp32 stored section after section (section g = rows section_ptr[g] ..
+        section_ptr[g + 1]), item_ids [N] int32 (distinct, >= 0), section_ptr [G + 1] int64, exclude [B, n_exclude] int64 ids or
+        None, bias [N] fp32 BY ROW or None (device, contiguous) -> (scores [B, G, k] fp32, ids [B, G, k] int64): per user and
+        section the k items of largest user . item (+ bias[row]), no [B, N] matrix (nrms_topk_sections_dot).  Order and
+        padding as top_k, with item ids in place of rows; an empty section gives an all-padding row.  slice_tiles: 0 (the
+        library chooses) or the 32-row tiles per slice of the launch geometry; the result does not depend on it.  Users go in
+        chunks whose workspace stays under ``retrieval_chunk_bytes``; the result does not depend on the chunking."""
+        k, slice_tiles = int(k), int(slice_tiles)
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        for name, t, dt, nd in (("user", user, torch.float32, 2), ("items", items, torch.float32, 2),
+                                ("item_ids", item_ids, torch.int32, 1), ("section_ptr", section_ptr, torch.int64, 1)):
+            if t.dim() != nd or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise _lib.NrmsError("top_k_sections: %s must be a contiguous %d-D %s tensor on %s (got %s %s on %s%s)"
+                                     % (name, nd, dt, self.device, tuple(t.shape), t.dtype, t.device,
+                                        "" if t.is_contiguous() else ", not contiguous"))
+        B, d = user.shape
+        N = items.shape[0]
+        G = section_ptr.shape[0] - 1
+        if items.shape[1] != d:
+            raise _lib.NrmsError("top_k_sections: items width %d != user width %d" % (items.shape[1], d))
+        if item_ids.shape[0] != N:
+            raise _lib.NrmsError("top_k_sections: item_ids must be [%d] (got %s)" % (N, tuple(item_ids.shape)))
+        n_ex = 0
+        if exclude is not None:
+            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
+                    or not exclude.is_contiguous()):
+                raise _lib.NrmsError("top_k_sections: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
+                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
+            n_ex = exclude.shape[1]
+            if n_ex == 0:
+                exclude = None
+        if bias is not None:
+            self._item_bias("top_k_sections", bias, N, dev)
+        query = self.lib.nrms_topk_sections_dot_workspace_bytes
+        if G < 1 or query(B, N, d, k, G, slice_tiles) == 0:
+            raise _lib.NrmsError("top_k_sections: arguments rejected (B=%d, N=%d, d=%d, k=%d, G=%d, slice_tiles=%d; 1 <= k <= 256, "
+                                 "1 <= G <= 4096, B * G * k < 2^31)" % (B, N, d, k, G, slice_tiles))
+        scores = torch.empty(B, G, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, G, k, dtype=torch.int64, device=self.device)
+        # the most users (at least 1, whole 32-user tiles) whose workspace fits: the entries grow with b, the tables do not
+        step = B
+        while step > 1 and query(step, N, d, k, G, slice_tiles) > int(self.retrieval_chunk_bytes):
+            step = max(1, step // 2)
+        if 32 <= step < B:
+            step = step // 32 * 32
+        for b0 in range(0, B, max(1, step)):
+            b1 = min(B, b0 + step)
+            nbytes = query(b1 - b0, N, d, k, G, slice_tiles)
+            ws = self._buf("topk_ws", (nbytes + 15) // 16 * 2, torch.int64)
+            ex = None if exclude is None else exclude[b0:b1]
+            rc = self.lib.nrms_topk_sections_dot(b1 - b0, C.c_int64(N), d, k, G, slice_tiles, _lib.ptr(user[b0:b1]), _lib.ptr(items),
+                                                 _lib.ptr(item_ids), _lib.ptr(section_ptr), _lib.ptr(bias), _lib.ptr(ex), n_ex,
+                                                 _lib.ptr(scores[b0:b1]), _lib.ptr(ids[b0:b1]), _lib.ptr(ws),
+                                                 C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_topk_sections_dot")
+        return scores, ids
+
     # ---- inference with unique-title caching (SURVEY f-1) -------------------------------------
     def group_rows(self, rows):
         """rows [N, L] int64 (device) -> (inverse [N] int32, rep_rows [U] int32, U): exact grouping of equal rows

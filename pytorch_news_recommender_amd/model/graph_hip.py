@@ -234,6 +234,12 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: recommend is not available: a candidate's score depends on its neighbours in the "
                                   "click graph, not on a catalogue row alone")
 
+    CATALOGUE_SECTIONS = False
+
+    def recommend_sections(self, batch, k, sectioned, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("graph: recommend_sections is not available: a candidate's score depends on its neighbours in "
+                                  "the click graph, not on a catalogue row alone (no recommend either)")
+
     def attach_click_graph(self, graph, titles):
         """From now on a batch without ``neighbor_rows`` takes its neighbours from ``graph`` (click_graph.ClickGraph on the
         model's device) instead of the batch-induced host sampler; titles [graph.n_news, L]: the word ids of every news, row r =

@@ -355,6 +355,13 @@ class Model(FlatHipModel):
         raise NotImplementedError("hierec: rank_targets is not available: HieRec scores the catalogue with a query per (topic, "
                                   "sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot ranks plain dot products only")
 
+    CATALOGUE_SECTIONS = False
+
+    def recommend_sections(self, batch, k, sectioned, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("hierec: recommend_sections is not available: HieRec scores the catalogue with a query per "
+                                  "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_topk_sections_dot scores every "
+                                  "section with one user row")
+
     def _zero_frozen_rows(self, gflat):
         # padding_idx = 0 of the two embedding tables: row 0 takes no gradient (nn.Embedding semantics)
         self._layout.view(gflat, "subtopic_embedding.weight")[0].zero_()

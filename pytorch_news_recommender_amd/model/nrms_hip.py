@@ -85,6 +85,23 @@ def _ids_on(dev, x):
     return t.to(dev, dtype=torch.int32 if t.dtype == torch.int32 else torch.int64, non_blocking=True)
 
 
+class SectionedCatalogue:
+    """A catalogue cut into sections for Model.recommend_sections (Model.section_catalogue builds it): row r = news id r.
+    vectors [N, width]: the catalogue as given, in id order (the user vectors are built from it); items [N - 1, width]: rows 1..
+    (the padding title is never a candidate) sorted stably by section, ids ascending inside a section; item_ids int32 [N - 1]:
+    their news ids; section_ptr int64 [G + 1]; n_sections: G."""
+
+    def __init__(self, vectors, section_of, n_sections):
+        dev = vectors.device
+        self.vectors, self.n_sections = vectors, int(n_sections)
+        sec = section_of[1:]
+        order = torch.sort(sec, stable=True).indices + 1
+        self.items = vectors.index_select(0, order)
+        self.item_ids = order.to(torch.int32)
+        counts = torch.bincount(sec, minlength=self.n_sections)
+        self.section_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), counts.cumsum(0)])
+
+
 class Model(FlatHipModel):
     """NRMS network: 1+K candidate titles and the clicked-title history -> click logits."""
 
@@ -215,6 +232,48 @@ class Model(FlatHipModel):
         res = self._engine.mmr_rerank(cat[1:], s_ids, s_scores, k, lam, return_ild=return_ild)
         return (torch.where(res[0] >= 0, res[0] + 1, res[0]), res[1]) + tuple(res[2:])
 
+    @staticmethod
+    @torch.no_grad()
+    def section_catalogue(catalogue, section_of, n_sections):
+        """catalogue: encode_catalogue's [N, width]; section_of int64 [N]: the section of every news id (e.g.
+        ``DeviceFeed.news_info()["categ"]``; section 0, "unknown", is an ordinary section; entry 0, the padding title's, is not
+        read); n_sections: G -> a SectionedCatalogue for recommend_sections, on the catalogue's device (torch ops only).  A
+        value outside [0, n_sections) raises NrmsError here (one host synchronisation)."""
+        cat = torch.as_tensor(catalogue)
+        G = int(n_sections)
+        sec = torch.as_tensor(section_of).to(cat.device, dtype=torch.int64).reshape(-1)
+        if cat.dim() != 2 or cat.dtype != torch.float32 or sec.shape[0] != cat.shape[0] or cat.shape[0] < 1:
+            raise _lib.NrmsError("section_catalogue: catalogue must be [N >= 1, width] float32 and section_of [N] (got %s %s, %s)"
+                                 % (tuple(cat.shape), cat.dtype, tuple(sec.shape)))
+        if G < 1:
+            raise _lib.NrmsError("section_catalogue: n_sections must be >= 1 (got %d)" % G)
+        n_bad = int(((sec[1:] < 0) | (sec[1:] >= G)).sum().item())
+        if n_bad:
+            raise _lib.NrmsError("section_catalogue: %d section ids outside [0, %d)" % (n_bad, G))
+        return SectionedCatalogue(cat.contiguous(), sec, G)
+
+    @torch.no_grad()
+    def recommend_sections(self, batch, k, sectioned, exclude_history=True, *, item_bias=None):
+        """The front page by section: for each user of ``batch`` the k best news of EVERY section -> (news_ids [B, G, k]
+        int64, scores [B, G, k] fp32), row (b, g) best first (score descending, then the smaller id), in one call over the
+        catalogue (include/nrms_hip.h nrms_topk_sections_dot).  Row (b, g) is recommend's full ranking for user b filtered
+        to section g and cut at k, ids and score bits.
+
+        sectioned: section_catalogue(...).  The user vector, ``browsed_ids``, the counting of ids outside the catalogue
+        (check_recommend_ids), the id-0 rule, ``exclude_history`` and ``item_bias`` (float32 [N] by news id, NaN = a global
+        block-list) are recommend's.  A section with fewer than k eligible news ends in id -1 / score -inf; an empty one is
+        all padding."""
+        if not isinstance(sectioned, SectionedCatalogue):
+            raise _lib.NrmsError("recommend_sections: needs a SectionedCatalogue (section_catalogue(catalogue, section_of, n_sections))")
+        user, cat, exclude = self._catalogue_query(batch, sectioned.vectors, exclude_history, "recommend_sections")
+        bias = self._item_bias_rows(item_bias, cat, "recommend_sections")
+        if bias is not None:          # by news id -> by row of the sectioned layout
+            bias = item_bias.index_select(0, sectioned.item_ids)
+        if exclude is not None:       # the kernel's ids are news ids here, not rows of cat[1:]; the padding slots become id 0, no item's
+            exclude = exclude + 1
+        scores, ids = self._engine.top_k_sections(user, sectioned.items, sectioned.item_ids, sectioned.section_ptr, k, exclude, bias=bias)
+        return ids, scores
+
     @torch.no_grad()
     def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None):
         """The exact position of given news in each user's ranking of the whole catalogue -> (ranks [B, T] int32, scores
@@ -317,6 +376,7 @@ class Model(FlatHipModel):
     CATALOGUE_RETRIEVAL = True          # recommend / encode_catalogue are available (run_v0 --recommend checks this)
     CATALOGUE_RANKING = True            # the catalogue score is a plain dot product: rank_targets (run_v0 --retrieval_metrics)
     CATALOGUE_SAMPLING = True           # ... so negatives can be drawn from its softmax: sample_negatives (run_v0 --negatives adaptive)
+    CATALOGUE_SECTIONS = True           # ... and selected per section: recommend_sections (run_v0 --sections)
 
     def check_recommend_ids(self):
         """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read

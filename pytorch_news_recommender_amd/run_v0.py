@@ -25,7 +25,7 @@ from . import parallel
 from .config import Config
 from .data_handler import ClickFeed, DeviceFeed, ImpressionFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
 from .model import Model
-from .train_eval import evaluate_retrieval, recommend, test, train
+from .train_eval import evaluate_retrieval, recommend, recommend_sections, test, train
 
 # rank r adds r * this to its dropout seeds (FlatHipModel._next_seed), so that the ranks of a data-parallel job draw unrelated masks
 DROPOUT_RANK_SALT = 0x632BE59BD9B4E019
@@ -86,7 +86,26 @@ def build_parser():
                         "per-news prior ALPHA * log(1 + the number of training users who clicked the news) to every catalogue score of "
                         '--recommend (with or without --diversity) and --retrieval_metrics (0 = none; held-out clicks are not counted)')
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
+    parser.add_argument('--sections', type=str, default=None, choices=('category', 'subcategory'), help='--recommend: write the front '
+                        'page by section instead, the top K news of every category (or sub-category) per impression, as '
+                        '"<impression> <section> [ids]" lines (models whose catalogue score is a plain dot product; not with --diversity)')
     return parser
+
+
+def check_sections_args(args):
+    """--sections fails before any data is read or any step is trained: it shapes the list of --recommend, has no re-ranking
+    inside a section, and needs a model that selects per section."""
+    if args.sections is None:
+        return
+    if args.recommend is None:
+        raise SystemExit('--sections: the sections of the list of --recommend K (give --recommend)')
+    if args.diversity is not None:
+        raise SystemExit('--sections: no diversity re-ranking inside a section (drop --diversity)')
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_SECTIONS', False):
+        raise SystemExit('--sections: model %r cannot select per section (its catalogue score is no plain dot product)' % args.model)
 
 
 def check_recommend_args(args):
@@ -224,6 +243,7 @@ def check_loss_args(args):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_recommend_args(args)
+    check_sections_args(args)
     retrieval_ks = check_retrieval_args(args)
     check_prior_args(args)
     check_graph_args(args)
@@ -307,6 +327,12 @@ def main(argv=None):
         # the catalogue is the feed's title table (row r = news id r), so this step always runs on a DeviceFeed
         feed = DeviceFeed(config, samples, type=1, id2title_dict=titles, id2abst_dict=absts, batch_size=config.batch_size,
                           device=config.device)
+        if args.sections is not None:
+            info = feed.news_info()
+            sections = ((info['categ'], config.category_nums) if args.sections == 'category'
+                        else (info['subcateg'], config.subcategory_nums))
+            return recommend_sections(config, recommender, feed, feed.titles, args.recommend, sections, out_file=args.recommend_out,
+                                      **item_prior)
         if args.diversity is None:
             return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior)
         # the plain list is the re-ranker's at lambda = 1 (bit for bit), which measures it with the same kernel

@@ -386,6 +386,33 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     return file_name
 
 
+def recommend_sections(config, model, data_iter, titles, k, sections, out_file=None, exclude_history=True, news_info=None,
+                       item_bias=None):
+    """The front page by section: writes ``<impression index> <section> [id1,id2,...]`` lines (the index 1-based, as
+    recommend()): per impression of data_iter and per section the k news ids of that section the model recommends, best
+    first (``model.recommend_sections``).  sections: (section_of, n_sections), the section of every news id (int64 [N], e.g.
+    ``DeviceFeed.news_info()["categ"]``) and their count.  titles / news_info / exclude_history / item_bias as in
+    recommend(); the catalogue is encoded and sectioned once.  A section that holds no eligible news for a user is skipped,
+    one with fewer than k gives a shorter line.  Returns the file name."""
+    net = _inner(model)
+    prior = {} if item_bias is None else {"item_bias": item_bias}
+    section_of, n_sections = sections
+    sectioned = net.section_catalogue(net.encode_catalogue(titles, **(news_info or {})), section_of, n_sections)
+    rows = []
+    for datas in data_iter:
+        ids, _ = net.recommend_sections(datas, k, sectioned, exclude_history=exclude_history, **prior)
+        rows.extend(ids.cpu().tolist())
+    net.engine.check_ids()
+    net.check_recommend_ids()
+    file_name = out_file or 'recommend_sections_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
+    with open(file_name, 'w') as f:
+        for i, per_section in enumerate(rows):
+            for g, row in enumerate(per_section):
+                got = [n for n in row if n >= 0]
+                if got:
+                    f.write('%d %d %s\n' % (i + 1, g, str(got).replace(' ', '')))
+    return file_name
+
 
 def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
                        verbose=True, item_bias=None):
