@@ -497,6 +497,56 @@ int nrms_rank_dot_biased(int32_t B, int64_t N, int32_t d, int32_t T, const float
                          int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- A per-user time window on the catalogue in retrieval and ranking (news expires: evaluation against the news that were live
+ * at the moment of the click, serving with a request time per user; PARITY UNPINNED, the reference scores shown candidates only) ----
+ * nrms_topk_dot_biased and nrms_rank_dot_biased over the items whose timestamp lies in the user's own interval.  item_time [N]
+ * int32: one tick per item (any unit the caller likes); window [B, 2] int32: user b's interval [lo, hi) = [window[b, 0], window[b, 1]);
+ * both REQUIRED and 4-byte aligned.  bias [N] fp32, 4-byte aligned, NULLABLE: NULL means no prior, s' = s.  Every other argument is
+ * the biased call's.
+ * Eligible: item n is eligible for user b iff window[b, 0] <= item_time[n] < window[b, 1], n is not in exclude[b, :] and s'(b, n)
+ *   is not NaN.  The interval is half-open and compared as signed int32.  lo >= hi is the EMPTY window: row b is all padding
+ *   (id -1 / score -inf) and every target of user b gets rank 0 / score -inf.  An item whose time is INT32_MAX is never eligible,
+ *   for any window (hi <= INT32_MAX): this is the "not published" value.  INT32_MIN is an ordinary, earliest, tick.
+ * Score, order and output.  s and s' are the biased call's, the same code and the same bits: the window never touches a score.
+ *   Order (s' descending, +inf first, equal s' put the SMALLER n first), -0.0 equals +0.0 (returned as +0.0), padding (-1 / -inf),
+ *   invalid targets (outside [0, N), excluded, NaN s': rank 0 / -inf), limits (1 <= k <= 256, 1 <= T <= 32, d >= 1,
+ *   0 <= N <= 0x7FFF0000, B >= 0; B = 0 is a no-op, N = 0 writes padding / rank 0) are nrms_topk_dot_biased's and
+ *   nrms_rank_dot_biased's.
+ * Targets.  A target whose time is outside its user's window is invalid: rank 0 / score -inf.  A valid target is ranked against
+ *   the items eligible for its user, so ranks[b, j] = 1 + #{n eligible for b : (s'(b, n), n) precedes (s'(b, t), t)}.  An excluded
+ *   id outside the window is taken out of nothing.
+ * Consequences.
+ *   (a) With every window [INT32_MIN, INT32_MAX) and every time below INT32_MAX, ids, ranks and score bits equal the _biased
+ *       call's with the same bias (NULL: the unbiased call's).
+ *   (b) Row b equals nrms_topk_dot_biased at B = 1 for user b with bias'[n] = bias[n] (0 when bias is NULL) where
+ *       window[b, 0] <= item_time[n] < window[b, 1] and NaN elsewhere; the same holds for the ranks and target scores of
+ *       nrms_rank_dot_biased.  (With bias NULL, s + 0.0 differs from s only for s = -0.0, which is returned as +0.0 anyway.)
+ *   (c) The ids nrms_topk_dot_windowed returns for user b get ranks 1 .. k, in order, from nrms_rank_dot_windowed with the same
+ *       arguments, and the same score bits.
+ *   (d) The result does not depend on the row order of the catalogue (items, bias and item_time permuted together, ids mapped
+ *       back; the tie rule then speaks of the mapped ids only when scores tie), on B, the user's position in the batch, k, T, the
+ *       launch geometry, the run or what the workspace held.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_windowed: ...", "rank_dot_windowed: ...");
+ *   a NULL or misaligned item_time (N > 0) or window is one of them.  An undersized workspace returns NRMS_EWORKSPACE.  Nothing is
+ *   launched after an error.
+ * Workspace: the _windowed_workspace_bytes queries return exactly nrms_topk_dot_workspace_bytes(B, N, d, k) and
+ *   nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude) (0 = arguments rejected); 8-byte aligned.
+ * The same kernel counts as the unwindowed calls, on `stream`, no host synchronisation, no allocation; plain vector loads and
+ *   stores, no atomics beyond the integer counters of the unwindowed kernels.  A wave whose 64 items are closed to all 32 users of
+ *   its block loads no item row and runs no MFMA for that step: with a catalogue stored in time order, a narrow window costs little
+ *   more than the items inside it.  The results are the same with that skip compiled out (csrc/topk_entry.h TK_WINDOW_SKIP). */
+size_t nrms_topk_dot_windowed_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                           const float* bias /* [N], nullable */, const int32_t* item_time /* [N] */,
+                           const int32_t* window /* [B, 2] */, const int64_t* exclude, int32_t n_exclude, float* top_scores,
+                           int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+size_t nrms_rank_dot_windowed_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude);
+int nrms_rank_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                           const float* bias /* [N], nullable */, const int32_t* item_time /* [N] */,
+                           const int32_t* window /* [B, 2] */, const int64_t* targets, const int64_t* exclude,
+                           int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ---- Negatives from the model's own softmax over the whole catalogue (csrc/softmaxsample.hip; training: "which S news does the
  * model itself confuse with the positive right now?"; PARITY UNPINNED, the reference draws its negatives offline) ----
  * For each user b < B: S items drawn WITHOUT replacement from softmax(s(b, .) * inv_temperature) over the eligible items, never

@@ -18,6 +18,9 @@
 // nrms_rank_dot_biased ranks by s'(b, n) = s(b, n) + bias[n] (one fp32 add on the finished accumulator): the BIAS instantiations
 // of A and B add bias[id] / bias[n] to the score just before tk_entry; C works on entries and is the same kernel.
 //
+// nrms_rank_dot_windowed ranks inside a per-user interval on a per-item timestamp: the WINDOW instantiations of A and B test
+// lo <= item_time[n] < hi in front of tk_entry, and B skips the waves whose 64 items are closed to its whole block; C is the same.
+//
 // The chain is topk_slice_kernel's, restated in rk_chain (same operand staging, same k order, one accumulator):
 // tests/test_hip_rank.py pins the score bits to nrms_topk_dot's.
 #include "topk_entry.h"
@@ -101,12 +104,15 @@ __device__ __forceinline__ void rk_chain(tk_f32x16 (&acc)[TK_TN], const float* a
 // Kernel A.  One wave per block; block (x, y): user tile x, gathered positions 64 (y + i gridDim.y) .. + 63 of the tile's list
 // of 32 M ids, M = T + n_exclude: position g is list slot m = g % M of user u0 + g / M (slots [0, T): targets, then the
 // exclude ids).  ent [B, M].  Blocks y = 0 also zero the tile's counts [B, T] for kernel B.  Needs N >= 1.
-template <bool VEC, bool BIAS>
+// WINDOW: an id whose time is outside its owner's [lo, hi) gets entry 0, like a NaN score: such a target is invalid, such an
+// excluded id was never counted by kernel B and is taken out of nothing.
+template <bool VEC, bool BIAS, bool WINDOW>
 __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, int T, int n_exclude,
                                                           const float* __restrict__ user, const float* __restrict__ items,
                                                           const int64_t* __restrict__ targets,
                                                           const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
-                                                          uint32_t* __restrict__ counts, const float* __restrict__ bias) {
+                                                          uint32_t* __restrict__ counts, const float* __restrict__ bias,
+                                                          TkWindow win) {
     __shared__ int rows[64];
     __shared__ __attribute__((aligned(16))) float stage[64 * TK_BP];
     const int lane = threadIdx.x;
@@ -150,7 +156,13 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
             if constexpr (BIAS) {
                 if (idc >= 0 && idc < N) s = s + bias[idc];
             }
-            const bool ok = idc >= 0 && idc < N && !__builtin_isnan(s);
+            bool ok = idc >= 0 && idc < N && !__builtin_isnan(s);
+            if constexpr (WINDOW) {
+                if (ok) {
+                    const int tv = win.item_time[idc];
+                    ok = tv >= win.window[2 * (long)(u0 + uc)] && tv < win.window[2 * (long)(u0 + uc) + 1];
+                }
+            }
             ent[(long)(u0 + uc) * M + mc] = ok ? tk_entry(s, (uint32_t)idc) : 0;
         }
     }
@@ -158,11 +170,15 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
 
 // Kernel B.  Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step.  ent [B, M]:
 // the first T entries of a row are the user's targets.  counts [B, T] += #{live non-NaN n in the slice : entry(n) > target}.
-template <int W, bool VEC, bool BIAS>
+// WINDOW: topk_slice_kernel's window filter and dead-tile skip.  The block stages its users' (lo, hi) in LDS and forms their
+// hull [blo, bhi); a score becomes an entry only if lo <= item_time[n] < hi for its user; a wave none of whose 64 item times
+// lies in the hull (one __ballot, wave-uniform) goes to its next step with zero entries: no item loads, no staging, no MFMA.
+// The step loop holds no block barrier, so a skipping wave meets the two barriers around it like every other wave.
+template <int W, bool VEC, bool BIAS, bool WINDOW>
 __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d, int T, int M, int slice_len,
                                                             const float* __restrict__ user, const float* __restrict__ items,
                                                             const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts,
-                                                            const float* __restrict__ bias) {
+                                                            const float* __restrict__ bias, TkWindow win) {
     __shared__ uint64_t tgt[TK_UT][RK_MAX_T];
     __shared__ uint32_t cnts[TK_UT][RK_MAX_T];
     __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
@@ -178,7 +194,15 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
         tgt[u][j] = (u0 + u < B && j < T) ? ent[(long)(u0 + u) * M + j] : ~0ull;
         cnts[u][j] = 0;
     }
+    int2* wwin = nullptr;          // WINDOW: the block's 32 (lo, hi)
+    if constexpr (WINDOW) {
+        __shared__ int2 wwin_lds[TK_UT];
+        wwin = wwin_lds;
+        tk_window_stage(wwin, win.window, u0, B);
+    }
     __syncthreads();
+    int blo = 0, bhi = 0;
+    if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
 
     const int r = lane & 31, h = lane >> 5;
     const float* arow = user + (long)min(u0 + r, B - 1) * d;
@@ -187,6 +211,17 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
     for (int n0 = n_begin; n0 < n_end; n0 += IT) {
         const int nw = n0 + 64 * wave;
         if (nw >= n_end) continue;
+        int tv[WINDOW ? TK_TN : 1] = {};         // WINDOW: the time of this lane's item in column tile c
+        if constexpr (WINDOW) {
+            bool any = false;
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) {
+                const int n = nw + 32 * c + r;
+                tv[c] = win.item_time[min(n, N - 1)];
+                any |= n < n_end && tv[c] >= blo && tv[c] < bhi;
+            }
+            if (TK_WINDOW_SKIP && __ballot(any) == 0) continue;       // wave-uniform: nothing here is open to any user of the block
+        }
         tk_f32x16 acc[TK_TN];
 #pragma unroll
         for (int c = 0; c < TK_TN; ++c) acc[c] = tk_f32x16{};
@@ -206,7 +241,12 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
             for (int q = 0; q < 16; ++q) {
                 float s = acc[c][q];
                 if constexpr (BIAS) s = s + bv[c];
-                e[c][q] = (live && !__builtin_isnan(s)) ? tk_entry(s, (uint32_t)n) : 0;       // 0 precedes nothing
+                bool open = live && !__builtin_isnan(s);
+                if constexpr (WINDOW) {
+                    const int2 w = wwin[(q & 3) + 8 * (q >> 2) + 4 * h];
+                    open = open && tv[c] >= w.x && tv[c] < w.y;
+                }
+                e[c][q] = open ? tk_entry(s, (uint32_t)n) : 0;       // 0 precedes nothing
             }
         }
         for (int j = 0; j < T; ++j) {
@@ -310,9 +350,10 @@ extern "C" size_t nrms_rank_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
     return 256 + rank_entry_bytes(B, T, n_exclude) + (size_t)B * (size_t)T * sizeof(uint32_t);
 }
 
-// nrms_rank_dot (bias null, who "rank_dot") and nrms_rank_dot_biased: one body.
+// nrms_rank_dot (bias null, who "rank_dot"), nrms_rank_dot_biased and nrms_rank_dot_windowed (windowed: item_time and window are
+// required): one body.
 static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
-                         const float* bias, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                         const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
                          float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
     NRMS_REQUIRE(B >= 0, "%s: B must be >= 0 (B=%d)", who, B);
     NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "%s: N must be in [0, %d] (N=%lld)", who, TK_MAX_N, (long long)N);
@@ -323,6 +364,12 @@ static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     NRMS_REQUIRE(user, "%s: user is null", who);
     NRMS_REQUIRE(items || N == 0, "%s: items is null", who);
     NRMS_REQUIRE(((uintptr_t)bias & 3) == 0, "%s: bias must be 4-byte aligned", who);
+    if (windowed) {
+        NRMS_REQUIRE(item_time || N == 0, "%s: item_time is null", who);
+        NRMS_REQUIRE(((uintptr_t)item_time & 3) == 0, "%s: item_time must be 4-byte aligned", who);
+        NRMS_REQUIRE(window, "%s: window is null", who);
+        NRMS_REQUIRE(((uintptr_t)window & 3) == 0, "%s: window must be 4-byte aligned", who);
+    }
     NRMS_REQUIRE(targets, "%s: targets is null", who);
     NRMS_REQUIRE(ranks, "%s: ranks is null", who);
     NRMS_REQUIRE(workspace, "%s: workspace is null", who);
@@ -339,34 +386,47 @@ static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     uint32_t* counts = (uint32_t*)((char*)workspace + rank_entry_bytes(B, T, n_exclude));
     const RankGeom g = rank_geom(B, N);
     const int n = (int)N, M = T + n_exclude;
+    const TkWindow win = windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr};
     char what[64];
     if (g.S > 0) {
         const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
         const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64));
-#define RK_LAUNCH_A(V, BI)                                                                                                 \
-    hipLaunchKernelGGL((rank_entries_kernel<V, BI>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets, exclude, \
-                       ent, counts, bias)
-        if (bias) {
-            if (vec) RK_LAUNCH_A(true, true);
-            else RK_LAUNCH_A(false, true);
+#define RK_LAUNCH_A(V, BI, WI)                                                                                             \
+    hipLaunchKernelGGL((rank_entries_kernel<V, BI, WI>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets, exclude, \
+                       ent, counts, bias, win)
+        if (windowed && bias) {
+            if (vec) RK_LAUNCH_A(true, true, true);
+            else RK_LAUNCH_A(false, true, true);
+        } else if (windowed) {
+            if (vec) RK_LAUNCH_A(true, false, true);
+            else RK_LAUNCH_A(false, false, true);
+        } else if (bias) {
+            if (vec) RK_LAUNCH_A(true, true, false);
+            else RK_LAUNCH_A(false, true, false);
         } else {
-            if (vec) RK_LAUNCH_A(true, false);
-            else RK_LAUNCH_A(false, false);
+            if (vec) RK_LAUNCH_A(true, false, false);
+            else RK_LAUNCH_A(false, false, false);
         }
 #undef RK_LAUNCH_A
         snprintf(what, sizeof what, "%s(entries)", who);
         int rc = check_launch(what);
         if (rc != NRMS_OK) return rc;
         const dim3 grid_b(g.tiles, g.S);
-#define RK_LAUNCH_B(V, BI)                                                                                                 \
-    hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, V, BI>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M, g.slice_len, user, \
-                       items, ent, counts, bias)
-        if (bias) {
-            if (vec) RK_LAUNCH_B(true, true);
-            else RK_LAUNCH_B(false, true);
+#define RK_LAUNCH_B(V, BI, WI)                                                                                             \
+    hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, V, BI, WI>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M, g.slice_len, user, \
+                       items, ent, counts, bias, win)
+        if (windowed && bias) {
+            if (vec) RK_LAUNCH_B(true, true, true);
+            else RK_LAUNCH_B(false, true, true);
+        } else if (windowed) {
+            if (vec) RK_LAUNCH_B(true, false, true);
+            else RK_LAUNCH_B(false, false, true);
+        } else if (bias) {
+            if (vec) RK_LAUNCH_B(true, true, false);
+            else RK_LAUNCH_B(false, true, false);
         } else {
-            if (vec) RK_LAUNCH_B(true, false);
-            else RK_LAUNCH_B(false, false);
+            if (vec) RK_LAUNCH_B(true, false, false);
+            else RK_LAUNCH_B(false, false, false);
         }
 #undef RK_LAUNCH_B
         snprintf(what, sizeof what, "%s(count)", who);
@@ -382,7 +442,7 @@ static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
 extern "C" int nrms_rank_dot(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
                              const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
                              float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
-    return rank_dot_call("rank_dot", B, N, d, T, user, items, nullptr, targets, exclude, n_exclude, ranks, target_scores, workspace,
+    return rank_dot_call("rank_dot", B, N, d, T, user, items, nullptr, false, nullptr, nullptr, targets, exclude, n_exclude, ranks, target_scores, workspace,
                          workspace_bytes, stream);
 }
 
@@ -394,6 +454,19 @@ extern "C" size_t nrms_rank_dot_biased_workspace_bytes(int32_t B, int64_t N, int
 extern "C" int nrms_rank_dot_biased(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
                                     const float* bias, const int64_t* targets, const int64_t* exclude, int32_t n_exclude,
                                     int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
-    return rank_dot_call("rank_dot_biased", B, N, d, T, user, items, bias, targets, exclude, n_exclude, ranks, target_scores,
-                         workspace, workspace_bytes, stream);
+    return rank_dot_call("rank_dot_biased", B, N, d, T, user, items, bias, false, nullptr, nullptr, targets, exclude, n_exclude,
+                         ranks, target_scores, workspace, workspace_bytes, stream);
+}
+
+// The windowed call's workspace is the unwindowed call's: the same entries and counts.
+extern "C" size_t nrms_rank_dot_windowed_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude) {
+    return nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude);
+}
+
+extern "C" int nrms_rank_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                                      const float* bias, const int32_t* item_time, const int32_t* window, const int64_t* targets,
+                                      const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    return rank_dot_call("rank_dot_windowed", B, N, d, T, user, items, bias, true, item_time, window, targets, exclude, n_exclude,
+                         ranks, target_scores, workspace, workspace_bytes, stream);
 }

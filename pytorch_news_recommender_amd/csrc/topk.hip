@@ -21,6 +21,10 @@
 //
 // nrms_topk_dot_biased runs the two kernels of nrms_topk_dot with a per-item prior added to every finished score (the BIAS
 // instantiations of topk_slice_kernel): entries carry s' = s + bias[n], everything after the add is the same code.
+//
+// nrms_topk_dot_windowed adds a per-user eligibility interval on a per-item timestamp (the WINDOW instantiations, with or
+// without BIAS): two integer compares in the filter, and a wave whose 64 items are closed to all 32 users of its block skips
+// its loads and its MFMA chain (topk_kernels.h describes the skip and why no block barrier can notice it).
 #include "topk_kernels.h"    // the kernels and their launcher, shared with softmaxsample.hip
 
 namespace nrms {
@@ -82,9 +86,10 @@ extern "C" size_t nrms_topk_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
     return 256 + (size_t)B * (size_t)g.S * (size_t)k * sizeof(uint64_t);     // never 0 for accepted arguments
 }
 
-// nrms_topk_dot (bias null, who "topk_dot") and nrms_topk_dot_biased: one body, so the checks and the launch cannot drift apart.
+// nrms_topk_dot (bias null, who "topk_dot"), nrms_topk_dot_biased and nrms_topk_dot_windowed (windowed: item_time and window
+// are required): one body, so the checks and the launch cannot drift apart.
 static int topk_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
-                         const float* bias, const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids,
+                         const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids,
                          void* workspace, size_t workspace_bytes, void* stream) {
     NRMS_REQUIRE(B >= 0, "%s: B must be >= 0 (B=%d)", who, B);
     NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "%s: N must be in [0, %d] (N=%lld)", who, TK_MAX_N, (long long)N);
@@ -95,6 +100,12 @@ static int topk_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     NRMS_REQUIRE(user, "%s: user is null", who);
     NRMS_REQUIRE(items || N == 0, "%s: items is null", who);
     NRMS_REQUIRE(((uintptr_t)bias & 3) == 0, "%s: bias must be 4-byte aligned", who);
+    if (windowed) {
+        NRMS_REQUIRE(item_time || N == 0, "%s: item_time is null", who);
+        NRMS_REQUIRE(((uintptr_t)item_time & 3) == 0, "%s: item_time must be 4-byte aligned", who);
+        NRMS_REQUIRE(window, "%s: window is null", who);
+        NRMS_REQUIRE(((uintptr_t)window & 3) == 0, "%s: window must be 4-byte aligned", who);
+    }
     NRMS_REQUIRE(top_scores, "%s: top_scores is null", who);
     NRMS_REQUIRE(top_ids, "%s: top_ids is null", who);
     NRMS_REQUIRE(workspace, "%s: workspace is null", who);
@@ -108,13 +119,14 @@ static int topk_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     hipStream_t s = (hipStream_t)stream;
     TimingScope ts(who, s);
     return topk_launch(false, B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids,
-                       (uint64_t*)workspace, s, who, TkNoise{nullptr, 0.0f, 0}, bias);
+                       (uint64_t*)workspace, s, who, TkNoise{nullptr, 0.0f, 0}, bias,
+                       windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr});
 }
 
 extern "C" int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
                              const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    return topk_dot_call("topk_dot", B, N, d, k, user, items, nullptr, exclude, n_exclude, top_scores, top_ids, workspace,
+    return topk_dot_call("topk_dot", B, N, d, k, user, items, nullptr, false, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids, workspace,
                          workspace_bytes, stream);
 }
 
@@ -126,8 +138,21 @@ extern "C" size_t nrms_topk_dot_biased_workspace_bytes(int32_t B, int64_t N, int
 extern "C" int nrms_topk_dot_biased(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
                                     const float* bias, const int64_t* exclude, int32_t n_exclude, float* top_scores,
                                     int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream) {
-    return topk_dot_call("topk_dot_biased", B, N, d, k, user, items, bias, exclude, n_exclude, top_scores, top_ids, workspace,
-                         workspace_bytes, stream);
+    return topk_dot_call("topk_dot_biased", B, N, d, k, user, items, bias, false, nullptr, nullptr, exclude, n_exclude, top_scores,
+                         top_ids, workspace, workspace_bytes, stream);
+}
+
+// The windowed call's workspace is the unwindowed call's: the same slice lists, of the eligible entries only.
+extern "C" size_t nrms_topk_dot_windowed_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k) {
+    return nrms_topk_dot_workspace_bytes(B, N, d, k);
+}
+
+extern "C" int nrms_topk_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                                      const float* bias, const int32_t* item_time, const int32_t* window, const int64_t* exclude,
+                                      int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    return topk_dot_call("topk_dot_windowed", B, N, d, k, user, items, bias, true, item_time, window, exclude, n_exclude,
+                         top_scores, top_ids, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t nrms_topk_grouped_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G) {

@@ -147,15 +147,29 @@ __device__ inline void tk_drop_excluded(uint64_t* buf, int cnt, const int32_t* e
 // read per tile, issued before the MFMA loop so that the loop hides its latency) and, before the filter, adds it to the tile's 16
 // finished accumulator registers: one fp32 add per score, after the chain, never folded into it.  A NaN sum fails the filter's
 // NaN test like a NaN score; entries simply carry s'.
-template <int P, int W, bool VEC, bool GROUPED, bool NOISE, bool BIAS>
+//
+// WINDOW (nrms_topk_dot_windowed; with or without BIAS): the block stages its 32 users' (lo, hi) in LDS once and forms their
+// hull [blo, bhi).  Lane (r, h) loads item_time[n] of its item in each of its two column tiles where bv[] is loaded, and the
+// filter takes (user, item) only if lo <= time < hi (hi <= INT32_MAX, so a time of INT32_MAX is open to nobody).  Dead-tile
+// skip: one __ballot over "my item's time lies in [blo, bhi)" decides, wave-uniformly, whether the wave has anything to offer
+// in this step; if not it issues no item loads, no LDS staging and no MFMA and goes to the block's __syncthreads_or with
+// pend == 0.  The skipped region holds the chain alone, which touches only the wave's private stage[wave] and wave-level
+// syncs: every wave still meets every block barrier, the same number of times.
+//
+// The window's two pointers are a kernel argument of the WINDOW instantiations alone (WIN is TkWindow there and empty
+// elsewhere), so every other instantiation keeps the signature, the kernarg layout and the code it had without the flag.
+template <int P, int W, bool VEC, bool GROUPED, bool NOISE, bool BIAS, bool WINDOW, class... WIN>
 __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d, int k, int slice_len, int S,
                                                             const float* __restrict__ user, const float* __restrict__ items,
                                                             const int64_t* __restrict__ exclude, int n_exclude,
                                                             uint64_t* __restrict__ ws, int G, int n_tiles,
                                                             const TkTile* __restrict__ tiles,
                                                             const int32_t* __restrict__ item_ids, TkNoise noise,
-                                                            const float* __restrict__ bias) {
+                                                            const float* __restrict__ bias, WIN... win_arg) {
+    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0), "WINDOW kernels take one TkWindow, the others none");
+    const TkWindow win = tk_window_arg(win_arg...);
     static_assert(!(NOISE && GROUPED), "the perturbation is keyed by the item's row");
+    static_assert(!(WINDOW && (GROUPED || NOISE)), "the window is for the plain and the biased top-k only");
     static_assert(!(BIAS && (GROUPED || NOISE)), "the prior is for the plain top-k only");
     __shared__ uint64_t buf[TK_UT][P];
     __shared__ uint64_t rseed[NOISE ? TK_UT : 1];
@@ -171,6 +185,12 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     const int n_begin = slice * slice_len;
     const int n_end = min(GROUPED ? 32 * n_tiles : N, n_begin + slice_len);      // (grouped: tile rows, not catalogue rows)
     const bool ex_lds = n_exclude <= TK_EX_LDS;
+    int2* wwin = nullptr;          // WINDOW: the block's 32 (lo, hi)
+    if constexpr (WINDOW) {
+        __shared__ int2 wwin_lds[TK_UT];
+        wwin = wwin_lds;
+        tk_window_stage(wwin, win.window, u0, B);
+    }
 
     if (threadIdx.x < TK_UT) {
         thr[threadIdx.x] = 0;
@@ -185,6 +205,8 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
             else ex[u][e] = (v >= n_begin && v < n_end) ? (int32_t)v : -1;
         }
     __syncthreads();
+    int blo = 0, bhi = 0;
+    if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
 
     // cut user i's buffer (c entries) down to its best k, excluded ids dropped; returns the new threshold, sets c
     auto flush = [&](int i, int& c) {
@@ -223,7 +245,21 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 for (int c = 0; c < TK_TN; ++c) bv[c] = bias[min(nw + 32 * c + r, N - 1)];
             }
         }
-        if (nw < n_end && (!GROUPED || tlen[0] + tlen[1] > 0)) {
+        int tv[WINDOW ? TK_TN : 1] = {};         // WINDOW: the time of this lane's item in column tile c
+        bool dead = false;                       // WINDOW: no item of this wave's step is open to any user of the block (wave-uniform)
+        if constexpr (WINDOW) {
+            if (nw < n_end) {
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) {
+                    const int n = nw + 32 * c + r;
+                    tv[c] = win.item_time[min(n, N - 1)];
+                    any |= n < n_end && tv[c] >= blo && tv[c] < bhi;
+                }
+                dead = TK_WINDOW_SKIP && __ballot(any) == 0;
+            }
+        }
+        if (nw < n_end && (!GROUPED || tlen[0] + tlen[1] > 0) && !(WINDOW && dead)) {
             const float* srow[8];           // rows this lane stages: 8j + lane / 8
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -322,10 +358,16 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 live = live && r < tlen[c];
                 if (live) gid[c] = (uint32_t)item_ids[trow[c] + r];
             }
+            if constexpr (WINDOW) live = live && !dead;       // a skipped wave offers nothing: its accumulators hold no score
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int b = u0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if (live && b < B && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
+                if constexpr (WINDOW) {
+                    const int2 w = wwin[b - u0];
+                    if (live && b < B && tv[c] >= w.x && tv[c] < w.y && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
+                } else {
+                    if (live && b < B && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
+                }
             }
         }
         bool first = true;
@@ -427,11 +469,13 @@ static bool topk_args_ok(int32_t B, int64_t N, int32_t d, int32_t k) {
 }
 
 // Both kernels of one call.  grouped: `user` is the query [B, G, d], the slices run over the tile rows of `tiles`.
-// bias (plain top-k only, [N] fp32): non-null selects the BIAS instantiations.
+// bias (plain top-k only, [N] fp32): non-null selects the BIAS instantiations.  win (plain top-k only, with or without bias):
+// a non-null window selects the WINDOW instantiations.
 static int topk_launch(bool grouped, int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int64_t n_tiles, const float* user,
                        const float* items, const int32_t* item_ids, const TkTile* tiles, const int64_t* exclude, int32_t n_exclude,
                        float* top_scores, int64_t* top_ids, uint64_t* ws, hipStream_t s, const char* who,
-                       TkNoise noise = TkNoise{nullptr, 0.0f, 0}, const float* bias = nullptr) {
+                       TkNoise noise = TkNoise{nullptr, 0.0f, 0}, const float* bias = nullptr,
+                       TkWindow win = TkWindow{nullptr, nullptr}) {
     const TopkGeom g = topk_geom(B, grouped ? 32 * n_tiles : N);
     char what[64];
     if (g.S > 0) {
@@ -439,8 +483,11 @@ static int topk_launch(bool grouped, int32_t B, int64_t N, int32_t d, int32_t k,
         const dim3 grid(g.tiles, g.S);
         const int n = (int)N, nt = (int)n_tiles;
 #define TK_LAUNCH_G(P, W, V, GR, NS, BI)                                                                                   \
-    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, GR, NS, BI>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S, user, \
+    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, GR, NS, BI, false>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S, user, \
                        items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias)
+#define TK_LAUNCH_W(P, W, V, BI)                                                                                           \
+    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, false, false, BI, true, TkWindow>), grid, dim3(64 * W), 0, s, B, n, d, k,     \
+                       g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias, win)
 #define TK_LAUNCH(P, W)                                                                                                    \
     do {                                                                                                                   \
         if (grouped) {                                                                                                     \
@@ -449,6 +496,12 @@ static int topk_launch(bool grouped, int32_t B, int64_t N, int32_t d, int32_t k,
         } else if (noise.row_key) {                                                                                        \
             if (vec) TK_LAUNCH_G(P, W, true, false, true, false);                                                          \
             else TK_LAUNCH_G(P, W, false, false, true, false);                                                             \
+        } else if (win.window && bias) {                                                                                   \
+            if (vec) TK_LAUNCH_W(P, W, true, true);                                                    \
+            else TK_LAUNCH_W(P, W, false, true);                                                       \
+        } else if (win.window) {                                                                                           \
+            if (vec) TK_LAUNCH_W(P, W, true, false);                                                   \
+            else TK_LAUNCH_W(P, W, false, false);                                                      \
         } else if (bias) {                                                                                                 \
             if (vec) TK_LAUNCH_G(P, W, true, false, false, true);                                                          \
             else TK_LAUNCH_G(P, W, false, false, false, true);                                                             \
@@ -462,6 +515,7 @@ static int topk_launch(bool grouped, int32_t B, int64_t N, int32_t d, int32_t k,
         else TK_LAUNCH(512, 2);
 #undef TK_LAUNCH
 #undef TK_LAUNCH_G
+#undef TK_LAUNCH_W
         snprintf(what, sizeof what, "%s(slices)", who);
         const int rc = check_launch(what);
         if (rc != NRMS_OK) return rc;

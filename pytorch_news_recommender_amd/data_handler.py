@@ -227,6 +227,7 @@ class SyntheticMind:
         self.rng = rng
         self.imp_rng = np.random.default_rng(seed + 2000003)       # train_impressions' own stream, as the abstracts have theirs
         self.click_rng = np.random.default_rng(seed + 3000003)     # click_log's own stream
+        self.tick_seed = seed + 4000003                            # click_ticks' own generator, made anew by every call
         self.by_topic = [np.flatnonzero(self.topic == t) + 1 for t in range(n_topics)]   # 1-based ids
 
     def embedding_table(self, d, seed=0):
@@ -320,6 +321,24 @@ class SyntheticMind:
             clicks += self._pick(t, n, rng=rng)
             lens.append(n)
         return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(clicks, dtype=np.int64)
+
+    def click_ticks(self, user_ptr, horizon=100000, max_step=200):
+        """Ticks for an existing ``click_log``: int64 [len(clicks)] for ``ClickFeed(click_time=...)``.  Every user gets a start tick
+        in [0, horizon) and rising increments in [1, max_step] from click to click, so the ticks rise strictly inside a user and
+        stay below horizon + max_step * (the longest log).  A function of (the corpus seed, user_ptr, horizon, max_step) alone:
+        the generator is made anew by every call, and neither ``click_log`` nor any other stream moves."""
+        user_ptr = np.asarray(user_ptr, dtype=np.int64).reshape(-1)
+        rng = np.random.default_rng(self.tick_seed)
+        lens = np.diff(user_ptr)
+        total = int(user_ptr[-1])
+        start = rng.integers(0, int(horizon), size=lens.size)
+        step = rng.integers(1, int(max_step) + 1, size=total)
+        first = user_ptr[:-1][lens > 0]
+        step[first] = 0
+        run = np.cumsum(step)
+        ticks = run - np.repeat(run[first], lens[lens > 0]) + np.repeat(start[lens > 0], lens[lens > 0])
+        assert ticks.size == 0 or ticks.max() < 2 ** 31 - 1
+        return ticks.astype(np.int64)
 
 
 class LazyBatch(Mapping):
@@ -720,6 +739,11 @@ class ClickFeed(DeviceFeed):
     draw over the catalogue minus a few dozen news, a relative change of about (the weight share of those news), far below what
     the correction is for.
 
+    ``click_time``: int64 [len(clicks)] ticks (any unit), non-decreasing inside every user, in [0, 2^31 - 1), or None.  With it
+    ``news_first_seen()`` gives the per-news timestamp and ``heldout_times()`` the request tick of every held-out sample, for
+    ranking inside a time window of the catalogue (``evaluate_retrieval(item_time=..., request_time=..., window_span=...)``);
+    nothing else reads it, and without it everything is as it was.
+
     ``negatives="adaptive"`` (default ``"popularity"``, everything above) draws a row's S negatives from the MODEL's own softmax
     over the catalogue instead, softmax(score / ``temperature``) without replacement (``Model.sample_negatives``,
     ``nrms_softmax_sample_dot``), with the weights of the model named by ``attach_scorer(model)`` as they are when the epoch
@@ -737,8 +761,9 @@ class ClickFeed(DeviceFeed):
 
     def __init__(self, config, user_ptr, clicks, id2title_dict=None, id2abst_dict=None, news_categ=None, news_subcateg=None, holdout=1,
                  min_history=1, popularity_power=0.75, weights=None, batch_size=None, device="cuda", shuffle=False, drop_last=False, seed=0,
-                 resample=True, rank=0, world=1, negatives="popularity", temperature=1.0):
+                 resample=True, rank=0, world=1, negatives="popularity", temperature=1.0, click_time=None):
         user_ptr, clicks = np.asarray(user_ptr, dtype=np.int64).reshape(-1), np.asarray(clicks, dtype=np.int64).reshape(-1)
+        self.click_time = self._checked_click_time(click_time, user_ptr, clicks)
         if negatives not in ("popularity", "adaptive"):
             raise ValueError("ClickFeed: negatives = %r must be 'popularity' or 'adaptive'" % (negatives,))
         if not (float(temperature) > 0.0 and np.isfinite(float(temperature))):
@@ -818,6 +843,55 @@ class ClickFeed(DeviceFeed):
         self.draws, self.drawn_seed, self.n_short = 0, None, None
         self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)     # n_short, n_bad
         self._ws = None
+
+    @staticmethod
+    def _checked_click_time(click_time, user_ptr, clicks):
+        """None, or the log's ticks as an int64 host array: one per click, non-decreasing inside every user, in [0, 2^31 - 1)."""
+        if click_time is None:
+            return None
+        t = np.asarray(click_time)
+        if t.dtype.kind not in "iu" or t.shape != (clicks.size,):
+            raise ValueError("ClickFeed: click_time must be an integer array of len(clicks) = %d ticks, got %s %s"
+                             % (clicks.size, t.dtype, t.shape))
+        t = t.astype(np.int64)
+        if t.size and (t.min() < 0 or t.max() >= 2 ** 31 - 1):
+            raise ValueError("ClickFeed: click_time must lie in [0, 2^31 - 1) (2^31 - 1 is the 'not published' value), got [%d, %d]"
+                             % (t.min(), t.max()))
+        if t.size > 1 and user_ptr.size >= 1 and user_ptr[0] == 0 and int(user_ptr[-1]) == t.size:
+            falls = np.diff(t) < 0
+            starts = user_ptr[1:-1][(user_ptr[1:-1] > 0) & (user_ptr[1:-1] < t.size)]
+            falls[starts - 1] = False                        # a new user may start earlier than the last one ended
+            if falls.any():
+                raise ValueError("ClickFeed: click_time must not decrease inside a user (it does at log position %d)"
+                                 % (int(np.flatnonzero(falls)[0]) + 1))
+        return t
+
+    def _need_click_time(self, who):
+        if self.click_time is None:
+            raise ValueError("ClickFeed.%s: the feed was built without click_time" % who)
+        return self.click_time
+
+    def news_first_seen(self):
+        """int32 [N] on the feed's device: the earliest tick at which anyone clicked the news, over the WHOLE log, held-out clicks
+        included (when a news appeared is catalogue metadata, not a label); a never-clicked news and entry 0, the padding
+        title's, hold INT32_MAX, "not published".  The ``item_time`` of ``Model.recommend`` / ``rank_targets``."""
+        t = self._need_click_time("news_first_seen")
+        first = np.full(self.n_news, 2 ** 31 - 1, dtype=np.int64)
+        np.minimum.at(first, self.clicks.cpu().numpy(), t)
+        first[0] = 2 ** 31 - 1
+        return torch.from_numpy(first.astype(np.int32)).to(self.device)
+
+    def heldout_times(self):
+        """int64 host array: the request tick of every sample of ``heldout_samples()``, in the same order: the tick of the user's
+        first held-out click."""
+        t = self._need_click_time("heldout_times")
+        user_ptr = self.user_ptr.cpu().numpy()
+        out = []
+        for u in np.flatnonzero(self.live_users):
+            end = int(user_ptr[u] + self._train_len[u])
+            if end < int(user_ptr[u + 1]):
+                out.append(int(t[end]))
+        return np.asarray(out, dtype=np.int64)
 
     @staticmethod
     def pool_logq(pos_rows, weights, sample_size):

@@ -754,13 +754,36 @@ class NRMSEngine:
             raise _lib.NrmsError("%s: bias must be a contiguous [%d] float32 tensor on %s (got %s)" % (who, N, self.device, got))
         return bias
 
-    def top_k(self, user_vec, items, k, exclude=None, bias=None):
+    def _time_window(self, who, item_time, window, N, B, dev):
+        """The checked time window of top_k / rank_of: (item_time [N], window [B, 2]) as contiguous int32 tensors on the device,
+        or (None, None) when neither is given.  int64 tensors are accepted when every value fits int32 (one host check)."""
+        if item_time is None and window is None:
+            return None, None
+        if item_time is None or window is None:
+            raise _lib.NrmsError("%s: item_time and window go together (window %s, item_time %s)"
+                                 % (who, "missing" if window is None else "given", "missing" if item_time is None else "given"))
+        out = []
+        for name, t, shape in (("item_time", item_time, (N,)), ("window", window, (B, 2))):
+            if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype not in (torch.int32, torch.int64) or t.device != dev):
+                got = ("%s %s on %s" % (tuple(t.shape), t.dtype, t.device)) if torch.is_tensor(t) else type(t).__name__
+                raise _lib.NrmsError("%s: %s must be an int32 (or int64) %s tensor on %s (got %s)" % (who, name, list(shape), self.device, got))
+            if t.dtype == torch.int64:
+                if t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) > 2 ** 31 - 1):
+                    raise _lib.NrmsError("%s: %s holds values outside int32 (min %d, max %d)" % (who, name, int(t.min()), int(t.max())))
+                t = t.to(torch.int32)
+            out.append(t.contiguous())
+        return out[0], out[1]
+
+    def top_k(self, user_vec, items, k, exclude=None, bias=None, *, item_time=None, window=None):
         """user_vec [B, d], items [N, d] fp32, exclude [B, n_exclude] int64 or None (device, contiguous) -> (scores [B, k]
         fp32, ids [B, k] int64): per user the k items of largest user . item, no [B, N] matrix (nrms_topk_dot).  Order:
         score descending, then the smaller id; rows with fewer than k eligible items end in id -1 / score -inf; excluded
         ids and NaN scores are never returned.  bias [N] fp32 (device, contiguous) or None: a per-item prior, the order and
         the returned scores are those of user . item + bias[n] (one fp32 add; a NaN bias removes the item for every user;
-        nrms_topk_dot_biased).  None calls nrms_topk_dot as before.  include/nrms_hip.h states the contract."""
+        nrms_topk_dot_biased).  None calls nrms_topk_dot as before.  item_time [N] int32 and window [B, 2] int32 (device; both
+        or neither): user b only gets items with window[b, 0] <= item_time[n] < window[b, 1] (signed, half-open; lo >= hi is an
+        all-padding row; a time of INT32_MAX is never eligible; nrms_topk_dot_windowed, with the bias when one is given).
+        include/nrms_hip.h states the contract."""
         k = int(k)
         dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32)):
@@ -783,12 +806,19 @@ class NRMSEngine:
                 exclude = None
         if bias is not None:
             self._item_bias("top_k", bias, N, dev)
+        item_time, window = self._time_window("top_k", item_time, window, N, B, dev)
         nbytes = self.lib.nrms_topk_dot_workspace_bytes(B, N, d, k)
         if nbytes == 0:
             raise _lib.NrmsError("top_k: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (B, N, d, k))
         ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
         scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
         ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        if window is not None:
+            rc = self.lib.nrms_topk_dot_windowed(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                                 _lib.ptr(item_time), _lib.ptr(window), _lib.ptr(exclude), n_ex, _lib.ptr(scores),
+                                                 _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_topk_dot_windowed")
+            return scores, ids
         if bias is not None:
             rc = self.lib.nrms_topk_dot_biased(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
                                                _lib.ptr(exclude), n_ex, _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws),
@@ -891,7 +921,7 @@ class NRMSEngine:
             out += (ild,)
         return out
 
-    def rank_of(self, user_vec, items, targets, exclude=None, bias=None):
+    def rank_of(self, user_vec, items, targets, exclude=None, bias=None, *, item_time=None, window=None):
         """user_vec [B, d], items [N, d] fp32, targets [B, T] int64, exclude [B, n_exclude] int64 or None (device, contiguous)
         -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position of every target in top_k's order over the
         whole catalogue (the same score bits, exclude list, NaN rule and tie rule), at any depth and without a [B, N] matrix
@@ -899,7 +929,9 @@ class NRMSEngine:
         back as rank 0 / score -inf; targets do not remove each other.  The kernel takes 32 targets per call: wider
         ``targets`` go in column chunks of 32.  bias [N] fp32 (device, contiguous) or None: top_k's per-item prior, ranks and
         scores are those of user . item + bias[n] (a target whose bias is NaN gets rank 0 / -inf; nrms_rank_dot_biased).  None
-        calls nrms_rank_dot as before.  include/nrms_hip.h states the contract."""
+        calls nrms_rank_dot as before.  item_time [N] int32 and window [B, 2] int32 (device; both or neither): top_k's time window,
+        ranks count the items inside user b's window only and a target outside it gets rank 0 / -inf (nrms_rank_dot_windowed).
+        include/nrms_hip.h states the contract."""
         dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32), ("targets", targets, torch.int64)):
             if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
@@ -923,6 +955,7 @@ class NRMSEngine:
                 exclude = None
         if bias is not None:
             self._item_bias("rank_of", bias, N, dev)
+        item_time, window = self._time_window("rank_of", item_time, window, N, B, dev)
         T_all = targets.shape[1]
         ranks = torch.empty(B, T_all, dtype=torch.int32, device=self.device)
         scores = torch.empty(B, T_all, dtype=torch.float32, device=self.device)
@@ -936,7 +969,12 @@ class NRMSEngine:
             if nbytes == 0:
                 raise _lib.NrmsError("rank_of: arguments rejected (B=%d, N=%d, d=%d, T=%d, n_exclude=%d)" % (B, N, d, T, n_ex))
             ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
-            if bias is not None:
+            if window is not None:
+                rc = self.lib.nrms_rank_dot_windowed(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                                     _lib.ptr(item_time), _lib.ptr(window), _lib.ptr(tg), _lib.ptr(exclude), n_ex,
+                                                     _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+                _lib.check(rc, "nrms_rank_dot_windowed")
+            elif bias is not None:
                 rc = self.lib.nrms_rank_dot_biased(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
                                                    _lib.ptr(tg), _lib.ptr(exclude), n_ex, _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws),
                                                    C.c_size_t(ws.numel() * 8), _stream())

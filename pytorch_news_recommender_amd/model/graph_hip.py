@@ -215,7 +215,10 @@ class Model(FlatHipModel):
     CATALOGUE_RANKING = False
     CATALOGUE_SAMPLING = False          # the catalogue score is not one dot product per user: no sample_negatives
 
-    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None):
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        if item_time is not None or window is not None:
+            raise _lib.NrmsError("graph: rank_targets takes no item_time / window: the model cannot rank a catalogue at all, a "
+                                 "candidate's score depends on its neighbours in the click graph")
         if item_bias is not None:
             raise _lib.NrmsError("graph: rank_targets takes no item_bias: the model cannot rank a catalogue at all, a candidate's "
                                  "score depends on its neighbours in the click graph")
@@ -223,7 +226,10 @@ class Model(FlatHipModel):
                                   "click graph, not on a catalogue row alone (no recommend either)")
 
     def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
-                  item_bias=None):
+                  item_bias=None, item_time=None, window=None):
+        if item_time is not None or window is not None:
+            raise _lib.NrmsError("graph: recommend takes no item_time / window: the model cannot recommend from a catalogue at "
+                                 "all, a candidate's score depends on its neighbours in the click graph")
         if item_bias is not None:
             raise _lib.NrmsError("graph: recommend takes no item_bias: the model cannot recommend from a catalogue at all, a "
                                  "candidate's score depends on its neighbours in the click graph")

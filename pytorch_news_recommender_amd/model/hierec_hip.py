@@ -306,7 +306,7 @@ class Model(FlatHipModel):
 
     @torch.no_grad()
     def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
-                  item_bias=None):
+                  item_bias=None, item_time=None, window=None):
         """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores [B, k]
         fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_grouped_dot).  The diversity
         re-ranking of nrms_hip.Model.recommend is refused (NrmsError): it works on a row-ordered catalogue.  So is its
@@ -317,6 +317,9 @@ class Model(FlatHipModel):
         a news item's score is its forward score as that user's candidate.  Ids outside the catalogue are read as padding
         and counted (check_recommend_ids raises).  News id 0 is never returned, with exclude_history neither is a browsed
         id; missing slots get id -1 / score -inf."""
+        if item_time is not None or window is not None:
+            raise _lib.NrmsError("hierec: recommend takes no item_time / window: its catalogue is scored with a query per (topic, "
+                                 "sub-topic) group (nrms_topk_grouped_dot), which has no time window")
         if item_bias is not None:
             raise _lib.NrmsError("hierec: recommend takes no item_bias: its catalogue is scored with a query per (topic, "
                                  "sub-topic) group (nrms_topk_grouped_dot), which has no per-item prior")
@@ -348,7 +351,10 @@ class Model(FlatHipModel):
     CATALOGUE_RANKING = False
     CATALOGUE_SAMPLING = False          # the catalogue score is not one dot product per user: no sample_negatives
 
-    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None):
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        if item_time is not None or window is not None:
+            raise _lib.NrmsError("hierec: rank_targets takes no item_time / window: HieRec scores the catalogue with a query per "
+                                 "(topic, sub-topic) group (nrms_topk_grouped_dot), which has no time window and no exact rank")
         if item_bias is not None:
             raise _lib.NrmsError("hierec: rank_targets takes no item_bias: HieRec scores the catalogue with a query per (topic, "
                                  "sub-topic) group (nrms_topk_grouped_dot), which has no per-item prior and no exact rank")

@@ -187,7 +187,7 @@ class Model(FlatHipModel):
 
     @torch.no_grad()
     def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
-                  item_bias=None):
+                  item_bias=None, item_time=None, window=None):
         """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores
         [B, k] fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_dot).
 
@@ -210,7 +210,13 @@ class Model(FlatHipModel):
         item_bias[id] (one fp32 add; include/nrms_hip.h nrms_topk_dot_biased), e.g. ``ClickFeed.popularity_prior``, a
         freshness decay or an editorial boost.  A NaN entry removes that news for every user (a global block-list); -inf
         puts it last.  With ``diversity`` the shortlist comes from the biased top-k and the re-ranker scales the biased
-        scores to relevance; diversity = 1 with a bias is the biased plain list, bit for bit.  None is the call as it was."""
+        scores to relevance; diversity = 1 with a bias is the biased plain list, bit for bit.  None is the call as it was.
+
+        item_time: int [N] on the model's device, one tick per news id like the catalogue (entry 0 is never read); window:
+        int [B, 2].  Both or neither.  User b only gets news with window[b, 0] <= item_time[id] < window[b, 1] (signed int32,
+        half-open; lo >= hi gives an all-padding row; a time of INT32_MAX, "not published", is never eligible;
+        include/nrms_hip.h nrms_topk_dot_windowed), e.g. ``ClickFeed.news_first_seen()`` and a request time per user.  With
+        ``diversity`` the shortlist comes from the windowed top-k and the re-ranker is untouched.  None is the call as it was."""
         if diversity is None and shortlist is not None:
             raise _lib.NrmsError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
         if diversity is not None:
@@ -222,13 +228,14 @@ class Model(FlatHipModel):
                 raise _lib.NrmsError("recommend: with diversity, 1 <= k <= shortlist <= 256 (k=%d, shortlist=%d)" % (k, M))
         user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend")
         bias = self._item_bias_rows(item_bias, cat, "recommend")
+        win = self._time_window_rows(item_time, window, cat, user.shape[0], "recommend")
         if diversity is None:
-            scores, ids = self._engine.top_k(user, cat[1:], k, exclude, bias=bias)
+            scores, ids = self._engine.top_k(user, cat[1:], k, exclude, bias=bias, **win)
             out = (torch.where(ids >= 0, ids + 1, ids), scores)
             if return_ild:      # the plain list's ILD is the re-ranker's at lambda = 1, which keeps the list as it is
                 out += (self._engine.mmr_rerank(cat[1:], ids, scores, ids.shape[1], 1.0, return_ild=True)[2],)
             return out
-        s_scores, s_ids = self._engine.top_k(user, cat[1:], M, exclude, bias=bias)
+        s_scores, s_ids = self._engine.top_k(user, cat[1:], M, exclude, bias=bias, **win)
         res = self._engine.mmr_rerank(cat[1:], s_ids, s_scores, k, lam, return_ild=return_ild)
         return (torch.where(res[0] >= 0, res[0] + 1, res[0]), res[1]) + tuple(res[2:])
 
@@ -275,7 +282,7 @@ class Model(FlatHipModel):
         return ids, scores
 
     @torch.no_grad()
-    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None):
+    def rank_targets(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None):
         """The exact position of given news in each user's ranking of the whole catalogue -> (ranks [B, T] int32, scores
         [B, T] fp32): ranks[b, j] is the 1-based place news id targets[b, j] would take in recommend()'s list for user b
         were k unbounded (the same user vector, score bits, exclusions and tie rule; include/nrms_hip.h nrms_rank_dot), so
@@ -288,14 +295,19 @@ class Model(FlatHipModel):
 
         item_bias: recommend's per-news prior (float32 [N] by news id, or None).  Ranks and scores are then those of dot
         product + item_bias[id] (include/nrms_hip.h nrms_rank_dot_biased), so with the same ``item_bias`` the ids
-        recommend(k) returns still rank 1 .. k; a target whose prior is NaN is rank 0 / score -inf."""
+        recommend(k) returns still rank 1 .. k; a target whose prior is NaN is rank 0 / score -inf.
+
+        item_time, window: recommend's time window (int [N] by news id, int [B, 2]; both or neither).  Ranks then count the
+        news inside user b's window only (include/nrms_hip.h nrms_rank_dot_windowed), so with the same arguments the ids
+        recommend(k) returns still rank 1 .. k; a target outside its user's window is rank 0 / score -inf."""
         user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "rank_targets")
         bias = self._item_bias_rows(item_bias, cat, "rank_targets")
+        win = self._time_window_rows(item_time, window, cat, user.shape[0], "rank_targets")
         tg = torch.as_tensor(targets).to(user.device, dtype=torch.int64)
         if tg.dim() != 2 or tg.shape[0] != user.shape[0]:
             raise _lib.NrmsError("rank_targets: targets must be [%d, T] news ids (got %s)" % (user.shape[0], tuple(tg.shape)))
         # rows 1.. as in recommend: news id n is row n - 1, so id 0 (and -1) fall out of range and get rank 0
-        return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude, bias=bias)
+        return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude, bias=bias, **win)
 
     @torch.no_grad()
     def sample_negatives(self, batch, row_key, S, catalogue, temperature, seed, exclude=None):
@@ -335,6 +347,23 @@ class Model(FlatHipModel):
             raise _lib.NrmsError("%s: item_bias must be [%d] float32 on %s, indexed by news id like the catalogue (got %s)"
                                  % (who, N, cat.device, got))
         return item_bias.contiguous()[1:]
+
+    @staticmethod
+    def _time_window_rows(item_time, window, cat, B, who):
+        """The kernels' view of a time window: {} when neither is given, else item_time rows 1.. like the catalogue's and the
+        window, as keywords of engine.top_k / rank_of (which check dtype and range)."""
+        if item_time is None and window is None:
+            return {}
+        if item_time is None or window is None:
+            raise _lib.NrmsError("%s: item_time and window go together (window %s, item_time %s)"
+                                 % (who, "missing" if window is None else "given", "missing" if item_time is None else "given"))
+        N = cat.shape[0]
+        for name, t, shape in (("item_time", item_time, (N,)), ("window", window, (B, 2))):
+            if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype not in (torch.int32, torch.int64) or t.device != cat.device):
+                got = ("%s %s on %s" % (tuple(t.shape), t.dtype, t.device)) if torch.is_tensor(t) else type(t).__name__
+                raise _lib.NrmsError("%s: %s must be an int32 or int64 %s tensor on %s%s (got %s)"
+                                     % (who, name, list(shape), cat.device, ", indexed by news id like the catalogue" if name == "item_time" else "", got))
+        return {"item_time": item_time.contiguous()[1:], "window": window}
 
     def _catalogue_query(self, batch, catalogue, exclude_history, who):
         """What recommend and rank_targets share: (user vectors [B, width], the checked catalogue, the exclude list in

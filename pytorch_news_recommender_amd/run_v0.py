@@ -85,6 +85,9 @@ def build_parser():
     parser.add_argument('--popularity_prior', type=float, default=None, metavar='ALPHA', help='--negatives catalogue / adaptive: add the '
                         "per-news prior ALPHA * log(1 + the number of training users who clicked the news) to every catalogue score of "
                         '--recommend (with or without --diversity) and --retrieval_metrics (0 = none; held-out clicks are not counted)')
+    parser.add_argument('--catalogue_window', type=int, default=None, metavar='SPAN', help='--negatives catalogue / adaptive: give the '
+                        'synthetic click log ticks, and let --recommend and --retrieval_metrics see, per held-out click, only the news '
+                        'first clicked in the SPAN ticks up to the moment of that click (SPAN >= 1): the news that were live then')
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     parser.add_argument('--sections', type=str, default=None, choices=('category', 'subcategory'), help='--recommend: write the front '
                         'page by section instead, the top K news of every category (or sub-category) per impression, as '
@@ -176,6 +179,30 @@ def check_prior_args(args):
                          'row-ordered catalogue)' % args.model)
 
 
+def check_window_args(args):
+    """--catalogue_window fails before any data is read or any step is trained: SPAN >= 1, a list or a metric to apply it to, a
+    click log to take the ticks from, and a model that ranks a row-ordered catalogue."""
+    if args.catalogue_window is None:
+        return
+    if args.catalogue_window < 1:
+        raise SystemExit('--catalogue_window SPAN: SPAN must be >= 1 (got %d)' % args.catalogue_window)
+    if args.recommend is None and args.retrieval_metrics is None:
+        raise SystemExit('--catalogue_window SPAN: the window of --recommend K and --retrieval_metrics K (give one of them)')
+    if args.negatives not in ('catalogue', 'adaptive'):
+        raise SystemExit('--catalogue_window: the ticks belong to a click log (--negatives catalogue or adaptive, got %r)'
+                         % args.negatives)
+    if args.test:
+        raise SystemExit('--catalogue_window with --test: the request times are those of the held-out clicks of a training run')
+    if args.sections is not None:
+        raise SystemExit('--catalogue_window: the front page by section has no time window (drop --sections)')
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_RANKING', False):
+        raise SystemExit('--catalogue_window: model %r takes no time window (its catalogue score is no plain dot product over a '
+                         'row-ordered catalogue)' % args.model)
+
+
 def check_graph_args(args):
     """--graph global fails before any data is read: the graph model on the device feed only."""
     if args.graph != 'global':
@@ -246,6 +273,7 @@ def main(argv=None):
     check_sections_args(args)
     retrieval_ks = check_retrieval_args(args)
     check_prior_args(args)
+    check_window_args(args)
     check_graph_args(args)
     check_negatives_args(args)
     check_loss_args(args)
@@ -321,6 +349,7 @@ def main(argv=None):
                           num_workers=args.num_workers, drop_last=(world > 1 and typ == 0), shuffle=shuffle,
                           pin_memory=True)
 
+    item_window = {}         # item_time / request_time / window_span with --catalogue_window, otherwise no keyword at all
     item_prior = {}          # item_bias = the click feed's popularity prior with --popularity_prior, otherwise no keyword at all
 
     def recommend_top(samples):
@@ -334,13 +363,14 @@ def main(argv=None):
             return recommend_sections(config, recommender, feed, feed.titles, args.recommend, sections, out_file=args.recommend_out,
                                       **item_prior)
         if args.diversity is None:
-            return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior)
+            return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
+                             **item_window)
         # the plain list is the re-ranker's at lambda = 1 (bit for bit), which measures it with the same kernel
         net = recommender.model if hasattr(recommender, 'model') else recommender
         out = None
         for name, lam, dst in (('plain', 1.0, os.devnull), ('diversity %g' % args.diversity, args.diversity, args.recommend_out)):
             out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=dst, diversity=lam,
-                            shortlist=args.shortlist, **item_prior)
+                            shortlist=args.shortlist, **item_prior, **item_window)
             st = net.last_recommend_stats
             print('{}: ILD@{}: {:.4f}  coverage: {:.4f}  users: {}'.format(name, args.recommend, st['ild'], st['coverage'],
                                                                             st['n_users']))
@@ -353,7 +383,7 @@ def main(argv=None):
         net = recommender.model if hasattr(recommender, 'model') else recommender
         needs_info = 'categ' in inspect.signature(net.encode_catalogue).parameters           # nrms_naml's feature rows
         return evaluate_retrieval(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
-                                  news_info=feed.news_info() if needs_info else None, **item_prior)
+                                  news_info=feed.news_info() if needs_info else None, **item_prior, **item_window)
 
     def attach_graph(feed, samples=None):
         # the click graph is replicated: every rank builds it from ALL training samples (users shard, the graph does not)
@@ -379,10 +409,14 @@ def main(argv=None):
                                    popularity_power=args.negative_power, batch_size=config.batch_size, device=config.device, shuffle=True,
                                    drop_last=world > 1, seed=422, rank=rank, world=world,
                                    negatives='adaptive' if args.negatives == 'adaptive' else 'popularity',
-                                   temperature=args.negative_temperature)
+                                   temperature=args.negative_temperature,
+                                   click_time=corpus.click_ticks(click_ptr) if args.catalogue_window is not None else None)
             if args.negatives == 'adaptive':
                 train_feed.attach_scorer(recommender)
             held_samples, held_labels = train_feed.heldout_samples()
+            if args.catalogue_window is not None:
+                item_window.update(item_time=train_feed.news_first_seen(), request_time=train_feed.heldout_times(),
+                                   window_span=args.catalogue_window)
             if args.popularity_prior is not None:
                 item_prior['item_bias'] = train_feed.popularity_prior(args.popularity_prior)
         else:

@@ -329,8 +329,36 @@ def test(config, model, data_iter, test_list_nums=None, ckpt_file=None, out_file
     return file_name
 
 
+class _RequestWindows:
+    """The time-window keywords of recommend() / evaluate_retrieval(), turned into ``model.recommend`` / ``rank_targets`` keywords
+    batch by batch: sample i is served inside [request_time[i] - window_span, request_time[i] + 1), clamped to int32.  All three or
+    none (ValueError); with none, ``of`` returns {} and the model is called exactly as before."""
+
+    def __init__(self, who, item_time, request_time, window_span):
+        given = [item_time is not None, request_time is not None, window_span is not None]
+        self.on = all(given)
+        if any(given) and not self.on:
+            raise ValueError("%s: item_time, request_time and window_span go together" % who)
+        if not self.on:
+            return
+        span = int(window_span)
+        if span < 1:
+            raise ValueError("%s: window_span must be >= 1 (got %r)" % (who, window_span))
+        rt = np.asarray(request_time, dtype=np.int64).reshape(-1)
+        lo, hi = np.iinfo(np.int32).min, np.iinfo(np.int32).max
+        self.who, self.item_time = who, item_time
+        self.window = np.stack([np.clip(rt - span, lo, hi), np.clip(rt + 1, lo, hi)], axis=1).astype(np.int32)
+
+    def of(self, done, B, dev):
+        if not self.on:
+            return {}
+        if done + B > len(self.window):
+            raise ValueError("%s: %d request times for %d samples" % (self.who, len(self.window), done + B))
+        return {"item_time": self.item_time, "window": torch.from_numpy(self.window[done:done + B]).to(dev)}
+
+
 def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
-              shortlist=None, item_bias=None):
+              shortlist=None, item_bias=None, item_time=None, request_time=None, window_span=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
@@ -345,9 +373,15 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     synchronisation at the end; without it the attribute is set to None and the model is called exactly as before.
 
     item_bias: ``model.recommend``'s per-news prior (float32 [N] by news id on the model's device, e.g.
-    ``ClickFeed.popularity_prior(alpha)``), with or without ``diversity``.  None: the keyword is not passed at all."""
+    ``ClickFeed.popularity_prior(alpha)``), with or without ``diversity``.  None: the keyword is not passed at all.
+
+    item_time / request_time / window_span (all three or none): a time window of the catalogue per sample.  item_time: int [N]
+    by news id on the model's device (``ClickFeed.news_first_seen()``); request_time: one tick per sample of data_iter, in its
+    order; sample i only gets news with request_time[i] - window_span <= item_time[id] <= request_time[i]
+    (``model.recommend(item_time=..., window=...)``).  None: the keywords are not passed at all."""
     net = _inner(model)
     prior = {} if item_bias is None else {"item_bias": item_bias}
+    windows, done = _RequestWindows("recommend", item_time, request_time, window_span), 0
     if diversity is None and shortlist is not None:
         raise ValueError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
@@ -355,11 +389,19 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     if diversity is None:
         net.last_recommend_stats = None
         for datas in data_iter:
+            if windows.on:
+                B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
+                prior.update(windows.of(done, B, catalogue.device))
+                done += B
             ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history, **prior)
             lines.extend(ids.cpu().tolist())
     else:
         rows, ilds = [], []
         for datas in data_iter:
+            if windows.on:
+                B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
+                prior.update(windows.of(done, B, catalogue.device))
+                done += B
             ids, _, ild = net.recommend(datas, k, catalogue, exclude_history=exclude_history, diversity=diversity,
                                         shortlist=shortlist, return_ild=True, **prior)
             rows.append(ids)
@@ -415,7 +457,7 @@ def recommend_sections(config, model, data_iter, titles, k, sections, out_file=N
 
 
 def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
-                       verbose=True, item_bias=None):
+                       verbose=True, item_bias=None, item_time=None, request_time=None, window_span=None):
     """Full-catalogue retrieval quality on held-out clicks: per impression of data_iter the targets are its clicked news (the
     ``candidate_ids`` whose label in y_true is 1) and each is ranked against the whole catalogue in recommend()'s own order
     (``model.rank_targets``: the exact position, at any depth).  titles / news_info / exclude_history as in recommend();
@@ -429,9 +471,16 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     One host synchronisation, at the end.
 
     item_bias: ``model.rank_targets``'s per-news prior, so that the metrics describe the order ``recommend`` serves with the
-    same prior.  None: the keyword is not passed at all."""
+    same prior.  None: the keyword is not passed at all.
+
+    item_time / request_time / window_span (all three or none): recommend()'s time window.  Sample i's targets are ranked against
+    the news with request_time[i] - window_span <= item_time[id] <= request_time[i] only (``model.rank_targets(item_time=...,
+    window=...)``): the news that were live at the moment of the click, not news that did not exist yet or had long gone.  A
+    target outside its window counts as skipped.  For a target inside it the windowed rank is at most the unwindowed one.
+    None: the keywords are not passed at all."""
     net = _inner(model)
     prior = {} if item_bias is None else {"item_bias": item_bias}
+    windows = _RequestWindows("evaluate_retrieval", item_time, request_time, window_span)
     ks = tuple(int(k) for k in ks)
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
     dev = catalogue.device
@@ -440,6 +489,7 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
         cand = torch.as_tensor(datas["candidate_ids"]).to(dev, dtype=torch.int64)
         B, S = cand.shape
         rows = y_true[done:done + B]
+        prior.update(windows.of(done, B, dev))
         done += B
         if len(rows) < B:
             raise ValueError("evaluate_retrieval: %d label rows for %d impressions" % (len(y_true), done))
