@@ -21,85 +21,14 @@
 // nrms_rank_dot_windowed ranks inside a per-user interval on a per-item timestamp: the WINDOW instantiations of A and B test
 // lo <= item_time[n] < hi in front of tk_entry, and B skips the waves whose 64 items are closed to its whole block; C is the same.
 //
-// The chain is topk_slice_kernel's, restated in rk_chain (same operand staging, same k order, one accumulator):
-// tests/test_hip_rank.py pins the score bits to nrms_topk_dot's.
+// The scores are tk_chain's (topk_entry.h), the one chain topk_slice_kernel runs too, with one A operand: nrms_topk_dot's bits
+// (tests/test_hip_rank.py checks it end to end).
 #include "topk_entry.h"
 
 namespace nrms {
 
 constexpr int RK_MAX_T = 32;
 constexpr int RK_A_CHUNKS = 4096;              // grid.y bound of kernel A (longer gathered lists are walked in a loop)
-
-// One wave: acc[c] += the 32 x 32 score tile of user rows arow (lane (r, h): the row of user r) against item rows
-// row_of(32 c + 0 .. 31), c = 0, 1.  row_of(i), i in [0, 64): a valid row of `items` (callers clamp).  topk_slice_kernel's
-// chain: each whole block of 32 floats of k is staged in the wave's LDS block st through coalesced loads (lane l of load j
-// reads row 8j + l / 8, floats 4 (l % 8) .. + 3) and read back in the MFMA layout, the next block is loaded while the MFMAs
-// of this one run; MFMA t of block m sums k = 32m + t (h = 0) and 32m + 16 + t (h = 1); the rest of d goes in zero-padded
-// groups of 8.
-template <bool VEC, class RowOf>
-__device__ __forceinline__ void rk_chain(tk_f32x16 (&acc)[TK_TN], const float* arow, const float* __restrict__ items, int d,
-                                         float* st, int lane, RowOf row_of) {
-    const int r = lane & 31, h = lane >> 5;
-    const int m_full = d / 32;
-    const float* srow[8];           // rows this lane stages: 8j + lane / 8
-#pragma unroll
-    for (int j = 0; j < 8; ++j) srow[j] = items + (long)row_of(8 * j + (lane >> 3)) * d + 4 * (lane & 7);
-#define RK_GLOAD(m)                                                                                                        \
-    do {                                                                                                               \
-        const int k0_ = 32 * (m);                                                                                      \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                                \
-            if (VEC) {                                                                                                 \
-                const float4 v_ = *reinterpret_cast<const float4*>(srow[j] + k0_);                                     \
-                g[j][0] = v_.x; g[j][1] = v_.y; g[j][2] = v_.z; g[j][3] = v_.w;                                        \
-            } else {                                                                                                   \
-                _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) g[j][e_] = srow[j][k0_ + e_];                         \
-            }                                                                                                          \
-        }                                                                                                              \
-        _Pragma("unroll") for (int t = 0; t < 16; ++t) a[t] = arow[k0_ + 16 * h + t];                                  \
-    } while (0)
-    if (m_full > 0) {
-        float g[8][4];
-        float a[16];
-        RK_GLOAD(0);
-        for (int m = 0; m < m_full; ++m) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                *reinterpret_cast<float4*>(st + (8 * j + (lane >> 3)) * TK_BP + 4 * (lane & 7)) =
-                    make_float4(g[j][0], g[j][1], g[j][2], g[j][3]);
-            tk_wave_sync();
-            float b[TK_TN][16];
-#pragma unroll
-            for (int c = 0; c < TK_TN; ++c)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float4 v = *reinterpret_cast<const float4*>(st + (32 * c + r) * TK_BP + 16 * h + 4 * t);
-                    b[c][4 * t] = v.x; b[c][4 * t + 1] = v.y; b[c][4 * t + 2] = v.z; b[c][4 * t + 3] = v.w;
-                }
-            float acur[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) acur[t] = a[t];
-            if (m + 1 < m_full) RK_GLOAD(m + 1);
-#pragma unroll
-            for (int t = 0; t < 16; ++t)
-#pragma unroll
-                for (int c = 0; c < TK_TN; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[t], b[c][t], acc[c], 0, 0, 0);
-            tk_wave_sync();        // this block's LDS reads stay ahead of the next block's writes
-        }
-    }
-#undef RK_GLOAD
-    for (int g8 = 4 * m_full; 8 * g8 < d; ++g8) {       // zero-padded groups of 8 past the last whole block
-        const int k0 = 8 * g8 + 4 * h;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float at = tk_ld(arow, k0 + t, d);
-#pragma unroll
-            for (int c = 0; c < TK_TN; ++c) {
-                const float* brow = items + (long)row_of(32 * c + r) * d;
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(at, tk_ld(brow, k0 + t, d), acc[c], 0, 0, 0);
-            }
-        }
-    }
-}
 
 // Kernel A.  One wave per block; block (x, y): user tile x, gathered positions 64 (y + i gridDim.y) .. + 63 of the tile's list
 // of 32 M ids, M = T + n_exclude: position g is list slot m = g % M of user u0 + g / M (slots [0, T): targets, then the
@@ -125,7 +54,7 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
             const int b = u0 + i / T;
             if (b < B) counts[(long)b * T + (i % T)] = 0;
         }
-    const float* arow = user + (long)min(u0 + r, B - 1) * d;
+    const float* arow[1] = {user + (long)min(u0 + r, B - 1) * d};
     for (long g0 = 64L * blockIdx.y; g0 < total; g0 += 64L * gridDim.y) {
         // this lane's own list position: the id it names, and the row the wave reads for it (row 0 for an id that names none)
         const long g = g0 + lane;
@@ -140,7 +69,7 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
         tk_f32x16 acc[TK_TN];
 #pragma unroll
         for (int c = 0; c < TK_TN; ++c) acc[c] = tk_f32x16{};
-        rk_chain<VEC>(acc, arow, items, d, stage, lane, [&](int i) { return rows[i]; });
+        tk_chain<VEC>(acc, arow, items, d, stage, lane, [&](int i) { return rows[i]; });
         // C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5): the score of
         // position g0 + 32 c + r against its owner u sits in half (u >> 2) & 1, register (u & 3) + 4 (u >> 3)
 #pragma unroll
@@ -205,7 +134,7 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
 
     const int r = lane & 31, h = lane >> 5;
-    const float* arow = user + (long)min(u0 + r, B - 1) * d;
+    const float* arow[1] = {user + (long)min(u0 + r, B - 1) * d};
     float* st = stage[wave];
     uint32_t cnt[16] = {};          // lane (j, h): items above target j of user (q & 3) + 8 (q >> 2) + 4 h
     for (int n0 = n_begin; n0 < n_end; n0 += IT) {
@@ -230,7 +159,7 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
 #pragma unroll
             for (int c = 0; c < TK_TN; ++c) bv[c] = bias[min(nw + 32 * c + r, N - 1)];
         }
-        rk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
+        tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
         // C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
         uint64_t e[TK_TN][16];
 #pragma unroll
@@ -318,20 +247,6 @@ __global__ __launch_bounds__(64) void rank_finish_kernel(int B, int N, int T, in
     }
 }
 
-struct RankGeom {
-    int tiles, S, slice_len;
-};
-
-// Slices so that tiles x S is about one 8-wave block per CU; whole block steps per slice.
-static RankGeom rank_geom(int32_t B, int64_t N) {
-    RankGeom g{cdiv(B, TK_UT), 0, 0};
-    if (N == 0 || B == 0) return g;
-    const int s = std::max(1, cdiv(TK_TARGET_BLOCKS, g.tiles));
-    g.slice_len = cdiv(cdiv(N, s), TK_IT) * TK_IT;
-    g.S = cdiv(N, g.slice_len);
-    return g;
-}
-
 static bool rank_args_ok(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude) {
     return B >= 0 && N >= 0 && N <= TK_MAX_N && d >= 1 && T >= 1 && T <= RK_MAX_T && n_exclude >= 0;
 }
@@ -353,84 +268,39 @@ extern "C" size_t nrms_rank_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
 // nrms_rank_dot (bias null, who "rank_dot"), nrms_rank_dot_biased and nrms_rank_dot_windowed (windowed: item_time and window are
 // required): one body.
 static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
-                         const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
-                         float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
-    NRMS_REQUIRE(B >= 0, "%s: B must be >= 0 (B=%d)", who, B);
-    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "%s: N must be in [0, %d] (N=%lld)", who, TK_MAX_N, (long long)N);
-    NRMS_REQUIRE(d >= 1, "%s: d must be >= 1 (d=%d)", who, d);
-    NRMS_REQUIRE(T >= 1 && T <= RK_MAX_T, "%s: T must be in [1, %d] (T=%d)", who, RK_MAX_T, T);
-    NRMS_REQUIRE(n_exclude >= 0, "%s: n_exclude must be >= 0 (n_exclude=%d)", who, n_exclude);
-    if (B == 0) return NRMS_OK;
-    NRMS_REQUIRE(user, "%s: user is null", who);
-    NRMS_REQUIRE(items || N == 0, "%s: items is null", who);
-    NRMS_REQUIRE(((uintptr_t)bias & 3) == 0, "%s: bias must be 4-byte aligned", who);
-    if (windowed) {
-        NRMS_REQUIRE(item_time || N == 0, "%s: item_time is null", who);
-        NRMS_REQUIRE(((uintptr_t)item_time & 3) == 0, "%s: item_time must be 4-byte aligned", who);
-        NRMS_REQUIRE(window, "%s: window is null", who);
-        NRMS_REQUIRE(((uintptr_t)window & 3) == 0, "%s: window must be 4-byte aligned", who);
-    }
-    NRMS_REQUIRE(targets, "%s: targets is null", who);
-    NRMS_REQUIRE(ranks, "%s: ranks is null", who);
-    NRMS_REQUIRE(workspace, "%s: workspace is null", who);
+                         const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* targets,
+                         const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "T", T, RK_MAX_T, n_exclude);
+    if (rc != NRMS_OK || B == 0) return rc;
     if (!exclude) n_exclude = 0;
-    const size_t need = nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
-        return NRMS_EWORKSPACE;
-    }
-    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+    rc = tk_check_ptrs(who, {{"user", user, true, 1}, {"items", items, N != 0, 1}, {"bias", bias, false, 4},
+                             {"item_time", item_time, windowed && N != 0, 4}, {"window", window, windowed, 4},
+                             {"targets", targets, true, 1}, {"ranks", ranks, true, 1}},
+                       workspace, workspace_bytes, nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude), 8);
+    if (rc != NRMS_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     TimingScope ts(who, s);
     uint64_t* ent = (uint64_t*)workspace;
     uint32_t* counts = (uint32_t*)((char*)workspace + rank_entry_bytes(B, T, n_exclude));
-    const RankGeom g = rank_geom(B, N);
+    const TkGeom g = tk_geom(B, N, false);          // no minimum slice: the workspace does not grow with the slice count
     const int n = (int)N, M = T + n_exclude;
     const TkWindow win = windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr};
     char what[64];
     if (g.S > 0) {
-        const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
-        const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64));
-#define RK_LAUNCH_A(V, BI, WI)                                                                                             \
-    hipLaunchKernelGGL((rank_entries_kernel<V, BI, WI>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets, exclude, \
-                       ent, counts, bias, win)
-        if (windowed && bias) {
-            if (vec) RK_LAUNCH_A(true, true, true);
-            else RK_LAUNCH_A(false, true, true);
-        } else if (windowed) {
-            if (vec) RK_LAUNCH_A(true, false, true);
-            else RK_LAUNCH_A(false, false, true);
-        } else if (bias) {
-            if (vec) RK_LAUNCH_A(true, true, false);
-            else RK_LAUNCH_A(false, true, false);
-        } else {
-            if (vec) RK_LAUNCH_A(true, false, false);
-            else RK_LAUNCH_A(false, false, false);
-        }
-#undef RK_LAUNCH_A
-        snprintf(what, sizeof what, "%s(entries)", who);
-        int rc = check_launch(what);
-        if (rc != NRMS_OK) return rc;
-        const dim3 grid_b(g.tiles, g.S);
-#define RK_LAUNCH_B(V, BI, WI)                                                                                             \
-    hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, V, BI, WI>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M, g.slice_len, user, \
-                       items, ent, counts, bias, win)
-        if (windowed && bias) {
-            if (vec) RK_LAUNCH_B(true, true, true);
-            else RK_LAUNCH_B(false, true, true);
-        } else if (windowed) {
-            if (vec) RK_LAUNCH_B(true, false, true);
-            else RK_LAUNCH_B(false, false, true);
-        } else if (bias) {
-            if (vec) RK_LAUNCH_B(true, true, false);
-            else RK_LAUNCH_B(false, true, false);
-        } else {
-            if (vec) RK_LAUNCH_B(true, false, false);
-            else RK_LAUNCH_B(false, false, false);
-        }
-#undef RK_LAUNCH_B
-        snprintf(what, sizeof what, "%s(count)", who);
-        rc = check_launch(what);
+        const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64)), grid_b(g.tiles, g.S);
+        tk_with_flags([&](auto V, auto BI, auto WI) {
+            constexpr bool v = decltype(V)::value, bi = decltype(BI)::value, wi = decltype(WI)::value;
+            hipLaunchKernelGGL((rank_entries_kernel<v, bi, wi>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
+                               exclude, ent, counts, bias, win);
+            snprintf(what, sizeof what, "%s(entries)", who);
+            rc = check_launch(what);
+            if (rc != NRMS_OK) return;
+            hipLaunchKernelGGL((rank_count_kernel<TK_WAVES, v, bi, wi>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M, g.slice_len,
+                               user, items, ent, counts, bias, win);
+            snprintf(what, sizeof what, "%s(count)", who);
+            rc = check_launch(what);
+        }, tk_vec_ok(d, user, items), bias != nullptr, windowed);
         if (rc != NRMS_OK) return rc;
     }
     hipLaunchKernelGGL(rank_finish_kernel, dim3(B), dim3(64), 0, s, B, n, T, n_exclude, targets, exclude, ent, counts, ranks,

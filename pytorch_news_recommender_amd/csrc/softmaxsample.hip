@@ -34,7 +34,7 @@ using namespace nrms;
 
 extern "C" size_t nrms_softmax_sample_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t S, int32_t n_exclude) {
     if (!softmax_sample_args_ok(B, N, d, S, n_exclude)) return 0;
-    const TopkGeom g = topk_geom(B, N);
+    const TkGeom g = topk_geom(B, N);
     return 256 + (size_t)B * (size_t)g.S * (size_t)S * sizeof(uint64_t);     // never 0 for accepted arguments
 }
 
@@ -42,30 +42,20 @@ extern "C" int nrms_softmax_sample_dot(int32_t B, int64_t N, int32_t d, int32_t 
                                        const int64_t* row_key, float inv_temperature, uint64_t seed, const int64_t* exclude,
                                        int32_t n_exclude, int64_t* ids, float* keys, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-    NRMS_REQUIRE(B >= 0, "softmax_sample_dot: B must be >= 0 (B=%d)", B);
-    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "softmax_sample_dot: N must be in [0, %d] (N=%lld)", TK_MAX_N, (long long)N);
-    NRMS_REQUIRE(d >= 1, "softmax_sample_dot: d must be >= 1 (d=%d)", d);
-    NRMS_REQUIRE(S >= 1 && S <= TK_MAX_K, "softmax_sample_dot: S must be in [1, %d] (S=%d)", TK_MAX_K, S);
-    NRMS_REQUIRE(n_exclude >= 0, "softmax_sample_dot: n_exclude must be >= 0 (n_exclude=%d)", n_exclude);
-    NRMS_REQUIRE(inv_temperature >= 0.0f && isfinite(inv_temperature),
-                 "softmax_sample_dot: inv_temperature must be finite and >= 0 (inv_temperature=%g)", (double)inv_temperature);
+    const char* who = "softmax_sample_dot";
+    int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "S", S, TK_MAX_K, n_exclude);
+    if (rc != NRMS_OK) return rc;
+    NRMS_REQUIRE(inv_temperature >= 0.0f && isfinite(inv_temperature), "%s: inv_temperature must be finite and >= 0 (inv_temperature=%g)",
+                 who, (double)inv_temperature);
     if (B == 0) return NRMS_OK;
-    NRMS_REQUIRE(user, "softmax_sample_dot: user is null");
-    NRMS_REQUIRE(items || N == 0, "softmax_sample_dot: items is null");
-    NRMS_REQUIRE(row_key, "softmax_sample_dot: row_key is null");
-    NRMS_REQUIRE(ids, "softmax_sample_dot: ids is null");
-    NRMS_REQUIRE(workspace, "softmax_sample_dot: workspace is null");
-    const size_t need = nrms_softmax_sample_dot_workspace_bytes(B, N, d, S, n_exclude);
-    if (workspace_bytes < need) {
-        set_error("softmax_sample_dot: workspace %zu < required %zu bytes", workspace_bytes, need);
-        return NRMS_EWORKSPACE;
-    }
-    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "softmax_sample_dot: workspace must be 8-byte aligned");
+    rc = tk_check_ptrs(who, {{"user", user, true, 1}, {"items", items, N != 0, 1}, {"row_key", row_key, true, 1}, {"ids", ids, true, 1}},
+                       workspace, workspace_bytes, nrms_softmax_sample_dot_workspace_bytes(B, N, d, S, n_exclude), 8);
+    if (rc != NRMS_OK) return rc;
     if (!exclude) n_exclude = 0;
     hipStream_t s = (hipStream_t)stream;
-    TimingScope ts("softmax_sample_dot", s);
-    return topk_launch(false, B, N, d, S, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, keys, ids, (uint64_t*)workspace, s,
-                       "softmax_sample_dot", TkNoise{row_key, inv_temperature, seed});
+    TimingScope ts(who, s);
+    return topk_launch<false, true>(B, N, d, S, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, keys, ids, (uint64_t*)workspace,
+                                    s, who, TkNoise{row_key, inv_temperature, seed});
 }
 
 extern "C" int nrms_softmax_sample_noise(int32_t B, int64_t N, const int64_t* row_key, uint64_t seed, uint32_t* words, float* gumbel,

@@ -2,13 +2,14 @@
 // matrix (include/nrms_hip.h: nrms_topk_dot, whose header comment states the order and the padding rule).
 //
 // Kernel 1 (topk_slice_kernel): grid = 32-user tiles x catalogue slices.  Each wave forms two 32 x 32 score tiles on
-// v_mfma_f32_32x32x2_f32 straight from global memory (one accumulator over all of d, no split-K), and every score that
-// beats its user's running threshold is appended to the user's LDS buffer.  When a buffer is full, excluded ids are
-// dropped, the best k are selected (bitwise search for the k-th entry over registers, no sort) and the user's threshold is
-// raised to the k-th entry; the scores that found it full are still in the accumulators and are offered again.  The block
-// writes one k-list per (user, slice) into the workspace.
+// v_mfma_f32_32x32x2_f32 (tk_chain, topk_entry.h: one accumulator over all of d, no split-K; the one score chain of every
+// catalogue kernel, rankdot.hip's included), and every score that beats its user's running threshold is appended to the
+// user's LDS buffer (TkFilter, topk_kernels.h).  When a buffer is full, excluded ids are dropped, the best k are selected
+// (bitwise search for the k-th entry over registers, no sort) and the user's threshold is raised to the k-th entry; the scores
+// that found it full are still in the accumulators and are offered again.  The block writes one k-list per (user, slice) into
+// the workspace.
 // Kernel 2 (topk_merge_kernel): one wave per user runs the same filter / buffer / select over the user's slice lists and
-// sorts the final k once (wave bitonic sort in LDS).
+// sorts the final k once (tk_merge: wave bitonic sort in LDS).
 //
 // An entry is one uint64: the score as an order-preserving 32-bit key (-0.0 canonicalised to +0.0) above the complement of
 // the 32-bit item id, so larger entry = higher score, then smaller id.  Entry 0 lies below every real entry and is padding.
@@ -37,16 +38,10 @@ __global__ __launch_bounds__(1024) void topk_tiles_kernel(int N, int G, int n_ti
     __shared__ long part[1024];
     const int per = (G + 1023) / 1024;
     const int lo = min(G, (int)threadIdx.x * per), hi = min(G, lo + per);
-    auto span = [&](int g, int& row, int& len) {
-        const long a = min((long)N, max(0L, (long)group_ptr[g]));
-        const long e = min((long)N, max(0L, (long)group_ptr[g + 1]));
-        row = (int)a;
-        len = (int)max(0L, e - a);
-    };
     long s = 0;
     for (int g = lo; g < hi; ++g) {
         int row, len;
-        span(g, row, len);
+        tk_group_span(group_ptr, g, N, row, len);
         s += (len + 31) / 32;
     }
     part[threadIdx.x] = s;
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(1024) void topk_tiles_kernel(int N, int G, int n_ti
     long t = threadIdx.x == 0 ? 0 : part[threadIdx.x];
     for (int g = lo; g < hi; ++g) {
         int row, len;
-        span(g, row, len);
+        tk_group_span(group_ptr, g, N, row, len);
         for (int j = 0; j < len && t < n_tiles; j += 32, ++t) tiles[t] = TkTile{row + j, min(32, len - j), g, 0};
     }
     for (long u = total + threadIdx.x; u < n_tiles; u += 1024) tiles[u] = TkTile{0, 0, 0, 0};
@@ -82,45 +77,29 @@ using namespace nrms;
 
 extern "C" size_t nrms_topk_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k) {
     if (!topk_args_ok(B, N, d, k)) return 0;
-    const TopkGeom g = topk_geom(B, N);
+    const TkGeom g = topk_geom(B, N);
     return 256 + (size_t)B * (size_t)g.S * (size_t)k * sizeof(uint64_t);     // never 0 for accepted arguments
 }
 
 // nrms_topk_dot (bias null, who "topk_dot"), nrms_topk_dot_biased and nrms_topk_dot_windowed (windowed: item_time and window
 // are required): one body, so the checks and the launch cannot drift apart.
 static int topk_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
-                         const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-    NRMS_REQUIRE(B >= 0, "%s: B must be >= 0 (B=%d)", who, B);
-    NRMS_REQUIRE(N >= 0 && N <= TK_MAX_N, "%s: N must be in [0, %d] (N=%lld)", who, TK_MAX_N, (long long)N);
-    NRMS_REQUIRE(d >= 1, "%s: d must be >= 1 (d=%d)", who, d);
-    NRMS_REQUIRE(k >= 1 && k <= TK_MAX_K, "%s: k must be in [1, %d] (k=%d)", who, TK_MAX_K, k);
-    NRMS_REQUIRE(n_exclude >= 0, "%s: n_exclude must be >= 0 (n_exclude=%d)", who, n_exclude);
-    if (B == 0) return NRMS_OK;
-    NRMS_REQUIRE(user, "%s: user is null", who);
-    NRMS_REQUIRE(items || N == 0, "%s: items is null", who);
-    NRMS_REQUIRE(((uintptr_t)bias & 3) == 0, "%s: bias must be 4-byte aligned", who);
-    if (windowed) {
-        NRMS_REQUIRE(item_time || N == 0, "%s: item_time is null", who);
-        NRMS_REQUIRE(((uintptr_t)item_time & 3) == 0, "%s: item_time must be 4-byte aligned", who);
-        NRMS_REQUIRE(window, "%s: window is null", who);
-        NRMS_REQUIRE(((uintptr_t)window & 3) == 0, "%s: window must be 4-byte aligned", who);
-    }
-    NRMS_REQUIRE(top_scores, "%s: top_scores is null", who);
-    NRMS_REQUIRE(top_ids, "%s: top_ids is null", who);
-    NRMS_REQUIRE(workspace, "%s: workspace is null", who);
-    const size_t need = nrms_topk_dot_workspace_bytes(B, N, d, k);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
-        return NRMS_EWORKSPACE;
-    }
-    NRMS_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+                         const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* exclude,
+                         int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "k", k, TK_MAX_K, n_exclude);
+    if (rc != NRMS_OK || B == 0) return rc;
+    rc = tk_check_ptrs(who, {{"user", user, true, 1}, {"items", items, N != 0, 1}, {"bias", bias, false, 4},
+                             {"item_time", item_time, windowed && N != 0, 4}, {"window", window, windowed, 4},
+                             {"top_scores", top_scores, true, 1}, {"top_ids", top_ids, true, 1}},
+                       workspace, workspace_bytes, nrms_topk_dot_workspace_bytes(B, N, d, k), 8);
+    if (rc != NRMS_OK) return rc;
     if (!exclude) n_exclude = 0;
     hipStream_t s = (hipStream_t)stream;
     TimingScope ts(who, s);
-    return topk_launch(false, B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids,
-                       (uint64_t*)workspace, s, who, TkNoise{nullptr, 0.0f, 0}, bias,
-                       windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr});
+    return topk_launch<false, false>(B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids,
+                                     (uint64_t*)workspace, s, who, TkNoise{nullptr, 0.0f, 0}, bias,
+                                     windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr});
 }
 
 extern "C" int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
@@ -158,45 +137,32 @@ extern "C" int nrms_topk_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t k
 extern "C" size_t nrms_topk_grouped_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G) {
     if (!topk_grouped_args_ok(B, N, d, k, G)) return 0;
     const int64_t nt = topk_grouped_tiles(N, G);
-    const TopkGeom g = topk_geom(B, 32 * nt);
+    const TkGeom g = topk_geom(B, 32 * nt);
     return 256 + topk_tile_bytes(nt) + (size_t)B * (size_t)g.S * (size_t)k * sizeof(uint64_t);
 }
 
 extern "C" int nrms_topk_grouped_dot(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, const float* query, const float* items,
                                      const int32_t* item_ids, const int64_t* group_ptr, const int64_t* exclude, int32_t n_exclude,
                                      float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream) {
-    NRMS_REQUIRE(B >= 0, "topk_grouped_dot: B must be >= 0 (B=%d)", B);
-    NRMS_REQUIRE(G >= 1, "topk_grouped_dot: G must be >= 1 (G=%d)", G);
-    NRMS_REQUIRE(N >= 0 && N + 32 * (int64_t)G <= TK_MAX_N, "topk_grouped_dot: N must be in [0, %d - 32 G] (N=%lld, G=%d)",
-                 TK_MAX_N, (long long)N, G);
-    NRMS_REQUIRE(d >= 1, "topk_grouped_dot: d must be >= 1 (d=%d)", d);
-    NRMS_REQUIRE(k >= 1 && k <= TK_MAX_K, "topk_grouped_dot: k must be in [1, %d] (k=%d)", TK_MAX_K, k);
-    NRMS_REQUIRE(n_exclude >= 0, "topk_grouped_dot: n_exclude must be >= 0 (n_exclude=%d)", n_exclude);
-    if (B == 0) return NRMS_OK;
-    NRMS_REQUIRE(query, "topk_grouped_dot: query is null");
-    NRMS_REQUIRE(items || N == 0, "topk_grouped_dot: items is null");
-    NRMS_REQUIRE(item_ids || N == 0, "topk_grouped_dot: item_ids is null");
-    NRMS_REQUIRE(group_ptr || N == 0, "topk_grouped_dot: group_ptr is null");
-    NRMS_REQUIRE(top_scores, "topk_grouped_dot: top_scores is null");
-    NRMS_REQUIRE(top_ids, "topk_grouped_dot: top_ids is null");
-    NRMS_REQUIRE(workspace, "topk_grouped_dot: workspace is null");
-    const size_t need = nrms_topk_grouped_dot_workspace_bytes(B, N, d, k, G);
-    if (workspace_bytes < need) {
-        set_error("topk_grouped_dot: workspace %zu < required %zu bytes", workspace_bytes, need);
-        return NRMS_EWORKSPACE;
-    }
-    NRMS_REQUIRE(((uintptr_t)workspace & 15) == 0, "topk_grouped_dot: workspace must be 16-byte aligned");
+    const char* who = "topk_grouped_dot";
+    NRMS_REQUIRE(G >= 1, "%s: G must be >= 1 (G=%d)", who, G);
+    int rc = tk_check_dims(who, B, N, TK_MAX_N - 32 * (int64_t)G, d, "k", k, TK_MAX_K, n_exclude);
+    if (rc != NRMS_OK || B == 0) return rc;
+    rc = tk_check_ptrs(who, {{"query", query, true, 1}, {"items", items, N != 0, 1}, {"item_ids", item_ids, N != 0, 1},
+                             {"group_ptr", group_ptr, N != 0, 1}, {"top_scores", top_scores, true, 1}, {"top_ids", top_ids, true, 1}},
+                       workspace, workspace_bytes, nrms_topk_grouped_dot_workspace_bytes(B, N, d, k, G), 16);
+    if (rc != NRMS_OK) return rc;
     if (!exclude) n_exclude = 0;
     hipStream_t s = (hipStream_t)stream;
-    TimingScope ts("topk_grouped_dot", s);
+    TimingScope ts(who, s);
     const int64_t nt = topk_grouped_tiles(N, G);
     TkTile* tiles = (TkTile*)workspace;
     uint64_t* ws = (uint64_t*)((char*)workspace + topk_tile_bytes(nt));
     if (nt > 0) {
         hipLaunchKernelGGL(topk_tiles_kernel, dim3(1), dim3(1024), 0, s, (int)N, G, (int)nt, group_ptr, tiles);
-        const int rc = check_launch("topk_grouped_dot(tiles)");
+        rc = check_launch("topk_grouped_dot(tiles)");
         if (rc != NRMS_OK) return rc;
     }
-    return topk_launch(true, B, N, d, k, G, nt, query, items, item_ids, tiles, exclude, n_exclude, top_scores, top_ids, ws, s,
-                       "topk_grouped_dot");
+    return topk_launch<true, false>(B, N, d, k, G, nt, query, items, item_ids, tiles, exclude, n_exclude, top_scores, top_ids, ws, s,
+                                    who);
 }

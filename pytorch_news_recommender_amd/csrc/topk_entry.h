@@ -1,9 +1,14 @@
-// What the catalogue kernels share (topk.hip: the k best items per user; rankdot.hip: the exact rank of given items in that
-// order): the tile constants of the score chain and the uint64 entry that carries the order.
+// What the catalogue kernels share (topk.hip and topksec.hip: the k best items per user; softmaxsample.hip: a Gumbel-top-S draw;
+// rankdot.hip: the exact rank of given items in that order): the tile constants, the uint64 entry that carries the order, the
+// one score chain every one of their kernels runs (tk_chain), the time window, and the host side every entry point shares:
+// the launch geometry, the argument checks and the choice of a kernel instantiation.
 //
 // An entry is the score as an order-preserving 32-bit key (-0.0 canonicalised to +0.0) above the complement of the 32-bit
 // item id, so larger entry = higher score, then smaller id.  Entry 0 lies below every real entry and is padding.
 #pragma once
+#include <initializer_list>
+#include <type_traits>
+
 #include "common.h"
 
 namespace nrms {
@@ -14,6 +19,7 @@ constexpr int TK_TN = 2;                       // 32-item column tiles per wave
 constexpr int TK_BP = 36;                      // LDS row pitch (floats) of a wave's staged 64 x 32 item block
 constexpr int TK_IT = 32 * TK_TN * TK_WAVES;   // catalogue items per block step at the largest wave count
 constexpr int TK_TARGET_BLOCKS = 256;          // one 8-wave block per CU on 256 CUs
+constexpr int TK_MIN_SLICE = 4 * TK_IT;        // top-k: no slice shorter than this, each slice list costs k workspace entries
 constexpr int TK_MAX_N = 0x7FFF0000;           // ids are held in 32 bits
 
 typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
@@ -85,5 +91,171 @@ __device__ __forceinline__ void tk_window_hull(const int2* win, int& blo, int& b
 }
 
 __device__ __forceinline__ float tk_ld(const float* p, int kk, int d) { return kk < d ? p[kk] : 0.0f; }
+
+// The score chain of every catalogue kernel.  One wave: acc[c] += the 32 x 32 score tile of A rows (lane (r, h): the row of
+// user r; arow[c] feeds column tile c when NA = TK_TN, arow[0] feeds both when NA = 1) against item rows row_of(32 c + 0 .. 31),
+// c = 0, 1.  row_of(i), i in [0, 64): a valid row of `items` (callers clamp).
+//
+// Operands: each whole block of 32 floats of k is staged in the wave's private LDS block st through coalesced loads (lane l of
+// load j reads row 8j + l / 8, floats 4 (l % 8) .. + 3: eight full 128-byte row segments per instruction) and read back in the
+// MFMA layout; the A rows come straight from global memory (shared by the block's waves in L1).  The next block of k is loaded
+// into registers while the MFMAs of this one run.  Lane (r, h) feeds A[user r][k'=h] and B[k'=h][item r]; MFMA t of block m sums
+// k = 32m + t (h = 0) and 32m + 16 + t (h = 1).  The rest of d goes in groups of 8 (8g + t and 8g + 4 + t, zero past d).  The
+// same fixed chain for every (user, item) pair of every caller: their score bits are equal.  It touches only st and wave-level
+// syncs, never a block barrier.
+template <bool VEC, int NA, class RowOf>
+__device__ __forceinline__ void tk_chain(tk_f32x16 (&acc)[TK_TN], const float* const (&arow)[NA], const float* __restrict__ items,
+                                         int d, float* st, int lane, RowOf row_of) {
+    static_assert(NA == 1 || NA == TK_TN, "one A operand, or one per column tile");
+    const int r = lane & 31, h = lane >> 5;
+    const int m_full = d / 32;
+    const float* srow[8];           // rows this lane stages: 8j + lane / 8
+#pragma unroll
+    for (int j = 0; j < 8; ++j) srow[j] = items + (long)row_of(8 * j + (lane >> 3)) * d + 4 * (lane & 7);
+    auto gload = [&](int m, float (&g)[8][4], float (&a)[NA][16]) {
+        const int k0 = 32 * m;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if constexpr (VEC) {
+                const float4 v = *reinterpret_cast<const float4*>(srow[j] + k0);
+                g[j][0] = v.x; g[j][1] = v.y; g[j][2] = v.z; g[j][3] = v.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g[j][e] = srow[j][k0 + e];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NA; ++c)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) a[c][t] = arow[c][k0 + 16 * h + t];
+    };
+    if (m_full > 0) {
+        float g[8][4];
+        float a[NA][16];
+        gload(0, g, a);
+        for (int m = 0; m < m_full; ++m) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                *reinterpret_cast<float4*>(st + (8 * j + (lane >> 3)) * TK_BP + 4 * (lane & 7)) =
+                    make_float4(g[j][0], g[j][1], g[j][2], g[j][3]);
+            tk_wave_sync();
+            float b[TK_TN][16];
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float4 v = *reinterpret_cast<const float4*>(st + (32 * c + r) * TK_BP + 16 * h + 4 * t);
+                    b[c][4 * t] = v.x; b[c][4 * t + 1] = v.y; b[c][4 * t + 2] = v.z; b[c][4 * t + 3] = v.w;
+                }
+            float acur[NA][16];
+#pragma unroll
+            for (int c = 0; c < NA; ++c)
+#pragma unroll
+                for (int t = 0; t < 16; ++t) acur[c][t] = a[c][t];
+            if (m + 1 < m_full) gload(m + 1, g, a);
+#pragma unroll
+            for (int t = 0; t < 16; ++t)
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c)
+                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[NA == 1 ? 0 : c][t], b[c][t], acc[c], 0, 0, 0);
+            tk_wave_sync();        // this block's LDS reads stay ahead of the next block's writes
+        }
+    }
+    for (int g8 = 4 * m_full; 8 * g8 < d; ++g8) {       // zero-padded groups of 8 past the last whole block
+        const int k0 = 8 * g8 + 4 * h;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            float at[NA];
+#pragma unroll
+            for (int c = 0; c < NA; ++c) at[c] = tk_ld(arow[c], k0 + t, d);
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) {
+                const float* brow = items + (long)row_of(32 * c + r) * d;
+                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(at[NA == 1 ? 0 : c], tk_ld(brow, k0 + t, d), acc[c], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+// The launch geometry of the slice and count kernels: 32-user tiles x S catalogue slices of slice_len items (whole block
+// steps), about one 8-wave block per CU.  min_slice (the top-k calls, whose workspace grows with S): no slice shorter than
+// TK_MIN_SLICE.
+struct TkGeom {
+    int tiles, S, slice_len;
+};
+
+static TkGeom tk_geom(int32_t B, int64_t N, bool min_slice) {
+    TkGeom g{cdiv(B, TK_UT), 0, 0};
+    if (N == 0 || B == 0) return g;
+    int s = std::max(1, cdiv(TK_TARGET_BLOCKS, g.tiles));
+    if (min_slice) s = std::min(s, std::max(1, cdiv(N, TK_MIN_SLICE)));
+    g.slice_len = cdiv(cdiv(N, s), TK_IT) * TK_IT;
+    g.S = cdiv(N, g.slice_len);
+    return g;
+}
+
+// The extent checks every entry point starts with, in this order: B, N in [0, n_max], d, the list length (kname "k", "S" or
+// "T", in [1, k_max]) and n_exclude.
+static int tk_check_dims(const char* who, int32_t B, int64_t N, int64_t n_max, int32_t d, const char* kname, int32_t k,
+                         int32_t k_max, int32_t n_exclude) {
+    NRMS_REQUIRE(B >= 0, "%s: B must be >= 0 (B=%d)", who, B);
+    NRMS_REQUIRE(N >= 0 && N <= n_max, "%s: N must be in [0, %lld] (N=%lld)", who, (long long)n_max, (long long)N);
+    NRMS_REQUIRE(d >= 1, "%s: d must be >= 1 (d=%d)", who, d);
+    NRMS_REQUIRE(k >= 1 && k <= k_max, "%s: %s must be in [1, %d] (%s=%d)", who, kname, k_max, kname, k);
+    NRMS_REQUIRE(n_exclude >= 0, "%s: n_exclude must be >= 0 (n_exclude=%d)", who, n_exclude);
+    return NRMS_OK;
+}
+
+// One pointer argument: required (else it may be null), and aligned to align bytes when align > 1.
+struct TkPtr {
+    const char* name;
+    const void* p;
+    bool required;
+    unsigned align;
+};
+
+// The pointer checks (after the B == 0 return), in list order, then the workspace: not null, at least `need` bytes
+// (NRMS_EWORKSPACE otherwise), aligned to ws_align.
+static int tk_check_ptrs(const char* who, std::initializer_list<TkPtr> ptrs, const void* workspace, size_t workspace_bytes,
+                         size_t need, unsigned ws_align) {
+    for (const TkPtr& a : ptrs) {
+        NRMS_REQUIRE(a.p || !a.required, "%s: %s is null", who, a.name);
+        NRMS_REQUIRE(a.align <= 1 || ((uintptr_t)a.p & (a.align - 1)) == 0, "%s: %s must be %u-byte aligned", who, a.name, a.align);
+    }
+    NRMS_REQUIRE(workspace, "%s: workspace is null", who);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
+        return NRMS_EWORKSPACE;
+    }
+    NRMS_REQUIRE(((uintptr_t)workspace & (ws_align - 1)) == 0, "%s: workspace must be %u-byte aligned", who, ws_align);
+    return NRMS_OK;
+}
+
+// The chain's loads are float4 when every row starts on 16 bytes.
+static bool tk_vec_ok(int32_t d, const float* user, const float* items) {
+    return (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
+}
+
+// f(std::bool_constant<b>...) for run-time flags: picks the <VEC, BIAS, WINDOW, ...> instantiation of a kernel.
+template <class F>
+static void tk_with_flags(F f) {
+    f();
+}
+template <class F, class... Rest>
+static void tk_with_flags(F f, bool b, Rest... rest) {
+    if (b) tk_with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else tk_with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// f(P, W) as integral constants: the buffer length P >= k + 64 (a power of two) of the slice and merge kernels and the waves
+// per block W of the slice kernels (2 at the largest P, whose buffers fill the LDS).
+template <class F>
+static void tk_with_pw(int k, F f) {
+    if (k + 64 <= 128) f(std::integral_constant<int, 128>{}, std::integral_constant<int, TK_WAVES>{});
+    else if (k + 64 <= 256) f(std::integral_constant<int, 256>{}, std::integral_constant<int, TK_WAVES>{});
+    else f(std::integral_constant<int, 512>{}, std::integral_constant<int, 2>{});
+}
 
 }  // namespace nrms

@@ -1,14 +1,16 @@
-// The kernels of the catalogue selections and their launcher (topk.hip, whose head comment describes them: nrms_topk_dot and
-// nrms_topk_grouped_dot; softmaxsample.hip: nrms_softmax_sample_dot, the same slices and merge with a keyed Gumbel perturbation
-// added to every score before it meets the threshold).
+// The pieces of the catalogue selections, each written once: the candidate filter of a slice kernel's block (TkFilter), the
+// one-wave merge of slice lists (tk_merge), the tiles of a grouped catalogue (TkTile, TkWaveTiles), and the slice and merge
+// kernels with their launcher.  topk.hip (whose head comment describes the two kernels): nrms_topk_dot, its biased and windowed
+// forms and nrms_topk_grouped_dot; softmaxsample.hip: nrms_softmax_sample_dot, the same slices and merge with a keyed Gumbel
+// perturbation added to every score before it meets the threshold; topksec.hip: nrms_topk_sections_dot, a slice kernel of its
+// own (one slice-table entry per block) and a merge kernel of its own (one section per block) over the same pieces.
 #pragma once
-#include "topk_entry.h"      // the entry, the tile constants and the helpers rankdot.hip shares
+#include "topk_entry.h"      // the entry, the tile constants, the score chain and the host helpers rankdot.hip shares
 
 namespace nrms {
 
 constexpr int TK_EX_LDS = 64;                  // exclude lists up to this long are staged in LDS, longer ones read globally
 constexpr int TK_MAX_K = 256;
-constexpr int TK_MIN_SLICE = 4 * TK_IT;        // no slice shorter than this: each slice list costs k workspace entries
 
 // The perturbation of nrms_softmax_sample_dot (include/nrms_hip.h states it): null row_key = none, the kernels are top-k's.
 struct TkNoise {
@@ -123,18 +125,186 @@ __device__ inline void tk_drop_excluded(uint64_t* buf, int cnt, const int32_t* e
     tk_wave_sync();
 }
 
-// Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step (two 32-item column
-// tiles per wave).  Scores go through the filter and the LDS buffers of the block's users; the exclude lists are applied
-// when a buffer is sorted, so the filter is one compare per score.  A candidate that finds its user's buffer full stays
-// pending in its lane (its score is still in the accumulator); the block then sorts the full buffers down to k, raises their
-// thresholds and offers the pending candidates again, until none is left.
+// Group (or section) g of a catalogue stored group after group: rows [ptr[g], ptr[g + 1]), clamped to [0, N], so that a ptr
+// that is not nondecreasing from 0 to N cannot name a row outside the catalogue.  N = 0: empty (ptr may be null).
+__device__ __forceinline__ void tk_group_span(const int64_t* __restrict__ ptr, int g, int N, int& row, int& len) {
+    row = 0;
+    len = 0;
+    if (N == 0) return;
+    const long a = min((long)N, max(0L, (long)ptr[g]));
+    const long e = min((long)N, max(0L, (long)ptr[g + 1]));
+    row = (int)a;
+    len = (int)max(0L, e - a);
+}
+
+// The wave's two 32-row tiles of a grouped or sectioned catalogue in the step that starts at tile row nw (tiles at or past
+// t_end: none, len 0).  Wave-uniform.
+struct TkWaveTiles {
+    int row[TK_TN], len[TK_TN], grp[TK_TN];
+
+    __device__ __forceinline__ TkWaveTiles(const TkTile* __restrict__ tiles, int t_end, int nw) {
+#pragma unroll
+        for (int c = 0; c < TK_TN; ++c) {
+            const int t = nw / 32 + c;
+            TkTile tl{0, 0, 0, 0};
+            if (t < t_end) tl = tiles[t];
+            row[c] = __builtin_amdgcn_readfirstlane(tl.row);
+            len[c] = __builtin_amdgcn_readfirstlane(tl.len);
+            grp[c] = __builtin_amdgcn_readfirstlane(tl.grp);
+        }
+    }
+    // the clamped catalogue row of staged position i in [0, 64)
+    __device__ __forceinline__ int row_of(int i, int N) const { return min((i < 32 ? row[0] : row[1]) + (i & 31), N - 1); }
+    // is row r of column tile c a real item of the slice [.., n_end), and if so its id
+    __device__ __forceinline__ bool live(int c, int nw, int n_end, int r, const int32_t* __restrict__ item_ids, uint32_t& id) const {
+        const bool l = nw + 32 * c + r < n_end && r < len[c];
+        if (l) id = (uint32_t)item_ids[row[c] + r];
+        return l;
+    }
+};
+
+// The candidate filter of a slice kernel's block: per user an LDS buffer of P entries, a threshold and a count, and the
+// block's exclude ids.  Scores that beat their user's threshold are appended to the user's buffer; the exclude lists are
+// applied when a buffer is cut down, so the filter is one compare per score.  A candidate that finds its user's buffer full
+// stays pending in its lane (its score is still in the accumulator); the block then cuts the full buffers down to k, raises
+// their thresholds and offers the pending candidates again, until none is left.
 //
-// Operands: each wave stages its 64 item rows, 32 floats of k at a time, in a private LDS block through coalesced loads
-// (lane l of load j reads row 8j + l / 8, floats 4 (l % 8) .. + 3: eight full 128-byte row segments per instruction), and
-// reads them back in the MFMA layout; the block's 32 user rows come straight from global memory (shared by the W waves in
-// L1).  The next block of k is loaded into registers while the MFMAs of this one run.  Lane (r, h) feeds A[user r][k'=h]
-// and B[k'=h][item r]; MFMA t of block m sums k = 32m + t (h = 0) and 32m + 16 + t (h = 1).  The rest of d goes in groups of
-// 8 (8g + t and 8g + 4 + t, zero past d).  The same fixed chain for every (user, item) pair.
+// Its LDS: buf [32][P] entries, thr [32] thresholds, cnt [32] counts (past P: that many candidates are pending), ex [32][64]
+// staged exclude ids.  A slice kernel declares them with TK_FILTER_LDS as four separate __shared__ objects, so that the
+// compiler knows they do not overlap (as one struct they cost every slice kernel 30 to 50 VGPRs).
+template <int P>
+struct TkFilterLds {
+    uint64_t (*buf)[P];
+    uint64_t* thr;
+    int* cnt;
+    int32_t (*ex)[TK_EX_LDS];
+};
+#define TK_FILTER_LDS(name, P)                 \
+    __shared__ uint64_t name##_buf[TK_UT][P];  \
+    __shared__ uint64_t name##_thr[TK_UT];     \
+    __shared__ int name##_cnt[TK_UT];          \
+    __shared__ int32_t name##_ex[TK_UT][TK_EX_LDS]; \
+    const TkFilterLds<P> name{name##_buf, name##_thr, name##_cnt, name##_ex}
+
+// Which (user, item) pairs of a step the filter may take: user(i) reads what user row i of the block contributes, item(c, w)
+// tests this lane's item of column tile c against it.  Every pair, or the pairs with lo <= time < hi (WINDOW kernels: win is
+// the block's 32 staged (lo, hi), tv the times of this lane's two items).
+struct TkOpenAll {
+    __device__ __forceinline__ int user(int) const { return 0; }
+    __device__ __forceinline__ bool item(int, int) const { return true; }
+};
+struct TkOpenWindow {
+    const int2* win;
+    const int (&tv)[TK_TN];
+    __device__ __forceinline__ int2 user(int i) const { return win[i]; }
+    __device__ __forceinline__ bool item(int c, int2 w) const { return tv[c] >= w.x && tv[c] < w.y; }
+};
+
+template <int P, int W>
+struct TkFilter {
+    TkFilterLds<P> s;
+    const int64_t* __restrict__ exclude;
+    int n_exclude, k, u0, B, lane, wave;
+
+    __device__ __forceinline__ bool ex_lds() const { return n_exclude <= TK_EX_LDS; }
+
+    // Empty buffers, and the block's exclude lists in LDS when they are short enough: only the ids in [id_lo, id_hi) matter
+    // (a plain catalogue: the rows of this slice; item ids: every 31-bit id, in any slice), everything else becomes -1.  The
+    // caller's next __syncthreads() publishes it.
+    __device__ __forceinline__ void start(int64_t id_lo, int64_t id_hi) {
+        if (threadIdx.x < TK_UT) {
+            s.thr[threadIdx.x] = 0;
+            s.cnt[threadIdx.x] = 0;
+        }
+        if (ex_lds())
+            for (int i = threadIdx.x; i < TK_UT * n_exclude; i += 64 * W) {
+                const int u = i / n_exclude, e = i - u * n_exclude;
+                const int64_t v = u0 + u < B ? exclude[(long)(u0 + u) * n_exclude + e] : -1;
+                s.ex[u][e] = (v >= id_lo && v < id_hi) ? (int32_t)v : -1;
+            }
+    }
+
+    // one wave: cut user i's buffer (c entries) down to its best k, excluded ids dropped; returns the new threshold, sets c
+    __device__ __forceinline__ uint64_t flush(int i, int& c) {
+        tk_drop_excluded(s.buf[i], c, ex_lds() ? s.ex[i] : nullptr, exclude + (long)(u0 + i) * n_exclude, n_exclude, lane);
+        return tk_select<P>(s.buf[i], c, k, lane);
+    }
+
+    // The scores of a step that have to be offered, bit 16 c + q of the result.  C/D layout: item = lane & 31 of column tile
+    // c, user row i = (q & 3) + 8 (q >> 2) + 4 (lane >> 5).  live[c]: this lane's item of tile c is a real one; open: which
+    // (user, item) pairs are eligible (TkOpenAll, TkOpenWindow).  NaN scores are never offered.
+    template <class Open>
+    __device__ __forceinline__ uint32_t pending(const tk_f32x16 (&acc)[TK_TN], const bool (&live)[TK_TN], Open open) const {
+        uint32_t pend = 0;
+#pragma unroll
+        for (int c = 0; c < TK_TN; ++c)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int i = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                const auto w = open.user(i);          // read ahead of the tests, not inside them
+                if (live[c] && u0 + i < B && open.item(c, w) && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
+            }
+        return pend;
+    }
+
+    // Offers the pending scores of a step; id_of(c): the id of this lane's item in column tile c.  This holds block barriers:
+    // EVERY wave of the block calls it on EVERY step, with pend == 0 when it has nothing to offer (a wave past the slice's
+    // end, a WINDOW wave that skipped its chain), so that all waves meet the same barriers the same number of times.
+    template <class IdOf>
+    __device__ __forceinline__ void offer(const tk_f32x16 (&acc)[TK_TN], uint32_t pend, IdOf id_of) {
+        bool first = true;
+        while (__syncthreads_or(pend != 0)) {
+            if (!first) {
+                // cut every full buffer down to its best k (cnt may have run past P: those candidates are pending)
+                for (int i = wave; i < TK_UT; i += W) {
+                    if (s.cnt[i] >= P) {
+                        int c = P;
+                        const uint64_t t = flush(i, c);
+                        if (lane == 0) {
+                            s.thr[i] = t;
+                            s.cnt[i] = c;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            first = false;
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const uint32_t bit = 1u << (16 * c + q);
+                    if (!(pend & bit)) continue;
+                    const int i = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                    const uint64_t e = tk_entry(acc[c][q], id_of(c));
+                    bool keep = false;
+                    if (e > s.thr[i]) {
+                        const int slot = atomicAdd(&s.cnt[i], 1);
+                        if (slot < P) s.buf[i][slot] = e;
+                        else keep = true;
+                    }
+                    if (!keep) pend &= ~bit;
+                }
+            }
+        }
+    }
+
+    // The slice's list of every user of the block: its best k, unsorted, 0-padded, at ws[user][slice of S][k].
+    __device__ __forceinline__ void write(uint64_t* __restrict__ ws, int S, int slice) {
+        for (int i = wave; i < TK_UT; i += W) {
+            const int b = u0 + i;
+            if (b >= B) break;
+            int c = min(s.cnt[i], P);
+            flush(i, c);
+            uint64_t* dst = ws + ((long)b * S + slice) * k;
+            for (int j = lane; j < k; j += 64) dst[j] = j < c ? s.buf[i][j] : 0;
+        }
+    }
+};
+
+// Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step (two 32-item column
+// tiles per wave): tk_chain (topk_entry.h) forms the scores from the block's 32 user rows and the wave's 64 item rows, and
+// they go through the block's TkFilter.  The block writes one k-list per (user, slice).
 //
 // GROUPED (nrms_topk_grouped_dot): the slices run over the tiles of `tiles` (32 rows each, slice_len and IT are whole tiles),
 // user = the query [B, G, d], and each of a wave's two column tiles takes its A operand from query[user, the tile's group];
@@ -144,7 +314,7 @@ __device__ inline void tk_drop_excluded(uint64_t* buf, int cnt, const int32_t* e
 // fmaf(score, inv_temperature, g(row key, item)); the block's 32 row seeds are formed once, in LDS.
 //
 // BIAS (nrms_topk_dot_biased): lane (r, h) loads bias[n] of its item in each of its two column tiles (one coalesced 128-byte
-// read per tile, issued before the MFMA loop so that the loop hides its latency) and, before the filter, adds it to the tile's 16
+// read per tile, issued before the chain so that it hides the latency) and, before the filter, adds it to the tile's 16
 // finished accumulator registers: one fp32 add per score, after the chain, never folded into it.  A NaN sum fails the filter's
 // NaN test like a NaN score; entries simply carry s'.
 //
@@ -152,12 +322,12 @@ __device__ inline void tk_drop_excluded(uint64_t* buf, int cnt, const int32_t* e
 // hull [blo, bhi).  Lane (r, h) loads item_time[n] of its item in each of its two column tiles where bv[] is loaded, and the
 // filter takes (user, item) only if lo <= time < hi (hi <= INT32_MAX, so a time of INT32_MAX is open to nobody).  Dead-tile
 // skip: one __ballot over "my item's time lies in [blo, bhi)" decides, wave-uniformly, whether the wave has anything to offer
-// in this step; if not it issues no item loads, no LDS staging and no MFMA and goes to the block's __syncthreads_or with
-// pend == 0.  The skipped region holds the chain alone, which touches only the wave's private stage[wave] and wave-level
-// syncs: every wave still meets every block barrier, the same number of times.
+// in this step; if not it issues no item loads, no LDS staging and no MFMA and goes to the filter's offer with pend == 0.  The
+// skipped region holds the chain alone, which touches only the wave's private stage[wave] and wave-level syncs: every wave
+// still meets every block barrier, the same number of times.
 //
 // The window's two pointers are a kernel argument of the WINDOW instantiations alone (WIN is TkWindow there and empty
-// elsewhere), so every other instantiation keeps the signature, the kernarg layout and the code it had without the flag.
+// elsewhere), so every other instantiation keeps its signature and kernarg layout.
 template <int P, int W, bool VEC, bool GROUPED, bool NOISE, bool BIAS, bool WINDOW, class... WIN>
 __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d, int k, int slice_len, int S,
                                                             const float* __restrict__ user, const float* __restrict__ items,
@@ -171,11 +341,8 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     static_assert(!(NOISE && GROUPED), "the perturbation is keyed by the item's row");
     static_assert(!(WINDOW && (GROUPED || NOISE)), "the window is for the plain and the biased top-k only");
     static_assert(!(BIAS && (GROUPED || NOISE)), "the prior is for the plain top-k only");
-    __shared__ uint64_t buf[TK_UT][P];
+    TK_FILTER_LDS(lds, P);
     __shared__ uint64_t rseed[NOISE ? TK_UT : 1];
-    __shared__ uint64_t thr[TK_UT];
-    __shared__ int cnt[TK_UT];
-    __shared__ int32_t ex[TK_UT][TK_EX_LDS];
     __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
     constexpr int IT = 64 * W;
     const int lane = threadIdx.x & 63;
@@ -184,61 +351,38 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     const int slice = blockIdx.y;
     const int n_begin = slice * slice_len;
     const int n_end = min(GROUPED ? 32 * n_tiles : N, n_begin + slice_len);      // (grouped: tile rows, not catalogue rows)
-    const bool ex_lds = n_exclude <= TK_EX_LDS;
+    TkFilter<P, W> flt{lds, exclude, n_exclude, k, u0, B, lane, wave};
     int2* wwin = nullptr;          // WINDOW: the block's 32 (lo, hi)
     if constexpr (WINDOW) {
         __shared__ int2 wwin_lds[TK_UT];
         wwin = wwin_lds;
         tk_window_stage(wwin, win.window, u0, B);
     }
-
-    if (threadIdx.x < TK_UT) {
-        thr[threadIdx.x] = 0;
-        cnt[threadIdx.x] = 0;
-        if constexpr (NOISE) rseed[threadIdx.x] = tk_noise_row_seed(noise.seed, (uint64_t)noise.row_key[min(u0 + (int)threadIdx.x, B - 1)]);
+    if constexpr (NOISE) {
+        if (threadIdx.x < TK_UT) rseed[threadIdx.x] = tk_noise_row_seed(noise.seed, (uint64_t)noise.row_key[min(u0 + (int)threadIdx.x, B - 1)]);
     }
-    if (ex_lds)      // only this slice's ids matter; everything else (ids outside [0, N) included) becomes -1
-        for (int i = threadIdx.x; i < TK_UT * n_exclude; i += 64 * W) {
-            const int u = i / n_exclude, e = i - u * n_exclude;
-            const int64_t v = u0 + u < B ? exclude[(long)(u0 + u) * n_exclude + e] : -1;
-            if constexpr (GROUPED) ex[u][e] = (v >= 0 && v <= 0x7FFFFFFF) ? (int32_t)v : -1;    // ids, in any slice
-            else ex[u][e] = (v >= n_begin && v < n_end) ? (int32_t)v : -1;
-        }
+    if constexpr (GROUPED) flt.start(0, 0x80000000L);
+    else flt.start(n_begin, n_end);
     __syncthreads();
     int blo = 0, bhi = 0;
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
-
-    // cut user i's buffer (c entries) down to its best k, excluded ids dropped; returns the new threshold, sets c
-    auto flush = [&](int i, int& c) {
-        tk_drop_excluded(buf[i], c, ex_lds ? ex[i] : nullptr, exclude + (long)(u0 + i) * n_exclude, n_exclude, lane);
-        return tk_select<P>(buf[i], c, k, lane);
-    };
 
     const int r = lane & 31, h = lane >> 5;
     constexpr int NA = GROUPED ? TK_TN : 1;           // A operands per k-block: one per column tile when grouped
     const float* arow[NA];
     if constexpr (!GROUPED) arow[0] = user + (long)min(u0 + r, B - 1) * d;
     float* st = stage[wave];
-    const int m_full = d / 32;
     for (int n0 = n_begin; n0 < n_end; n0 += IT) {
         const int nw = n0 + 64 * wave;
         tk_f32x16 acc[TK_TN];
 #pragma unroll
         for (int c = 0; c < TK_TN; ++c) acc[c] = tk_f32x16{};
-        // grouped: the wave's two tiles (row of their first item, valid rows, group); wave-uniform
-        int trow[TK_TN] = {}, tlen[TK_TN] = {};
+        const TkWaveTiles tl(tiles, GROUPED ? n_tiles : 0, nw);          // grouped only
         if constexpr (GROUPED) {
 #pragma unroll
-            for (int c = 0; c < TK_TN; ++c) {
-                const int t = nw / 32 + c;
-                TkTile tl{0, 0, 0, 0};
-                if (t < n_tiles) tl = tiles[t];
-                trow[c] = __builtin_amdgcn_readfirstlane(tl.row);
-                tlen[c] = __builtin_amdgcn_readfirstlane(tl.len);
-                arow[c] = user + ((long)min(u0 + r, B - 1) * G + __builtin_amdgcn_readfirstlane(tl.grp)) * d;
-            }
+            for (int c = 0; c < TK_TN; ++c) arow[c] = user + ((long)min(u0 + r, B - 1) * G + tl.grp[c]) * d;
         }
-        float bv[BIAS ? TK_TN : 1] = {};          // BIAS: loaded here so that the MFMA loop hides the latency, added after it
+        float bv[BIAS ? TK_TN : 1] = {};          // BIAS: loaded here so that the chain hides the latency, added after it
         if constexpr (BIAS) {
             if (nw < n_end) {
 #pragma unroll
@@ -259,73 +403,9 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 dead = TK_WINDOW_SKIP && __ballot(any) == 0;
             }
         }
-        if (nw < n_end && (!GROUPED || tlen[0] + tlen[1] > 0) && !(WINDOW && dead)) {
-            const float* srow[8];           // rows this lane stages: 8j + lane / 8
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if constexpr (GROUPED) srow[j] = items + (long)min(trow[j >> 2] + 8 * (j & 3) + (lane >> 3), N - 1) * d + 4 * (lane & 7);
-                else srow[j] = items + (long)min(nw + 8 * j + (lane >> 3), N - 1) * d + 4 * (lane & 7);
-            }
-#define TK_GLOAD(m)                                                                                                        \
-    do {                                                                                                               \
-        const int k0_ = 32 * (m);                                                                                      \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                                \
-            if (VEC) {                                                                                                 \
-                const float4 v_ = *reinterpret_cast<const float4*>(srow[j] + k0_);                                     \
-                g[j][0] = v_.x; g[j][1] = v_.y; g[j][2] = v_.z; g[j][3] = v_.w;                                        \
-            } else {                                                                                                   \
-                _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) g[j][e_] = srow[j][k0_ + e_];                         \
-            }                                                                                                          \
-        }                                                                                                              \
-        _Pragma("unroll") for (int c_ = 0; c_ < NA; ++c_)                                                              \
-            _Pragma("unroll") for (int t = 0; t < 16; ++t) a[c_][t] = arow[c_][k0_ + 16 * h + t];                      \
-    } while (0)
-            if (m_full > 0) {
-                float g[8][4];
-                float a[NA][16];
-                TK_GLOAD(0);
-                for (int m = 0; m < m_full; ++m) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        *reinterpret_cast<float4*>(st + (8 * j + (lane >> 3)) * TK_BP + 4 * (lane & 7)) =
-                            make_float4(g[j][0], g[j][1], g[j][2], g[j][3]);
-                    tk_wave_sync();
-                    float b[TK_TN][16];
-#pragma unroll
-                    for (int c = 0; c < TK_TN; ++c)
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const float4 v = *reinterpret_cast<const float4*>(st + (32 * c + r) * TK_BP + 16 * h + 4 * t);
-                            b[c][4 * t] = v.x; b[c][4 * t + 1] = v.y; b[c][4 * t + 2] = v.z; b[c][4 * t + 3] = v.w;
-                        }
-                    float acur[NA][16];
-#pragma unroll
-                    for (int c = 0; c < NA; ++c)
-#pragma unroll
-                        for (int t = 0; t < 16; ++t) acur[c][t] = a[c][t];
-                    if (m + 1 < m_full) TK_GLOAD(m + 1);
-#pragma unroll
-                    for (int t = 0; t < 16; ++t)
-#pragma unroll
-                        for (int c = 0; c < TK_TN; ++c)
-                            acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[GROUPED ? c : 0][t], b[c][t], acc[c], 0, 0, 0);
-                    tk_wave_sync();        // this block's LDS reads stay ahead of the next block's writes
-                }
-            }
-#undef TK_GLOAD
-            for (int g8 = 4 * m_full; 8 * g8 < d; ++g8) {       // zero-padded groups of 8 past the last whole block
-                const int k0 = 8 * g8 + 4 * h;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float at = tk_ld(arow[0], k0 + t, d);
-#pragma unroll
-                    for (int c = 0; c < TK_TN; ++c) {
-                        const float* brow = items + (long)min(GROUPED ? trow[c] + r : nw + 32 * c + r, N - 1) * d;
-                        const float ac = GROUPED ? tk_ld(arow[GROUPED ? c : 0], k0 + t, d) : at;
-                        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, tk_ld(brow, k0 + t, d), acc[c], 0, 0, 0);
-                    }
-                }
-            }
+        if (nw < n_end && (!GROUPED || tl.len[0] + tl.len[1] > 0) && !(WINDOW && dead)) {
+            if constexpr (GROUPED) tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return tl.row_of(i, N); });
+            else tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
         }
         if constexpr (NOISE) {
             if (nw < n_end) {
@@ -346,87 +426,31 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                     for (int q = 0; q < 16; ++q) acc[c][q] = acc[c][q] + bv[c];
             }
         }
-        // filter.  C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5).
-        // Bit 16 c + q of `pend`: that score still has to be offered.
-        uint32_t pend = 0;
-        uint32_t gid[TK_TN] = {};           // grouped: the id of this lane's item in column tile c
+        bool live[TK_TN];
+        uint32_t id[TK_TN] = {};            // the id of this lane's item in column tile c
 #pragma unroll
         for (int c = 0; c < TK_TN; ++c) {
-            const int n = nw + 32 * c + r;
-            bool live = n < n_end;
-            if constexpr (GROUPED) {
-                live = live && r < tlen[c];
-                if (live) gid[c] = (uint32_t)item_ids[trow[c] + r];
-            }
-            if constexpr (WINDOW) live = live && !dead;       // a skipped wave offers nothing: its accumulators hold no score
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int b = u0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if constexpr (WINDOW) {
-                    const int2 w = wwin[b - u0];
-                    if (live && b < B && tv[c] >= w.x && tv[c] < w.y && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
-                } else {
-                    if (live && b < B && !__builtin_isnan(acc[c][q])) pend |= 1u << (16 * c + q);
-                }
+            if constexpr (GROUPED) live[c] = tl.live(c, nw, n_end, r, item_ids, id[c]);
+            else {
+                id[c] = (uint32_t)(nw + 32 * c + r);
+                live[c] = nw + 32 * c + r < n_end && !(WINDOW && dead);       // a skipped wave's accumulators hold no score
             }
         }
-        bool first = true;
-        while (__syncthreads_or(pend != 0)) {
-            if (!first) {
-                // sort every full buffer down to its best k (cnt may have run past P: those candidates are pending)
-                for (int i = wave; i < TK_UT; i += W) {
-                    if (cnt[i] >= P) {
-                        int c = P;
-                        const uint64_t t = flush(i, c);
-                        if (lane == 0) {
-                            thr[i] = t;
-                            cnt[i] = c;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-            first = false;
-#pragma unroll
-            for (int c = 0; c < TK_TN; ++c) {
-                const int n = nw + 32 * c + r;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const uint32_t bit = 1u << (16 * c + q);
-                    if (!(pend & bit)) continue;
-                    const int i = (q & 3) + 8 * (q >> 2) + 4 * h;
-                    const uint64_t e = tk_entry(acc[c][q], GROUPED ? gid[c] : (uint32_t)n);
-                    bool keep = false;
-                    if (e > thr[i]) {
-                        const int slot = atomicAdd(&cnt[i], 1);
-                        if (slot < P) buf[i][slot] = e;
-                        else keep = true;
-                    }
-                    if (!keep) pend &= ~bit;
-                }
-            }
-        }
+        uint32_t pend;
+        if constexpr (WINDOW) pend = flt.pending(acc, live, TkOpenWindow{wwin, tv});
+        else pend = flt.pending(acc, live, TkOpenAll{});
+        // unconditional: the offer holds the block's barriers, and a wave with pend == 0 has to meet them too
+        flt.offer(acc, pend, [&](int c) { return id[c]; });
     }
-    for (int i = wave; i < TK_UT; i += W) {
-        const int b = u0 + i;
-        if (b >= B) break;
-        int c = min(cnt[i], P);
-        flush(i, c);
-        uint64_t* dst = ws + ((long)b * S + slice) * k;          // the slice's best k, unsorted, 0-padded
-        for (int j = lane; j < k; j += 64) dst[j] = j < c ? buf[i][j] : 0;
-    }
+    flt.write(ws, S, slice);
 }
 
-// One wave per user: the best k of the user's S slice lists, sorted at the end.  Needs P >= k + 64.  top_scores may be null.
+// One wave: the best k of src[0, total) (entries of slice lists, 0 = padding), sorted at the end in buf[0, P), P >= k + 64;
+// their scores (-inf for padding; `scores` may be null) and ids (-1 for padding) go to scores[0, k) and ids[0, k).
 template <int P>
-__global__ __launch_bounds__(64) void topk_merge_kernel(int B, int k, int S, const uint64_t* __restrict__ ws,
-                                                        float* __restrict__ top_scores, int64_t* __restrict__ top_ids) {
-    __shared__ uint64_t buf[P];
-    const int lane = threadIdx.x;
-    const int b = blockIdx.x;
+__device__ __forceinline__ void tk_merge(uint64_t* buf, const uint64_t* __restrict__ src, long total, int k, int lane,
+                                         float* __restrict__ scores, int64_t* __restrict__ ids) {
     const unsigned long long below = (1ull << lane) - 1ull;
-    const uint64_t* src = ws + (long)b * S * k;
-    const long total = (long)S * k;
     int cnt = 0;
     uint64_t thr = 0;
     for (long c0 = 0; c0 < total; c0 += 64) {
@@ -445,86 +469,61 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(int B, int k, int S, con
     tk_flush<P>(buf, cnt, k, lane);
     for (int j = lane; j < k; j += 64) {
         const uint64_t e = buf[j];
-        if (top_scores) top_scores[(long)b * k + j] = e ? tk_entry_score(e) : -__builtin_huge_valf();
-        top_ids[(long)b * k + j] = e ? tk_entry_id(e) : -1;
+        if (scores) scores[j] = e ? tk_entry_score(e) : -__builtin_huge_valf();
+        ids[j] = e ? tk_entry_id(e) : -1;
     }
 }
 
-struct TopkGeom {
-    int tiles, S, slice_len;
-};
-
-static TopkGeom topk_geom(int32_t B, int64_t N) {
-    TopkGeom g{cdiv(B, TK_UT), 0, 0};
-    if (N == 0 || B == 0) return g;
-    int s = std::max(1, cdiv(TK_TARGET_BLOCKS, g.tiles));
-    s = std::min(s, std::max(1, cdiv(N, TK_MIN_SLICE)));
-    g.slice_len = cdiv(cdiv(N, s), TK_IT) * TK_IT;
-    g.S = cdiv(N, g.slice_len);
-    return g;
+// One wave per user: the best k of the user's S slice lists.  top_scores may be null.
+template <int P>
+__global__ __launch_bounds__(64) void topk_merge_kernel(int B, int k, int S, const uint64_t* __restrict__ ws,
+                                                        float* __restrict__ top_scores, int64_t* __restrict__ top_ids) {
+    __shared__ uint64_t buf[P];
+    const long b = blockIdx.x;
+    tk_merge<P>(buf, ws + b * S * k, (long)S * k, k, threadIdx.x, top_scores ? top_scores + b * k : nullptr, top_ids + b * k);
 }
+
+static TkGeom topk_geom(int32_t B, int64_t N) { return tk_geom(B, N, true); }
 
 static bool topk_args_ok(int32_t B, int64_t N, int32_t d, int32_t k) {
     return B >= 0 && N >= 0 && N <= TK_MAX_N && d >= 1 && k >= 1 && k <= TK_MAX_K;
 }
 
-// Both kernels of one call.  grouped: `user` is the query [B, G, d], the slices run over the tile rows of `tiles`.
-// bias (plain top-k only, [N] fp32): non-null selects the BIAS instantiations.  win (plain top-k only, with or without bias):
-// a non-null window selects the WINDOW instantiations.
-static int topk_launch(bool grouped, int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int64_t n_tiles, const float* user,
+// Both kernels of one call.  GROUPED: `user` is the query [B, G, d], the slices run over the tile rows of `tiles`.  NOISE: the
+// perturbation of nrms_softmax_sample_dot.  Neither (the plain top-k): a non-null bias ([N] fp32) selects the BIAS
+// instantiations, a non-null window the WINDOW ones.
+template <bool GROUPED, bool NOISE>
+static int topk_launch(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int64_t n_tiles, const float* user,
                        const float* items, const int32_t* item_ids, const TkTile* tiles, const int64_t* exclude, int32_t n_exclude,
                        float* top_scores, int64_t* top_ids, uint64_t* ws, hipStream_t s, const char* who,
                        TkNoise noise = TkNoise{nullptr, 0.0f, 0}, const float* bias = nullptr,
                        TkWindow win = TkWindow{nullptr, nullptr}) {
-    const TopkGeom g = topk_geom(B, grouped ? 32 * n_tiles : N);
+    const TkGeom g = topk_geom(B, GROUPED ? 32 * n_tiles : N);
+    int rc = NRMS_OK;
     char what[64];
-    if (g.S > 0) {
-        const bool vec = (d & 3) == 0 && ((uintptr_t)user & 15) == 0 && ((uintptr_t)items & 15) == 0;
-        const dim3 grid(g.tiles, g.S);
-        const int n = (int)N, nt = (int)n_tiles;
-#define TK_LAUNCH_G(P, W, V, GR, NS, BI)                                                                                   \
-    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, GR, NS, BI, false>), grid, dim3(64 * W), 0, s, B, n, d, k, g.slice_len, g.S, user, \
-                       items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias)
-#define TK_LAUNCH_W(P, W, V, BI)                                                                                           \
-    hipLaunchKernelGGL((topk_slice_kernel<P, W, V, false, false, BI, true, TkWindow>), grid, dim3(64 * W), 0, s, B, n, d, k,     \
-                       g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias, win)
-#define TK_LAUNCH(P, W)                                                                                                    \
-    do {                                                                                                                   \
-        if (grouped) {                                                                                                     \
-            if (vec) TK_LAUNCH_G(P, W, true, true, false, false);                                                          \
-            else TK_LAUNCH_G(P, W, false, true, false, false);                                                             \
-        } else if (noise.row_key) {                                                                                        \
-            if (vec) TK_LAUNCH_G(P, W, true, false, true, false);                                                          \
-            else TK_LAUNCH_G(P, W, false, false, true, false);                                                             \
-        } else if (win.window && bias) {                                                                                   \
-            if (vec) TK_LAUNCH_W(P, W, true, true);                                                    \
-            else TK_LAUNCH_W(P, W, false, true);                                                       \
-        } else if (win.window) {                                                                                           \
-            if (vec) TK_LAUNCH_W(P, W, true, false);                                                   \
-            else TK_LAUNCH_W(P, W, false, false);                                                      \
-        } else if (bias) {                                                                                                 \
-            if (vec) TK_LAUNCH_G(P, W, true, false, false, true);                                                          \
-            else TK_LAUNCH_G(P, W, false, false, false, true);                                                             \
-        } else {                                                                                                           \
-            if (vec) TK_LAUNCH_G(P, W, true, false, false, false);                                                         \
-            else TK_LAUNCH_G(P, W, false, false, false, false);                                                            \
-        }                                                                                                                  \
-    } while (0)
-        if (k + 64 <= 128) TK_LAUNCH(128, TK_WAVES);
-        else if (k + 64 <= 256) TK_LAUNCH(256, TK_WAVES);
-        else TK_LAUNCH(512, 2);
-#undef TK_LAUNCH
-#undef TK_LAUNCH_G
-#undef TK_LAUNCH_W
-        snprintf(what, sizeof what, "%s(slices)", who);
-        const int rc = check_launch(what);
-        if (rc != NRMS_OK) return rc;
-    }
-    if (k + 64 <= 128) hipLaunchKernelGGL(topk_merge_kernel<128>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
-    else if (k + 64 <= 256) hipLaunchKernelGGL(topk_merge_kernel<256>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
-    else hipLaunchKernelGGL(topk_merge_kernel<512>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
-    snprintf(what, sizeof what, "%s(merge)", who);
-    return check_launch(what);
+    tk_with_pw(k, [&](auto P, auto W) {
+        constexpr int p = decltype(P)::value, w = decltype(W)::value;
+        if (g.S > 0) {
+            const dim3 grid(g.tiles, g.S), block(64 * w);
+            const int n = (int)N, nt = (int)n_tiles;
+            tk_with_flags([&](auto V, auto BI, auto WI) {
+                constexpr bool v = decltype(V)::value, bi = decltype(BI)::value, wi = decltype(WI)::value;
+                if constexpr (wi && !GROUPED && !NOISE)
+                    hipLaunchKernelGGL((topk_slice_kernel<p, w, v, false, false, bi, true, TkWindow>), grid, block, 0, s, B, n, d, k,
+                                       g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias, win);
+                else if constexpr (!wi && (!bi || (!GROUPED && !NOISE)))
+                    hipLaunchKernelGGL((topk_slice_kernel<p, w, v, GROUPED, NOISE, bi, false>), grid, block, 0, s, B, n, d, k,
+                                       g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias);
+            }, tk_vec_ok(d, user, items), bias != nullptr, win.window != nullptr);
+            snprintf(what, sizeof what, "%s(slices)", who);
+            rc = check_launch(what);
+            if (rc != NRMS_OK) return;
+        }
+        hipLaunchKernelGGL(topk_merge_kernel<p>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
+        snprintf(what, sizeof what, "%s(merge)", who);
+        rc = check_launch(what);
+    });
+    return rc;
 }
 
 }  // namespace nrms

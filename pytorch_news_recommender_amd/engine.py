@@ -746,6 +746,29 @@ class NRMSEngine:
         return impression_metrics(self.lib, self.device, scores, labels, lens, ks, ranks)
 
     # ---- retrieval over a whole catalogue ---------------------------------------------------------
+    def _cuda_device(self):
+        """The engine's device with its index resolved: what the .device of a tensor on it compares equal to."""
+        return self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def _check_tensor(self, who, name, t, dtype, ndim):
+        """Raises unless t is a contiguous ndim-D tensor of dtype on the engine's device."""
+        if t.dim() != ndim or t.dtype != dtype or t.device != self._cuda_device() or not t.is_contiguous():
+            raise _lib.NrmsError("%s: %s must be a contiguous %d-D %s tensor on %s (got %s %s on %s%s)"
+                                 % (who, name, ndim, dtype, self.device, tuple(t.shape), t.dtype, t.device,
+                                    "" if t.is_contiguous() else ", not contiguous"))
+
+    def _exclude_arg(self, who, exclude, B):
+        """The checked exclude list of a retrieval call -> (exclude, n_exclude): a contiguous [B, n] int64 tensor on the device,
+        or (None, 0) for None and for n = 0."""
+        if exclude is None:
+            return None, 0
+        if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != self._cuda_device()
+                or not exclude.is_contiguous()):
+            raise _lib.NrmsError("%s: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
+                                 % (who, self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
+        n_ex = exclude.shape[1]
+        return (exclude, n_ex) if n_ex else (None, 0)
+
     def _item_bias(self, who, bias, N, dev):
         """The checked per-item prior of top_k / rank_of: a contiguous float32 [N] tensor on the device."""
         if (not torch.is_tensor(bias) or bias.dim() != 1 or bias.shape[0] != N or bias.dtype != torch.float32 or bias.device != dev
@@ -785,25 +808,14 @@ class NRMSEngine:
         all-padding row; a time of INT32_MAX is never eligible; nrms_topk_dot_windowed, with the bias when one is given).
         include/nrms_hip.h states the contract."""
         k = int(k)
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
-        for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32)):
-            if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NrmsError("top_k: %s must be a contiguous 2-D %s tensor on %s (got %s %s on %s%s)"
-                                     % (name, dt, self.device, tuple(t.shape), t.dtype, t.device,
-                                        "" if t.is_contiguous() else ", not contiguous"))
+        dev = self._cuda_device()
+        self._check_tensor("top_k", "user_vec", user_vec, torch.float32, 2)
+        self._check_tensor("top_k", "items", items, torch.float32, 2)
         B, d = user_vec.shape
         N = items.shape[0]
         if items.shape[1] != d:
             raise _lib.NrmsError("top_k: items width %d != user_vec width %d" % (items.shape[1], d))
-        n_ex = 0
-        if exclude is not None:
-            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
-                    or not exclude.is_contiguous()):
-                raise _lib.NrmsError("top_k: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
-                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
-            n_ex = exclude.shape[1]
-            if n_ex == 0:
-                exclude = None
+        exclude, n_ex = self._exclude_arg("top_k", exclude, B)
         if bias is not None:
             self._item_bias("top_k", bias, N, dev)
         item_time, window = self._time_window("top_k", item_time, window, N, B, dev)
@@ -838,27 +850,15 @@ class NRMSEngine:
         vector, items, row key, inv_temperature, seed, its exclude list) only; rows with fewer than S eligible items end in
         id -1 / key -inf.  inv_temperature 0 is the uniform draw.  include/nrms_hip.h states the contract."""
         S = int(S)
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt, nd in (("user_vec", user_vec, torch.float32, 2), ("items", items, torch.float32, 2), ("row_key", row_key, torch.int64, 1)):
-            if t.dim() != nd or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NrmsError("softmax_sample: %s must be a contiguous %d-D %s tensor on %s (got %s %s on %s%s)"
-                                     % (name, nd, dt, self.device, tuple(t.shape), t.dtype, t.device,
-                                        "" if t.is_contiguous() else ", not contiguous"))
+            self._check_tensor("softmax_sample", name, t, dt, nd)
         B, d = user_vec.shape
         N = items.shape[0]
         if items.shape[1] != d:
             raise _lib.NrmsError("softmax_sample: items width %d != user_vec width %d" % (items.shape[1], d))
         if row_key.shape[0] != B:
             raise _lib.NrmsError("softmax_sample: row_key must be [%d] (got %s)" % (B, tuple(row_key.shape)))
-        n_ex = 0
-        if exclude is not None:
-            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
-                    or not exclude.is_contiguous()):
-                raise _lib.NrmsError("softmax_sample: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
-                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
-            n_ex = exclude.shape[1]
-            if n_ex == 0:
-                exclude = None
+        exclude, n_ex = self._exclude_arg("softmax_sample", exclude, B)
         nbytes = self.lib.nrms_softmax_sample_dot_workspace_bytes(B, N, d, S, n_ex)
         if nbytes == 0:
             raise _lib.NrmsError("softmax_sample: arguments rejected (B=%d, N=%d, d=%d, S=%d; 1 <= S <= 256)" % (B, N, d, S))
@@ -884,13 +884,9 @@ class NRMSEngine:
         order.  A row's result does not depend on the rest of the batch, so batches whose workspace would pass
         MMR_WORKSPACE_CAP go in row chunks.  include/nrms_hip.h states the contract."""
         k, lam = int(k), float(lam)
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt in (("items", items, torch.float32), ("short_ids", short_ids, torch.int64),
                             ("short_scores", short_scores, torch.float32)):
-            if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NrmsError("mmr_rerank: %s must be a contiguous 2-D %s tensor on %s (got %s %s on %s%s)"
-                                     % (name, dt, self.device, tuple(t.shape), t.dtype, t.device,
-                                        "" if t.is_contiguous() else ", not contiguous"))
+            self._check_tensor("mmr_rerank", name, t, dt, 2)
         N, d = items.shape
         B, M = short_ids.shape
         if short_scores.shape != short_ids.shape:
@@ -932,27 +928,16 @@ class NRMSEngine:
         calls nrms_rank_dot as before.  item_time [N] int32 and window [B, 2] int32 (device; both or neither): top_k's time window,
         ranks count the items inside user b's window only and a target outside it gets rank 0 / -inf (nrms_rank_dot_windowed).
         include/nrms_hip.h states the contract."""
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = self._cuda_device()
         for name, t, dt in (("user_vec", user_vec, torch.float32), ("items", items, torch.float32), ("targets", targets, torch.int64)):
-            if t.dim() != 2 or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NrmsError("rank_of: %s must be a contiguous 2-D %s tensor on %s (got %s %s on %s%s)"
-                                     % (name, dt, self.device, tuple(t.shape), t.dtype, t.device,
-                                        "" if t.is_contiguous() else ", not contiguous"))
+            self._check_tensor("rank_of", name, t, dt, 2)
         B, d = user_vec.shape
         N = items.shape[0]
         if items.shape[1] != d:
             raise _lib.NrmsError("rank_of: items width %d != user_vec width %d" % (items.shape[1], d))
         if targets.shape[0] != B:
             raise _lib.NrmsError("rank_of: targets must be [%d, T] (got %s)" % (B, tuple(targets.shape)))
-        n_ex = 0
-        if exclude is not None:
-            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
-                    or not exclude.is_contiguous()):
-                raise _lib.NrmsError("rank_of: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
-                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
-            n_ex = exclude.shape[1]
-            if n_ex == 0:
-                exclude = None
+        exclude, n_ex = self._exclude_arg("rank_of", exclude, B)
         if bias is not None:
             self._item_bias("rank_of", bias, N, dev)
         item_time, window = self._time_window("rank_of", item_time, window, N, B, dev)
@@ -1036,13 +1021,9 @@ class NRMSEngine:
         [B, N] matrix (nrms_topk_grouped_dot).  Order and padding as top_k, with item ids in place of rows.  Users go in
         chunks of grouped_chunk_users; the result does not depend on the chunking."""
         k = int(k)
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt, nd in (("query", query, torch.float32, 3), ("items", items, torch.float32, 2),
                                 ("item_ids", item_ids, torch.int32, 1), ("group_ptr", group_ptr, torch.int64, 1)):
-            if t.dim() != nd or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NrmsError("top_k_grouped: %s must be a contiguous %d-D %s tensor on %s (got %s %s on %s%s)"
-                                     % (name, nd, dt, self.device, tuple(t.shape), t.dtype, t.device,
-                                        "" if t.is_contiguous() else ", not contiguous"))
+            self._check_tensor("top_k_grouped", name, t, dt, nd)
         B, G, d = query.shape
         N = items.shape[0]
         if items.shape[1] != d:
@@ -1050,15 +1031,7 @@ class NRMSEngine:
         if item_ids.shape[0] != N or group_ptr.shape[0] != G + 1:
             raise _lib.NrmsError("top_k_grouped: item_ids must be [%d] and group_ptr [%d] (got %s, %s)"
                                  % (N, G + 1, tuple(item_ids.shape), tuple(group_ptr.shape)))
-        n_ex = 0
-        if exclude is not None:
-            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
-                    or not exclude.is_contiguous()):
-                raise _lib.NrmsError("top_k_grouped: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
-                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
-            n_ex = exclude.shape[1]
-            if n_ex == 0:
-                exclude = None
+        exclude, n_ex = self._exclude_arg("top_k_grouped", exclude, B)
         if self.lib.nrms_topk_grouped_dot_workspace_bytes(B, N, d, k, G) == 0:
             raise _lib.NrmsError("top_k_grouped: arguments rejected (B=%d, N=%d, d=%d, k=%d, G=%d; 1 <= k <= 256, G >= 1)"
                                  % (B, N, d, k, G))
@@ -1086,13 +1059,9 @@ class NRMSEngine:
         library chooses) or the 32-row tiles per slice of the launch geometry; the result does not depend on it.  Users go in
         chunks whose workspace stays under ``retrieval_chunk_bytes``; the result does not depend on the chunking."""
         k, slice_tiles = int(k), int(slice_tiles)
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         for name, t, dt, nd in (("user", user, torch.float32, 2), ("items", items, torch.float32, 2),
                                 ("item_ids", item_ids, torch.int32, 1), ("section_ptr", section_ptr, torch.int64, 1)):
-            if t.dim() != nd or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise _lib.NrmsError("top_k_sections: %s must be a contiguous %d-D %s tensor on %s (got %s %s on %s%s)"
-                                     % (name, nd, dt, self.device, tuple(t.shape), t.dtype, t.device,
-                                        "" if t.is_contiguous() else ", not contiguous"))
+            self._check_tensor("top_k_sections", name, t, dt, nd)
         B, d = user.shape
         N = items.shape[0]
         G = section_ptr.shape[0] - 1
@@ -1100,17 +1069,9 @@ class NRMSEngine:
             raise _lib.NrmsError("top_k_sections: items width %d != user width %d" % (items.shape[1], d))
         if item_ids.shape[0] != N:
             raise _lib.NrmsError("top_k_sections: item_ids must be [%d] (got %s)" % (N, tuple(item_ids.shape)))
-        n_ex = 0
-        if exclude is not None:
-            if (exclude.dim() != 2 or exclude.shape[0] != B or exclude.dtype != torch.int64 or exclude.device != dev
-                    or not exclude.is_contiguous()):
-                raise _lib.NrmsError("top_k_sections: exclude must be a contiguous [B, n] int64 tensor on %s (got %s %s on %s)"
-                                     % (self.device, tuple(exclude.shape), exclude.dtype, exclude.device))
-            n_ex = exclude.shape[1]
-            if n_ex == 0:
-                exclude = None
+        exclude, n_ex = self._exclude_arg("top_k_sections", exclude, B)
         if bias is not None:
-            self._item_bias("top_k_sections", bias, N, dev)
+            self._item_bias("top_k_sections", bias, N, self._cuda_device())
         query = self.lib.nrms_topk_sections_dot_workspace_bytes
         if G < 1 or query(B, N, d, k, G, slice_tiles) == 0:
             raise _lib.NrmsError("top_k_sections: arguments rejected (B=%d, N=%d, d=%d, k=%d, G=%d, slice_tiles=%d; 1 <= k <= 256, "
