@@ -547,6 +547,62 @@ int nrms_rank_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t T, const flo
                            int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- The exact top-k through an fp16 shortlist with a certificate (csrc/topkcoarse.hip; serving: nrms_topk_dot's rows for less
+ * than nrms_topk_dot's scan; PARITY UNPINNED, the reference has no catalogue retrieval) ----
+ * A coarse pass over an fp16 copy of the catalogue on v_mfma_f32_32x32x16_f16 picks a shortlist of M items per user, the shortlist
+ * is re-scored with nrms_topk_dot's exact chain, and a per-user certificate proves from norms formed beforehand that no item
+ * outside the shortlist can reach the top k.
+ * GUARANTEE: a row with certified[b] = 1 equals nrms_topk_dot's row b (same user, items, exclude, k) bit for bit, ids and
+ *   scores.  A row with certified[b] = 0 is the exact top k of the shortlist only: send it through nrms_topk_dot.
+ *
+ * nrms_catalogue_f16_pitch(d) = 32 * ceil(d / 32): the halves per row of the packed copy (0 = d rejected).
+ *
+ * nrms_catalogue_pack_f16: items [N, d] fp32 -> items16 [N, pitch] uint16 (fp16 bits; 16-byte aligned; N * pitch * 2 bytes) and
+ *   stats float [2] on the device (4-byte aligned).
+ *   Element rule h(x): a magnitude above 65504 becomes +-65504, a magnitude below 2^-14 becomes +-0 (both decided on the fp32
+ *     input), everything else is rounded to nearest even: no subnormal and no infinity is ever stored, so the MFMA's input-flush
+ *     mode cannot matter.  Columns >= d are 0.  A row holding a NaN or an infinity is stored as zeros and makes stats[0] = +inf.
+ *   stats[0] = NRM >= max_n ||items[n]||_2, stats[1] = ERR >= max_n ||items[n] - items16[n]||_2 (over the rows without NaN / inf):
+ *     the sums are formed in fp64 and rounded UP to fp32; the maximum over the rows is an integer atomic max on the float's bits,
+ *     so it has no order and two runs are bit-identical.  N = 0 gives stats = {0, 0}.
+ *   One memset and one kernel on `stream`, no host synchronisation.  Pack again whenever items changes.
+ *
+ * nrms_topk_dot_coarse: user [B, d], items [N, d] fp32, items16 / stats as packed from THESE items; exclude, top_scores [B, k],
+ *   top_ids [B, k] as nrms_topk_dot's; certified [B] uint8; short_scores [B, M] fp32 and short_ids [B, M] int64, both NULLABLE.
+ *   Limits: 1 <= k <= M <= 256; every other limit, B = 0 (a no-op) and N = 0 (all-padding rows, certified) are nrms_topk_dot's.
+ *   (a) Per user: u16 = h(user[b]) padded to the pitch, in the workspace, and in fp64, rounded up, un >= ||u||, un16 >= ||u16||,
+ *       ue >= ||u - u16||.  A user row holding a NaN or an infinity is stored as zeros with infinite norms (never certified).
+ *   (b) Coarse score c(b, n): ONE fp32 accumulator over the whole pitch on v_mfma_f32_32x32x16_f16, no split-K, each whole
+ *       superblock sb of 64 halves in four instructions (halves 64 sb + 32 h + 8 s + j of lane half h, instruction s, element j),
+ *       a last block of 32 halves in two (16 h + 8 s + j of it), the same fixed order for every (user, item): its bits do not
+ *       depend on B, N, M, the item's row, the exclude list or the run.  Eligibility (exclude,
+ *       NaN) and the order (score descending, smaller n first, -0.0 = +0.0) are nrms_topk_dot's, through the same filter.
+ *   (c) The shortlist: the M eligible items of largest c(b, n) in that order, L = min(M, #eligible) real entries, then id -1 /
+ *       score -inf; written to short_scores / short_ids when given.  It is nrms_topk_dot at k = M over the coarse scores.
+ *   (d) Every shortlist entry's exact score s(b, n) is nrms_topk_dot's chain against the fp32 row it names (the same code, the same
+ *       bits); row b of top_scores / top_ids is the first min(k, L) shortlist entries in nrms_topk_dot's order of their EXACT
+ *       scores, then id -1 / score -inf.
+ *   Certificate, in fp64 with every product and sum rounded up: certified[b] = 1 iff stats and the user's norms are finite,
+ *       un * NRM <= 2^100, and either L < M (every eligible item is in the shortlist) or s_k > c_M + E_b strictly, s_k the k-th
+ *       exact score of the row and c_M the M-th coarse score, with
+ *         E_b = ue*NRM + un16*ERR + gamma_d*un*NRM + alpha_d*un16*(NRM + ERR) + d*2^-140,
+ *         gamma_d = d*2^-24 / (1 - d*2^-24)  (the exact fmaf chain),   alpha_d = d*2^-21  (the fp16 MFMA's fp32 accumulation).
+ *       Soundness: u.n - u16.n16 = (u - u16).n + u16.(n - n16), both terms bounded by Cauchy-Schwarz with the norms; an item outside
+ *       a full shortlist has c <= c_M, so its exact score is <= c_M + E_b < s_k: it can neither enter the top k nor tie into it.
+ *   Argument errors return NRMS_EINVAL with a message that starts "topk_dot_coarse: ..." and names the argument (items16 must be
+ *     16-byte aligned, stats 4-byte); an undersized workspace returns NRMS_EWORKSPACE.  Nothing is launched after an error.
+ *   Workspace: nrms_topk_dot_coarse_workspace_bytes(B, N, d, k, M) bytes, 8-byte aligned (0 = arguments rejected: k < 1, k > M,
+ *     M > 256 and whatever nrms_topk_dot_workspace_bytes rejects).  What it holds on entry does not matter.
+ *   Five kernels on `stream` (user, slices, merge, re-score, finish), no host synchronisation, no allocation; plain vector loads
+ *     and stores, no atomics beyond the LDS counters of nrms_topk_dot's slice kernel. */
+int32_t nrms_catalogue_f16_pitch(int32_t d);
+int nrms_catalogue_pack_f16(int64_t N, int32_t d, const float* items, uint16_t* items16, float* stats, void* stream);
+size_t nrms_topk_dot_coarse_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k, int32_t M);
+int nrms_topk_dot_coarse(int32_t B, int64_t N, int32_t d, int32_t k, int32_t M, const float* user, const float* items,
+                         const uint16_t* items16, const float* stats, const int64_t* exclude, int32_t n_exclude,
+                         float* top_scores, int64_t* top_ids, uint8_t* certified, float* short_scores /* [B, M], nullable */,
+                         int64_t* short_ids /* [B, M], nullable */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Negatives from the model's own softmax over the whole catalogue (csrc/softmaxsample.hip; training: "which S news does the
  * model itself confuse with the positive right now?"; PARITY UNPINNED, the reference draws its negatives offline) ----
  * For each user b < B: S items drawn WITHOUT replacement from softmax(s(b, .) * inv_temperature) over the eligible items, never

@@ -130,6 +130,21 @@ def impression_metrics(lib, device, scores, labels, lens, ks=(5, 10), ranks=Fals
     return out
 
 
+class PackedCatalogue:
+    """What NRMSEngine.pack_catalogue returns and top_k_coarse reads: items [N, d] fp32, the rows it was made from (kept: the exact
+    re-scoring reads them); items16 [N, pitch] int16, their fp16 bits (include/nrms_hip.h nrms_catalogue_pack_f16); stats [2] fp32
+    on the device: the bounds NRM and ERR of the certificate.  source: (data_ptr, shape) of the tensor the caller named (for
+    Model.pack_catalogue the whole catalogue, whose rows 1.. are ``items``), by which a stale pack is told."""
+
+    def __init__(self, items, items16, stats, source=None):
+        self.items, self.items16, self.stats = items, items16, stats
+        self.source = source if source is not None else (items.data_ptr(), tuple(items.shape))
+
+    @property
+    def nbytes(self):
+        return self.items16.numel() * 2
+
+
 class NRMSEngine:
     """One NRMS forward / backward / optimizer step on one GPU."""
 
@@ -841,6 +856,53 @@ class NRMSEngine:
                                     _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
         _lib.check(rc, "nrms_topk_dot")
         return scores, ids
+
+    def pack_catalogue(self, items):
+        """items [N, d] fp32 (device, contiguous) -> PackedCatalogue: the fp16 copy top_k_coarse scans (N * pitch * 2 bytes, pitch =
+        32 ceil(d / 32)) and its two norm bounds, beside the fp32 rows it was made from (nrms_catalogue_pack_f16).  Pack again
+        whenever the rows change."""
+        self._check_tensor("pack_catalogue", "items", items, torch.float32, 2)
+        N, d = items.shape
+        pitch = self.lib.nrms_catalogue_f16_pitch(d)
+        if pitch == 0:
+            raise _lib.NrmsError("pack_catalogue: arguments rejected (N=%d, d=%d; d >= 1)" % (N, d))
+        items16 = torch.empty(N, pitch, dtype=torch.int16, device=self.device)
+        stats = torch.empty(2, dtype=torch.float32, device=self.device)
+        rc = self.lib.nrms_catalogue_pack_f16(C.c_int64(N), d, _lib.ptr(items), _lib.ptr(items16), _lib.ptr(stats), _stream())
+        _lib.check(rc, "nrms_catalogue_pack_f16")
+        return PackedCatalogue(items, items16, stats)
+
+    def top_k_coarse(self, user_vec, packed, k, M, exclude=None, return_shortlist=False):
+        """user_vec [B, d] fp32, packed: pack_catalogue(items), exclude as top_k's -> (scores [B, k] fp32, ids [B, k] int64, certified
+        [B] uint8), with return_shortlist also the coarse shortlist (short_scores [B, M] fp32, short_ids [B, M] int64).  A row with
+        certified = 1 is top_k's row bit for bit; a row with certified = 0 is the exact top k of its fp16 shortlist only and has to go
+        through top_k (nrms_topk_dot_coarse; include/nrms_hip.h states the certificate).  1 <= k <= M <= 256."""
+        k, M = int(k), int(M)
+        if not isinstance(packed, PackedCatalogue):
+            raise _lib.NrmsError("top_k_coarse: packed must be a PackedCatalogue (pack_catalogue(items)), got %s" % type(packed).__name__)
+        items = packed.items
+        self._check_tensor("top_k_coarse", "user_vec", user_vec, torch.float32, 2)
+        self._check_tensor("top_k_coarse", "items", items, torch.float32, 2)
+        B, d = user_vec.shape
+        N = items.shape[0]
+        if items.shape[1] != d:
+            raise _lib.NrmsError("top_k_coarse: items width %d != user_vec width %d" % (items.shape[1], d))
+        exclude, n_ex = self._exclude_arg("top_k_coarse", exclude, B)
+        nbytes = self.lib.nrms_topk_dot_coarse_workspace_bytes(B, N, d, k, M)
+        if nbytes == 0:
+            raise _lib.NrmsError("top_k_coarse: arguments rejected (B=%d, N=%d, d=%d, k=%d, M=%d; 1 <= k <= M <= 256)" % (B, N, d, k, M))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        cert = torch.empty(B, dtype=torch.uint8, device=self.device)
+        ss = torch.empty(B, M, dtype=torch.float32, device=self.device) if return_shortlist else None
+        si = torch.empty(B, M, dtype=torch.int64, device=self.device) if return_shortlist else None
+        rc = self.lib.nrms_topk_dot_coarse(B, C.c_int64(N), d, k, M, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(packed.items16),
+                                           _lib.ptr(packed.stats), _lib.ptr(exclude), n_ex, _lib.ptr(scores), _lib.ptr(ids),
+                                           _lib.ptr(cert), _lib.ptr(ss), _lib.ptr(si), _lib.ptr(ws), C.c_size_t(ws.numel() * 8),
+                                           _stream())
+        _lib.check(rc, "nrms_topk_dot_coarse")
+        return (scores, ids, cert, ss, si) if return_shortlist else (scores, ids, cert)
 
     def softmax_sample(self, user_vec, items, row_key, S, inv_temperature, seed, exclude=None, return_keys=False):
         """user_vec [B, d], items [N, d] fp32, row_key [B] int64 in [0, 2^48), exclude [B, n_exclude] int64 or None (device,

@@ -226,7 +226,10 @@ class Model(FlatHipModel):
                                   "click graph, not on a catalogue row alone (no recommend either)")
 
     def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
-                  item_bias=None, item_time=None, window=None):
+                  item_bias=None, item_time=None, window=None, coarse=None, coarse_shortlist=None, return_certified=False):
+        if coarse is not None or coarse_shortlist is not None or return_certified:
+            raise _lib.NrmsError("graph: recommend takes no coarse / coarse_shortlist / return_certified: the model cannot "
+                                 "recommend from a catalogue at all, a candidate's score depends on its neighbours in the click graph")
         if item_time is not None or window is not None:
             raise _lib.NrmsError("graph: recommend takes no item_time / window: the model cannot recommend from a catalogue at "
                                  "all, a candidate's score depends on its neighbours in the click graph")

@@ -306,7 +306,7 @@ class Model(FlatHipModel):
 
     @torch.no_grad()
     def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
-                  item_bias=None, item_time=None, window=None):
+                  item_bias=None, item_time=None, window=None, coarse=None, coarse_shortlist=None, return_certified=False):
         """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores [B, k]
         fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_grouped_dot).  The diversity
         re-ranking of nrms_hip.Model.recommend is refused (NrmsError): it works on a row-ordered catalogue.  So is its
@@ -316,7 +316,12 @@ class Model(FlatHipModel):
         categories are catalogue rows, a slot is valid where its id is not 0, and the interests are those forward builds;
         a news item's score is its forward score as that user's candidate.  Ids outside the catalogue are read as padding
         and counted (check_recommend_ids raises).  News id 0 is never returned, with exclude_history neither is a browsed
-        id; missing slots get id -1 / score -inf."""
+        id; missing slots get id -1 / score -inf.  The fp16 shortlist path (``coarse``) is refused too: its certificate bounds
+        one dot product per user, not a query per group."""
+        if coarse is not None or coarse_shortlist is not None or return_certified:
+            raise _lib.NrmsError("hierec: recommend takes no coarse / coarse_shortlist / return_certified: its catalogue is scored "
+                                 "with a query per (topic, sub-topic) group (nrms_topk_grouped_dot), which has no fp16 shortlist "
+                                 "and no certificate")
         if item_time is not None or window is not None:
             raise _lib.NrmsError("hierec: recommend takes no item_time / window: its catalogue is scored with a query per (topic, "
                                  "sub-topic) group (nrms_topk_grouped_dot), which has no time window")

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import FlatLayout, ModelDims, NRMSEngine
+from ..engine import FlatLayout, ModelDims, NRMSEngine, PackedCatalogue
 from ._flat_model import FlatHipModel
 
 
@@ -186,8 +186,60 @@ class Model(FlatHipModel):
         return self._engine.encode_titles(self._flat, _ids_on(dev, titles), tag="news_eval")
 
     @torch.no_grad()
+    def pack_catalogue(self, catalogue):
+        """catalogue: encode_catalogue's [N, width] (contiguous) -> a PackedCatalogue for recommend(coarse=...): the fp16 copy of
+        rows 1.., as recommend reads them ((N - 1) * 32 ceil(width / 32) * 2 bytes), and its norm bounds (include/nrms_hip.h
+        nrms_catalogue_pack_f16).  It belongs to this very tensor: pack again after every encode_catalogue."""
+        dev = self._prepare()
+        cat = torch.as_tensor(catalogue)
+        d = self._catalogue_width()
+        if cat.dim() != 2 or cat.shape[1] != d or cat.dtype != torch.float32 or cat.device != dev or cat.shape[0] < 1 or not cat.is_contiguous():
+            raise _lib.NrmsError("pack_catalogue: catalogue must be a contiguous [N >= 1, %d] float32 tensor on %s (encode_catalogue), got %s %s on %s"
+                                 % (d, dev, tuple(cat.shape), cat.dtype, cat.device))
+        packed = self._engine.pack_catalogue(cat[1:])
+        packed.source = (cat.data_ptr(), tuple(cat.shape))
+        return packed
+
+    @staticmethod
+    def _coarse_args(who, k, coarse, coarse_shortlist, return_certified, diversity, shortlist, return_ild, item_bias, item_time, window):
+        """recommend's checks of the coarse path that need no device -> the shortlist length M (None without ``coarse``)."""
+        if coarse is None:
+            if coarse_shortlist is not None or return_certified:
+                raise _lib.NrmsError("%s: coarse_shortlist / return_certified belong to the fp16 shortlist path (give coarse=pack_catalogue(catalogue))" % who)
+            return None
+        if diversity is not None or shortlist is not None or return_ild:
+            raise _lib.NrmsError("%s: coarse takes no diversity / shortlist / return_ild: the certificate covers the plain top-k only" % who)
+        if item_bias is not None:
+            raise _lib.NrmsError("%s: coarse takes no item_bias: the certificate covers the plain dot product only" % who)
+        if item_time is not None or window is not None:
+            raise _lib.NrmsError("%s: coarse takes no item_time / window: the certificate covers the whole catalogue only" % who)
+        if not isinstance(coarse, PackedCatalogue):
+            raise _lib.NrmsError("%s: coarse must be a PackedCatalogue (pack_catalogue(catalogue)), got %s" % (who, type(coarse).__name__))
+        k = int(k)
+        M = min(256, max(64, 4 * k)) if coarse_shortlist is None else int(coarse_shortlist)
+        if not 1 <= k <= M <= 256:
+            raise _lib.NrmsError("%s: with coarse, 1 <= k <= coarse_shortlist <= 256 (k=%d, coarse_shortlist=%d)" % (who, k, M))
+        return M
+
+    def _recommend_coarse(self, user, cat, exclude, k, M, packed, return_certified):
+        """The plain list through the fp16 shortlist: certified rows are top_k's bit for bit, the others are run through top_k."""
+        if packed.source != (cat.data_ptr(), tuple(cat.shape)):
+            raise _lib.NrmsError("recommend: coarse was packed from another catalogue tensor (packed %s at 0x%x, catalogue %s at 0x%x): "
+                                 "pack_catalogue again after every encode_catalogue"
+                                 % (packed.source[1], packed.source[0], tuple(cat.shape), cat.data_ptr()))
+        scores, ids, cert = self._engine.top_k_coarse(user, packed, k, M, exclude)
+        rows = (cert == 0).nonzero().view(-1)          # the one host synchronisation of the coarse path
+        if rows.numel():
+            f_scores, f_ids = self._engine.top_k(user.index_select(0, rows), packed.items, k,
+                                                 None if exclude is None else exclude.index_select(0, rows))
+            scores.index_copy_(0, rows, f_scores)
+            ids.index_copy_(0, rows, f_ids)
+        out = (torch.where(ids >= 0, ids + 1, ids), scores)
+        return out + (cert,) if return_certified else out
+
+    @torch.no_grad()
     def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
-                  item_bias=None, item_time=None, window=None):
+                  item_bias=None, item_time=None, window=None, coarse=None, coarse_shortlist=None, return_certified=False):
         """The k news ids of the whole catalogue each user of ``batch`` should see -> (news_ids [B, k] int64, scores
         [B, k] fp32), best first (score descending, then the smaller id; include/nrms_hip.h nrms_topk_dot).
 
@@ -216,7 +268,21 @@ class Model(FlatHipModel):
         int [B, 2].  Both or neither.  User b only gets news with window[b, 0] <= item_time[id] < window[b, 1] (signed int32,
         half-open; lo >= hi gives an all-padding row; a time of INT32_MAX, "not published", is never eligible;
         include/nrms_hip.h nrms_topk_dot_windowed), e.g. ``ClickFeed.news_first_seen()`` and a request time per user.  With
-        ``diversity`` the shortlist comes from the windowed top-k and the re-ranker is untouched.  None is the call as it was."""
+        ``diversity`` the shortlist comes from the windowed top-k and the re-ranker is untouched.  None is the call as it was.
+
+        coarse: pack_catalogue(catalogue), or None (the call as it was).  The same ids and score bits, always, for less than
+        the exact scan where the certificate holds: an fp16 pass picks ``coarse_shortlist`` news per user (default
+        min(256, max(64, 4 k)); k <= coarse_shortlist <= 256), the exact chain re-scores them, and a per-user certificate proves
+        that nothing outside the shortlist can reach the top k (include/nrms_hip.h nrms_topk_dot_coarse).  The rows it cannot
+        certify are gathered and run through the exact call (one ``nonzero``: the one host synchronisation, with ``coarse``
+        only).  return_certified appends the mask [B] uint8 as it stood before that fallback.  A pack made from another
+        catalogue tensor raises NrmsError.  Out of scope here: with ``diversity``, ``item_bias`` or ``item_time`` / ``window``,
+        ``coarse`` raises NrmsError."""
+        M_coarse = self._coarse_args("recommend", k, coarse, coarse_shortlist, return_certified, diversity, shortlist, return_ild,
+                                     item_bias, item_time, window)
+        if M_coarse is not None:
+            user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend")
+            return self._recommend_coarse(user, cat, exclude, int(k), M_coarse, coarse, return_certified)
         if diversity is None and shortlist is not None:
             raise _lib.NrmsError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
         if diversity is not None:

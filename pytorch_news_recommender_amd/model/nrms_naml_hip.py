@@ -135,16 +135,18 @@ class Model(nrms_hip.Model):
         return out
 
     def recommend(self, batch, k, catalogue, exclude_history=True, *, diversity=None, shortlist=None, return_ild=False,
-                  item_bias=None, item_time=None, window=None):
+                  item_bias=None, item_time=None, window=None, coarse=None, coarse_shortlist=None, return_certified=False):
         """nrms_hip.Model.recommend over encode_catalogue's feature rows: the user vector is the LayerNorm of the history's
         catalogue rows through the user encoder (_forward_dedup's path), the score a plain dot product (click_scores); with
         ``diversity`` the cosine of the re-ranking is between feature rows.  ``item_bias`` is nrms_hip.Model.recommend's
-        per-news prior, ``item_time`` / ``window`` its time window."""
+        per-news prior, ``item_time`` / ``window`` its time window, ``coarse`` / ``coarse_shortlist`` / ``return_certified`` its
+        fp16 shortlist path (pack_catalogue over the feature rows)."""
         if catalogue is None:
             raise NotImplementedError("nrms_naml: recommend needs a catalogue built with the per-news category tables: "
                                       "encode_catalogue(titles, absts, categ, subcateg)")
         return super().recommend(batch, k, catalogue, exclude_history, diversity=diversity, shortlist=shortlist,
-                                 return_ild=return_ild, item_bias=item_bias, item_time=item_time, window=window)
+                                 return_ild=return_ild, item_bias=item_bias, item_time=item_time, window=window, coarse=coarse,
+                                 coarse_shortlist=coarse_shortlist, return_certified=return_certified)
 
     def _catalogue_width(self):
         return self._dims.news_feature_size

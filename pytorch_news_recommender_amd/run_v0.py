@@ -88,6 +88,11 @@ def build_parser():
     parser.add_argument('--catalogue_window', type=int, default=None, metavar='SPAN', help='--negatives catalogue / adaptive: give the '
                         'synthetic click log ticks, and let --recommend and --retrieval_metrics see, per held-out click, only the news '
                         'first clicked in the SPAN ticks up to the moment of that click (SPAN >= 1): the news that were live then')
+    parser.add_argument('--coarse_catalogue', action='store_true', help='--recommend: serve through the fp16 shortlist with a '
+                        'certificate (model.recommend(coarse=...)): the same file, bit for bit; prints the share of users whose list the '
+                        'certificate covered (not with --diversity, --popularity_prior, --catalogue_window or --sections)')
+    parser.add_argument('--coarse_shortlist', type=int, default=None, metavar='M', help='--coarse_catalogue: the news the fp16 pass '
+                        'keeps per user (K <= M <= 256; default min(256, max(64, 4 K)))')
     parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
     parser.add_argument('--sections', type=str, default=None, choices=('category', 'subcategory'), help='--recommend: write the front '
                         'page by section instead, the top K news of every category (or sub-category) per impression, as '
@@ -109,6 +114,23 @@ def check_sections_args(args):
     module = import_module('.model.' + ALIASES.get(name, name), __package__)
     if not getattr(module.Model, 'CATALOGUE_SECTIONS', False):
         raise SystemExit('--sections: model %r cannot select per section (its catalogue score is no plain dot product)' % args.model)
+
+
+def check_coarse_args(args):
+    """--coarse_catalogue / --coarse_shortlist fail before any data is read or any step is trained: they serve the plain list of
+    --recommend only."""
+    if args.coarse_shortlist is not None and not args.coarse_catalogue:
+        raise SystemExit('--coarse_shortlist M: the shortlist length of --coarse_catalogue (give --coarse_catalogue)')
+    if not args.coarse_catalogue:
+        return
+    if args.recommend is None:
+        raise SystemExit('--coarse_catalogue: serves the list of --recommend K (give --recommend)')
+    for flag, on in (('--diversity', args.diversity is not None), ('--popularity_prior', args.popularity_prior is not None),
+                     ('--catalogue_window', args.catalogue_window is not None), ('--sections', args.sections is not None)):
+        if on:
+            raise SystemExit('--coarse_catalogue: the certificate covers the plain top-k only (drop %s)' % flag)
+    if args.coarse_shortlist is not None and not args.recommend <= args.coarse_shortlist <= 256:
+        raise SystemExit('--coarse_shortlist M: M must be in [K, 256] (got M=%d, K=%d)' % (args.coarse_shortlist, args.recommend))
 
 
 def check_recommend_args(args):
@@ -271,6 +293,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     check_recommend_args(args)
     check_sections_args(args)
+    check_coarse_args(args)
     retrieval_ks = check_retrieval_args(args)
     check_prior_args(args)
     check_window_args(args)
@@ -362,6 +385,12 @@ def main(argv=None):
                         else (info['subcateg'], config.subcategory_nums))
             return recommend_sections(config, recommender, feed, feed.titles, args.recommend, sections, out_file=args.recommend_out,
                                       **item_prior)
+        if args.coarse_catalogue:
+            out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, coarse=True,
+                            coarse_shortlist=args.coarse_shortlist)
+            st = (recommender.model if hasattr(recommender, 'model') else recommender).last_coarse_stats
+            print('coarse catalogue: certified share: {:.4f}  users: {}'.format(st['certified'], st['n_users']))
+            return out
         if args.diversity is None:
             return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
                              **item_window)

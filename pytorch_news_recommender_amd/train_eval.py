@@ -358,7 +358,8 @@ class _RequestWindows:
 
 
 def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
-              shortlist=None, item_bias=None, item_time=None, request_time=None, window_span=None):
+              shortlist=None, item_bias=None, item_time=None, request_time=None, window_span=None, coarse=False,
+              coarse_shortlist=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
@@ -378,15 +379,37 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     item_time / request_time / window_span (all three or none): a time window of the catalogue per sample.  item_time: int [N]
     by news id on the model's device (``ClickFeed.news_first_seen()``); request_time: one tick per sample of data_iter, in its
     order; sample i only gets news with request_time[i] - window_span <= item_time[id] <= request_time[i]
-    (``model.recommend(item_time=..., window=...)``).  None: the keywords are not passed at all."""
+    (``model.recommend(item_time=..., window=...)``).  None: the keywords are not passed at all.
+
+    coarse / coarse_shortlist: serve through ``model.recommend(coarse=...)``, the fp16 shortlist with a certificate: the catalogue
+    is packed once after it is encoded (``model.pack_catalogue``), the file is the same, bit for bit, and the call leaves
+    ``net.last_coarse_stats = {"certified": share of the users whose row the certificate covered, "n_users": users}`` (None
+    without ``coarse``, when the model is called exactly as before).  Not with diversity, item_bias or a time window (ValueError)."""
     net = _inner(model)
     prior = {} if item_bias is None else {"item_bias": item_bias}
     windows, done = _RequestWindows("recommend", item_time, request_time, window_span), 0
     if diversity is None and shortlist is not None:
         raise ValueError("recommend: shortlist is the candidate count of the diversity re-ranking (give diversity)")
+    if coarse_shortlist is not None and not coarse:
+        raise ValueError("recommend: coarse_shortlist is the shortlist length of the fp16 shortlist path (give coarse=True)")
+    if coarse and (diversity is not None or item_bias is not None or windows.on):
+        raise ValueError("recommend: coarse serves the plain list only (no diversity, item_bias or time window)")
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
     lines = []
-    if diversity is None:
+    net.last_coarse_stats = None
+    if coarse:
+        packed = net.pack_catalogue(catalogue)
+        net.last_recommend_stats = None
+        n_cert = torch.zeros((), dtype=torch.int64, device=catalogue.device)
+        n_users = 0
+        for datas in data_iter:
+            ids, _, cert = net.recommend(datas, k, catalogue, exclude_history=exclude_history, coarse=packed,
+                                         coarse_shortlist=coarse_shortlist, return_certified=True)
+            n_cert += cert.sum()
+            n_users += int(cert.shape[0])
+            lines.extend(ids.cpu().tolist())
+        net.last_coarse_stats = {"certified": int(n_cert.item()) / n_users if n_users else float("nan"), "n_users": n_users}
+    elif diversity is None:
         net.last_recommend_stats = None
         for datas in data_iter:
             if windows.on:
