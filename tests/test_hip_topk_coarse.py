@@ -2,7 +2,8 @@
 tests/topk_coarse_ref.py and against nrms_topk_dot itself.  Every comparison is exact unless stated.
 
 Measured on an MI355X (see DESIGN.md section 8h for the figures): the accumulation test prints its largest ratio
-|short_score - float64(u16 . n16)| / (alpha_d ||u16|| ||n16||), the Gaussian and near-tied tests their smallest / largest margin."""
+|short_score - float64(u16 . n16)| / (alpha_d ||u16|| ||n16||), the Gaussian and near-tied tests their smallest / largest margin, the
+graded, M = k and out-of-range tests their certified share, the smallest |margin - 1| and the rows that differ from nrms_topk_dot."""
 import ctypes as C
 import functools
 import os
@@ -113,6 +114,8 @@ LATTICE = [
     (33, "M-1", 8, 100, 192, 3), (70, 4100, 33, 100, 192, 64), (33, "M+1", 40, 100, 193, 3), (31, 2047, 1, 100, 193, 0),
     (70, 2049, 8, 100, 193, 65), (1, 0, 300, 256, 256, 3), (33, "M", 8, 256, 256, 0), (31, "M+1", 33, 256, 256, 64),
     (70, 4100, 40, 256, 256, 3), (33, 1, 300, 5, 16, 65),
+    # whole superblocks of 64 halves and a last block of 32 (pitch 96, 96, 160): the slice kernel's two k loops in one row
+    (33, 2049, 65, 5, 16, 65), (70, 4100, 96, 256, 256, 3), (31, "M", 150, 10, 64, 0), (1, 2047, 150, 100, 193, 64), (33, "M+1", 96, 1, 8, 3),
 ]
 
 
@@ -147,7 +150,7 @@ def _spread(rng, n, d):
     return x.astype(F)
 
 
-@pytest.mark.parametrize("d", [16, 300, 1024])
+@pytest.mark.parametrize("d", [16, 80, 300, 416, 1024])
 @pytest.mark.parametrize("kind", ["gaussian", "spread"])
 def test_fp16_mfma_accumulation_is_within_alpha(kind, d):
     rng = np.random.default_rng(d)
@@ -175,7 +178,7 @@ def test_fp16_mfma_accumulation_is_within_alpha(kind, d):
 
 # ---- 4 and 5: Gaussian and near-tied data -----------------------------------------------------------------------------------------
 SHAPES = [(33, 2500, 40, 5, 64), (33, 2500, 300, 10, 64), (70, 5000, 300, 10, 64), (33, 2500, 40, 5, 16), (33, 2500, 44, 100, 192),
-          (33, 2500, 300, 1, 8)]
+          (33, 2500, 300, 1, 8), (33, 2500, 80, 5, 64), (33, 2500, 400, 10, 64)]
 
 
 def _margins(user, items, k, M, out):
@@ -200,10 +203,7 @@ def test_gaussian_rows_are_certified_and_exact(B, N, d, k, M, seed):
 
 @functools.lru_cache(maxsize=None)
 def _near_tied(B, N, d, seed):
-    rng = np.random.default_rng(seed)
-    user = rng.standard_normal((B, d)).astype(F)
-    items = (rng.standard_normal((1, d)) + 1e-3 * rng.standard_normal((N, d))).astype(F)
-    return user, items
+    return ref.near_tied(B, N, d, seed)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -218,6 +218,72 @@ def test_near_tied_rows_are_not_certified(B, N, d, k, M, seed):
     sc, ids = _engine().top_k(tu, ti, k)
     c = out[2].bool()
     _same((out[0][c], out[1][c]), (sc[c], ids[c]), "certified => equal")
+
+
+# ---- 5b: the verdict where it depends on E_b ---------------------------------------------------------------------------------------
+def _verdicts(user, items, k, M):
+    """One call; asserts that the GPU's verdict is the restatement's for every row whose margin is not within 1e-9 of 1 (the GPU adds
+    the norms' squares in wave order, which tc_norm_up's slack of (d + 64) 2^-51 covers: E_b differs by parts in 1e-12) and that the
+    certified rows are nrms_topk_dot's.  -> (certified [B] bool, margin [B], rows that differ from nrms_topk_dot [B] bool)."""
+    tu, ti = _t(user, torch.float32), _t(items, torch.float32)
+    out = _coarse(tu, ti, k, M)
+    want_cert, margin = _margins(user, items, k, M, out)
+    cert = out[2].cpu().numpy().astype(bool)
+    band = np.abs(margin - 1) <= 1e-9
+    assert band.sum() <= len(cert) // 100, band.sum()
+    wrong = np.nonzero((cert != want_cert) & ~band)[0]
+    assert len(wrong) == 0, (wrong[:10], margin[wrong[:10]])
+    sc, ids = _engine().top_k(tu, ti, k)
+    c = out[2].bool()
+    _same((out[0][c], out[1][c]), (sc[c], ids[c]), "certified => equal")
+    return cert, margin, (out[1] != ids).any(dim=1).cpu().numpy()
+
+
+@pytest.mark.parametrize("B,N,d,k,M,eps,seed", ref.GRADED)
+def test_graded_margins_the_verdict_is_the_restatements(B, N, d, k, M, eps, seed):
+    """Margins from a third to three inside one batch.  tests/test_topk_coarse_host.py shows on the same data that leaving one term
+    of E_b out changes tens of verdicts, so a coarse_finish_kernel with a wrong E_b, a wrong slot of unorm or stats, or the wrong
+    shortlist entry fails here.  Measured on an MI355X: DESIGN.md section 8h."""
+    user, items = ref.graded(B, N, d, eps, seed)
+    cert, margin, _ = _verdicts(user, items, k, M)
+    print("graded d=%d k=%d M=%d: certified %d / %d, margin %.2f ... %.2f, min |margin - 1| %.1e"
+          % (d, k, M, cert.sum(), B, margin.min(), margin.max(), np.abs(margin - 1).min()))
+    assert np.isfinite(margin).all() and 0.2 * B <= cert.sum() <= 0.8 * B
+
+
+@pytest.mark.parametrize("B,N,d,k", ref.TIGHT)
+def test_a_shortlist_of_k_on_inexact_data(B, N, d, k):
+    """M = k, where the shortlist does lose true top-k items.  A full shortlist of k is never certified (the entry with the smallest
+    coarse score has c_j = c_M and s_k <= s_j <= c_j + E_b), so what keeps the served answer right here is that verdict: near-tied
+    rows differ from nrms_topk_dot and none of them is certified.  Dominant items: the k far ahead of the rest are the shortlist, the
+    rows equal nrms_topk_dot's uncertified, and one more slot certifies every one of them."""
+    user, items = _near_tied(B, N, d, 1)
+    cert, margin, differ = _verdicts(user, items, k, k)
+    print("near-tied d=%d M=k=%d: %d / %d rows differ from nrms_topk_dot, %d certified" % (d, k, differ.sum(), B, cert.sum()))
+    assert differ.sum() >= 1 and not cert.any() and not (differ & cert).any()
+    user, items = ref.dominant(B, N, d, k, 3)
+    cert, margin, differ = _verdicts(user, items, k, k)
+    assert not differ.any() and not cert.any()
+    cert, margin, differ = _verdicts(user, items, k, k + 1)
+    print("dominant d=%d k=%d M=k+1: %d / %d certified, margin %.1f ... %.1f" % (d, k, cert.sum(), B, margin.min(), margin.max()))
+    assert cert.all() and not differ.any()
+
+
+@pytest.mark.parametrize("d", [80, 300])
+def test_out_of_range_values_end_to_end(d):
+    """Clamped (|x| > 65504) and flushed (|x| < 2^-14) entries in the catalogue and in the users, through the pack, the slice kernel
+    and the certificate.  Users scaled by 2^-16 have h(u) = 0: every coarse score is 0, the shortlist is the first M ids, and
+    Cauchy-Schwarz itself forbids the certificate."""
+    B, N, k, M = 99, 2500, 1, 8
+    user, items, kind = ref.out_of_range(B, N, d, 1)
+    zero = torch.as_tensor(kind == 0, device=DEV)
+    _, _, _, ssc, sid, _ = _coarse(_t(user, torch.float32), _t(items, torch.float32), k, M)
+    assert (ssc[zero] == 0).all() and sid[zero].tolist() == [list(range(M))] * 33
+    cert, margin, differ = _verdicts(user, items, k, M)
+    n_cert = [int(cert[kind == i].sum()) for i in range(3)]
+    print("out of range d=%d: certified of 33 each: scaled by 2^-16 %d, an entry of 1e6 %d, untouched %d; min |margin - 1| %.1e; "
+          "%d uncertified rows differ" % (d, n_cert[0], n_cert[1], n_cert[2], np.nanmin(np.abs(margin - 1)), differ.sum()))
+    assert n_cert[0] == 0 and 2 <= n_cert[1] <= 31 and 2 <= n_cert[2] <= 31          # both verdicts among the other two kinds
 
 
 def _as_catalogue(items):
@@ -281,8 +347,13 @@ def _raw_coarse(user, items, packed, k, M, ex, poison):
 
 
 def test_invariance_and_determinism():
+    for d in (300, 80):                                               # pitch 320: superblocks only; pitch 96: a superblock and the tail
+        _invariance_and_determinism(d)
+
+
+def _invariance_and_determinism(d):
     rng = np.random.default_rng(11)
-    B, N, d, k, M = 70, 5000, 300, 10, 64
+    B, N, k, M = 70, 5000, 10, 64
     user = rng.standard_normal((B, d)).astype(F)
     user[1::2] = _near_tied(B, N, d, 1)[0][1::2]
     items = np.concatenate([rng.standard_normal((N // 2, d)), _near_tied(B, N - N // 2, d, 1)[1]]).astype(F)

@@ -113,6 +113,100 @@ def test_certificate_refuses_what_it_cannot_bound():
     assert ref.topk_coarse(u, n[:3], 2, 4)["certified"].all()                                  # L < M: everything is in the shortlist
 
 
+# ---- 1b: the data the GPU tests pin the certificate with ------------------------------------------------------------------------
+def test_e_bound_is_the_rounded_up_sum_of_its_terms():
+    rng = np.random.default_rng(4)
+    up = ref.up
+    for _ in range(200):
+        d = int(rng.integers(1, 2000))
+        un, un16, ue, NRM, ERR = (float(v) for v in np.abs(rng.normal(size=5)) * 10.0 ** rng.integers(-6, 7, size=5))
+        t = ref.e_terms(d, un, un16, ue, NRM, ERR)
+        assert len(t) == len(ref.E_TERMS) == 5
+        gamma = up(up(d * 2.0 ** -24) / (1.0 - d * 2.0 ** -24))
+        want = [up(ue * NRM), up(un16 * ERR), up(gamma * up(un * NRM)), up(d * 2.0 ** -21 * up(un16 * up(NRM + ERR))), up(d * 2.0 ** -140)]
+        assert [float(v) for v in t] == [float(v) for v in want]
+        E = want[0]
+        for v in want[1:]:
+            E = up(E + v)
+        assert float(ref.e_bound(d, un, un16, ue, NRM, ERR)) == float(E) > sum(float(v) for v in want[:4]) * (1 - 1e-15)
+        for i, name in enumerate(ref.E_TERMS):
+            rest = [v for j, v in enumerate(want) if j != i]
+            E = rest[0]
+            for v in rest[1:]:
+                E = up(E + v)
+            assert float(ref.e_bound(d, un, un16, ue, NRM, ERR, drop=name)) == float(E)
+
+
+def _certified_rows_are_exact(got, user, items, k):
+    """-> the number of rows whose ids differ from the exact order's, after asserting that no certified row is among them."""
+    want_ids, want_sc = ref.ordered(ref.exact_scores64(user, items), None, k)
+    differ = (got["ids"] != want_ids).any(axis=1)
+    assert not (differ & got["certified"]).any()
+    c = got["certified"]
+    assert got["scores"][c].tobytes() == want_sc[c].tobytes()
+    return int(differ.sum())
+
+
+@pytest.mark.parametrize("B,N,d,k,M,eps,seed", ref.GRADED)
+def test_graded_margins_straddle_one_and_tell_the_terms_apart(B, N, d, k, M, eps, seed):
+    """What makes test_hip_topk_coarse.py::test_graded_margins_the_verdict_is_the_restatements a test of E_b: on this data the
+    verdict of a tenth of the batch or more changes when one of the three large terms is left out, and of some rows with gamma_d's."""
+    user, items = ref.graded(B, N, d, eps, seed)
+    got = ref.topk_coarse(user, items, k, M)
+    margin, cert = got["margin"], got["certified"]
+    assert np.isfinite(margin).all()
+    band = np.abs(margin - 1) <= 1e-9
+    print("graded d=%d k=%d M=%d: certified %d / %d, margin %.2f ... %.2f, min |margin - 1| %.1e"
+          % (d, k, M, cert.sum(), B, margin.min(), margin.max(), np.abs(margin - 1).min()))
+    assert band.sum() <= B // 100 and 0.2 * B <= cert.sum() <= 0.8 * B
+    assert (cert == (margin > 1))[~band].all()
+    _certified_rows_are_exact(got, user, items, k)
+    flips = {}
+    for name in ref.E_TERMS[:4]:                                     # (d 2^-140 decides nothing at these magnitudes)
+        wrong, _ = ref.certificate(d, k, M, got["unorm"], got["stats"], got["short_ids"], got["short_scores"], got["scores"], drop=name)
+        flips[name] = int((wrong != cert).sum())
+        assert not (cert & ~wrong).any()                             # a smaller bound only certifies more
+    print("  rows whose verdict changes without", flips)
+    assert min(flips["ue*NRM"], flips["un16*ERR"], flips["alpha"]) >= 10 and flips["gamma"] >= 2, flips
+
+
+@pytest.mark.parametrize("B,N,d,k", ref.TIGHT)
+def test_a_shortlist_of_k_loses_items_and_is_never_certified(B, N, d, k):
+    """M = k.  A full shortlist of k cannot be certified: the entry with the smallest coarse score has c_j = c_M and s_j >= s_k, and
+    s_j <= c_j + E_b is what E_b bounds, so s_k > c_M + E_b is false.  On near-tied items the shortlist does lose true top-k items;
+    on dominant items it does not, and one more slot (M = k + 1) certifies every row."""
+    user, items = ref.near_tied(B, N, d, 1)
+    got = ref.topk_coarse(user, items, k, k)
+    lost = _certified_rows_are_exact(got, user, items, k)
+    print("near-tied d=%d M=k=%d: %d / %d rows differ from the exact order" % (d, k, lost, B))
+    assert lost >= 1 and not got["certified"].any()
+    user, items = ref.dominant(B, N, d, k, 3)
+    got = ref.topk_coarse(user, items, k, k)
+    assert _certified_rows_are_exact(got, user, items, k) == 0 and not got["certified"].any()
+    got = ref.topk_coarse(user, items, k, k + 1)
+    assert _certified_rows_are_exact(got, user, items, k) == 0 and got["certified"].all()
+    print("dominant d=%d k=%d M=k+1: margin %.1f ... %.1f" % (d, k, got["margin"].min(), got["margin"].max()))
+
+
+@pytest.mark.parametrize("d", [80, 300])
+def test_out_of_range_values_through_the_certificate(d):
+    B, N, k, M = 99, 2500, 1, 8
+    user, items, kind = ref.out_of_range(B, N, d, 1)
+    bits, stats = ref.pack(items)
+    v16 = ref.halves(bits, d)
+    assert (np.abs(v16) == 65504).sum() == 6 and (np.abs(items) > 65504).sum() == 6
+    assert ((v16 == 0) & (items != 0)).sum() >= 300 and 69000 < stats[0] < 71000 and 3000 < stats[1] < 5000
+    u16 = ref.halves(ref.pack_rows(user)[0], d)
+    assert not u16[kind == 0].any() and (np.abs(u16[kind == 1]) == 65504).sum() == 33
+    got = ref.topk_coarse(user, items, k, M)
+    _certified_rows_are_exact(got, user, items, k)
+    n_cert = [int(got["certified"][kind == i].sum()) for i in range(3)]
+    print("out of range d=%d: certified of 33 each: scaled by 2^-16 %d, an entry of 1e6 %d, untouched %d; min |margin - 1| %.1e"
+          % (d, n_cert[0], n_cert[1], n_cert[2], np.nanmin(np.abs(got["margin"] - 1))))
+    assert (got["short_scores"][kind == 0] == 0).all() and n_cert[0] == 0
+    assert 5 <= n_cert[1] <= 28 and 5 <= n_cert[2] <= 31 and not (np.abs(got["margin"] - 1) <= 1e-9).any()
+
+
 # ---- 2: the symbols ----------------------------------------------------------------------------------------------------------
 def test_new_symbols_in_header_signatures_and_library():
     text = open(os.path.join(ROOT, "include", "nrms_hip.h")).read()
