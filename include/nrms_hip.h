@@ -547,6 +547,67 @@ int nrms_rank_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t T, const flo
                            int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- Paging through the exact ranking: a cursor on the top-k, and lists up to 4096 (candidate generation for a re-ranker, a feed
+ * that scrolls: "the next 20 after what I showed"; PARITY UNPINNED, the reference has no catalogue retrieval) ----
+ * The order of nrms_topk_dot[_biased|_windowed] is total (s' descending, then the SMALLER n, -0.0 equal to +0.0) and a score's bits
+ * do not depend on B, N, k, the row's position or the run, so "everything after (s, n) in user b's ranking" is well defined and a
+ * page needs no state but the last (score, id) its reader saw.
+ *
+ * nrms_topk_dot_after: one page.  after_scores [B] fp32 and after_ids [B] int64, both REQUIRED, 4- / 8-byte aligned: user b's
+ * cursor.  bias [N] fp32, NULLABLE, as nrms_topk_dot_biased's; item_time [N] int32 and window [B, 2] int32, NULLABLE, given both or
+ * neither, as nrms_topk_dot_windowed's (NULL: no window).  Every other argument is nrms_topk_dot's; 1 <= k <= 256.
+ * Eligible, score, order, padding: the uncursored call's (with the prior s' = s + bias[n], with the window its eligibility).
+ * Cursor.  Row b holds, in order, the first k eligible items n with (s'(b, n), n) strictly AFTER (after_scores[b], after_ids[b])
+ *   in that order: s' < after_scores[b], or s' equal to it and n > after_ids[b]; then -1 / -inf.
+ *   after_ids[b] == -2 (NRMS_CURSOR_BEGIN): no cursor; after_scores[b] is not inspected, row b is the uncursored call's row, bit
+ *     for bit.  Users on different pages, first pages included, can share one call.
+ *   after_ids[b] == -1, any other negative id, or a NaN after_scores[b]: END, row b is all padding.  -1 / -inf is what a page
+ *     leaves in the columns a list did not reach, so feeding the last column of a finished page back in yields padding again.
+ *   after_ids[b] >= 0: a position in the order, not an item: the id need not be eligible, un-excluded, inside the window or below
+ *     N.  Ids above 0x7FFF0000 are read as 0x7FFF0000, which follows every item at the same score.  -0.0 is +0.0; +inf and -inf
+ *     are ordinary scores.
+ *
+ * nrms_topk_dot_deep: 1 <= K <= 4096; top_scores [B, K] fp32 and top_ids [B, K] int64, both REQUIRED, 4- / 8-byte aligned.  Row
+ * b holds the first min(K, #eligible) items of user b's ranking in order, then -1 / -inf; every element is written.  It runs
+ * ceil(K / 256) pages: the first is min(256, K) columns with no cursor, each later one min(256, rest) columns whose cursor is the
+ * last column of the page before, read on the device.  Arguments as nrms_topk_dot_after's without the cursor.
+ *
+ * Consequences.
+ *   (a) With every after_ids[b] == -2, nrms_topk_dot_after equals nrms_topk_dot / _biased / _windowed with the same arguments, bit
+ *       for bit, ids and scores.
+ *   (b) Chaining pages of any lengths, each from the last column of the page before, reproduces the uncursored list: no item is
+ *       repeated or skipped, across runs of equal scores included, and a finished list returns padding from then on.
+ *   (c) nrms_topk_dot_deep at K <= 256 equals nrms_topk_dot / _biased / _windowed at k = K, bit for bit (the same kernels).
+ *   (d) The first K' columns of nrms_topk_dot_deep(K) are nrms_topk_dot_deep(K').
+ *   (e) The ids of row b of nrms_topk_dot_deep get ranks 1, 2, ... from nrms_rank_dot / _biased / _windowed with the same
+ *       arguments, and the same score bits.
+ *   (f) The result does not depend on B, the row's position in the batch, the page lengths, the other rows' cursors, the launch
+ *       geometry, what the workspace held or the run.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_after: ...", "topk_dot_deep: ..."); a NULL
+ *   or misaligned after_scores / after_ids, and an item_time (N > 0) without a window or a window without an item_time, are among
+ *   them.  An undersized workspace returns NRMS_EWORKSPACE.  Nothing is launched after an error.  B = 0 is a no-op, N = 0 writes
+ *   padding.
+ * Workspace: nrms_topk_dot_after_workspace_bytes returns exactly nrms_topk_dot_workspace_bytes(B, N, d, k), and
+ *   nrms_topk_dot_deep_workspace_bytes that of its longest page, nrms_topk_dot_workspace_bytes(B, N, d, min(K, 256)) (0 =
+ *   arguments rejected); 8-byte aligned.
+ * nrms_topk_dot_after launches the same kernel counts as the uncursored call, nrms_topk_dot_deep those of its pages one after the
+ *   other; all on `stream`, no host synchronisation, no allocation; plain vector loads and stores, no atomics beyond the integer
+ *   LDS counters of nrms_topk_dot's slice kernel.  A block of 32 users who are all at END loads no item row.  The results are the
+ *   same with that exit compiled out (csrc/topk_entry.h TK_CURSOR_EXIT). */
+#define NRMS_CURSOR_BEGIN (-2)
+size_t nrms_topk_dot_after_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_after(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                        const float* bias /* [N], nullable */, const int32_t* item_time /* [N], nullable */,
+                        const int32_t* window /* [B, 2], nullable */, const float* after_scores /* [B] */,
+                        const int64_t* after_ids /* [B] */, const int64_t* exclude, int32_t n_exclude, float* top_scores,
+                        int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+size_t nrms_topk_dot_deep_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t K);
+int nrms_topk_dot_deep(int32_t B, int64_t N, int32_t d, int32_t K, const float* user, const float* items,
+                       const float* bias /* [N], nullable */, const int32_t* item_time /* [N], nullable */,
+                       const int32_t* window /* [B, 2], nullable */, const int64_t* exclude, int32_t n_exclude,
+                       float* top_scores /* [B, K] */, int64_t* top_ids /* [B, K] */, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- The exact top-k through an fp16 shortlist with a certificate (csrc/topkcoarse.hip; serving: nrms_topk_dot's rows for less
  * than nrms_topk_dot's scan; PARITY UNPINNED, the reference has no catalogue retrieval) ----
  * A coarse pass over an fp16 copy of the catalogue on v_mfma_f32_32x32x16_f16 picks a shortlist of M items per user, the shortlist

@@ -177,6 +177,12 @@ SIGNATURES = {
     "nrms_topk_dot_windowed_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "nrms_topk_dot_windowed": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]
                                + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "nrms_topk_dot_after_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "nrms_topk_dot_after": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32]
+                            + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "nrms_topk_dot_deep_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "nrms_topk_dot_deep": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]
+                           + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "nrms_rank_dot_windowed_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "nrms_rank_dot_windowed": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32]
                                + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),

@@ -26,6 +26,11 @@
 // nrms_topk_dot_windowed adds a per-user eligibility interval on a per-item timestamp (the WINDOW instantiations, with or
 // without BIAS): two integer compares in the filter, and a wave whose 64 items are closed to all 32 users of its block skips
 // its loads and its MFMA chain (topk_kernels.h describes the skip and why no block barrier can notice it).
+//
+// nrms_topk_dot_after is a page of that ranking: a per-user cursor, the last (score, id) the caller saw, as one 64-bit key, and
+// one more integer compare in the filter (the CURSOR instantiations, with or without BIAS and WINDOW): only entries strictly
+// below the key are offered.  nrms_topk_dot_deep chains such pages on the stream, each reading its cursor from the last column the
+// page before wrote and merging into its own columns of the [B, K] result (the merge kernel's output row stride).
 #include "topk_kernels.h"    // the kernels and their launcher, shared with softmaxsample.hip
 
 namespace nrms {
@@ -81,16 +86,19 @@ extern "C" size_t nrms_topk_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
     return 256 + (size_t)B * (size_t)g.S * (size_t)k * sizeof(uint64_t);     // never 0 for accepted arguments
 }
 
-// nrms_topk_dot (bias null, who "topk_dot"), nrms_topk_dot_biased and nrms_topk_dot_windowed (windowed: item_time and window
-// are required): one body, so the checks and the launch cannot drift apart.
+// nrms_topk_dot (bias null, who "topk_dot"), nrms_topk_dot_biased, nrms_topk_dot_windowed (windowed: item_time and window are
+// required) and nrms_topk_dot_after (cursored: after_scores and after_ids are required): one body, so the checks and the launch
+// cannot drift apart.
 static int topk_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
                          const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* exclude,
                          int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes,
-                         void* stream) {
+                         void* stream, bool cursored = false, const float* after_scores = nullptr,
+                         const int64_t* after_ids = nullptr) {
     int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "k", k, TK_MAX_K, n_exclude);
     if (rc != NRMS_OK || B == 0) return rc;
     rc = tk_check_ptrs(who, {{"user", user, true, 1}, {"items", items, N != 0, 1}, {"bias", bias, false, 4},
                              {"item_time", item_time, windowed && N != 0, 4}, {"window", window, windowed, 4},
+                             {"after_scores", after_scores, cursored, 4}, {"after_ids", after_ids, cursored, 8},
                              {"top_scores", top_scores, true, 1}, {"top_ids", top_ids, true, 1}},
                        workspace, workspace_bytes, nrms_topk_dot_workspace_bytes(B, N, d, k), 8);
     if (rc != NRMS_OK) return rc;
@@ -99,7 +107,8 @@ static int topk_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     TimingScope ts(who, s);
     return topk_launch<false, false>(B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids,
                                      (uint64_t*)workspace, s, who, TkNoise{nullptr, 0.0f, 0}, bias,
-                                     windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr});
+                                     windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr},
+                                     cursored ? TkCursor{after_scores, after_ids, 1} : TkCursor{nullptr, nullptr, 0});
 }
 
 extern "C" int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
@@ -107,6 +116,57 @@ extern "C" int nrms_topk_dot(int32_t B, int64_t N, int32_t d, int32_t k, const f
                              size_t workspace_bytes, void* stream) {
     return topk_dot_call("topk_dot", B, N, d, k, user, items, nullptr, false, nullptr, nullptr, exclude, n_exclude, top_scores, top_ids, workspace,
                          workspace_bytes, stream);
+}
+
+// One page after a cursor.  The workspace is the uncursored call's: the same slice lists, of the entries below the cursor only.
+extern "C" size_t nrms_topk_dot_after_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k) {
+    return nrms_topk_dot_workspace_bytes(B, N, d, k);
+}
+
+extern "C" int nrms_topk_dot_after(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                                   const float* bias, const int32_t* item_time, const int32_t* window, const float* after_scores,
+                                   const int64_t* after_ids, const int64_t* exclude, int32_t n_exclude, float* top_scores,
+                                   int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    // item_time and window go together: either one makes both required (item_time only where there is an item to read it for)
+    return topk_dot_call("topk_dot_after", B, N, d, k, user, items, bias, item_time != nullptr || window != nullptr, item_time,
+                         window, exclude, n_exclude, top_scores, top_ids, workspace, workspace_bytes, stream, true, after_scores,
+                         after_ids);
+}
+
+// The deep list: pages of at most TK_MAX_K columns, one after the other in the one workspace of the longest page.
+constexpr int TK_DEEP_MAX_K = 4096;
+
+extern "C" size_t nrms_topk_dot_deep_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t K) {
+    if (K < 1 || K > TK_DEEP_MAX_K) return 0;
+    return nrms_topk_dot_workspace_bytes(B, N, d, std::min(K, TK_MAX_K));
+}
+
+extern "C" int nrms_topk_dot_deep(int32_t B, int64_t N, int32_t d, int32_t K, const float* user, const float* items,
+                                  const float* bias, const int32_t* item_time, const int32_t* window, const int64_t* exclude,
+                                  int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    const char* who = "topk_dot_deep";
+    const bool windowed = item_time != nullptr || window != nullptr;
+    int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "K", K, TK_DEEP_MAX_K, n_exclude);
+    if (rc != NRMS_OK || B == 0) return rc;
+    rc = tk_check_ptrs(who, {{"user", user, true, 1}, {"items", items, N != 0, 1}, {"bias", bias, false, 4},
+                             {"item_time", item_time, windowed && N != 0, 4}, {"window", window, windowed, 4},
+                             {"top_scores", top_scores, true, 4}, {"top_ids", top_ids, true, 8}},
+                       workspace, workspace_bytes, nrms_topk_dot_deep_workspace_bytes(B, N, d, K), 8);
+    if (rc != NRMS_OK) return rc;
+    if (!exclude) n_exclude = 0;
+    hipStream_t s = (hipStream_t)stream;
+    TimingScope ts(who, s);
+    const TkWindow win = windowed ? TkWindow{item_time, window} : TkWindow{nullptr, nullptr};
+    for (int32_t c0 = 0; c0 < K; c0 += TK_MAX_K) {
+        // page c0 / 256 fills columns [c0, c0 + k); its cursor is column c0 - 1, which the page before wrote on this stream
+        const int32_t k = std::min(TK_MAX_K, K - c0);
+        const TkCursor cur = c0 ? TkCursor{top_scores + c0 - 1, top_ids + c0 - 1, K} : TkCursor{nullptr, nullptr, 0};
+        rc = topk_launch<false, false>(B, N, d, k, 1, 0, user, items, nullptr, nullptr, exclude, n_exclude, top_scores + c0,
+                                       top_ids + c0, (uint64_t*)workspace, s, who, TkNoise{nullptr, 0.0f, 0}, bias, win, cur, K);
+        if (rc != NRMS_OK) return rc;
+    }
+    return NRMS_OK;
 }
 
 // The biased call's workspace is the unbiased call's: entries carry s' in the same slice lists.

@@ -52,11 +52,26 @@ struct TkWindow {
     const int32_t* window;       // [B, 2]
 };
 
-// The TkWindow of a kernel whose trailing argument pack holds one, the null window of a kernel whose pack is empty.
+// The cursor of nrms_topk_dot_after / nrms_topk_dot_deep (include/nrms_hip.h states it): user b is offered only what comes
+// strictly after the position (after_scores[b * stride], after_ids[b * stride]) of the order.  stride 1: the caller's [B] arrays;
+// stride K: a column of a [B, K] result (the deep call's pages read the page before).  Null after_ids = none.
+struct TkCursor {
+    const float* after_scores;
+    const int64_t* after_ids;
+    long stride;
+};
+constexpr int64_t TK_CURSOR_BEGIN = -2;        // after_ids value: no cursor, the row of the uncursored call (NRMS_CURSOR_BEGIN)
+
+// The T of a kernel whose trailing argument pack holds one (TkWindow, TkCursor), the null T of a kernel whose pack has none.
+template <class T, class... EXT>
+__device__ __forceinline__ T tk_pack_arg(EXT... e) {
+    T out{};
+    ([&] { if constexpr (std::is_same<EXT, T>::value) out = e; }(), ...);
+    return out;
+}
 template <class... WIN>
 __device__ __forceinline__ TkWindow tk_window_arg(WIN... w) {
-    if constexpr (sizeof...(WIN) == 1) return (w, ...);
-    else return TkWindow{nullptr, nullptr};
+    return tk_pack_arg<TkWindow>(w...);
 }
 
 // The dead-tile skip of the WINDOW kernels: a wave none of whose 64 item times lies in its block's [blo, bhi) runs no chain
@@ -88,6 +103,40 @@ __device__ __forceinline__ void tk_window_hull(const int2* win, int& blo, int& b
             bhi = max(bhi, w.y);
         }
     }
+}
+
+// The all-END exit of the CURSOR kernels: a block whose 32 users have all reached the end of their lists writes its empty slice
+// lists and returns before its first item row.  false compiles the exit out (the block scans its slice, the filter refuses every
+// score): same results, bit for bit (a diagnostic build with -DNRMS_TK_CURSOR_EXIT=0, e.g. through NRMS_HIPCC_EXTRA, passes
+// tests/test_hip_topk_after.py unchanged).
+#ifndef NRMS_TK_CURSOR_EXIT
+#define NRMS_TK_CURSOR_EXIT 1
+#endif
+constexpr bool TK_CURSOR_EXIT = NRMS_TK_CURSOR_EXIT != 0;
+
+// A cursor as a key in the entries' order: user b is offered the entries strictly below it.  BEGIN (id -2) is the largest key,
+// which only a NaN score's entry could reach, and NaN scores are never offered; END (any other negative id, a NaN score) is 0,
+// below which nothing lies.  An id above TK_MAX_N is read as TK_MAX_N, which follows every item of the same score.
+__device__ __forceinline__ uint64_t tk_cursor_key(float s, int64_t id) {
+    if (id == TK_CURSOR_BEGIN) return ~0ull;
+    if (id < 0 || s != s) return 0;
+    return tk_entry(s, (uint32_t)(id > TK_MAX_N ? (int64_t)TK_MAX_N : id));
+}
+
+// One block's cursor keys (CURSOR kernels).  Threads [0, 32) write user u0 + threadIdx.x's key to cur[threadIdx.x]; rows at or
+// past B are at END.  Call before the block's first barrier.
+__device__ __forceinline__ void tk_cursor_stage(uint64_t* cur, TkCursor c, int u0, int B) {
+    if (threadIdx.x < TK_UT) {
+        const int b = u0 + (int)threadIdx.x;
+        cur[threadIdx.x] = b < B ? tk_cursor_key(c.after_scores[b * c.stride], c.after_ids[b * c.stride]) : 0;
+    }
+}
+
+// After that barrier, every thread: has every user of the block reached the end of its list?  Block-uniform.
+__device__ __forceinline__ bool tk_cursor_all_end(const uint64_t* cur) {
+    uint64_t any = 0;
+    for (int u = 0; u < TK_UT; ++u) any |= cur[u];
+    return any == 0;
 }
 
 __device__ __forceinline__ float tk_ld(const float* p, int kk, int d) { return kk < d ? p[kk] : 0.0f; }

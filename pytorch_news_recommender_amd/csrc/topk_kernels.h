@@ -247,6 +247,22 @@ struct TkFilter {
         return pend;
     }
 
+    // CURSOR kernels: of the pending scores, those whose entry lies strictly below their user's cursor key (cur: the block's 32
+    // keys, tk_cursor_stage): one 64-bit compare per pending score, on the entry the offer forms from the same score and id.
+    template <class IdOf>
+    __device__ __forceinline__ uint32_t after(const tk_f32x16 (&acc)[TK_TN], uint32_t pend, const uint64_t* cur, IdOf id_of) const {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const uint64_t key = cur[(q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)];          // read ahead of the tests, not inside them
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) {
+                const uint32_t bit = 1u << (16 * c + q);
+                if ((pend & bit) && !(tk_entry(acc[c][q], id_of(c)) < key)) pend &= ~bit;
+            }
+        }
+        return pend;
+    }
+
     // Offers the pending scores of a step; id_of(c): the id of this lane's item in column tile c.  This holds block barriers:
     // EVERY wave of the block calls it on EVERY step, with pend == 0 when it has nothing to offer (a wave past the slice's
     // end, a WINDOW wave that skipped its chain), so that all waves meet the same barriers the same number of times.
@@ -326,8 +342,15 @@ struct TkFilter {
 // skipped region holds the chain alone, which touches only the wave's private stage[wave] and wave-level syncs: every wave
 // still meets every block barrier, the same number of times.
 //
-// The window's two pointers are a kernel argument of the WINDOW instantiations alone (WIN is TkWindow there and empty
-// elsewhere), so every other instantiation keeps its signature and kernarg layout.
+// CURSOR (nrms_topk_dot_after, the later pages of nrms_topk_dot_deep; with or without BIAS and WINDOW): the block stages its 32
+// users' cursors once, as 64-bit keys in LDS (tk_cursor_stage), and a pending score is offered only if its entry, formed from s'
+// where there is a prior, lies strictly below its user's key (TkFilter::after).  Everything else is the uncursored kernel's.
+// All-END exit: a block whose 32 keys are all 0 writes its empty slice lists and returns before its first item row; the test
+// reads LDS after a barrier, so it is block-uniform and no wave is left waiting at a later barrier.
+//
+// The window's two pointers are a kernel argument of the WINDOW instantiations alone, and the cursor's of the CURSOR
+// instantiations alone (WIN holds a TkWindow, a TkCursor, both in that order, or nothing; CURSOR is read off the pack), so every
+// other instantiation keeps its name, its signature and its kernarg layout.
 template <int P, int W, bool VEC, bool GROUPED, bool NOISE, bool BIAS, bool WINDOW, class... WIN>
 __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d, int k, int slice_len, int S,
                                                             const float* __restrict__ user, const float* __restrict__ items,
@@ -336,11 +359,14 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                                                             const TkTile* __restrict__ tiles,
                                                             const int32_t* __restrict__ item_ids, TkNoise noise,
                                                             const float* __restrict__ bias, WIN... win_arg) {
-    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0), "WINDOW kernels take one TkWindow, the others none");
+    constexpr bool CURSOR = (std::is_same<WIN, TkCursor>::value || ...);
+    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0),
+                  "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, the others neither");
     const TkWindow win = tk_window_arg(win_arg...);
     static_assert(!(NOISE && GROUPED), "the perturbation is keyed by the item's row");
     static_assert(!(WINDOW && (GROUPED || NOISE)), "the window is for the plain and the biased top-k only");
     static_assert(!(BIAS && (GROUPED || NOISE)), "the prior is for the plain top-k only");
+    static_assert(!(CURSOR && (GROUPED || NOISE)), "the cursor is for the plain, the biased and the windowed top-k only");
     TK_FILTER_LDS(lds, P);
     __shared__ uint64_t rseed[NOISE ? TK_UT : 1];
     __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
@@ -358,6 +384,12 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         wwin = wwin_lds;
         tk_window_stage(wwin, win.window, u0, B);
     }
+    uint64_t* cur = nullptr;       // CURSOR: the block's 32 cursor keys
+    if constexpr (CURSOR) {
+        __shared__ uint64_t cur_lds[TK_UT];
+        cur = cur_lds;
+        tk_cursor_stage(cur, tk_pack_arg<TkCursor>(win_arg...), u0, B);
+    }
     if constexpr (NOISE) {
         if (threadIdx.x < TK_UT) rseed[threadIdx.x] = tk_noise_row_seed(noise.seed, (uint64_t)noise.row_key[min(u0 + (int)threadIdx.x, B - 1)]);
     }
@@ -366,6 +398,12 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     __syncthreads();
     int blo = 0, bhi = 0;
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
+    if constexpr (CURSOR) {
+        if (TK_CURSOR_EXIT && tk_cursor_all_end(cur)) {
+            flt.write(ws, S, slice);
+            return;
+        }
+    }
 
     const int r = lane & 31, h = lane >> 5;
     constexpr int NA = GROUPED ? TK_TN : 1;           // A operands per k-block: one per column tile when grouped
@@ -439,6 +477,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         uint32_t pend;
         if constexpr (WINDOW) pend = flt.pending(acc, live, TkOpenWindow{wwin, tv});
         else pend = flt.pending(acc, live, TkOpenAll{});
+        if constexpr (CURSOR) pend = flt.after(acc, pend, cur, [&](int c) { return id[c]; });
         // unconditional: the offer holds the block's barriers, and a wave with pend == 0 has to meet them too
         flt.offer(acc, pend, [&](int c) { return id[c]; });
     }
@@ -474,13 +513,16 @@ __device__ __forceinline__ void tk_merge(uint64_t* buf, const uint64_t* __restri
     }
 }
 
-// One wave per user: the best k of the user's S slice lists.  top_scores may be null.
+// One wave per user: the best k of the user's S slice lists, written to row b of outputs whose rows are out_stride >= k elements
+// apart (k: a [B, k] result; K: columns [c0, c0 + k) of a [B, K] one, the pointers already at column c0).  top_scores may be null.
 template <int P>
 __global__ __launch_bounds__(64) void topk_merge_kernel(int B, int k, int S, const uint64_t* __restrict__ ws,
-                                                        float* __restrict__ top_scores, int64_t* __restrict__ top_ids) {
+                                                        float* __restrict__ top_scores, int64_t* __restrict__ top_ids,
+                                                        int out_stride) {
     __shared__ uint64_t buf[P];
     const long b = blockIdx.x;
-    tk_merge<P>(buf, ws + b * S * k, (long)S * k, k, threadIdx.x, top_scores ? top_scores + b * k : nullptr, top_ids + b * k);
+    tk_merge<P>(buf, ws + b * S * k, (long)S * k, k, threadIdx.x, top_scores ? top_scores + b * out_stride : nullptr,
+                top_ids + b * out_stride);
 }
 
 static TkGeom topk_geom(int32_t B, int64_t N) { return tk_geom(B, N, true); }
@@ -491,13 +533,15 @@ static bool topk_args_ok(int32_t B, int64_t N, int32_t d, int32_t k) {
 
 // Both kernels of one call.  GROUPED: `user` is the query [B, G, d], the slices run over the tile rows of `tiles`.  NOISE: the
 // perturbation of nrms_softmax_sample_dot.  Neither (the plain top-k): a non-null bias ([N] fp32) selects the BIAS
-// instantiations, a non-null window the WINDOW ones.
+// instantiations, a non-null window the WINDOW ones, a cursor with non-null after_ids the CURSOR ones.  out_stride: the row
+// pitch of top_scores / top_ids in elements (0: k).
 template <bool GROUPED, bool NOISE>
 static int topk_launch(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, int64_t n_tiles, const float* user,
                        const float* items, const int32_t* item_ids, const TkTile* tiles, const int64_t* exclude, int32_t n_exclude,
                        float* top_scores, int64_t* top_ids, uint64_t* ws, hipStream_t s, const char* who,
                        TkNoise noise = TkNoise{nullptr, 0.0f, 0}, const float* bias = nullptr,
-                       TkWindow win = TkWindow{nullptr, nullptr}) {
+                       TkWindow win = TkWindow{nullptr, nullptr}, TkCursor cur = TkCursor{nullptr, nullptr, 0},
+                       int32_t out_stride = 0) {
     const TkGeom g = topk_geom(B, GROUPED ? 32 * n_tiles : N);
     int rc = NRMS_OK;
     char what[64];
@@ -506,20 +550,29 @@ static int topk_launch(int32_t B, int64_t N, int32_t d, int32_t k, int32_t G, in
         if (g.S > 0) {
             const dim3 grid(g.tiles, g.S), block(64 * w);
             const int n = (int)N, nt = (int)n_tiles;
-            tk_with_flags([&](auto V, auto BI, auto WI) {
-                constexpr bool v = decltype(V)::value, bi = decltype(BI)::value, wi = decltype(WI)::value;
-                if constexpr (wi && !GROUPED && !NOISE)
+            tk_with_flags([&](auto V, auto BI, auto WI, auto CU) {
+                constexpr bool v = decltype(V)::value, bi = decltype(BI)::value, wi = decltype(WI)::value, cu = decltype(CU)::value;
+                if constexpr (cu) {
+                    if constexpr (wi && !GROUPED && !NOISE)
+                        hipLaunchKernelGGL((topk_slice_kernel<p, w, v, false, false, bi, true, TkWindow, TkCursor>), grid, block, 0, s, B,
+                                           n, d, k, g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise,
+                                           bias, win, cur);
+                    else if constexpr (!GROUPED && !NOISE)
+                        hipLaunchKernelGGL((topk_slice_kernel<p, w, v, false, false, bi, false, TkCursor>), grid, block, 0, s, B, n, d, k,
+                                           g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias, cur);
+                } else if constexpr (wi && !GROUPED && !NOISE)
                     hipLaunchKernelGGL((topk_slice_kernel<p, w, v, false, false, bi, true, TkWindow>), grid, block, 0, s, B, n, d, k,
                                        g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias, win);
                 else if constexpr (!wi && (!bi || (!GROUPED && !NOISE)))
                     hipLaunchKernelGGL((topk_slice_kernel<p, w, v, GROUPED, NOISE, bi, false>), grid, block, 0, s, B, n, d, k,
                                        g.slice_len, g.S, user, items, exclude, n_exclude, ws, G, nt, tiles, item_ids, noise, bias);
-            }, tk_vec_ok(d, user, items), bias != nullptr, win.window != nullptr);
+            }, tk_vec_ok(d, user, items), bias != nullptr, win.window != nullptr, cur.after_ids != nullptr);
             snprintf(what, sizeof what, "%s(slices)", who);
             rc = check_launch(what);
             if (rc != NRMS_OK) return;
         }
-        hipLaunchKernelGGL(topk_merge_kernel<p>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids);
+        hipLaunchKernelGGL(topk_merge_kernel<p>, dim3(B), dim3(64), 0, s, B, k, g.S, ws, top_scores, top_ids,
+                           out_stride ? out_stride : k);
         snprintf(what, sizeof what, "%s(merge)", who);
         rc = check_launch(what);
     });

@@ -464,7 +464,7 @@ extern "C" int nrms_topk_dot_coarse(int32_t B, int64_t N, int32_t d, int32_t k, 
             if (rc != NRMS_OK) return;
         }
         TimingScope t3("coarse_stage(merge)", s);
-        hipLaunchKernelGGL(topk_merge_kernel<p>, dim3(B), dim3(64), 0, s, B, M, g.S, lists, sscores, sids);
+        hipLaunchKernelGGL(topk_merge_kernel<p>, dim3(B), dim3(64), 0, s, B, M, g.S, lists, sscores, sids, M);
         rc = check_launch("topk_dot_coarse(merge)");
     });
     if (rc != NRMS_OK) return rc;

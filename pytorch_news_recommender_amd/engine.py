@@ -857,6 +857,68 @@ class NRMSEngine:
         _lib.check(rc, "nrms_topk_dot")
         return scores, ids
 
+    def _top_k_args(self, who, user_vec, items, exclude, bias, item_time, window):
+        """The checks top_k_after and top_k_deep share with top_k -> (B, N, d, exclude, n_exclude, item_time, window)."""
+        dev = self._cuda_device()
+        self._check_tensor(who, "user_vec", user_vec, torch.float32, 2)
+        self._check_tensor(who, "items", items, torch.float32, 2)
+        B, d = user_vec.shape
+        N = items.shape[0]
+        if items.shape[1] != d:
+            raise _lib.NrmsError("%s: items width %d != user_vec width %d" % (who, items.shape[1], d))
+        exclude, n_ex = self._exclude_arg(who, exclude, B)
+        if bias is not None:
+            self._item_bias(who, bias, N, dev)
+        item_time, window = self._time_window(who, item_time, window, N, B, dev)
+        return B, N, d, exclude, n_ex, item_time, window
+
+    def top_k_after(self, user_vec, items, k, after_scores, after_ids, exclude=None, bias=None, *, item_time=None, window=None):
+        """One page of top_k's ranking: per user the k items that come strictly AFTER the position (after_scores[b], after_ids[b])
+        in top_k's order (score descending, then the smaller id) -> (scores [B, k] fp32, ids [B, k] int64).  after_scores [B] fp32,
+        after_ids [B] int64 (device, contiguous): the last column of the page before.  after_ids[b] = -2 (PAGE_BEGIN): no cursor,
+        the row is top_k's bit for bit; -1, any other negative id or a NaN score: the list is exhausted, the row is all padding
+        (-1 / -inf, which is what a page leaves in the columns it could not fill); >= 0: a position, the id need not be an
+        eligible item.  Every other argument is top_k's (nrms_topk_dot_after; include/nrms_hip.h states the contract)."""
+        who = "top_k_after"
+        k = int(k)
+        B, N, d, exclude, n_ex, item_time, window = self._top_k_args(who, user_vec, items, exclude, bias, item_time, window)
+        for name, t, dtype in (("after_scores", after_scores, torch.float32), ("after_ids", after_ids, torch.int64)):
+            if not torch.is_tensor(t) or tuple(t.shape) != (B,):
+                raise _lib.NrmsError("%s: %s must be a [%d] %s tensor (got %s)"
+                                     % (who, name, B, dtype, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+            self._check_tensor(who, name, t, dtype, 1)
+        nbytes = self.lib.nrms_topk_dot_after_workspace_bytes(B, N, d, k)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (who, B, N, d, k))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot_after(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                          _lib.ptr(item_time), _lib.ptr(window), _lib.ptr(after_scores), _lib.ptr(after_ids),
+                                          _lib.ptr(exclude), n_ex, _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws),
+                                          C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_topk_dot_after")
+        return scores, ids
+
+    def top_k_deep(self, user_vec, items, K, exclude=None, bias=None, *, item_time=None, window=None):
+        """top_k at a depth of up to 4096: (scores [B, K] fp32, ids [B, K] int64), per user the first K items of top_k's order, then
+        -1 / -inf.  ceil(K / 256) pages of top_k_after chained on the device, each reading its cursor from the page before: no
+        host synchronisation (nrms_topk_dot_deep).  K <= 256 is top_k, bit for bit; the arguments are top_k's."""
+        who = "top_k_deep"
+        K = int(K)
+        B, N, d, exclude, n_ex, item_time, window = self._top_k_args(who, user_vec, items, exclude, bias, item_time, window)
+        nbytes = self.lib.nrms_topk_dot_deep_workspace_bytes(B, N, d, K)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, K=%d; 1 <= K <= 4096)" % (who, B, N, d, K))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, K, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, K, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot_deep(B, C.c_int64(N), d, K, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                         _lib.ptr(item_time), _lib.ptr(window), _lib.ptr(exclude), n_ex, _lib.ptr(scores),
+                                         _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_topk_dot_deep")
+        return scores, ids
+
     def pack_catalogue(self, items):
         """items [N, d] fp32 (device, contiguous) -> PackedCatalogue: the fp16 copy top_k_coarse scans (N * pitch * 2 bytes, pitch =
         32 ceil(d / 32)) and its two norm bounds, beside the fp32 rows it was made from (nrms_catalogue_pack_f16).  Pack again

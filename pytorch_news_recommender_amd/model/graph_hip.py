@@ -243,6 +243,16 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: recommend is not available: a candidate's score depends on its neighbours in the "
                                   "click graph, not on a catalogue row alone")
 
+    CATALOGUE_PAGING = False
+
+    def recommend_page(self, batch, k, catalogue, after=None, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        raise NotImplementedError("graph: recommend_page is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone (no recommend either, so no ranking to page through)")
+
+    def recommend_deep(self, batch, K, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        raise NotImplementedError("graph: recommend_deep is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone (no recommend either, at any depth)")
+
     CATALOGUE_SECTIONS = False
 
     def recommend_sections(self, batch, k, sectioned, exclude_history=True, *, item_bias=None):

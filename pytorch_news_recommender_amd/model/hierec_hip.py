@@ -366,6 +366,17 @@ class Model(FlatHipModel):
         raise NotImplementedError("hierec: rank_targets is not available: HieRec scores the catalogue with a query per (topic, "
                                   "sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot ranks plain dot products only")
 
+    CATALOGUE_PAGING = False
+
+    def recommend_page(self, batch, k, catalogue, after=None, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        raise NotImplementedError("hierec: recommend_page is not available: HieRec scores the catalogue with a query per (topic, "
+                                  "sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no cursor")
+
+    def recommend_deep(self, batch, K, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        raise NotImplementedError("hierec: recommend_deep is not available: HieRec scores the catalogue with a query per (topic, "
+                                  "sub-topic) group (nrms_topk_grouped_dot), whose lists stop at 256 and which has no cursor to "
+                                  "chain pages with")
+
     CATALOGUE_SECTIONS = False
 
     def recommend_sections(self, batch, k, sectioned, exclude_history=True, *, item_bias=None):

@@ -21,6 +21,8 @@ from .. import _lib
 from ..engine import FlatLayout, ModelDims, NRMSEngine, PackedCatalogue
 from ._flat_model import FlatHipModel
 
+PAGE_BEGIN = -2          # recommend_page: the cursor id of a row that starts over (include/nrms_hip.h NRMS_CURSOR_BEGIN)
+
 
 class _MultiHeadSelfAttentionParams(nn.Module):
     """Parameter holder mirroring nrms_v0.py:26-44 (W_Q, W_K, W_V Linear(d,d), xavier-uniform weights)."""
@@ -305,6 +307,56 @@ class Model(FlatHipModel):
         res = self._engine.mmr_rerank(cat[1:], s_ids, s_scores, k, lam, return_ild=return_ild)
         return (torch.where(res[0] >= 0, res[0] + 1, res[0]), res[1]) + tuple(res[2:])
 
+    @torch.no_grad()
+    def recommend_page(self, batch, k, catalogue, after=None, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        """One page of recommend's ranking -> (news_ids [B, k] int64, scores [B, k] fp32): per user the k news that follow the
+        position ``after`` in recommend's list were it unbounded (the same user vector, score bits, exclusions and tie rule;
+        include/nrms_hip.h nrms_topk_dot_after).  1 <= k <= 256.
+
+        after: None, the first page (recommend(k), bit for bit), or (ids [B], scores [B]): the LAST COLUMN of the page before,
+        in news ids, as this method returned it.  No state is kept between pages: a feed that scrolls sends back the last news it
+        showed.  Id -1 (what a page leaves in the slots its list did not reach) means exhausted: the row is all padding, id -1 /
+        score -inf, and stays so.  ``PAGE_BEGIN`` as an id marks a row that starts over (its score is not read), so users on
+        different pages share a batch.  Any id >= 1 is a position, not an item: it need not be recommendable.  Id 0, the padding
+        title, is read as -1.
+
+        catalogue, ``browsed_ids``, exclude_history, item_bias, item_time and window are recommend's, and have to be the same
+        from page to page for the pages to chain."""
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend_page")
+        bias = self._item_bias_rows(item_bias, cat, "recommend_page")
+        win = self._time_window_rows(item_time, window, cat, user.shape[0], "recommend_page")
+        B, dev = user.shape[0], user.device
+        if after is None:
+            a_ids = torch.full((B,), PAGE_BEGIN, dtype=torch.int64, device=dev)
+            a_scores = torch.zeros(B, dtype=torch.float32, device=dev)
+        else:
+            try:
+                a_ids, a_scores = after
+            except (TypeError, ValueError):
+                raise _lib.NrmsError("recommend_page: after must be None or (ids [B], scores [B]), the last column of the page before")
+            a_ids = torch.as_tensor(a_ids).to(dev, dtype=torch.int64).reshape(-1)
+            a_scores = torch.as_tensor(a_scores).to(dev, dtype=torch.float32).reshape(-1).contiguous()
+            if a_ids.shape[0] != B or a_scores.shape[0] != B:
+                raise _lib.NrmsError("recommend_page: after must be (ids [%d], scores [%d]) (got %s, %s)"
+                                     % (B, B, tuple(a_ids.shape), tuple(a_scores.shape)))
+            # news id n is row n - 1 of cat[1:], as in recommend; -1, PAGE_BEGIN and every other negative id pass through
+            # unshifted.  Id 0, the padding title, is no row and no page returns it: it is read as -1, exhausted.
+            a_ids = torch.where(a_ids > 0, a_ids - 1, torch.where(a_ids == 0, torch.full_like(a_ids, -1), a_ids)).contiguous()
+        scores, ids = self._engine.top_k_after(user, cat[1:], k, a_scores, a_ids, exclude, bias=bias, **win)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    @torch.no_grad()
+    def recommend_deep(self, batch, K, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        """recommend at a depth of up to 4096 (candidates for a re-ranker) -> (news_ids [B, K] int64, scores [B, K] fp32): the
+        first K news of recommend's ranking, then id -1 / score -inf; ceil(K / 256) pages chained on the device without a host
+        synchronisation (include/nrms_hip.h nrms_topk_dot_deep).  K <= 256 is recommend(K), bit for bit; rank_targets of row b's
+        ids gives 1, 2, ...  The arguments are recommend's (no diversity re-ranking and no fp16 shortlist at this depth)."""
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend_deep")
+        bias = self._item_bias_rows(item_bias, cat, "recommend_deep")
+        win = self._time_window_rows(item_time, window, cat, user.shape[0], "recommend_deep")
+        scores, ids = self._engine.top_k_deep(user, cat[1:], K, exclude, bias=bias, **win)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
     @staticmethod
     @torch.no_grad()
     def section_catalogue(catalogue, section_of, n_sections):
@@ -472,6 +524,7 @@ class Model(FlatHipModel):
     CATALOGUE_RANKING = True            # the catalogue score is a plain dot product: rank_targets (run_v0 --retrieval_metrics)
     CATALOGUE_SAMPLING = True           # ... so negatives can be drawn from its softmax: sample_negatives (run_v0 --negatives adaptive)
     CATALOGUE_SECTIONS = True           # ... and selected per section: recommend_sections (run_v0 --sections)
+    CATALOGUE_PAGING = True             # ... and paged through with a cursor: recommend_page / recommend_deep (run_v0 --recommend_deep)
 
     def check_recommend_ids(self):
         """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read

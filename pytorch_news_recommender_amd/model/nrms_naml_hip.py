@@ -148,6 +148,21 @@ class Model(nrms_hip.Model):
                                  return_ild=return_ild, item_bias=item_bias, item_time=item_time, window=window, coarse=coarse,
                                  coarse_shortlist=coarse_shortlist, return_certified=return_certified)
 
+    def recommend_page(self, batch, k, catalogue, after=None, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        """nrms_hip.Model.recommend_page over encode_catalogue's feature rows (the user vector and the score are recommend's)."""
+        if catalogue is None:
+            raise NotImplementedError("nrms_naml: recommend_page needs a catalogue built with the per-news category tables: "
+                                      "encode_catalogue(titles, absts, categ, subcateg)")
+        return super().recommend_page(batch, k, catalogue, after, exclude_history, item_bias=item_bias, item_time=item_time,
+                                      window=window)
+
+    def recommend_deep(self, batch, K, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None):
+        """nrms_hip.Model.recommend_deep over encode_catalogue's feature rows (the user vector and the score are recommend's)."""
+        if catalogue is None:
+            raise NotImplementedError("nrms_naml: recommend_deep needs a catalogue built with the per-news category tables: "
+                                      "encode_catalogue(titles, absts, categ, subcateg)")
+        return super().recommend_deep(batch, K, catalogue, exclude_history, item_bias=item_bias, item_time=item_time, window=window)
+
     def _catalogue_width(self):
         return self._dims.news_feature_size
 

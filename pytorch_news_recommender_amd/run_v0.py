@@ -25,7 +25,7 @@ from . import parallel
 from .config import Config
 from .data_handler import ClickFeed, DeviceFeed, ImpressionFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
 from .model import Model
-from .train_eval import evaluate_retrieval, recommend, recommend_sections, test, train
+from .train_eval import evaluate_retrieval, recommend, recommend_deep, recommend_sections, test, train
 
 # rank r adds r * this to its dropout seeds (FlatHipModel._next_seed), so that the ranks of a data-parallel job draw unrelated masks
 DROPOUT_RANK_SALT = 0x632BE59BD9B4E019
@@ -93,7 +93,12 @@ def build_parser():
                         'certificate covered (not with --diversity, --popularity_prior, --catalogue_window or --sections)')
     parser.add_argument('--coarse_shortlist', type=int, default=None, metavar='M', help='--coarse_catalogue: the news the fp16 pass '
                         'keeps per user (K <= M <= 256; default min(256, max(64, 4 K)))')
-    parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend (default recommend_<model>_<time>.txt)')
+    parser.add_argument('--recommend_deep', type=int, default=None, metavar='K', help='finally write the first K news of the ranking '
+                        'of the whole catalogue per impression, 1 <= K <= 4096 (candidates for a re-ranker; pages of 256 chained on the '
+                        'device): the file and the split of --recommend, which it replaces; works with --popularity_prior and '
+                        '--catalogue_window, not with --diversity, --shortlist, --coarse_catalogue or --sections')
+    parser.add_argument('--recommend_out', type=str, default=None, help='file name of --recommend / --recommend_deep (default '
+                        'recommend_<model>_<time>.txt)')
     parser.add_argument('--sections', type=str, default=None, choices=('category', 'subcategory'), help='--recommend: write the front '
                         'page by section instead, the top K news of every category (or sub-category) per impression, as '
                         '"<impression> <section> [ids]" lines (models whose catalogue score is a plain dot product; not with --diversity)')
@@ -131,6 +136,28 @@ def check_coarse_args(args):
             raise SystemExit('--coarse_catalogue: the certificate covers the plain top-k only (drop %s)' % flag)
     if args.coarse_shortlist is not None and not args.recommend <= args.coarse_shortlist <= 256:
         raise SystemExit('--coarse_shortlist M: M must be in [K, 256] (got M=%d, K=%d)' % (args.coarse_shortlist, args.recommend))
+
+
+def check_deep_args(args):
+    """--recommend_deep fails before any data is read or any step is trained: K in [1, 4096], the plain ranking only (no other
+    list of --recommend beside it, no re-ranking, no fp16 shortlist, no sections), a model that can page through its ranking."""
+    if args.recommend_deep is None:
+        return
+    if not 1 <= args.recommend_deep <= 4096:
+        raise SystemExit('--recommend_deep K: K must be in [1, 4096] (got %d)' % args.recommend_deep)
+    if args.recommend is not None:
+        raise SystemExit('--recommend_deep: writes the list of --recommend at its own depth (drop --recommend)')
+    for flag, on in (('--diversity', args.diversity is not None), ('--shortlist', args.shortlist is not None),
+                     ('--coarse_catalogue', args.coarse_catalogue or args.coarse_shortlist is not None),
+                     ('--sections', args.sections is not None)):
+        if on:
+            raise SystemExit('--recommend_deep: the plain ranking only, pages chained by a cursor (drop %s)' % flag)
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not (getattr(module.Model, 'CATALOGUE_RETRIEVAL', False) and getattr(module.Model, 'CATALOGUE_PAGING', False)):
+        raise SystemExit('--recommend_deep: model %r cannot page through a ranking of the whole catalogue (nrms_v0 / nrms_v1 / '
+                         'nrms_bert: a plain dot product over a row-ordered catalogue)' % args.model)
 
 
 def check_recommend_args(args):
@@ -190,8 +217,8 @@ def check_prior_args(args):
         return
     if not np.isfinite(args.popularity_prior):
         raise SystemExit('--popularity_prior ALPHA: ALPHA must be finite (got %r)' % args.popularity_prior)
-    if args.recommend is None and args.retrieval_metrics is None:
-        raise SystemExit('--popularity_prior ALPHA: the prior of --recommend K and --retrieval_metrics K (give one of them)')
+    if args.recommend is None and args.recommend_deep is None and args.retrieval_metrics is None:
+        raise SystemExit('--popularity_prior ALPHA: the prior of --recommend K, --recommend_deep K and --retrieval_metrics K (give one of them)')
     if args.negatives not in ('catalogue', 'adaptive'):
         raise SystemExit('--popularity_prior: popularity is counted in a click log (--negatives catalogue or adaptive, got %r)'
                          % args.negatives)
@@ -208,8 +235,8 @@ def check_window_args(args):
         return
     if args.catalogue_window < 1:
         raise SystemExit('--catalogue_window SPAN: SPAN must be >= 1 (got %d)' % args.catalogue_window)
-    if args.recommend is None and args.retrieval_metrics is None:
-        raise SystemExit('--catalogue_window SPAN: the window of --recommend K and --retrieval_metrics K (give one of them)')
+    if args.recommend is None and args.recommend_deep is None and args.retrieval_metrics is None:
+        raise SystemExit('--catalogue_window SPAN: the window of --recommend K, --recommend_deep K and --retrieval_metrics K (give one of them)')
     if args.negatives not in ('catalogue', 'adaptive'):
         raise SystemExit('--catalogue_window: the ticks belong to a click log (--negatives catalogue or adaptive, got %r)'
                          % args.negatives)
@@ -291,6 +318,7 @@ def check_loss_args(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    check_deep_args(args)
     check_recommend_args(args)
     check_sections_args(args)
     check_coarse_args(args)
@@ -379,6 +407,9 @@ def main(argv=None):
         # the catalogue is the feed's title table (row r = news id r), so this step always runs on a DeviceFeed
         feed = DeviceFeed(config, samples, type=1, id2title_dict=titles, id2abst_dict=absts, batch_size=config.batch_size,
                           device=config.device)
+        if args.recommend_deep is not None:
+            return recommend_deep(config, recommender, feed, feed.titles, args.recommend_deep, out_file=args.recommend_out,
+                                  **item_prior, **item_window)
         if args.sections is not None:
             info = feed.news_info()
             sections = ((info['categ'], config.category_nums) if args.sections == 'category'
@@ -469,7 +500,7 @@ def main(argv=None):
             print('click log: {} rows, {} slots left empty in the last draw'.format(train_feed.n_samples, train_feed.n_short))
         # a click log is evaluated on its own held-out clicks (each user's last one) against the whole catalogue
         top_samples, top_labels = (held_samples, held_labels) if args.negatives in ('catalogue', 'adaptive') else (dev_samples, dev_labels)
-        if args.recommend is not None and rank == 0:
+        if (args.recommend is not None or args.recommend_deep is not None) and rank == 0:
             print('recommendations saved to', recommend_top(top_samples))
         if retrieval_ks is not None and rank == 0:
             retrieval_quality(top_samples, top_labels)
@@ -487,7 +518,7 @@ def main(argv=None):
         out = test(config, recommender, test_feed, shown, ckpt_file=args.load,
                    pick_best=args.load is None)
         print('saved to', out)
-        if args.recommend is not None and rank == 0:
+        if (args.recommend is not None or args.recommend_deep is not None) and rank == 0:
             print('recommendations saved to', recommend_top(test_samples))
         if retrieval_ks is not None and rank == 0:
             retrieval_quality(test_samples, dev_labels)

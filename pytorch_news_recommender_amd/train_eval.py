@@ -451,6 +451,38 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     return file_name
 
 
+def recommend_deep(config, model, data_iter, titles, K, out_file=None, exclude_history=True, news_info=None, item_bias=None,
+                   item_time=None, request_time=None, window_span=None):
+    """recommend() at a depth of up to 4096 (candidates for a re-ranker): writes the same ``<impression index> [id1,id2,...]``
+    lines, per impression of data_iter the first K news ids of the model's ranking of the whole catalogue, best first
+    (``model.recommend_deep``: pages of 256 chained on the device).  titles / news_info / exclude_history / item_bias / item_time /
+    request_time / window_span as in recommend(); there is no diversity re-ranking and no fp16 shortlist at this depth.  Returns
+    the file name."""
+    net = _inner(model)
+    prior = {} if item_bias is None else {"item_bias": item_bias}
+    windows, done = _RequestWindows("recommend_deep", item_time, request_time, window_span), 0
+    K = int(K)
+    if not 1 <= K <= 4096:
+        raise ValueError("recommend_deep: K must be in [1, 4096] (got %d)" % K)
+    catalogue = net.encode_catalogue(titles, **(news_info or {}))
+    lines = []
+    for datas in data_iter:
+        if windows.on:
+            B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
+            prior.update(windows.of(done, B, catalogue.device))
+            done += B
+        ids, _ = net.recommend_deep(datas, K, catalogue, exclude_history=exclude_history, **prior)
+        lines.extend(ids.cpu().tolist())
+    net.engine.check_ids()
+    net.check_recommend_ids()
+    file_name = out_file or 'recommend_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
+    with open(file_name, 'w') as f:
+        for i, row in enumerate(lines):
+            f.write(str(i + 1) + ' ')
+            f.write(str([n for n in row if n >= 0]).replace(' ', '') + '\n')
+    return file_name
+
+
 def recommend_sections(config, model, data_iter, titles, k, sections, out_file=None, exclude_history=True, news_info=None,
                        item_bias=None):
     """The front page by section: writes ``<impression index> <section> [id1,id2,...]`` lines (the index 1-based, as
