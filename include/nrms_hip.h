@@ -752,6 +752,54 @@ int nrms_mmr_rerank(int32_t B, int32_t M, int32_t d, int32_t k, int64_t N, float
                     float* out_value /* [B, k], nullable */, float* ild /* [B], nullable */,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Why this item: a score split exactly over the clicks of the history (csrc/attribution.hip; serving: "because you read
+ * ..."; PARITY UNPINNED, the reference explains nothing) ----
+ * The user vector of the additive-attention user encoder is u[b] = sum_h w[b, h] ctx[b, h, :] (nrms_encoder_acts.w and .ctx,
+ * nrms_v0.py:110-125), so the score of any item x splits over the H history slots: u[b] . x = sum_h w[b, h] (ctx[b, h, :] . x).
+ * For each user b < B and each position j < K of the user's list, the H terms, their ordered sum, the m largest of them and the
+ * part carried by the slots the caller cannot name.
+ * ctx [B, H, d], w [B, H], items [N, d] fp32 row-major; ids [B, K] int64: catalogue rows, e.g. a row of nrms_topk_dot's or
+ * nrms_mmr_rerank's output, padding included; slot_named [B, H] uint8, NULLABLE (null = every slot is named); contrib [B, K, H]
+ * fp32, NULLABLE; total [B, K] fp32; top_slots [B, K, m] int32; top_contrib [B, K, m] fp32; unnamed_share [B, K] fp32, NULLABLE.
+ * Term.  c(b, j, h) = w[b, h] * s(ctx[b, h, :], items[ids[b, j], :]): s is nrms_topk_dot's chain (one fp32 accumulator over all
+ *   of d on v_mfma_f32_32x32x2_f32 in the same k order, csrc/topk_entry.h tk_chain), then ONE fp32 multiplication, rounded to
+ *   nearest, nothing fused.  The bits of c depend on (the ctx row, the w value, the item row) only: not on B, K, H, m, the position
+ *   in the list, the other ids or the run.  s(ctx row, item row) has the bits nrms_rank_dot returns as target_scores when that ctx
+ *   row is given as a user row.
+ * Total.  total[b, j] = the fp32 sum of c(b, j, h) over h = 0, 1, ..., H - 1 in that order, one sequential chain from +0.0.  It is
+ *   the model's score of the item up to the rounding of the two orders of summation.
+ * Reasons.  Slot h is ELIGIBLE when slot_named is NULL or slot_named[b, h] != 0, and c(b, j, h) is not NaN.  top_slots[b, j, :]
+ *   holds the first min(m, #eligible) eligible slots by c descending, top_contrib their c; equal values put the SMALLER slot first;
+ *   -0.0 equals +0.0 and is returned as +0.0 (nrms_topk_dot's order on (c, slot)).  The remaining places hold slot -1 and
+ *   contribution -inf.  Negative contributions are listed like any other: the caller cuts at 0.
+ * Unnamed share.  unnamed_share[b, j] = the fp32 sum, from +0.0 in slot order, of c(b, j, h) over the slots with slot_named[b, h]
+ *   == 0; 0 when slot_named is NULL.  (nrms_v0 masks nothing: a padding slot of the history has a non-zero ctx row and carries part
+ *   of the score.  This is that part.)
+ * NaN.  A NaN in ctx[b, h, :] or w[b, h] makes c(b, j, h) NaN for every j: slot h is never a reason, total[b, j] is NaN for every
+ *   valid j, and unnamed_share[b, j] is NaN if the slot is unnamed.  A NaN in an item row makes every term of the entries that name
+ *   it NaN: no reasons, total NaN.  contrib carries the NaNs.  Infinities are ordinary values.
+ * Invalid entries.  An entry whose ids[b, j] is outside [0, N) (-1 is the padding of every top-k call here) gets total -inf,
+ *   unnamed_share 0, m reasons -1 / -inf and a contrib row of zeros.  No item row is read for it.  An id that occurs twice makes
+ *   two entries with the same bits.
+ * Limits: 1 <= H <= 64, 1 <= K <= 256, 1 <= m <= 8, d >= 1, 0 <= N <= 0x7FFF0000, B >= 0; B = 0 is a no-op (no pointer is
+ *   inspected), N = 0 makes every entry invalid (items may be NULL).  Arguments outside the limits, a NULL required pointer, float /
+ *   int32 pointers not 4-byte aligned or ids not 8-byte aligned return NRMS_EINVAL with a message "attribution_dot: ..." naming the
+ *   argument; a workspace below the query's size returns NRMS_EWORKSPACE.  Nothing is launched after an error.
+ * Every element of total, top_slots, top_contrib and of contrib / unnamed_share when given is written; nothing else is.
+ * Workspace: nrms_attribution_dot_workspace_bytes(B, H, d, K, m) bytes, 8-byte aligned, required (0 = arguments rejected).  It is
+ *   256 reserved bytes today: a chunk's terms stay in LDS and the call neither reads nor writes the workspace.
+ * One kernel on `stream`, one wave per (user, 64 list positions); no host synchronisation, no allocation; plain vector loads and
+ *   stores, no atomics: two runs are bit-identical.  Row (b, j) is a function of (ctx[b], w[b], slot_named[b], the item row, m). */
+size_t nrms_attribution_dot_workspace_bytes(int32_t B, int32_t H, int32_t d, int32_t K, int32_t m);
+int nrms_attribution_dot(int32_t B, int32_t H, int64_t N, int32_t d, int32_t K, int32_t m,
+                         const float* ctx /* [B, H, d] */, const float* w /* [B, H] */,
+                         const float* items /* [N, d] */, const int64_t* ids /* [B, K] */,
+                         const uint8_t* slot_named /* [B, H], nullable */,
+                         float* contrib /* [B, K, H], nullable */, float* total /* [B, K] */,
+                         int32_t* top_slots /* [B, K, m] */, float* top_contrib /* [B, K, m] */,
+                         float* unnamed_share /* [B, K], nullable */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- nrms_naml pieces around the two encoder passes (model/nrms_naml.py) ----
  * LayerNorm over the last dimension (nn.LayerNorm(news_feature_size) on the history vectors, nrms_naml.py:207,238):
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance.  stats [n_rows, 2] = (mean, 1/std) is written when

@@ -180,6 +180,12 @@ class BertEngine(NRMSEngine):
         _lib.check(rc, "nrms_encoder_fwd(user)")
         return out
 
+    def user_parts(self, flat, x, mask):
+        """encode_users' inference pass on buffers of its own -> (user [B, E], ctx [B, H, E], w [B, H]): user[b] = sum_h w[b, h]
+        ctx[b, h], masked slots with w = 0 (NRMSEngine.user_parts; the input of `attribution`)."""
+        B, H, E = x.shape
+        return (self.encode_users(flat, x, mask, tag="user_parts"),) + self._parts_of("user_parts", B, H, E)
+
     # ---- full model ----------------------------------------------------------------------------------------------------
     def forward(self, flat, browsed_ids, cand_ids, browsed_mask, cand_mask, training, p_drop=0.0, seed=0):
         """Model.forward (nrms.py:317-366).  browsed_ids [B, H], cand_ids [B, C] int64, browsed_mask [B, H] uint8, cand_mask

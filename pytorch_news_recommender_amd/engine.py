@@ -401,6 +401,32 @@ class NRMSEngine:
         _lib.check(rc, "nrms_encoder_fwd(user)")
         return out
 
+    def _parts_of(self, tag, B, H, d):
+        """Copies of what the tag's last user-encoder pass left in acts.ctx / acts.w: (ctx [B, H, d], w [B, H])."""
+        M = B * H
+        return self._bufs[tag + ".ctx"][:M * d].view(B, H, d).clone(), self._bufs[tag + ".w"][:M].view(B, H).clone()
+
+    def user_parts(self, flat, news_vectors, mask=None, mask_mode=0):
+        """news_vectors [B, H, d] -> (user [B, d], ctx [B, H, d], w [B, H]): an inference pass of the user encoder (evaluation
+        precision, no dropout) that also hands out the two factors of its pooling sum, user[b] = sum_h w[b, h] ctx[b, h]
+        (nrms_encoder_acts.ctx and .w; the input of `attribution`).  It is the pass encode_users runs for this shape, the fused
+        one-kernel pass included, which stores ctx and w row-major like the chain: `user` has encode_users' bits.  (Only an fp16
+        user encoder, whose activations are fp16 with padded pitches, is replaced by the bf16x3 pass here.)  The buffers are the
+        tag "user_parts"'s own: neither a training forward's saved activations nor user_eval's are touched."""
+        B, H, d = news_vectors.shape
+        tag = "user_parts"
+        out = torch.empty(B, d, dtype=torch.float32, device=self.device)
+        wts = self._weights(flat, "user_encoder")
+        desc = self._desc("user_encoder", B, H, mask_mode=mask_mode if mask is not None else 0, training=False)
+        if desc.precision == _lib.NRMS_PRECISION_FP16:
+            desc.precision = _lib.PRECISIONS["bf16x3"]
+        acts = self._acts(tag, B * H, True, desc=desc)
+        rc = self.lib.nrms_encoder_fwd(C.byref(desc), C.byref(wts), None, C.c_void_p(news_vectors.data_ptr()),
+                                       _lib.ptr(None if mask is None else mask.contiguous()), C.byref(acts),
+                                       C.c_void_p(out.data_ptr()), _stream())
+        _lib.check(rc, "nrms_encoder_fwd(user parts)")
+        return (out,) + self._parts_of(tag, B, H, d)
+
     def click_scores(self, cand_vec, user_vec, cand_mask=None, out=None):
         B, Cn, d = cand_vec.shape
         if out is None:
@@ -1040,6 +1066,43 @@ class NRMSEngine:
         if return_ild:
             out += (ild,)
         return out
+
+    def attribution(self, ctx, w, items, ids, m, slot_named=None, return_contrib=False):
+        """ctx [B, H, d], w [B, H] fp32 (user_parts), items [N, d] fp32, ids [B, K] int64, slot_named [B, H] uint8 or None
+        (device, contiguous) -> (top_slots [B, K, m] int32, top_contrib [B, K, m] fp32, total [B, K] fp32, unnamed_share [B, K]
+        fp32), then with return_contrib the terms [B, K, H] fp32: the score of item ids[b, j] for user b split over the H history
+        slots, c = w[b, h] * (ctx[b, h] . item) (nrms_attribution_dot).  total is their ordered sum; the m largest terms of the
+        named slots come first to last, slot -1 / -inf where there are fewer; unnamed_share is the sum over the slots with
+        slot_named == 0.  Ids outside [0, N) get total -inf, no reasons and zero terms.  include/nrms_hip.h states the contract."""
+        m = int(m)
+        self._check_tensor("attribution", "ctx", ctx, torch.float32, 3)
+        self._check_tensor("attribution", "w", w, torch.float32, 2)
+        self._check_tensor("attribution", "items", items, torch.float32, 2)
+        self._check_tensor("attribution", "ids", ids, torch.int64, 2)
+        B, H, d = ctx.shape
+        N, K = items.shape[0], ids.shape[1]
+        if tuple(w.shape) != (B, H) or items.shape[1] != d or ids.shape[0] != B:
+            raise _lib.NrmsError("attribution: ctx %s needs w [%d, %d], items [N, %d] and ids [%d, K] (got %s, %s, %s)"
+                                 % (tuple(ctx.shape), B, H, d, B, tuple(w.shape), tuple(items.shape), tuple(ids.shape)))
+        if slot_named is not None:
+            self._check_tensor("attribution", "slot_named", slot_named, torch.uint8, 2)
+            if tuple(slot_named.shape) != (B, H):
+                raise _lib.NrmsError("attribution: slot_named must be [%d, %d] (got %s)" % (B, H, tuple(slot_named.shape)))
+        nbytes = self.lib.nrms_attribution_dot_workspace_bytes(B, H, d, K, m)
+        if nbytes == 0:
+            raise _lib.NrmsError("attribution: arguments rejected (B=%d, H=%d, d=%d, K=%d, m=%d; 1 <= H <= 64, 1 <= K <= 256, "
+                                 "1 <= m <= 8, d >= 1)" % (B, H, d, K, m))
+        ws = self._buf("attribution_ws", (nbytes + 7) // 8, torch.int64)
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        top_slots, top_contrib = new((B, K, m), torch.int32), new((B, K, m), torch.float32)
+        total, unnamed = new((B, K), torch.float32), new((B, K), torch.float32)
+        contrib = new((B, K, H), torch.float32) if return_contrib else None
+        rc = self.lib.nrms_attribution_dot(B, H, C.c_int64(N), d, K, m, _lib.ptr(ctx), _lib.ptr(w), _lib.ptr(items), _lib.ptr(ids),
+                                           _lib.ptr(slot_named), _lib.ptr(contrib), _lib.ptr(total), _lib.ptr(top_slots),
+                                           _lib.ptr(top_contrib), _lib.ptr(unnamed), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_attribution_dot")
+        out = (top_slots, top_contrib, total, unnamed)
+        return out + (contrib,) if return_contrib else out
 
     def rank_of(self, user_vec, items, targets, exclude=None, bias=None, *, item_time=None, window=None):
         """user_vec [B, d], items [N, d] fp32, targets [B, T] int64, exclude [B, n_exclude] int64 or None (device, contiguous)

@@ -259,6 +259,12 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: recommend_sections is not available: a candidate's score depends on its neighbours in "
                                   "the click graph, not on a catalogue row alone (no recommend either)")
 
+    CATALOGUE_EXPLAIN = False
+
+    def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):
+        raise NotImplementedError("graph: explain is not available: a candidate's score depends on its neighbours in the click "
+                                  "graph, so it is no sum of one term per click of the history (no recommend either)")
+
     def attach_click_graph(self, graph, titles):
         """From now on a batch without ``neighbor_rows`` takes its neighbours from ``graph`` (click_graph.ClickGraph on the
         model's device) instead of the batch-induced host sampler; titles [graph.n_news, L]: the word ids of every news, row r =

@@ -384,6 +384,13 @@ class Model(FlatHipModel):
                                   "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_topk_sections_dot scores every "
                                   "section with one user row")
 
+    CATALOGUE_EXPLAIN = False
+
+    def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):
+        raise NotImplementedError("hierec: explain is not available: HieRec's score is a mixture over an interest tree (user, "
+                                  "topic and sub-topic interests, each with its own weight), not one additive-attention sum over "
+                                  "the clicks, so it does not split into one term per click")
+
     def _zero_frozen_rows(self, gflat):
         # padding_idx = 0 of the two embedding tables: row 0 takes no gradient (nn.Embedding semantics)
         self._layout.view(gflat, "subtopic_embedding.weight")[0].zero_()

@@ -146,3 +146,7 @@ class Model(nrms_hip.Model):
     def _catalogue_users(self, hist, browsed=None):
         mask = (browsed != 0).to(torch.uint8)
         return self._engine.encode_users(self._flat, hist, mask)
+
+    def _catalogue_user_parts(self, hist, browsed=None):
+        mask = (browsed != 0).to(torch.uint8)
+        return self._engine.user_parts(self._flat, hist, mask)

@@ -428,6 +428,61 @@ class Model(FlatHipModel):
         return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude, bias=bias, **win)
 
     @torch.no_grad()
+    def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):
+        """Why these news: each score split exactly over the clicks of the user's history -> (reason_ids [B, K, m] int64,
+        reason_contrib [B, K, m] fp32, total [B, K] fp32, padding_share [B, K] fp32), then with return_contributions the terms
+        contrib [B, K, H] fp32 (include/nrms_hip.h nrms_attribution_dot).
+
+        The user vector is the additive-attention sum over the history, user = sum_h w[h] ctx[h], so the score of news x is
+        sum_h w[h] (ctx[h] . x): term h is what click h contributes, with no approximation.  news_ids [B, K] int64, K <= 256:
+        what recommend / recommend_page / recommend_deep (256 columns per call) or the diversity re-ranking returned, news ids
+        with -1 in the unfilled slots.  reason_ids[b, j] are the ``browsed_ids`` of the m history slots with the largest terms
+        for news_ids[b, j], largest first (equal terms: the earlier slot), reason_contrib their terms; -1 / -inf where the user
+        has fewer than m named clicks.  Negative terms are listed like any other: cut at 0 for "because you read".  1 <= m <= 8.
+
+        total is the ordered sum of all H terms: the model's score of that news WITHOUT any ``item_bias``, equal to recommend's
+        score up to the rounding of the two orders of summation (DESIGN.md section 8h has the measured difference).
+        padding_share is the part of total carried by the slots that name no news: padding slots (``browsed_ids`` 0, or an id
+        outside the catalogue, counted for check_recommend_ids as in recommend).  nrms_v0 masks nothing, so a padding slot has
+        a context row of its own and carries part of the score; models that mask their history (nrms_bert) give those slots
+        weight 0, except for a user without any click, whose softmax over equally masked slots is uniform: that score is all
+        padding share.
+        An entry of news_ids outside [0, N) gets total -inf, no reasons and zero terms.  Id 0, the padding title, is a
+        catalogue row like any other here.  catalogue and ``browsed_ids`` as in recommend."""
+        get = batch.get if hasattr(batch, "get") else batch.__getitem__
+        browsed = get("browsed_ids")
+        if browsed is None:
+            raise KeyError("explain: the batch dict lacks 'browsed_ids' (the news ids of the clicked history)")
+        dev = self._prepare()
+        cat = torch.as_tensor(catalogue)
+        d = self._catalogue_width()
+        if cat.dim() != 2 or cat.shape[1] != d or cat.dtype != torch.float32 or cat.device != dev:
+            raise _lib.NrmsError("explain: catalogue must be [N, %d] float32 on %s (encode_catalogue), got %s %s on %s"
+                                 % (d, dev, tuple(cat.shape), cat.dtype, cat.device))
+        cat = cat.contiguous()
+        browsed = torch.as_tensor(browsed).to(dev, dtype=torch.int64).contiguous()
+        B, H = browsed.shape
+        ids = torch.as_tensor(news_ids).to(dev, dtype=torch.int64).contiguous()
+        if ids.dim() != 2 or ids.shape[0] != B:
+            raise _lib.NrmsError("explain: news_ids must be [%d, K] news ids (got %s)" % (B, tuple(ids.shape)))
+        bad = (browsed < 0) | (browsed >= cat.shape[0])          # as _catalogue_query: counted, read as padding
+        browsed = browsed.masked_fill(bad, 0)
+        if self._bad_browsed is None or self._bad_browsed.device != dev:
+            self._bad_browsed = torch.zeros((), dtype=torch.int64, device=dev)
+        self._bad_browsed += bad.sum()
+        _, ctx, w = self._catalogue_user_parts(cat.index_select(0, browsed.view(-1)).view(B, H, d), browsed)
+        # the kernel's rows are catalogue rows, row 0 the padding title's: the whole catalogue and the ids as they are
+        res = self._engine.attribution(ctx, w, cat, ids, m, slot_named=(browsed != 0).to(torch.uint8),
+                                       return_contrib=return_contributions)
+        slots = res[0].to(torch.int64)
+        reason_ids = torch.where(slots >= 0, browsed.gather(1, slots.clamp(min=0).view(B, -1)).view_as(slots), slots)
+        return (reason_ids,) + tuple(res[1:])
+
+    def _catalogue_user_parts(self, hist, browsed=None):
+        """_catalogue_users' pass with its pooling factors: (user [B, width], ctx [B, H, width], w [B, H])."""
+        return self._engine.user_parts(self._flat, hist)
+
+    @torch.no_grad()
     def sample_negatives(self, batch, row_key, S, catalogue, temperature, seed, exclude=None):
         """S negatives per user of ``batch`` drawn from the model's own softmax over the whole catalogue -> news ids [B, S]
         int64, -1 in an empty slot: a draw without replacement from softmax(score / temperature) over the eligible news, in
@@ -525,6 +580,7 @@ class Model(FlatHipModel):
     CATALOGUE_SAMPLING = True           # ... so negatives can be drawn from its softmax: sample_negatives (run_v0 --negatives adaptive)
     CATALOGUE_SECTIONS = True           # ... and selected per section: recommend_sections (run_v0 --sections)
     CATALOGUE_PAGING = True             # ... and paged through with a cursor: recommend_page / recommend_deep (run_v0 --recommend_deep)
+    CATALOGUE_EXPLAIN = True            # ... and split over the clicks of the history: explain (run_v0 --explain)
 
     def check_recommend_ids(self):
         """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read

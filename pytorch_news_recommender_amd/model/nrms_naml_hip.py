@@ -171,5 +171,10 @@ class Model(nrms_hip.Model):
         normed = self._engine.layernorm(self._flat, hist.reshape(B * H, F))
         return self._engine.encode_users(self._flat, normed.view(B, H, F), 0.0, 0, "user_eval")
 
+    def _catalogue_user_parts(self, hist, browsed=None):
+        B, H, F = hist.shape
+        normed = self._engine.layernorm(self._flat, hist.reshape(B * H, F))
+        return self._engine.user_parts(self._flat, normed.view(B, H, F))
+
     CATALOGUE_RETRIEVAL = False
 

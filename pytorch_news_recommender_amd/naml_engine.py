@@ -263,6 +263,12 @@ class NamlEngine(NRMSEngine):
         _lib.check(rc, "nrms_encoder_fwd(user)")
         return out
 
+    def user_parts(self, flat, x):
+        """encode_users' inference pass on buffers of its own -> (user [B, F], ctx [B, H, F], w [B, H]): user[b] = sum_h w[b, h]
+        ctx[b, h] (NRMSEngine.user_parts; the input of `attribution`)."""
+        B, H, F = x.shape
+        return (self.encode_users(flat, x, 0.0, 0, "user_parts"),) + self._parts_of("user_parts", B, H, F)
+
     def _slot_inputs(self, batch, sfx):
         """History slots then candidate slots: validated copies of the four id tensors."""
         d = self.dims

@@ -102,7 +102,30 @@ def build_parser():
     parser.add_argument('--sections', type=str, default=None, choices=('category', 'subcategory'), help='--recommend: write the front '
                         'page by section instead, the top K news of every category (or sub-category) per impression, as '
                         '"<impression> <section> [ids]" lines (models whose catalogue score is a plain dot product; not with --diversity)')
+    parser.add_argument('--explain', type=int, default=None, metavar='M', help='--recommend: also write, per recommended news, the M '
+                        "clicks of the user's history that contribute most to its score (1 <= M <= 8; model.explain), to "
+                        '<recommend_out>.reasons; reads the final ids only, so it goes with --diversity, --popularity_prior, '
+                        '--catalogue_window and --coarse_catalogue (not with --sections or --recommend_deep)')
     return parser
+
+
+def check_explain_args(args):
+    """--explain fails before any data is read or any step is trained: it explains the list of --recommend, M in [1, 8], and needs
+    a model whose score is one additive-attention sum over the clicks."""
+    if args.explain is None:
+        return
+    if args.recommend is None:
+        raise SystemExit('--explain M: explains the list of --recommend K (give --recommend)')
+    if not 1 <= args.explain <= 8:
+        raise SystemExit('--explain M: M must be in [1, 8] (got %d)' % args.explain)
+    if args.sections is not None:
+        raise SystemExit('--explain: explains the one list of --recommend K, not a list per section (drop --sections)')
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_EXPLAIN', False):
+        raise SystemExit('--explain: model %r cannot split a score over the clicks of the history (its score is no single '
+                         'additive-attention sum over them; nrms_v0 / nrms_v1 / nrms_naml / nrms_bert can)' % args.model)
 
 
 def check_sections_args(args):
@@ -322,6 +345,7 @@ def main(argv=None):
     check_recommend_args(args)
     check_sections_args(args)
     check_coarse_args(args)
+    check_explain_args(args)
     retrieval_ks = check_retrieval_args(args)
     check_prior_args(args)
     check_window_args(args)
@@ -401,6 +425,7 @@ def main(argv=None):
                           pin_memory=True)
 
     item_window = {}         # item_time / request_time / window_span with --catalogue_window, otherwise no keyword at all
+    explain = {} if args.explain is None else {'explain': args.explain}       # otherwise no keyword at all
     item_prior = {}          # item_bias = the click feed's popularity prior with --popularity_prior, otherwise no keyword at all
 
     def recommend_top(samples):
@@ -418,19 +443,19 @@ def main(argv=None):
                                       **item_prior)
         if args.coarse_catalogue:
             out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, coarse=True,
-                            coarse_shortlist=args.coarse_shortlist)
+                            coarse_shortlist=args.coarse_shortlist, **explain)
             st = (recommender.model if hasattr(recommender, 'model') else recommender).last_coarse_stats
             print('coarse catalogue: certified share: {:.4f}  users: {}'.format(st['certified'], st['n_users']))
             return out
         if args.diversity is None:
             return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
-                             **item_window)
+                             **item_window, **explain)
         # the plain list is the re-ranker's at lambda = 1 (bit for bit), which measures it with the same kernel
         net = recommender.model if hasattr(recommender, 'model') else recommender
         out = None
         for name, lam, dst in (('plain', 1.0, os.devnull), ('diversity %g' % args.diversity, args.diversity, args.recommend_out)):
             out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=dst, diversity=lam,
-                            shortlist=args.shortlist, **item_prior, **item_window)
+                            shortlist=args.shortlist, **item_prior, **item_window, **({} if dst == os.devnull else explain))
             st = net.last_recommend_stats
             print('{}: ILD@{}: {:.4f}  coverage: {:.4f}  users: {}'.format(name, args.recommend, st['ild'], st['coverage'],
                                                                             st['n_users']))
@@ -502,6 +527,8 @@ def main(argv=None):
         top_samples, top_labels = (held_samples, held_labels) if args.negatives in ('catalogue', 'adaptive') else (dev_samples, dev_labels)
         if (args.recommend is not None or args.recommend_deep is not None) and rank == 0:
             print('recommendations saved to', recommend_top(top_samples))
+            if args.explain is not None:
+                print('reasons saved to', (recommender.model if hasattr(recommender, 'model') else recommender).last_explain_file)
         if retrieval_ks is not None and rank == 0:
             retrieval_quality(top_samples, top_labels)
         return hist
@@ -520,6 +547,8 @@ def main(argv=None):
         print('saved to', out)
         if (args.recommend is not None or args.recommend_deep is not None) and rank == 0:
             print('recommendations saved to', recommend_top(test_samples))
+            if args.explain is not None:
+                print('reasons saved to', (recommender.model if hasattr(recommender, 'model') else recommender).last_explain_file)
         if retrieval_ks is not None and rank == 0:
             retrieval_quality(test_samples, dev_labels)
         return out

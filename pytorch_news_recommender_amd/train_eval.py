@@ -359,7 +359,7 @@ class _RequestWindows:
 
 def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
               shortlist=None, item_bias=None, item_time=None, request_time=None, window_span=None, coarse=False,
-              coarse_shortlist=None):
+              coarse_shortlist=None, explain=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
@@ -384,8 +384,29 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     coarse / coarse_shortlist: serve through ``model.recommend(coarse=...)``, the fp16 shortlist with a certificate: the catalogue
     is packed once after it is encoded (``model.pack_catalogue``), the file is the same, bit for bit, and the call leaves
     ``net.last_coarse_stats = {"certified": share of the users whose row the certificate covered, "n_users": users}`` (None
-    without ``coarse``, when the model is called exactly as before).  Not with diversity, item_bias or a time window (ValueError)."""
+    without ``coarse``, when the model is called exactly as before).  Not with diversity, item_bias or a time window (ValueError).
+
+    explain = m in [1, 8]: also writes ``<file name>.reasons`` and leaves its name in ``net.last_explain_file`` (None without
+    ``explain``, when the model is called and the list is written exactly as before; the list file is the same either way).  One
+    line per recommended news, in the order of the list file:
+    ``<impression index> <news id> <total> <padding share> [<browsed id>:<contribution>,...]``: ``model.explain`` of the ids every
+    path above ends with (so it goes with diversity, item_bias, a time window and coarse): the score without any item_bias, the
+    part of it carried by the history's padding slots, and the up to m clicks of the history with the largest contributions,
+    largest first, negative ones included.  Numbers are written with 9 significant digits, which names every float32: two runs
+    give the same bytes.  Needs a model with ``CATALOGUE_EXPLAIN`` (ValueError otherwise, before anything is encoded)."""
     net = _inner(model)
+    if explain is not None:
+        if not getattr(net, "CATALOGUE_EXPLAIN", False):
+            raise ValueError("recommend: explain needs a model whose score is one additive-attention sum over the clicks of the "
+                             "history (model.explain; CATALOGUE_EXPLAIN)")
+        if not 1 <= int(explain) <= 8:
+            raise ValueError("recommend: explain = m must be in [1, 8] (got %r)" % (explain,))
+    reasons = []
+
+    def note(datas, ids):
+        if explain is not None:
+            reasons.append([t.cpu() for t in (ids,) + tuple(net.explain(datas, ids, catalogue, int(explain))[:4])])
+
     prior = {} if item_bias is None else {"item_bias": item_bias}
     windows, done = _RequestWindows("recommend", item_time, request_time, window_span), 0
     if diversity is None and shortlist is not None:
@@ -408,6 +429,7 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
             n_cert += cert.sum()
             n_users += int(cert.shape[0])
             lines.extend(ids.cpu().tolist())
+            note(datas, ids)
         net.last_coarse_stats = {"certified": int(n_cert.item()) / n_users if n_users else float("nan"), "n_users": n_users}
     elif diversity is None:
         net.last_recommend_stats = None
@@ -418,6 +440,7 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
                 done += B
             ids, _ = net.recommend(datas, k, catalogue, exclude_history=exclude_history, **prior)
             lines.extend(ids.cpu().tolist())
+            note(datas, ids)
     else:
         rows, ilds = [], []
         for datas in data_iter:
@@ -429,6 +452,7 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
                                         shortlist=shortlist, return_ild=True, **prior)
             rows.append(ids)
             ilds.append(ild)
+            note(datas, ids)
         n_news = int(catalogue.shape[0])
         dev = catalogue.device
         ids = torch.cat(rows) if rows else torch.zeros(0, int(k), dtype=torch.int64, device=dev)
@@ -448,6 +472,19 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
         for i, row in enumerate(lines):
             f.write(str(i + 1) + ' ')
             f.write(str([n for n in row if n >= 0]).replace(' ', '') + '\n')
+    net.last_explain_file = None
+    if explain is not None:
+        net.last_explain_file = file_name + '.reasons'
+        with open(net.last_explain_file, 'w') as f:
+            i = 0
+            for ids, r_ids, r_contrib, total, pad in reasons:
+                for b in range(ids.shape[0]):
+                    i += 1
+                    for j, n in enumerate(ids[b].tolist()):
+                        if n < 0:
+                            continue
+                        why = ','.join('%d:%.9g' % (r, c) for r, c in zip(r_ids[b, j].tolist(), r_contrib[b, j].tolist()) if r >= 0)
+                        f.write('%d %d %.9g %.9g [%s]\n' % (i, n, float(total[b, j]), float(pad[b, j]), why))
     return file_name
 
 
