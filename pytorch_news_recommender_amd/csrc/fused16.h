@@ -69,8 +69,8 @@ __device__ __forceinline__ long frag_off(long seq_block, int c16, int s, int l32
     return (seq_block * c16 + s) * 512 + l32 * 16 + 8 * hh;
 }
 
-// ---- the weight-tile ring shared by the forward and the backward kernel: tile n lives in LDS slot n % 3; while
-// tile n is consumed, tile n + 2 travels global -> registers -> LDS.  One barrier per tile.
+// ---- the register-staged weight-tile ring (the pooling backward, the 64-row attention backward, fused16_v1_bwd.hip): tile n
+// lives in LDS slot n % 3; while tile n is consumed, tile n + 2 travels global -> registers -> LDS.  One barrier per tile.
 struct TileRing {
     char* smem;
     const _Float16* src;          // tiles are contiguous [n_tiles][32][F16_KP]
@@ -171,11 +171,12 @@ struct TileRingDMA {
     // be an over-estimate (0 is always safe).
     template <int YOUNGER = 0>
     __device__ __forceinline__ void step_barrier(int n) {
-        static_assert(YOUNGER == 0 || YOUNGER == 2 || YOUNGER == 4 || YOUNGER == 8, "add the immediate below");
+        static_assert(YOUNGER == 0 || YOUNGER == 2 || YOUNGER == 4 || YOUNGER == 6 || YOUNGER == 8, "add the immediate below");
         if (SLOTS == 3 && n + 2 < n_tiles) {
             if (YOUNGER == 0) __asm__ volatile("s_waitcnt vmcnt(5)" ::: "memory");
             if (YOUNGER == 2) __asm__ volatile("s_waitcnt vmcnt(7)" ::: "memory");
             if (YOUNGER == 4) __asm__ volatile("s_waitcnt vmcnt(9)" ::: "memory");
+            if (YOUNGER == 6) __asm__ volatile("s_waitcnt vmcnt(11)" ::: "memory");
             if (YOUNGER == 8) __asm__ volatile("s_waitcnt vmcnt(13)" ::: "memory");
         } else {
             __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -11,8 +11,16 @@
 // Every product whose contraction index sits in the REGISTERS of a 32x32 accumulator takes that accumulator as an
 // operand directly (acc_frag); where the contraction index sits on the LANES, the tile is first transposed by one
 // extra product with a (k-permuted) identity, which costs 2 MFMAs and no LDS traffic.
+// Weight tiles (prep16b_kernel builds them from this call's own weights): the attention kernel of the 32-row titles takes its
+// 3 h head tiles W'_q | W_k | W_v from the forward's LDS-DMA ring (TileRingDMA, fused16.h: tiles in dma_tile_pos order, no staging
+// registers, counted vmcnt + raw s_barrier, the ring running through a workgroup's groups); the pooling kernel (h tiles
+// Wadd_h^T), the 64-row attention kernel and the attention kernel under NRMS_BWD_ATTN_STAGED=1 stage row-major tiles through
+// registers (TileRing) -- the pooling loop issues stores behind every tile step, where the DMA ring measured slower
+// (docs/EXPERIMENTS.md).
 // Replaces autograd through model/nrms_v0.py:13-23,46-76,100-126,154-176,188-199 (`loss.backward()`, train_eval.py:126).
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "fused16_bwd.h"
 
@@ -275,10 +283,21 @@ __global__ __launch_bounds__(F16_THREADS, SB == 1 ? 8 / F16_WAVES : 1) void fuse
 // formed), cross-title entries of S^T masked by the additive bias -- so the recomputed Q | K | V tiles, the softmax and the
 // five gradient products serve two titles at once.  The shared row's dQ | dK | dV are the sums over the padding tokens: they
 // enter the bias gradients (column sums over the tile's rows) and are not stored (a padding token has no dX, no share of dW).
-template <int SB>
+//
+// DMA (SB = 1): the 3 h head tiles arrive by LDS-DMA on the forward's ring (TileRingDMA, fused16.h; btiles in dma_tile_pos order).
+// Tile n + 2 is requested piece by piece behind the MFMA groups of step n, a step ends with a counted vmcnt and a raw s_barrier, and
+// the ring runs THROUGH the group loop: the steps of a workgroup are numbered over all its groups, so tiles 0 and 1 of the next
+// group travel under the last head of this one.  hipcc answers the first use of an ordinary global load with a full drain of the
+// DMA queue, so the head loop has none: the two d(ctx)16 fragments of a head come by DMA too, into 2 KiB of LDS per wave (a lane
+// reads back the 16 bytes it requested), issued at the top of the head's Q step -- older than that step's tile pieces, so the
+// step's counted wait covers them -- and read in its V step.  The ordinary loads of a group's prologue (title lists, x16 rows) do
+// drain the queue: once per group, where tile 0 is needed at once anyway.
+// DMA = false: the register-staged TileRing (the 64-row kernel; NRMS_BWD_ATTN_STAGED=1).  Same products, same sums, same bits.
+template <int SB, bool DMA>
 __global__ __launch_bounds__(F16_THREADS, SB == 1 ? 8 / F16_WAVES : 1) void fused_bwd16_attn_kernel(Bwd16Args a) {
+    static_assert(!DMA || SB == 1, "the DMA ring serves the 32-row kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* red = reinterpret_cast<float*>(smem + 3 * F16_SLOT);
+    float* red = reinterpret_cast<float*>(smem + (DMA ? 3 * F16_SLOT_DMA : 3 * F16_SLOT));
     float* stg = red + B16_RED;                       // [2][F16_WAVES][3][32]: per-wave shares of d(b_q), d(b_k), d(b_v) of one head,
                                                       // double buffered over the head loop's barriers (no atomics: see the pool kernel)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -299,10 +318,24 @@ __global__ __launch_bounds__(F16_THREADS, SB == 1 ? 8 / F16_WAVES : 1) void fuse
         g_ne = (n_ne + F16_WAVES - 1) / F16_WAVES;
         if (SB == 1 && a.n_cls == 3) { n_sh = a.order_cnt[2]; g_pair = (n_sh + 2 * F16_WAVES - 1) / (2 * F16_WAVES); }
     }
-    TileRing ring;
-    ring.smem = smem; ring.src = a.btiles + (long)a.h * 32 * KP; ring.n_tiles = 3 * a.h; ring.tid = tid; ring.l32 = l32; ring.hh = hh; ring.dbg = 0;
+    typename std::conditional<DMA, TileRingDMA<3>, TileRing>::type ring;
+    ring.smem = smem; ring.src = a.btiles + (long)a.h * 32 * KP; ring.l32 = l32; ring.hh = hh;
+    const int n_head_tiles = 3 * a.h;
+    int st = 0;                                       // DMA: tile step of this workgroup, counted over all its groups (slot st % 3)
+    const char* dcl = nullptr;                        // DMA: this wave's d(ctx)16 landing area, [2][64 lanes][16 B]
+    if constexpr (DMA) {
+        const int n_grp = g_pair + g_ne;
+        ring.wave = wave; ring.lane = lane;
+        ring.n_tiles = (int)blockIdx.x < n_grp ? n_head_tiles * ((n_grp - 1 - (int)blockIdx.x) / (int)gridDim.x + 1) : 0;
+        dcl = reinterpret_cast<const char*>(stg + 2 * F16_WAVES * 3 * 32) + wave * 2048;
+        if (ring.n_tiles > 0) { ring.load_at(0, 0); ring.load_at(1, 1); }            // (3 h >= 3 tiles)
+    } else {
+        ring.n_tiles = n_head_tiles; ring.tid = tid; ring.dbg = 0;
+    }
+    // DMA: the tile requested behind the MFMAs of the current step -- two steps ahead, wrapping into the next group's tiles
+    auto tile2 = [&](int n) { return n + 2 < n_head_tiles ? n + 2 : n + 2 - n_head_tiles; };
     const h8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-    __syncthreads();
+    __syncthreads();                                  // (DMA: red is zero; the first tiles are awaited in front of the head loop)
 #pragma unroll 1
     for (int grp = blockIdx.x; grp < g_pair + g_ne; grp += gridDim.x) {
         const bool pair = SB == 1 && grp < g_pair;                      // uniform over the workgroup
@@ -348,8 +381,10 @@ __global__ __launch_bounds__(F16_THREADS, SB == 1 ? 8 / F16_WAVES : 1) void fuse
             }
             kbias[r] = bsv;
         }
-        ring.load(0); ring.store(0);
-        ring.load(1); ring.store(1);
+        if constexpr (!DMA) {
+            ring.load(0); ring.store(0);
+            ring.load(1); ring.store(1);
+        }
         int n = 0;
         bool tok_ok[SB];
         long drow[SB];                                                  // x16 / dqkv16 row of this lane's token, -1: none
@@ -375,50 +410,87 @@ __global__ __launch_bounds__(F16_THREADS, SB == 1 ? 8 / F16_WAVES : 1) void fuse
                 for (int s = 0; s < F16_KS; ++s) xf[b][s] = z8;
             }
         }
-        __syncthreads();
+        // DMA: the stores this wave issues behind the V step's tile pieces (dV, dK, dQ: two each) are counted exactly at that step's
+        // wait -- they are issued if and only if one of its lanes owns a dqkv16 row
+        const bool has_rows = DMA && live && __ballot(drow[0] >= 0) != 0ull;
+        // the requests of one tile step: pieces behind the MFMA groups (pre), or all five at once by a wave without a title
+        auto pre = [&](int g) {
+            if constexpr (DMA) { if (st + 2 < ring.n_tiles) ring.load_piece_at(st + 2, tile2(n), g); }
+        };
+        auto idle_step = [&]() {
+            if constexpr (DMA) { if (!live && st + 2 < ring.n_tiles) ring.load_at(st + 2, tile2(n)); }
+        };
+        if constexpr (DMA) {
+            // the prologue's loads and tiles st, st + 1 have landed (the latter for every wave after the barrier).  The wait is the
+            // BUILTIN (vmcnt(0), gfx9 encoding): see fused_fwd16_kernel -- hipcc's wait-count pass does not see inline assembly and
+            // would put a vmcnt(0) for the x fragments in front of every tile's first MFMA
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        } else {
+            __syncthreads();
+        }
 #pragma unroll 1
         for (int head = 0; head < a.h; ++head) {
             // d(ctx)^T of this head as operand fragments (rows f = k); zero beyond the sequence
             h8 dc[SB][2];
+            if constexpr (DMA) {
+                if (live) {                             // lands in this wave's area: awaited with the Q step's tile, read in the V step
+                    const _Float16* dcsrc = a.dctx16 + (pair ? frag_off((long)myseq, F16_CS, 2 * head, myr, hh)
+                                                             : frag_off((long)seq, F16_CS, 2 * head, l32, hh));
 #pragma unroll
-            for (int b = 0; b < SB; ++b) {
-                // pair: column myr of title myp's COMPRESSED d(ctx) (fused_bwd16_pool_kernel); a missing second title: zeros
-                const _Float16* dcsrc = (SB == 1 && pair) ? a.dctx16 + frag_off((long)myseq, F16_CS, 2 * head, myr, hh)
-                                                          : a.dctx16 + frag_off((long)seq * SB + b, F16_CS, 2 * head, l32, hh);
-                dc[b][0] = *reinterpret_cast<const h8*>(dcsrc);             // (zeros beyond the sequence)
-                dc[b][1] = *reinterpret_cast<const h8*>(dcsrc + 512);
-                if (SB == 1 && pair && !myval) { dc[b][0] = z8; dc[b][1] = z8; }
+                    for (int i = 0; i < 2; ++i)
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(dcsrc + 512 * i),
+                                                         (__attribute__((address_space(3))) void*)(const_cast<char*>(dcl) + 1024 * i), 16, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < SB; ++b) {
+                    // pair: column myr of title myp's COMPRESSED d(ctx) (fused_bwd16_pool_kernel); a missing second title: zeros
+                    const _Float16* dcsrc = (SB == 1 && pair) ? a.dctx16 + frag_off((long)myseq, F16_CS, 2 * head, myr, hh)
+                                                              : a.dctx16 + frag_off((long)seq * SB + b, F16_CS, 2 * head, l32, hh);
+                    dc[b][0] = *reinterpret_cast<const h8*>(dcsrc);             // (zeros beyond the sequence)
+                    dc[b][1] = *reinterpret_cast<const h8*>(dcsrc + 512);
+                    if (SB == 1 && pair && !myval) { dc[b][0] = z8; dc[b][1] = z8; }
+                }
             }
             // ---- tiles W'_q, W_k, W_v: Q^T, K^T, V^T [f][tok], kept as operand fragments only (bias: the ones column)
             h8 qf[SB][2], kf[SB][2], vf[SB][2];
-            ring.load(n + 2);
+            if constexpr (DMA) idle_step(); else ring.load(n + 2);
 #pragma unroll
             for (int b = 0; b < SB; ++b) {
                 f32x16 t = zero16();
-                if (live) tile_mma<true>(t, ring, n, xf[b]);
+                if constexpr (DMA) { if (live) tile_mma<true>(t, ring, st, xf[b], pre); }
+                else { if (live) tile_mma<true>(t, ring, n, xf[b]); }
                 qf[b][0] = acc_frag(t, 0); qf[b][1] = acc_frag(t, 1);
             }
-            ring.store(n + 2);
-            __syncthreads();
+            if constexpr (DMA) { ring.step_barrier(st); ++st; } else { ring.store(n + 2); __syncthreads(); }
             ++n;
-            ring.load(n + 2);
+            if constexpr (DMA) idle_step(); else ring.load(n + 2);
 #pragma unroll
             for (int b = 0; b < SB; ++b) {
                 f32x16 t = zero16();
-                if (live) tile_mma<true>(t, ring, n, xf[b]);
+                if constexpr (DMA) { if (live) tile_mma<true>(t, ring, st, xf[b], pre); }
+                else { if (live) tile_mma<true>(t, ring, n, xf[b]); }
                 kf[b][0] = acc_frag(t, 0); kf[b][1] = acc_frag(t, 1);
             }
-            ring.store(n + 2);
-            __syncthreads();
+            if constexpr (DMA) { ring.step_barrier(st); ++st; } else { ring.store(n + 2); __syncthreads(); }
             ++n;
-            ring.load(n + 2);
+            if constexpr (DMA) {
+                idle_step();
+                dc[0][0] = *reinterpret_cast<const h8*>(dcl + lane * 16);           // (zeros beyond the sequence)
+                dc[0][1] = *reinterpret_cast<const h8*>(dcl + 1024 + lane * 16);
+                if (pair && !myval) { dc[0][0] = z8; dc[0][1] = z8; }
+            } else {
+                ring.load(n + 2);
+            }
 #pragma unroll
             for (int b = 0; b < SB; ++b) {
                 f32x16 t = zero16();
-                if (live) tile_mma<true>(t, ring, n, xf[b]);
+                if constexpr (DMA) { if (live) tile_mma<true>(t, ring, st, xf[b], pre); }
+                else { if (live) tile_mma<true>(t, ring, n, xf[b]); }
                 vf[b][0] = acc_frag(t, 0); vf[b][1] = acc_frag(t, 1);
             }
-            ring.store(n + 2);
+            if constexpr (!DMA) ring.store(n + 2);
             // column sums of dQ', dK, dV (= of d(ctx)) over this title's rows go to this wave's staging row as soon as they
             // are complete (short live ranges: the kernel sits at the 256-register limit); a wave without a live title adds zeros
             float* srow = stg + (((head & 1) * F16_WAVES + wave) * 3) * 32 + l32;
@@ -547,7 +619,13 @@ __global__ __launch_bounds__(F16_THREADS, SB == 1 ? 8 / F16_WAVES : 1) void fuse
                 sq += __shfl_xor(sq, 32, 64);
                 if (hh == 0) srow[0] = sq;
             }
-            __syncthreads();
+            // the staging rows are published by an LDS wait and a barrier; DMA: no drain of this head's stores, nor of tile n + 2
+            if constexpr (DMA) {
+                if (has_rows) ring.template step_barrier<6>(st); else ring.step_barrier(st);
+                ++st;
+            } else {
+                __syncthreads();
+            }
             if (tid < 96) {                                               // fixed order: waves ascending
                 float sum = 0.f;
 #pragma unroll
@@ -566,7 +644,9 @@ __global__ __launch_bounds__(F16_THREADS, SB == 1 ? 8 / F16_WAVES : 1) void fuse
                 }
             }
         }
-        __syncthreads();                                          // the ring restarts: nobody may still read a slot
+        // TileRing: the ring restarts, nobody may still read a slot.  DMA: the ring goes on -- the last step's barrier has every
+        // wave past its reads of the slot that the next group's first step refills
+        if constexpr (!DMA) __syncthreads();
     }
     __syncthreads();
     float* out = a.red + (long)blockIdx.x * B16_RED;
@@ -659,7 +739,9 @@ struct Prep16bArgs {
     const float* w_add;   // [q][d]
     const float* q_vec;   // [q]
     float* bqkv32;        // [3h][32] (Q part pre-scaled)
-    _Float16* btiles;     // [4h][32][KP]
+    _Float16* btiles;     // [4h][32][KP]: h tiles Wadd_h^T in padded-row order, then 3h head tiles -- in the LDS-DMA order of
+                          // fused16.h (dma_tile_pos, as prep16_kernel's wqkv16) when dma_tiles is set, else row-major too
+    int dma_tiles;
     _Float16* xtiles;     // dX GEMM (gemm16_dx_kernel): [DX_SLABS][4 k-steps][10 n-tiles][lane half][32 n][8 k]: the operand
                           // fragments of W' (rows = dqkv16 columns, 64 per slab; columns = input features) in the order a
                           // wave reads them -- one contiguous KiB per (k-step, n-tile), filled by LDS-DMA
@@ -674,14 +756,20 @@ __global__ __launch_bounds__(256) void prep16b_kernel(Prep16bArgs a) {
     const long n1 = (long)4 * a.h * 32 * KP, n2 = (long)30 * 32 * KP, n3 = F16_QP, n4 = (long)3 * a.h * 32;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n1 + n2 + n3 + n4; i += (long)gridDim.x * blockDim.x) {
         if (i < n1) {
-            const int c = (int)(i % KP);
+            int c = (int)(i % KP);
             const long r = i / KP;
-            const int f = (int)(r & 31), tile = (int)(r >> 5);
+            int f = (int)(r & 31);
+            const int tile = (int)(r >> 5);
             float v = 0.f;
             if (tile < a.h) {                                   // Wadd_h^T: row f, column q (natural order)
                 const int head = tile;
                 if (f < a.dk && c < a.q) v = a.w_add[(long)c * a.d + head * a.dk + f];
             } else {
+                if (a.dma_tiles) {                              // position p of the tile holds (row, column) with dma_tile_pos(row, column) = p:
+                    const int p = (int)(i - (long)tile * 32 * KP);      // walked in memory order, so that the stores stay coalesced
+                    f = (p >> 3) & 31;
+                    c = (p >> 8) * 8 + (p & 7);
+                }
                 const int t3 = tile - a.h, head = t3 / 3, which = t3 - 3 * head;
                 if (f < a.dk && c < a.d)
                     v = a.w_qkv[((long)which * a.d + head * a.dk + f) * a.d + c] * (which == 0 ? qscale : 1.0f);
@@ -1186,6 +1274,13 @@ int launch_tn16(int geom, const _Float16* A, int lda, int N, const _Float16* B, 
     return check_launch("tn16_reduce");
 }
 
+// the attention kernel on the DMA ring: ring + column sums + its staging rows + 2 KiB per wave for a head's d(ctx)16 fragments
+// (76.5 KB: two workgroups per CU inside the 160 KB)
+static size_t bwd16_attn_dma_lds() {
+    return (size_t)3 * F16_SLOT_DMA + (size_t)B16_RED * 4 + (size_t)2 * F16_WAVES * 3 * 32 * 4 + (size_t)F16_WAVES * 2048;
+}
+static_assert(2 * (3 * F16_SLOT_DMA + B16_RED * 4 + 2 * F16_WAVES * 3 * 32 * 4 + F16_WAVES * 2048) <= 160 * 1024, "two workgroups per CU");
+
 size_t bwd16_fused_lds(bool two) {
     // ring + column sums + the per-wave staging rows of the atomic-free reductions (the pooling kernel's are the larger)
     static_assert(F16_WAVES * 2 * F16_QT * 32 + 2 * F16_WAVES * 32 >= 2 * F16_WAVES * 3 * 32, "the attention kernel's staging fits the same size");
@@ -1277,10 +1372,15 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
     hipStream_t s_add = side ? ss->s[0] : stream, s_qkv = side ? ss->s[1] : stream;
     SideJoinGuard join_guard(ss, stream);
     const int Mp = f.n_seq * 32 * (f.S > 32 ? 2 : 1);         // fragment order: 32 rows per block, zero beyond a sequence
+    // the 32-row attention kernel takes its head tiles from the LDS-DMA ring (NRMS_BWD_ATTN_STAGED=1: A/B switch, read per call --
+    // the register-staged ring and its row-major tiles; the 64-row kernel always)
+    const char* staged_env = getenv("NRMS_BWD_ATTN_STAGED");
+    const bool attn_dma = f.S <= 32 && !(staged_env != nullptr && atoi(staged_env) != 0);
     {
         Prep16bArgs p{};
         p.d = f.d; p.h = f.h; p.dk = dk; p.q = f.q; p.w_qkv = f.w_qkv; p.b_qkv = f.b_qkv; p.w_add = f.w_add; p.q_vec = f.q_vec;
         p.btiles = btiles; p.xtiles = xtiles; p.qv16 = qv16; p.bqkv32 = bqkv32;
+        p.dma_tiles = attn_dma ? 1 : 0;
         p.max_bits = (unsigned*)(sc + 2);                       // (in place of a memset in front of absmax_kernel)
         TimingScope ts("prep16", stream);
         hipLaunchKernelGGL(prep16b_kernel, dim3(2048), dim3(256), 0, stream, p);
@@ -1313,8 +1413,9 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
     const int n_wg = a.n_groups < L.n_wg ? a.n_groups : L.n_wg;
     {
         const bool two = f.S > 32;
-        const size_t lds = bwd16_fused_lds(two);
-        const void* fa = two ? (const void*)fused_bwd16_attn_kernel<2> : (const void*)fused_bwd16_attn_kernel<1>;
+        const size_t lds = attn_dma ? bwd16_attn_dma_lds() : bwd16_fused_lds(two);
+        const void* fa = two ? (const void*)fused_bwd16_attn_kernel<2, false>
+                             : attn_dma ? (const void*)fused_bwd16_attn_kernel<1, true> : (const void*)fused_bwd16_attn_kernel<1, false>;
         const hipError_t e = hipFuncSetAttribute(fa, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { set_error("fused_bwd16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return NRMS_ELAUNCH; }
         {
@@ -1334,8 +1435,9 @@ int launch_fused_bwd16(const Fused16Bwd& f, hipStream_t stream) {
         b.red = red + (long)n_wg * B16_RED;                       // second set of per-workgroup sums
         {
             TimingScope ts(two ? "fused64_bwd16_attn" : "fused_bwd16_attn", stream);
-            if (two) hipLaunchKernelGGL(fused_bwd16_attn_kernel<2>, dim3(n_wg), dim3(F16_THREADS), lds, stream, b);
-            else hipLaunchKernelGGL(fused_bwd16_attn_kernel<1>, dim3(n_wg), dim3(F16_THREADS), lds, stream, b);
+            if (two) hipLaunchKernelGGL((fused_bwd16_attn_kernel<2, false>), dim3(n_wg), dim3(F16_THREADS), lds, stream, b);
+            else if (attn_dma) hipLaunchKernelGGL((fused_bwd16_attn_kernel<1, true>), dim3(n_wg), dim3(F16_THREADS), lds, stream, b);
+            else hipLaunchKernelGGL((fused_bwd16_attn_kernel<1, false>), dim3(n_wg), dim3(F16_THREADS), lds, stream, b);
         }
         int rc = check_launch("fused_bwd16");
         if (rc) return rc;

@@ -18,7 +18,7 @@ TIMER_OF = [("user64_fwd_kernel", "user64_fwd"), ("user64_bwd_kernel", "user64_b
             ("fused_fwd16v1_kernel", "fused_fwd16"), ("fused_bwd16v1_attn_kernel", "fused_bwd16_attn"), ("gemm16_tn_kernel<true, 4", "dwo_bwd"),
             ("fused_fwd16p_kernel", "fused_fwd16"), ("fused_fwd16_kernel<true, 1>", "fused_fwd16"), ("fused_fwd16_kernel<true, 2>", "fused64_fwd16"),
             ("fused_bwd16_pool_kernel<1>", "fused_bwd16_pool"), ("fused_bwd16_pool_kernel<2>", "fused64_bwd16_pool"),
-            ("fused_bwd16_attn_kernel<1>", "fused_bwd16_attn"), ("fused_bwd16_attn_kernel<2>", "fused64_bwd16_attn"),
+            ("fused_bwd16_attn_kernel<1,", "fused_bwd16_attn"), ("fused_bwd16_attn_kernel<2,", "fused64_bwd16_attn"),
             ("gemm16_tn_kernel<true", "dwadd_bwd"), ("gemm16_tn_kernel<false", "dwqkv_bwd"),
             ("gemm16_dx_kernel", "dx_bwd"), ("gather16_kernel", "gather_dropout"), ("scatter_grouped_kernel", "scatter_dropout"),
             ("adam_kernel", "adam"), ("attn_bwd", "attn_bwd"), ("attn_fwd", "attn_fwd"),
