@@ -705,6 +705,54 @@ int nrms_softmax_sample_dot(int32_t B, int64_t N, int32_t d, int32_t S, const fl
 int nrms_softmax_sample_noise(int32_t B, int64_t N, const int64_t* row_key /* [B] */, uint64_t seed,
                               uint32_t* words /* [B, N], nullable */, float* gumbel /* [B, N], nullable */, void* stream);
 
+/* ---- The exact log-partition of the served softmax over the whole catalogue (csrc/lsedot.hip; evaluation and calibration: "how
+ * much probability does the model put on this news?"; PARITY UNPINNED, the reference scores shown candidates only) ----
+ * For each user b < B and each of J variants j: lse(b, j) = log sum over the eligible n of exp(z_j(b, n)), never forming the
+ * [B, N] score matrix; the dot product, the expensive part, is shared by the J variants.  user [B, d], items [N, d] fp32 row-major;
+ * bias [N] fp32, 4-byte aligned, NULLABLE (the prior of nrms_topk_dot_biased); inv_temperature [J] and bias_scale [J] (nullable =
+ * all 1) are HOST arrays, read before the call returns; exclude [B, n_exclude] int64, nullable, as nrms_topk_dot's (duplicates and
+ * ids outside [0, N) are ignored); lse [B, J] fp32; zmax [B, J] fp32 and n_eligible [B, J] int32, each nullable.
+ * Score.  s(b, n) is nrms_topk_dot's chain for (user row, item row): the bits of nrms_topk_dot / nrms_rank_dot.
+ * Logit.  z_j(b, n) = fmaf(s(b, n), inv_temperature[j], c_j(n)) in fp32; c_j(n) = bias_scale[j] * bias[n], one fp32 multiply, and
+ *   +0.0 when bias is NULL.  inv_temperature[j] finite and >= 0 (0: the uniform distribution), bias_scale[j] finite.
+ * Eligible (for variant j): n is not in exclude[b, :] and z_j(b, n) is not NaN.  So a NaN bias[n] removes item n for everybody
+ *   (nrms_topk_dot_biased's block-list rule), a NaN score removes the pair, and so does a 0 * inf product (inv_temperature 0 and
+ *   an infinite score, bias_scale 0 and an infinite bias).  A z of -inf stays eligible and contributes 0.  Exclusion is applied
+ *   BEFORE the maximum and the sum, never taken back out afterwards: an excluded item, however high it scores, leaves no trace.
+ * Output.  n_eligible(b, j) = the number of eligible pairs.  zmax(b, j) = the exact maximum of the eligible z_j, -inf when there
+ *   is none, -0.0 returned as +0.0.  lse(b, j) = zmax + log(sum over eligible of exp(z_j - zmax)); -inf when nothing is eligible
+ *   or zmax = -inf; +inf when zmax = +inf.
+ * Reduction.  t = expf(z_j - zmax) lies in [0, 1] and is added up in fixed point, unit 2^-63, in two unsigned 64-bit limbs:
+ *   hi += floor(t 2^31), lo += floor(frac(t 2^31) 2^32), by integer atomics.  Every fp32 t >= 2^-40 enters exactly, a smaller one
+ *   truncated by less than 2^-63, and neither limb can overflow for N <= 0x7FFF0000.  The maximum term is expf(0) = 1, so
+ *   mass = hi 2^-31 + lo 2^-63 >= 1 and the accumulation itself is short of the exact sum of the t by less than N 2^-63, which
+ *   is below 2^-32 relative for every N.  lse = (float)((double) zmax + log(mass)) in fp64, rounded once.  What remains is the
+ *   error of expf itself (docs/EXPERIMENTS.md measures it).
+ * Invariance.  Integer addition is associative and a maximum is order-free, so lse, zmax and n_eligible of (b, j) are a pure
+ *   function of user row b, the multiset of its eligible z_j and variant j's two parameters, bit for bit: not of B or the row's
+ *   position, of the other rows or variants, of N when the extra rows are ineligible, of the order of the catalogue rows, of the
+ *   launch geometry, of what the workspace held, or of the run.
+ * Limits: 1 <= J <= 8, d >= 1, 0 <= N <= 0x7FFF0000, B >= 0, n_exclude >= 0; B = 0 is a no-op, N = 0 writes lse = zmax = -inf and
+ *   n_eligible = 0.  Arguments outside the limits return NRMS_EINVAL with a message that names the argument ("logsumexp_dot: ...").
+ * Workspace: nrms_logsumexp_dot_workspace_bytes(B, N, d, J, n_exclude) bytes, 8-byte aligned, O(B * J) (0 = arguments rejected);
+ *   a smaller one returns NRMS_EWORKSPACE.
+ * Four kernels on `stream` (init, the maxima, the masses, finish: two scans of the catalogue), no host synchronisation, no
+ *   allocation; plain vector loads and stores, integer atomics only (LDS or, add and global max, add), no float atomics. */
+size_t nrms_logsumexp_dot_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t J, int32_t n_exclude);
+int nrms_logsumexp_dot(int32_t B, int64_t N, int32_t d, int32_t J, const float* user /* [B, d] */, const float* items /* [N, d] */,
+                       const float* bias /* [N], nullable */, const float* inv_temperature /* [J] host */,
+                       const float* bias_scale /* [J] host, nullable = all 1 */,
+                       const int64_t* exclude /* [B, n_exclude], nullable */, int32_t n_exclude, float* lse /* [B, J] */,
+                       float* zmax /* [B, J], nullable */, int32_t* n_eligible /* [B, J], nullable */, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* Test hook, like nrms_softmax_sample_noise: the raw integer mass of nrms_logsumexp_dot, mass[b, j] = (hi, lo) as above (the same
+ * kernels; one item at the maximum weighs NRMS_LSE_MASS_ONE in hi and 0 in lo; all 0 where lse is infinite).  Same arguments,
+ * workspace and errors ("logsumexp_dot_mass: ..."). */
+#define NRMS_LSE_MASS_ONE 0x80000000ull
+int nrms_logsumexp_dot_mass(int32_t B, int64_t N, int32_t d, int32_t J, const float* user, const float* items, const float* bias,
+                            const float* inv_temperature, const float* bias_scale, const int64_t* exclude, int32_t n_exclude,
+                            uint64_t* mass /* [B, J, 2] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Diversified re-ranking of a shortlist (csrc/mmr.hip; serving: "which k of these M candidates, so that the list is not k
  * articles about one story?"; PARITY UNPINNED, the reference has no such step) ----
  * For each user b < B: k entries of the row's shortlist, picked greedily by maximal marginal relevance (Carbonell & Goldstein),

@@ -200,7 +200,12 @@ SIGNATURES = {
     "nrms_attribution_dot": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11
                              + [C.c_size_t, C.c_void_p]),
     "nrms_softmax_sample_noise": (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nrms_hier_query": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 10 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "nrms_logsumexp_dot_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "nrms_logsumexp_dot": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]
+                           + [C.c_void_p] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nrms_logsumexp_dot_mass": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]
+                                + [C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nrms_hier_query":(C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 10 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "nrms_dropout_keep_mask": (C.c_int, [C.c_uint64, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_void_p,
                                          C.c_void_p]),
     "nrms_layernorm_fwd": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,

@@ -1022,7 +1022,55 @@ class NRMSEngine:
         _lib.check(rc, "nrms_softmax_sample_dot")
         return (ids, keys) if return_keys else ids
 
-    MMR_WORKSPACE_CAP = 256 << 20       # bytes of Gram workspace per nrms_mmr_rerank call: larger batches go in row chunks
+    def log_partition(self, user_vec, items, inv_temperature, exclude=None, bias=None, bias_scale=None, return_mass=False):
+        """user_vec [B, d], items [N, d] fp32, exclude [B, n_exclude] int64 or None, bias [N] fp32 or None (device, contiguous);
+        inv_temperature: a float or a sequence of J <= 8 floats, each finite and >= 0; bias_scale: None (all 1) or J finite
+        floats -> (lse [B, J] fp32, zmax [B, J] fp32, n_eligible [B, J] int32): per user and variant j the exact
+        log sum over the eligible items of exp(fmaf(user . item, inv_temperature[j], bias_scale[j] * bias[n])), its largest
+        logit and the number of eligible items, no [B, N] matrix, one pass pair over the catalogue for all J variants
+        (nrms_logsumexp_dot).  Excluded ids never enter the maximum or the sum; a NaN bias removes the item for every user.
+        A row's result is bit for bit a function of its user vector, its eligible logits and the variant's parameters.
+        return_mass (the test hook nrms_logsumexp_dot_mass): the raw integer mass [B, J, 2] int64 instead.
+        include/nrms_hip.h states the contract."""
+        who = "log_partition"
+        dev = self._cuda_device()
+        self._check_tensor(who, "user_vec", user_vec, torch.float32, 2)
+        self._check_tensor(who, "items", items, torch.float32, 2)
+        B, d = user_vec.shape
+        N = items.shape[0]
+        if items.shape[1] != d:
+            raise _lib.NrmsError("%s: items width %d != user_vec width %d" % (who, items.shape[1], d))
+        exclude, n_ex = self._exclude_arg(who, exclude, B)
+        if bias is not None:
+            self._item_bias(who, bias, N, dev)
+        inv_t = [float(v) for v in (inv_temperature if hasattr(inv_temperature, "__len__") else [inv_temperature])]
+        J = len(inv_t)
+        scale = None if bias_scale is None else [float(v) for v in (bias_scale if hasattr(bias_scale, "__len__") else [bias_scale])]
+        if scale is not None and len(scale) != J:
+            raise _lib.NrmsError("%s: bias_scale has %d entries for %d inv_temperature" % (who, len(scale), J))
+        nbytes = self.lib.nrms_logsumexp_dot_workspace_bytes(B, N, d, J, n_ex)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, J=%d; 1 <= J <= 8)" % (who, B, N, d, J))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        it_arr = (C.c_float * J)(*inv_t)
+        sc_arr = None if scale is None else (C.c_float * J)(*scale)
+        if return_mass:
+            mass = torch.empty(B, J, 2, dtype=torch.int64, device=self.device)
+            rc = self.lib.nrms_logsumexp_dot_mass(B, C.c_int64(N), d, J, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias), it_arr,
+                                                  sc_arr, _lib.ptr(exclude), n_ex, _lib.ptr(mass), _lib.ptr(ws),
+                                                  C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_logsumexp_dot_mass")
+            return mass
+        lse = torch.empty(B, J, dtype=torch.float32, device=self.device)
+        zmax = torch.empty(B, J, dtype=torch.float32, device=self.device)
+        n_el = torch.empty(B, J, dtype=torch.int32, device=self.device)
+        rc = self.lib.nrms_logsumexp_dot(B, C.c_int64(N), d, J, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias), it_arr, sc_arr,
+                                         _lib.ptr(exclude), n_ex, _lib.ptr(lse), _lib.ptr(zmax), _lib.ptr(n_el), _lib.ptr(ws),
+                                         C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_logsumexp_dot")
+        return lse, zmax, n_el
+
+    MMR_WORKSPACE_CAP = 256 << 20      # bytes of Gram workspace per nrms_mmr_rerank call: larger batches go in row chunks
 
     def mmr_rerank(self, items, short_ids, short_scores, k, lam, return_value=False, return_ild=False):
         """items [N, d] fp32, short_ids [B, M] int64, short_scores [B, M] fp32 (device, contiguous; e.g. top_k's output at

@@ -259,6 +259,15 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: recommend_sections is not available: a candidate's score depends on its neighbours in "
                                   "the click graph, not on a catalogue row alone (no recommend either)")
 
+    CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
+
+    def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,
+                      return_stats=False):
+        raise NotImplementedError("graph: log_partition is not available: a candidate's score depends on its neighbours in the click graph, so there is no softmax over one dot product per user to normalise (no recommend either)")
+
+    def log_prob(self, batch, targets, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None):
+        raise NotImplementedError("graph: log_prob is not available: a candidate's score depends on its neighbours in the click graph, so there is no softmax over one dot product per user to normalise (no recommend either)")
+
     CATALOGUE_EXPLAIN = False
 
     def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):

@@ -384,6 +384,15 @@ class Model(FlatHipModel):
                                   "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_topk_sections_dot scores every "
                                   "section with one user row")
 
+    CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
+
+    def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,
+                      return_stats=False):
+        raise NotImplementedError("hierec: log_partition is not available: HieRec scores the catalogue with a query per (topic, sub-topic) group, so there is no single softmax over one dot product per user to normalise")
+
+    def log_prob(self, batch, targets, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None):
+        raise NotImplementedError("hierec: log_prob is not available: HieRec scores the catalogue with a query per (topic, sub-topic) group, so there is no single softmax over one dot product per user to normalise")
+
     CATALOGUE_EXPLAIN = False
 
     def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):

@@ -80,6 +80,35 @@ def _load_table(config, pretrained_word_embedding):
     return torch.as_tensor(np.asarray(pretrained_word_embedding, dtype=np.float32)).clone()
 
 
+def _fma32(a, b, c):
+    """The correctly rounded fp32 a * b + c of float32 tensors, on their device: the product is exact in float64, and the one
+    case in which rounding the float64 sum to fp32 differs from rounding the exact value (the sum sits on a fp32 midpoint the
+    exact value is not on) is decided by the sum's error term (TwoSum)."""
+    a, b, c = torch.broadcast_tensors(a.double(), b.double(), c.double())
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    tie = torch.isfinite(s) & torch.isfinite(err) & (err != 0) & ((s.contiguous().view(torch.int64) & 0x1FFFFFFF) == 0x10000000)
+    toward = torch.where(err > 0, torch.full_like(s, float("inf")), torch.full_like(s, float("-inf")))
+    return torch.where(tie, torch.nextafter(s, toward), s).float()
+
+
+def _target_log_prob(ranks, scores, rows, lse, inv_t, scale, bias):
+    """log_prob's last step: ranks, scores [B, T] of rank_of (no prior), rows [B, T] the targets' rows, lse [B, J] ->
+    [B, T, J] fp32, fmaf(score, inv_t[j], scale[j] * bias[row]) - lse[b, j], NaN where the rank is 0."""
+    dev = scores.device
+    it = torch.tensor(inv_t, dtype=torch.float32, device=dev)
+    if bias is None:
+        c = torch.zeros((), dtype=torch.float32, device=dev)
+    else:
+        sc = torch.tensor([1.0] * len(inv_t) if scale is None else scale, dtype=torch.float32, device=dev)
+        c = bias[rows.clamp(0, bias.shape[0] - 1)].unsqueeze(-1) * sc          # one fp32 multiply, as in the kernel
+    z = _fma32(scores.unsqueeze(-1), it, c)
+    out = z - lse.unsqueeze(1)
+    return torch.where((ranks > 0).unsqueeze(-1), out, torch.full_like(out, float("nan")))
+
+
 def _ids_on(dev, x):
     """Word ids on the device: int32 feeds stay int32 over PCIe (the library validates either width into its own
     int64 copy), anything else becomes the reference's int64."""
@@ -508,6 +537,65 @@ class Model(FlatHipModel):
         return torch.where(ids >= 0, ids + 1, ids)
 
     @staticmethod
+    def _likelihood_variants(who, temperature, bias_scale, item_bias):
+        """(inv_temperature [J], bias_scale [J] or None) of log_partition / log_prob from their ``temperature`` / ``bias_scale``."""
+        temps = [float(t) for t in (temperature if hasattr(temperature, "__len__") else [temperature])]
+        if not 1 <= len(temps) <= 8:
+            raise _lib.NrmsError("%s: temperature must be a float or 1 .. 8 floats (got %d)" % (who, len(temps)))
+        for t in temps:
+            if not t > 0.0:          # (refuses NaN too; inf is the uniform distribution)
+                raise _lib.NrmsError("%s: every temperature must be > 0 (inf: the uniform distribution); got %r" % (who, t))
+        inv_t = [0.0 if np.isinf(t) else 1.0 / t for t in temps]
+        if bias_scale is None:
+            return inv_t, None
+        if item_bias is None:
+            raise _lib.NrmsError("%s: bias_scale scales item_bias (give item_bias)" % who)
+        scale = [float(v) for v in (bias_scale if hasattr(bias_scale, "__len__") else [bias_scale] * len(temps))]
+        if len(scale) != len(temps) or not all(np.isfinite(v) for v in scale):
+            raise _lib.NrmsError("%s: bias_scale must be one finite float per temperature (got %r for %d temperatures)"
+                                 % (who, bias_scale, len(temps)))
+        return inv_t, scale
+
+    @torch.no_grad()
+    def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,
+                      return_stats=False):
+        """The log-partition of the served softmax over the whole catalogue -> lse [B, J] fp32 (with return_stats: (lse, zmax
+        [B, J] fp32, n_eligible [B, J] int32)): lse[b, j] = log sum over the news user b could be recommended of
+        exp(score / temperature[j] + bias_scale[j] * item_bias[id]), exactly and without a [B, N] matrix, all J variants in one
+        pass pair over the catalogue (include/nrms_hip.h nrms_logsumexp_dot).  Parity is unpinned: the reference scores shown
+        candidates only.
+
+        temperature: a float or up to 8 floats, each > 0; ``float('inf')`` is the uniform distribution (lse = log n_eligible).
+        item_bias: recommend's per-news prior (float32 [N] by news id; a NaN entry removes that news for everybody); bias_scale:
+        None (scale 1) or one finite float per temperature, e.g. a grid of ``--popularity_prior`` ALPHA over one log-popularity.
+        The user vector, the catalogue, the id-0 rule (the padding title never competes), ``exclude_history`` and the counting
+        of bad ``browsed_ids`` are recommend's.  There is no time window here yet."""
+        inv_t, scale = self._likelihood_variants("log_partition", temperature, bias_scale, item_bias)
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "log_partition")
+        bias = self._item_bias_rows(item_bias, cat, "log_partition")
+        lse, zmax, n_el = self._engine.log_partition(user, cat[1:], inv_t, exclude, bias=bias, bias_scale=scale)
+        return (lse, zmax, n_el) if return_stats else lse
+
+    @torch.no_grad()
+    def log_prob(self, batch, targets, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None):
+        """The log-probability of given news under the served softmax over the whole catalogue -> [B, T, J] fp32:
+        z_j(target) - lse_j with log_partition's lse and z_j(target) = fmaf(score, 1 / temperature[j], bias_scale[j] *
+        item_bias[id]) formed from rank_targets' score bits (the plain dot product, without the prior).  NaN where rank_targets
+        gives rank 0 (id 0, an id outside the catalogue, a NaN score or prior and, with exclude_history, a browsed id); <= 0
+        for every other target, and exp of it sums to 1 over a user's eligible catalogue.  The arguments are log_partition's and
+        rank_targets'."""
+        inv_t, scale = self._likelihood_variants("log_prob", temperature, bias_scale, item_bias)
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "log_prob")
+        bias = self._item_bias_rows(item_bias, cat, "log_prob")
+        tg = torch.as_tensor(targets).to(user.device, dtype=torch.int64)
+        if tg.dim() != 2 or tg.shape[0] != user.shape[0]:
+            raise _lib.NrmsError("log_prob: targets must be [%d, T] news ids (got %s)" % (user.shape[0], tuple(tg.shape)))
+        rows = (tg - 1).contiguous()
+        ranks, scores = self._engine.rank_of(user, cat[1:], rows, exclude)
+        lse, _, _ = self._engine.log_partition(user, cat[1:], inv_t, exclude, bias=bias, bias_scale=scale)
+        return _target_log_prob(ranks, scores, rows, lse, inv_t, scale, bias)
+
+    @staticmethod
     def _item_bias_rows(item_bias, cat, who):
         """The kernels' view of a per-news prior: rows 1.. like the catalogue's (None stays None)."""
         if item_bias is None:
@@ -581,6 +669,7 @@ class Model(FlatHipModel):
     CATALOGUE_SECTIONS = True           # ... and selected per section: recommend_sections (run_v0 --sections)
     CATALOGUE_PAGING = True             # ... and paged through with a cursor: recommend_page / recommend_deep (run_v0 --recommend_deep)
     CATALOGUE_EXPLAIN = True            # ... and split over the clicks of the history: explain (run_v0 --explain)
+    CATALOGUE_LIKELIHOOD = True         # ... and normalised over the catalogue: log_partition / log_prob (run_v0 --retrieval_nll)
 
     def check_recommend_ids(self):
         """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read

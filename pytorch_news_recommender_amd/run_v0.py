@@ -82,6 +82,10 @@ def build_parser():
                         'and of the re-ranked list')
     parser.add_argument('--shortlist', type=int, default=None, metavar='M', help='--diversity: the number of best news the re-ranking '
                         'picks from (K <= M <= 256; default min(256, 4 K))')
+    parser.add_argument('--retrieval_nll', type=str, default=None, metavar='T[,T...]', help='with --retrieval_metrics: also print the '
+                        'held-out negative log-likelihood of the clicked news under softmax(score / T) over the whole catalogue, one '
+                        'nll@T figure per temperature (up to 8, each > 0; with --popularity_prior the prior is part of the logit; not '
+                        'with --catalogue_window)')
     parser.add_argument('--popularity_prior', type=float, default=None, metavar='ALPHA', help='--negatives catalogue / adaptive: add the '
                         "per-news prior ALPHA * log(1 + the number of training users who clicked the news) to every catalogue score of "
                         '--recommend (with or without --diversity) and --retrieval_metrics (0 = none; held-out clicks are not counted)')
@@ -233,6 +237,31 @@ def check_retrieval_args(args):
     return ks
 
 
+def check_nll_args(args):
+    """--retrieval_nll fails before any data is read or any step is trained: up to 8 temperatures > 0, --retrieval_metrics to ride
+    on, no time window (there is no windowed log-partition), a model whose catalogue score a softmax can be put on.  Returns the
+    temperatures (None without the flag)."""
+    if args.retrieval_nll is None:
+        return None
+    try:
+        temps = tuple(float(v) for v in args.retrieval_nll.split(','))
+    except ValueError:
+        raise SystemExit('--retrieval_nll T[,T...]: numbers expected (got %r)' % args.retrieval_nll)
+    if not 1 <= len(temps) <= 8 or not all(t > 0 for t in temps):
+        raise SystemExit('--retrieval_nll T[,T...]: 1 to 8 temperatures, each > 0 (got %r)' % args.retrieval_nll)
+    if args.retrieval_metrics is None:
+        raise SystemExit('--retrieval_nll: the likelihood of the targets of --retrieval_metrics K (give it)')
+    if args.catalogue_window is not None:
+        raise SystemExit('--retrieval_nll: there is no log-partition inside a time window yet (drop --catalogue_window)')
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_LIKELIHOOD', False):
+        raise SystemExit('--retrieval_nll: model %r has no softmax over the whole catalogue (its catalogue score is not one dot '
+                         'product per user)' % args.model)
+    return temps
+
+
 def check_prior_args(args):
     """--popularity_prior fails before any data is read or any step is trained: a finite ALPHA, a list or a metric to apply it to,
     a click log to count popularity in, and a model that takes a per-news prior."""
@@ -347,6 +376,7 @@ def main(argv=None):
     check_coarse_args(args)
     check_explain_args(args)
     retrieval_ks = check_retrieval_args(args)
+    retrieval_nll = check_nll_args(args)
     check_prior_args(args)
     check_window_args(args)
     check_graph_args(args)
@@ -468,7 +498,8 @@ def main(argv=None):
         net = recommender.model if hasattr(recommender, 'model') else recommender
         needs_info = 'categ' in inspect.signature(net.encode_catalogue).parameters           # nrms_naml's feature rows
         return evaluate_retrieval(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
-                                  news_info=feed.news_info() if needs_info else None, **item_prior, **item_window)
+                                  news_info=feed.news_info() if needs_info else None, **item_prior, **item_window,
+                                  **({} if retrieval_nll is None else {'nll_temperatures': retrieval_nll}))
 
     def attach_graph(feed, samples=None):
         # the click graph is replicated: every rank builds it from ALL training samples (users shard, the graph does not)

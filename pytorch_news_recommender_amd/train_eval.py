@@ -549,7 +549,7 @@ def recommend_sections(config, model, data_iter, titles, k, sections, out_file=N
 
 
 def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
-                       verbose=True, item_bias=None, item_time=None, request_time=None, window_span=None):
+                       verbose=True, item_bias=None, item_time=None, request_time=None, window_span=None, nll_temperatures=None):
     """Full-catalogue retrieval quality on held-out clicks: per impression of data_iter the targets are its clicked news (the
     ``candidate_ids`` whose label in y_true is 1) and each is ranked against the whole catalogue in recommend()'s own order
     (``model.rank_targets``: the exact position, at any depth).  titles / news_info / exclude_history as in recommend();
@@ -569,14 +569,30 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     the news with request_time[i] - window_span <= item_time[id] <= request_time[i] only (``model.rank_targets(item_time=...,
     window=...)``): the news that were live at the moment of the click, not news that did not exist yet or had long gone.  A
     target outside its window counts as skipped.  For a target inside it the windowed rank is at most the unwindowed one.
-    None: the keywords are not passed at all."""
+    None: the keywords are not passed at all.
+
+    nll_temperatures: None, or up to 8 temperatures T > 0.  The result gains ``nll``: {T: the mean over the ranked targets (the
+    ones ``n_targets`` counts) of -log softmax(score / T + item_bias)[target]}, the softmax running over every news the user
+    could be recommended (``model.log_prob``; item_bias enters with scale 1), accumulated on the device.  There is no windowed
+    partition yet: together with item_time / window_span this raises ValueError.  None: nothing changes, the keyword is not
+    passed on and ``nll`` is absent."""
     net = _inner(model)
     prior = {} if item_bias is None else {"item_bias": item_bias}
+    nll_t = None
+    if nll_temperatures is not None:
+        if item_time is not None or request_time is not None or window_span is not None:
+            raise ValueError("evaluate_retrieval: nll_temperatures with item_time / request_time / window_span: there is no "
+                             "windowed log-partition yet")
+        nll_t = [float(t) for t in nll_temperatures]
+        if not getattr(type(net), "CATALOGUE_LIKELIHOOD", False):
+            raise NotImplementedError("evaluate_retrieval: nll_temperatures needs a model with CATALOGUE_LIKELIHOOD "
+                                      "(log_partition / log_prob); %s has none" % type(net).__module__)
     windows = _RequestWindows("evaluate_retrieval", item_time, request_time, window_span)
     ks = tuple(int(k) for k in ks)
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
     dev = catalogue.device
     ranks, targets, done = [], [], 0
+    nll_sum = None if nll_t is None else torch.zeros(len(nll_t), dtype=torch.float64, device=dev)
     for datas in data_iter:
         cand = torch.as_tensor(datas["candidate_ids"]).to(dev, dtype=torch.int64)
         B, S = cand.shape
@@ -598,6 +614,9 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
         rk, _ = net.rank_targets(datas, tg, catalogue, exclude_history=exclude_history, **prior)
         ranks.append(rk)
         targets.append(tg)
+        if nll_t is not None:
+            lp = net.log_prob(datas, tg, catalogue, temperature=nll_t, exclude_history=exclude_history, **prior)
+            nll_sum -= torch.where((rk > 0).unsqueeze(-1), lp, torch.zeros_like(lp)).double().sum(dim=(0, 1))
     T = max((r.shape[1] for r in ranks), default=1)
     pad = lambda t, v: torch.nn.functional.pad(t, (0, T - t.shape[1]), value=v)
     ranks = torch.cat([pad(r, 0) for r in ranks]) if ranks else torch.zeros(0, T, dtype=torch.int32, device=dev)
@@ -616,7 +635,11 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     vals += [(lo.double() + hi.double()) / 2, n_users.double(), n_targets.double(), ((targets >= 0) & ~ranked).sum().double()]
     bad = getattr(net, "_bad_browsed", None)
     vals.append(bad.double() if bad is not None else n_users.double() * 0)
+    if nll_t is not None:
+        vals = list(nll_sum / n_targets.clamp(min=1).double()) + vals
     vals = torch.stack(vals).cpu().tolist()                    # the one host synchronisation
+    nll = None if nll_t is None else dict(zip(nll_t, vals[:len(nll_t)]))
+    vals = vals[len(nll_t or ()):]
     net.engine.check_ids()                                     # (its count is on the host by now)
     if vals.pop():
         net.check_recommend_ids()                              # raises: browsed ids outside the catalogue
@@ -626,10 +649,13 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     if not res["n_users"]:
         for k in names + ["median_rank"]:
             res[k] = float("nan")
+    if nll is not None:
+        res["nll"] = nll if res["n_targets"] else {t: float("nan") for t in nll}
     net.last_retrieval_metrics = dict(m, ranks=ranks, targets=targets)
     if verbose:
         print("retrieval over {} news: ".format(int(catalogue.shape[0]) - 1)
               + "  ".join("{}: {:.4f}".format(k, res[k]) for k in names)
               + "  median rank: {:.1f}  users: {}  targets: {}  skipped: {}".format(res["median_rank"], res["n_users"],
-                                                                                   res["n_targets"], res["n_skipped"]))
+                                                                                   res["n_targets"], res["n_skipped"])
+              + "".join("  nll@T={:g}: {:.4f}".format(t, v) for t, v in (res.get("nll") or {}).items()))
     return res
