@@ -547,6 +547,55 @@ int nrms_rank_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t T, const flo
                            int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- A per-user set of item tags on the catalogue in retrieval and ranking (muted topics, "only what I follow", an edition, a
+ * publisher block; PARITY UNPINNED, the reference has no catalogue retrieval) ----
+ * nrms_topk_dot_biased and nrms_rank_dot_biased over the items whose tag the user allows.  item_tag [N] int32: one tag per item;
+ * allow [B, W] uint32, W = ceil(n_tags / 32): tag t is allowed for user b iff bit t & 31 of allow[b * W + (t >> 5)] is set; the bits of
+ * the last word at positions >= n_tags are ignored; both REQUIRED and 4-byte aligned.  bias [N] fp32, 4-byte aligned, NULLABLE:
+ * NULL means no prior, s' = s.  Every other argument is the biased call's.
+ * Eligible: item n is eligible for user b iff 0 <= item_tag[n] < n_tags, that tag is allowed for b, n is not in exclude[b, :] and
+ *   s'(b, n) is not NaN.  A tag outside [0, n_tags) is open to nobody: -1 is the "untagged, never served" value.  An all-zero allow
+ *   row is the EMPTY set: row b is all padding (id -1 / score -inf) and every target of user b gets rank 0 / score -inf.
+ * Score, order and output.  s and s' are the biased call's, the same code and the same bits: the tags never touch a score.
+ *   Order (s' descending, +inf first, equal s' put the SMALLER n first), -0.0 equals +0.0 (returned as +0.0), padding (-1 / -inf),
+ *   invalid targets (outside [0, N), excluded, NaN s': rank 0 / -inf), limits (1 <= k <= 256, 1 <= T <= 32, d >= 1,
+ *   0 <= N <= 0x7FFF0000, B >= 0; B = 0 is a no-op, N = 0 writes padding / rank 0) are nrms_topk_dot_biased's and
+ *   nrms_rank_dot_biased's; 1 <= n_tags <= 512.
+ * Targets.  A target whose tag is closed to its user is invalid: rank 0 / score -inf.  A valid target is ranked against the items
+ *   eligible for its user, so ranks[b, j] = 1 + #{n eligible for b : (s'(b, n), n) precedes (s'(b, t), t)}.  An excluded id that is
+ *   closed was never counted and is taken out of nothing.
+ * Consequences.
+ *   (a) With every tag in [0, n_tags) and every bit below n_tags set, ids, ranks and score bits equal the _biased call's with the
+ *       same bias (NULL: the unbiased call's).
+ *   (b) Row b equals nrms_topk_dot_biased at B = 1 for user b with bias'[n] = bias[n] (0 when bias is NULL) where n is open to b
+ *       and NaN where it is closed; the same holds for the ranks and target scores of nrms_rank_dot_biased.  (With bias NULL,
+ *       s + 0.0 differs from s only for s = -0.0, which is returned as +0.0 anyway.)
+ *   (c) Row b depends on user row b and allow row b only: not on B, the row's position in the batch, the other users' sets, the
+ *       ignored bits, the launch geometry, what the workspace held or the run.
+ *   (d) The first k' columns of a call with k are the call with k'.
+ *   (e) The ids nrms_topk_dot_tagged returns for user b get ranks 1 .. k, in order, from nrms_rank_dot_tagged with the same
+ *       arguments, and the same score bits.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_tagged: ...", "rank_dot_tagged: ...");
+ *   n_tags outside [1, 512] and a NULL or misaligned item_tag (N > 0) or allow are among them.  An undersized workspace returns
+ *   NRMS_EWORKSPACE.  Nothing is launched after an error.
+ * Workspace: the _tagged_workspace_bytes queries return exactly nrms_topk_dot_workspace_bytes(B, N, d, k) and
+ *   nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude) (0 = arguments rejected); 8-byte aligned.
+ * The same kernel counts as the untagged calls (two for the top-k, three for the rank), on `stream`, no host synchronisation, no
+ *   allocation; plain vector loads and stores, no atomics beyond the integer counters of the untagged kernels.  A block transposes its
+ *   32 users' sets once into n_tags words of LDS, so a score costs one bit test; a wave whose 64 items are closed to all 32 users of
+ *   its block loads no item row and runs no MFMA for that step.  The results are the same with that skip compiled out
+ *   (csrc/topk_entry.h TK_TAGS_SKIP). */
+size_t nrms_topk_dot_tagged_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_tagged(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                         const float* bias /* [N], nullable */, const int32_t* item_tag /* [N] */, int32_t n_tags,
+                         const uint32_t* allow /* [B, W] */, const int64_t* exclude, int32_t n_exclude, float* top_scores,
+                         int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+size_t nrms_rank_dot_tagged_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude);
+int nrms_rank_dot_tagged(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                         const float* bias /* [N], nullable */, const int32_t* item_tag /* [N] */, int32_t n_tags,
+                         const uint32_t* allow /* [B, W] */, const int64_t* targets, const int64_t* exclude, int32_t n_exclude,
+                         int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Paging through the exact ranking: a cursor on the top-k, and lists up to 4096 (candidate generation for a re-ranker, a feed
  * that scrolls: "the next 20 after what I showed"; PARITY UNPINNED, the reference has no catalogue retrieval) ----
  * The order of nrms_topk_dot[_biased|_windowed] is total (s' descending, then the SMALLER n, -0.0 equal to +0.0) and a score's bits

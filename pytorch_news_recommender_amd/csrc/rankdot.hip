@@ -21,6 +21,10 @@
 // nrms_rank_dot_windowed ranks inside a per-user interval on a per-item timestamp: the WINDOW instantiations of A and B test
 // lo <= item_time[n] < hi in front of tk_entry, and B skips the waves whose 64 items are closed to its whole block; C is the same.
 //
+// nrms_rank_dot_tagged ranks inside a per-user set of item tags: rank_entries_tagged_kernel and rank_count_tagged_kernel, the TAGS
+// forms of A and B (one body each, shared with the kernels above), test the owner's allow bit / the block's transposed bitmap in
+// front of tk_entry, and B skips the waves whose 64 items are closed to its whole block; C is the same.
+//
 // The scores are tk_chain's (topk_entry.h), the one chain topk_slice_kernel runs too, with one A operand: nrms_topk_dot's bits
 // (tests/test_hip_rank.py checks it end to end).
 #include "topk_entry.h"
@@ -35,13 +39,17 @@ constexpr int RK_A_CHUNKS = 4096;              // grid.y bound of kernel A (long
 // exclude ids).  ent [B, M].  Blocks y = 0 also zero the tile's counts [B, T] for kernel B.  Needs N >= 1.
 // WINDOW: an id whose time is outside its owner's [lo, hi) gets entry 0, like a NaN score: such a target is invalid, such an
 // excluded id was never counted by kernel B and is taken out of nothing.
-template <bool VEC, bool BIAS, bool WINDOW>
-__global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, int T, int n_exclude,
-                                                          const float* __restrict__ user, const float* __restrict__ items,
-                                                          const int64_t* __restrict__ targets,
-                                                          const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
-                                                          uint32_t* __restrict__ counts, const float* __restrict__ bias,
-                                                          TkWindow win) {
+// TAGS: the same for an id whose tag is closed to its owner (tk_tags_open: one word of the owner's allow row, from global
+// memory; the ids are gathered one by one, so there is no bitmap to share).
+// The body is written once; the kernels below are its instantiations (the TAGS forms are kernels of their own, so that the others
+// keep their names, signatures and kernarg layouts).
+template <bool VEC, bool BIAS, bool WINDOW, bool TAGS>
+__device__ __forceinline__ void rank_entries_body(int B, int N, int d, int T, int n_exclude, const float* __restrict__ user,
+                                                  const float* __restrict__ items, const int64_t* __restrict__ targets,
+                                                  const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
+                                                  uint32_t* __restrict__ counts, const float* __restrict__ bias, TkWindow win,
+                                                  TkTags tags) {
+    static_assert(!(TAGS && WINDOW), "the tag set is for the plain and the biased rank only");
     __shared__ int rows[64];
     __shared__ __attribute__((aligned(16))) float stage[64 * TK_BP];
     const int lane = threadIdx.x;
@@ -92,9 +100,34 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
                     ok = tv >= win.window[2 * (long)(u0 + uc)] && tv < win.window[2 * (long)(u0 + uc) + 1];
                 }
             }
+            if constexpr (TAGS) {
+                if (ok) ok = tk_tags_open(tags, u0 + uc, tags.item_tag[idc]);
+            }
             ent[(long)(u0 + uc) * M + mc] = ok ? tk_entry(s, (uint32_t)idc) : 0;
         }
     }
+}
+
+template <bool VEC, bool BIAS, bool WINDOW>
+__global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, int T, int n_exclude,
+                                                          const float* __restrict__ user, const float* __restrict__ items,
+                                                          const int64_t* __restrict__ targets,
+                                                          const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
+                                                          uint32_t* __restrict__ counts, const float* __restrict__ bias,
+                                                          TkWindow win) {
+    rank_entries_body<VEC, BIAS, WINDOW, false>(B, N, d, T, n_exclude, user, items, targets, exclude, ent, counts, bias, win,
+                                                TkTags{nullptr, nullptr, 0});
+}
+
+template <bool VEC, bool BIAS>
+__global__ __launch_bounds__(64) void rank_entries_tagged_kernel(int B, int N, int d, int T, int n_exclude,
+                                                                 const float* __restrict__ user, const float* __restrict__ items,
+                                                                 const int64_t* __restrict__ targets,
+                                                                 const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
+                                                                 uint32_t* __restrict__ counts, const float* __restrict__ bias,
+                                                                 TkTags tags) {
+    rank_entries_body<VEC, BIAS, false, true>(B, N, d, T, n_exclude, user, items, targets, exclude, ent, counts, bias,
+                                              TkWindow{nullptr, nullptr}, tags);
 }
 
 // Kernel B.  Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step.  ent [B, M]:
@@ -103,11 +136,15 @@ __global__ __launch_bounds__(64) void rank_entries_kernel(int B, int N, int d, i
 // hull [blo, bhi); a score becomes an entry only if lo <= item_time[n] < hi for its user; a wave none of whose 64 item times
 // lies in the hull (one __ballot, wave-uniform) goes to its next step with zero entries: no item loads, no staging, no MFMA.
 // The step loop holds no block barrier, so a skipping wave meets the two barriers around it like every other wave.
-template <int W, bool VEC, bool BIAS, bool WINDOW>
-__global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d, int T, int M, int slice_len,
-                                                            const float* __restrict__ user, const float* __restrict__ items,
-                                                            const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts,
-                                                            const float* __restrict__ bias, TkWindow win) {
+// TAGS: topk_slice_kernel's tag filter and dead-wave skip.  The block builds the transposed bitmap of its users' tag sets in LDS
+// (tk_tags_stage); a lane reads one LDS word per item, tm[c], and a score becomes an entry only if its user's bit of tm[c] is set;
+// a wave with tm[0] | tm[1] == 0 in every lane goes to its next step like a WINDOW wave outside the hull.
+template <int W, bool VEC, bool BIAS, bool WINDOW, bool TAGS>
+__device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int M, int slice_len, const float* __restrict__ user,
+                                                const float* __restrict__ items, const uint64_t* __restrict__ ent,
+                                                uint32_t* __restrict__ counts, const float* __restrict__ bias, TkWindow win,
+                                                TkTags tags) {
+    static_assert(!(TAGS && WINDOW), "the tag set is for the plain and the biased rank only");
     __shared__ uint64_t tgt[TK_UT][RK_MAX_T];
     __shared__ uint32_t cnts[TK_UT][RK_MAX_T];
     __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
@@ -128,6 +165,12 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
         __shared__ int2 wwin_lds[TK_UT];
         wwin = wwin_lds;
         tk_window_stage(wwin, win.window, u0, B);
+    }
+    uint32_t* ubt = nullptr;       // TAGS: the block's transposed tag bitmap
+    if constexpr (TAGS) {
+        __shared__ uint32_t ubt_lds[TK_MAX_TAGS];
+        ubt = ubt_lds;
+        tk_tags_stage(ubt, tags, u0, B, 64 * W);
     }
     __syncthreads();
     int blo = 0, bhi = 0;
@@ -150,6 +193,16 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
                 any |= n < n_end && tv[c] >= blo && tv[c] < bhi;
             }
             if (TK_WINDOW_SKIP && __ballot(any) == 0) continue;       // wave-uniform: nothing here is open to any user of the block
+        }
+        uint32_t tm[TAGS ? TK_TN : 1] = {};      // TAGS: the block's users that this lane's item of column tile c is open to
+        if constexpr (TAGS) {
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) {
+                const int n = nw + 32 * c + r;
+                const uint32_t m = tk_tags_mask(ubt, tags.item_tag[min(n, N - 1)], tags.n_tags);
+                tm[c] = n < n_end ? m : 0u;
+            }
+            if (TK_TAGS_SKIP && __ballot((tm[0] | tm[1]) != 0) == 0) continue;       // wave-uniform, as above
         }
         tk_f32x16 acc[TK_TN];
 #pragma unroll
@@ -175,6 +228,7 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
                     const int2 w = wwin[(q & 3) + 8 * (q >> 2) + 4 * h];
                     open = open && tv[c] >= w.x && tv[c] < w.y;
                 }
+                if constexpr (TAGS) open = open && ((tm[c] >> ((q & 3) + 8 * (q >> 2) + 4 * h)) & 1u);
                 e[c][q] = open ? tk_entry(s, (uint32_t)n) : 0;       // 0 precedes nothing
             }
         }
@@ -204,6 +258,24 @@ __global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d,
         const int u = i / RK_MAX_T, j = i % RK_MAX_T;
         if (u0 + u < B && j < T && cnts[u][j]) atomicAdd(&counts[(long)(u0 + u) * T + j], cnts[u][j]);
     }
+}
+
+template <int W, bool VEC, bool BIAS, bool WINDOW>
+__global__ __launch_bounds__(64 * W) void rank_count_kernel(int B, int N, int d, int T, int M, int slice_len,
+                                                            const float* __restrict__ user, const float* __restrict__ items,
+                                                            const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts,
+                                                            const float* __restrict__ bias, TkWindow win) {
+    rank_count_body<W, VEC, BIAS, WINDOW, false>(B, N, d, T, M, slice_len, user, items, ent, counts, bias, win,
+                                                 TkTags{nullptr, nullptr, 0});
+}
+
+template <int W, bool VEC, bool BIAS>
+__global__ __launch_bounds__(64 * W) void rank_count_tagged_kernel(int B, int N, int d, int T, int M, int slice_len,
+                                                                   const float* __restrict__ user, const float* __restrict__ items,
+                                                                   const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts,
+                                                                   const float* __restrict__ bias, TkTags tags) {
+    rank_count_body<W, VEC, BIAS, false, true>(B, N, d, T, M, slice_len, user, items, ent, counts, bias, TkWindow{nullptr, nullptr},
+                                               tags);
 }
 
 // Kernel C.  One wave per user.  N = 0: every target is invalid (ent and counts are not read).
@@ -265,17 +337,21 @@ extern "C" size_t nrms_rank_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
     return 256 + rank_entry_bytes(B, T, n_exclude) + (size_t)B * (size_t)T * sizeof(uint32_t);
 }
 
-// nrms_rank_dot (bias null, who "rank_dot"), nrms_rank_dot_biased and nrms_rank_dot_windowed (windowed: item_time and window are
-// required): one body.
+// nrms_rank_dot (bias null, who "rank_dot"), nrms_rank_dot_biased, nrms_rank_dot_windowed (windowed: item_time and window are
+// required) and nrms_rank_dot_tagged (tagged: item_tag and allow are required, 1 <= n_tags <= TK_MAX_TAGS): one body.
 static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
                          const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* targets,
                          const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
-                         size_t workspace_bytes, void* stream) {
+                         size_t workspace_bytes, void* stream, bool tagged = false, TkTags tags = TkTags{nullptr, nullptr, 0}) {
     int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "T", T, RK_MAX_T, n_exclude);
-    if (rc != NRMS_OK || B == 0) return rc;
+    if (rc != NRMS_OK) return rc;
+    NRMS_REQUIRE(!tagged || (tags.n_tags >= 1 && tags.n_tags <= TK_MAX_TAGS), "%s: n_tags must be in [1, %d] (n_tags=%d)", who,
+                 TK_MAX_TAGS, tags.n_tags);
+    if (B == 0) return rc;
     if (!exclude) n_exclude = 0;
     rc = tk_check_ptrs(who, {{"user", user, true, 1}, {"items", items, N != 0, 1}, {"bias", bias, false, 4},
                              {"item_time", item_time, windowed && N != 0, 4}, {"window", window, windowed, 4},
+                             {"item_tag", tags.item_tag, tagged && N != 0, 4}, {"allow", tags.allow, tagged, 4},
                              {"targets", targets, true, 1}, {"ranks", ranks, true, 1}},
                        workspace, workspace_bytes, nrms_rank_dot_workspace_bytes(B, N, d, T, n_exclude), 8);
     if (rc != NRMS_OK) return rc;
@@ -289,7 +365,19 @@ static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     char what[64];
     if (g.S > 0) {
         const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64)), grid_b(g.tiles, g.S);
-        tk_with_flags([&](auto V, auto BI, auto WI) {
+        if (tagged) tk_with_flags([&](auto V, auto BI) {
+            constexpr bool v = decltype(V)::value, bi = decltype(BI)::value;
+            hipLaunchKernelGGL((rank_entries_tagged_kernel<v, bi>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
+                               exclude, ent, counts, bias, tags);
+            snprintf(what, sizeof what, "%s(entries)", who);
+            rc = check_launch(what);
+            if (rc != NRMS_OK) return;
+            hipLaunchKernelGGL((rank_count_tagged_kernel<TK_WAVES, v, bi>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M,
+                               g.slice_len, user, items, ent, counts, bias, tags);
+            snprintf(what, sizeof what, "%s(count)", who);
+            rc = check_launch(what);
+        }, tk_vec_ok(d, user, items), bias != nullptr);
+        else tk_with_flags([&](auto V, auto BI, auto WI) {
             constexpr bool v = decltype(V)::value, bi = decltype(BI)::value, wi = decltype(WI)::value;
             hipLaunchKernelGGL((rank_entries_kernel<v, bi, wi>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
                                exclude, ent, counts, bias, win);
@@ -339,4 +427,12 @@ extern "C" int nrms_rank_dot_windowed(int32_t B, int64_t N, int32_t d, int32_t T
                                       void* workspace, size_t workspace_bytes, void* stream) {
     return rank_dot_call("rank_dot_windowed", B, N, d, T, user, items, bias, true, item_time, window, targets, exclude, n_exclude,
                          ranks, target_scores, workspace, workspace_bytes, stream);
+}
+
+// nrms_rank_dot_tagged's body (its C entry point is in topktags.hip, with the tagged top-k's).
+int nrms::rank_dot_tagged_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
+                               TkTags tags, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                               float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
+    return rank_dot_call("rank_dot_tagged", B, N, d, T, user, items, bias, false, nullptr, nullptr, targets, exclude, n_exclude, ranks,
+                         target_scores, workspace, workspace_bytes, stream, true, tags);
 }

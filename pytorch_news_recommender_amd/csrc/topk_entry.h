@@ -1,6 +1,6 @@
 // What the catalogue kernels share (topk.hip and topksec.hip: the k best items per user; softmaxsample.hip: a Gumbel-top-S draw;
 // rankdot.hip: the exact rank of given items in that order): the tile constants, the uint64 entry that carries the order, the
-// one score chain every one of their kernels runs (tk_chain), the time window, and the host side every entry point shares:
+// one score chain every one of their kernels runs (tk_chain), the time window, the tag set, and the host side every entry point shares:
 // the launch geometry, the argument checks and the choice of a kernel instantiation.
 //
 // An entry is the score as an order-preserving 32-bit key (-0.0 canonicalised to +0.0) above the complement of the 32-bit
@@ -137,6 +137,50 @@ __device__ __forceinline__ bool tk_cursor_all_end(const uint64_t* cur) {
     uint64_t any = 0;
     for (int u = 0; u < TK_UT; ++u) any |= cur[u];
     return any == 0;
+}
+
+// The per-user tag set of nrms_topk_dot_tagged / nrms_rank_dot_tagged (include/nrms_hip.h states it): item n is open to user b iff
+// 0 <= item_tag[n] < n_tags and bit item_tag[n] & 31 of allow[b * W + (item_tag[n] >> 5)] is set, W = ceil(n_tags / 32).  Null
+// allow = none, the kernels are the untagged ones.
+struct TkTags {
+    const int32_t* item_tag;     // [N]
+    const uint32_t* allow;       // [B, W]
+    int n_tags;
+};
+constexpr int TK_MAX_TAGS = 512;
+
+// The dead-wave skip of the TAGS kernels: a wave none of whose 64 items carries a tag that a user of its block allows runs no
+// chain for that step.  false compiles the skip out: same results, bit for bit (a diagnostic build with -DNRMS_TK_TAGS_SKIP=0,
+// e.g. through NRMS_HIPCC_EXTRA, passes tests/test_hip_topk_tags.py unchanged).
+#ifndef NRMS_TK_TAGS_SKIP
+#define NRMS_TK_TAGS_SKIP 1
+#endif
+constexpr bool TK_TAGS_SKIP = NRMS_TK_TAGS_SKIP != 0;
+
+// One block's transposed tag bitmap (TAGS kernels): bit i of ubt[t] is set iff user u0 + i allows tag t, t in [0, n_tags); rows at
+// or past B allow nothing.  Every thread of the block (nthreads of them) takes part; call before the block's first barrier.  The
+// bits of allow's last word at positions >= n_tags are never read.
+__device__ __forceinline__ void tk_tags_stage(uint32_t* ubt, TkTags t, int u0, int B, int nthreads) {
+    const int W = (t.n_tags + 31) >> 5;
+    const int nu = min(TK_UT, B - u0);
+    for (int tag = threadIdx.x; tag < t.n_tags; tag += nthreads) {
+        const uint32_t* col = t.allow + (long)u0 * W + (tag >> 5);
+        uint32_t m = 0;
+        for (int i = 0; i < nu; ++i) m |= ((col[(long)i * W] >> (tag & 31)) & 1u) << i;
+        ubt[tag] = m;
+    }
+}
+
+// The block's users that item tag `tag` is open to, as a 32-bit mask (0 for a tag outside [0, n_tags): open to nobody).
+__device__ __forceinline__ uint32_t tk_tags_mask(const uint32_t* ubt, int tag, int n_tags) {
+    return (uint32_t)tag < (uint32_t)n_tags ? ubt[tag] : 0u;
+}
+
+// Is tag `tag` open to user b (read from global memory: the gathered ids of rank_entries_kernel).
+__device__ __forceinline__ bool tk_tags_open(TkTags t, long b, int tag) {
+    if ((uint32_t)tag >= (uint32_t)t.n_tags) return false;
+    const int W = (t.n_tags + 31) >> 5;
+    return (t.allow[b * W + (tag >> 5)] >> (tag & 31)) & 1u;
 }
 
 __device__ __forceinline__ float tk_ld(const float* p, int kk, int d) { return kk < d ? p[kk] : 0.0f; }
@@ -281,6 +325,11 @@ static int tk_check_ptrs(const char* who, std::initializer_list<TkPtr> ptrs, con
     NRMS_REQUIRE(((uintptr_t)workspace & (ws_align - 1)) == 0, "%s: workspace must be %u-byte aligned", who, ws_align);
     return NRMS_OK;
 }
+
+// nrms_rank_dot_tagged's body: rankdot.hip defines it beside the rank kernels, topktags.hip holds the C entry point.
+int rank_dot_tagged_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
+                         TkTags tags, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                         float* target_scores, void* workspace, size_t workspace_bytes, void* stream);
 
 // The chain's loads are float4 when every row starts on 16 bytes.
 static bool tk_vec_ok(int32_t d, const float* user, const float* items) {

@@ -188,7 +188,8 @@ struct TkFilterLds {
 
 // Which (user, item) pairs of a step the filter may take: user(i) reads what user row i of the block contributes, item(c, w)
 // tests this lane's item of column tile c against it.  Every pair, or the pairs with lo <= time < hi (WINDOW kernels: win is
-// the block's 32 staged (lo, hi), tv the times of this lane's two items).
+// the block's 32 staged (lo, hi), tv the times of this lane's two items), or the pairs whose user allows the item's tag (TAGS
+// kernels: tm[c] is the block's transposed bitmap word of this lane's item of column tile c, bit i = user row i allows its tag).
 struct TkOpenAll {
     __device__ __forceinline__ int user(int) const { return 0; }
     __device__ __forceinline__ bool item(int, int) const { return true; }
@@ -198,6 +199,12 @@ struct TkOpenWindow {
     const int (&tv)[TK_TN];
     __device__ __forceinline__ int2 user(int i) const { return win[i]; }
     __device__ __forceinline__ bool item(int c, int2 w) const { return tv[c] >= w.x && tv[c] < w.y; }
+};
+
+struct TkOpenTags {
+    const uint32_t (&tm)[TK_TN];
+    __device__ __forceinline__ int user(int i) const { return i; }
+    __device__ __forceinline__ bool item(int c, int i) const { return (tm[c] >> i) & 1u; }
 };
 
 template <int P, int W>
@@ -265,7 +272,7 @@ struct TkFilter {
 
     // Offers the pending scores of a step; id_of(c): the id of this lane's item in column tile c.  This holds block barriers:
     // EVERY wave of the block calls it on EVERY step, with pend == 0 when it has nothing to offer (a wave past the slice's
-    // end, a WINDOW wave that skipped its chain), so that all waves meet the same barriers the same number of times.
+    // end, a WINDOW or TAGS wave that skipped its chain), so that all waves meet the same barriers the same number of times.
     template <class IdOf>
     __device__ __forceinline__ void offer(const tk_f32x16 (&acc)[TK_TN], uint32_t pend, IdOf id_of) {
         bool first = true;
@@ -348,9 +355,17 @@ struct TkFilter {
 // All-END exit: a block whose 32 keys are all 0 writes its empty slice lists and returns before its first item row; the test
 // reads LDS after a barrier, so it is block-uniform and no wave is left waiting at a later barrier.
 //
-// The window's two pointers are a kernel argument of the WINDOW instantiations alone, and the cursor's of the CURSOR
-// instantiations alone (WIN holds a TkWindow, a TkCursor, both in that order, or nothing; CURSOR is read off the pack), so every
-// other instantiation keeps its name, its signature and its kernarg layout.
+// TAGS (nrms_topk_dot_tagged; with or without BIAS): the block builds, once, the transposed bitmap ubt[t] of its 32 users' tag
+// sets in LDS (tk_tags_stage: bit i of ubt[t] = user u0 + i allows tag t; n_tags words, at most 2 KB).  Lane (r, h) loads
+// item_tag[n] of its item in each of its two column tiles where bv[] is loaded and reads ONE LDS word per item, tm[c] =
+// ubt[tag] (0 for a tag outside [0, n_tags) and for a row past the slice); the filter takes (user i, item) iff bit i of tm[c] is
+// set, a register test, not 32 LDS reads per score.  Dead-wave skip: __ballot(tm[0] | tm[1]) == 0, wave-uniform, under exactly the
+// WINDOW skip's barrier discipline: the skipping wave still calls offer with pend == 0.
+//
+// The window's two pointers are a kernel argument of the WINDOW instantiations alone, the cursor's of the CURSOR instantiations
+// alone and the tag set's of the TAGS instantiations alone (WIN holds a TkWindow, a TkCursor, both in that order, a TkTags, or
+// nothing; CURSOR and TAGS are read off the pack), so every other instantiation keeps its name, its signature and its kernarg
+// layout.
 template <int P, int W, bool VEC, bool GROUPED, bool NOISE, bool BIAS, bool WINDOW, class... WIN>
 __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d, int k, int slice_len, int S,
                                                             const float* __restrict__ user, const float* __restrict__ items,
@@ -360,8 +375,10 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                                                             const int32_t* __restrict__ item_ids, TkNoise noise,
                                                             const float* __restrict__ bias, WIN... win_arg) {
     constexpr bool CURSOR = (std::is_same<WIN, TkCursor>::value || ...);
-    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0),
-                  "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, the others neither");
+    constexpr bool TAGS = (std::is_same<WIN, TkTags>::value || ...);
+    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0),
+                  "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, TAGS kernels one TkTags, the others none");
+    static_assert(!(TAGS && (GROUPED || NOISE || WINDOW || CURSOR)), "the tag set is for the plain and the biased top-k only");
     const TkWindow win = tk_window_arg(win_arg...);
     static_assert(!(NOISE && GROUPED), "the perturbation is keyed by the item's row");
     static_assert(!(WINDOW && (GROUPED || NOISE)), "the window is for the plain and the biased top-k only");
@@ -389,6 +406,17 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         __shared__ uint64_t cur_lds[TK_UT];
         cur = cur_lds;
         tk_cursor_stage(cur, tk_pack_arg<TkCursor>(win_arg...), u0, B);
+    }
+    uint32_t* ubt = nullptr;       // TAGS: the block's transposed tag bitmap
+    [[maybe_unused]] int n_tags = 0;
+    [[maybe_unused]] const int32_t* item_tag = nullptr;
+    if constexpr (TAGS) {
+        __shared__ uint32_t ubt_lds[TK_MAX_TAGS];
+        ubt = ubt_lds;
+        const TkTags tags = tk_pack_arg<TkTags>(win_arg...);
+        n_tags = tags.n_tags;
+        item_tag = tags.item_tag;
+        tk_tags_stage(ubt, tags, u0, B, 64 * W);
     }
     if constexpr (NOISE) {
         if (threadIdx.x < TK_UT) rseed[threadIdx.x] = tk_noise_row_seed(noise.seed, (uint64_t)noise.row_key[min(u0 + (int)threadIdx.x, B - 1)]);
@@ -428,7 +456,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
             }
         }
         int tv[WINDOW ? TK_TN : 1] = {};         // WINDOW: the time of this lane's item in column tile c
-        bool dead = false;                       // WINDOW: no item of this wave's step is open to any user of the block (wave-uniform)
+        bool dead = false;                       // WINDOW, TAGS: no item of this wave's step is open to any user of the block (wave-uniform)
         if constexpr (WINDOW) {
             if (nw < n_end) {
                 bool any = false;
@@ -441,7 +469,19 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 dead = TK_WINDOW_SKIP && __ballot(any) == 0;
             }
         }
-        if (nw < n_end && (!GROUPED || tl.len[0] + tl.len[1] > 0) && !(WINDOW && dead)) {
+        uint32_t tm[TAGS ? TK_TN : 1] = {};      // TAGS: the block's users that this lane's item of column tile c is open to
+        if constexpr (TAGS) {
+            if (nw < n_end) {
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) {
+                    const int n = nw + 32 * c + r;
+                    const uint32_t m = tk_tags_mask(ubt, item_tag[min(n, N - 1)], n_tags);
+                    tm[c] = n < n_end ? m : 0u;
+                }
+                dead = TK_TAGS_SKIP && __ballot((tm[0] | tm[1]) != 0) == 0;
+            }
+        }
+        if (nw < n_end && (!GROUPED || tl.len[0] + tl.len[1] > 0) && !((WINDOW || TAGS) && dead)) {
             if constexpr (GROUPED) tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return tl.row_of(i, N); });
             else tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
         }
@@ -471,11 +511,12 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
             if constexpr (GROUPED) live[c] = tl.live(c, nw, n_end, r, item_ids, id[c]);
             else {
                 id[c] = (uint32_t)(nw + 32 * c + r);
-                live[c] = nw + 32 * c + r < n_end && !(WINDOW && dead);       // a skipped wave's accumulators hold no score
+                live[c] = nw + 32 * c + r < n_end && !((WINDOW || TAGS) && dead);       // a skipped wave's accumulators hold no score
             }
         }
         uint32_t pend;
         if constexpr (WINDOW) pend = flt.pending(acc, live, TkOpenWindow{wwin, tv});
+        else if constexpr (TAGS) pend = flt.pending(acc, live, TkOpenTags{tm});
         else pend = flt.pending(acc, live, TkOpenAll{});
         if constexpr (CURSOR) pend = flt.after(acc, pend, cur, [&](int c) { return id[c]; });
         // unconditional: the offer holds the block's barriers, and a wave with pend == 0 has to meet them too

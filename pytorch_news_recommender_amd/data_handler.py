@@ -915,6 +915,32 @@ class ClickFeed(DeviceFeed):
         prior[0] = 0.0
         return torch.from_numpy(prior).to(self.device)
 
+    def clicked_tags(self, item_tag, n_tags):
+        """bool [n_users, n_tags] on the feed's device: out[u, t] iff user u's TRAINING part holds a click on a news with
+        item_tag[id] == t (item_tag: int [N] by news id, e.g. ``news_info()["categ"]``; a tag outside [0, n_tags) sets nothing).
+        Built from the resident rejection sets, so a held-out click is never counted (the set cannot leak it) and a user who does
+        not train has an all-False row.  The ``allow`` of ``Model.recommend_tagged`` / ``rank_targets_tagged`` for "only the
+        topics I follow": index it with ``heldout_users()`` for the samples of ``heldout_samples()``."""
+        n_tags = int(n_tags)
+        if n_tags < 1:
+            raise ValueError("ClickFeed.clicked_tags: n_tags = %r must be >= 1" % (n_tags,))
+        tag = torch.as_tensor(item_tag).to(self.device, dtype=torch.int64).reshape(-1)
+        if tag.shape[0] != self.n_news:
+            raise ValueError("ClickFeed.clicked_tags: item_tag must be [N = %d], got %s" % (self.n_news, tuple(tag.shape)))
+        out = torch.zeros(self.n_users, n_tags, dtype=torch.bool, device=self.device)
+        if self.set_news.numel():
+            user = torch.repeat_interleave(torch.arange(self.n_users, device=self.device), self.set_ptr[1:] - self.set_ptr[:-1])
+            t = tag[self.set_news.long()]
+            ok = (t >= 0) & (t < n_tags)
+            out[user[ok], t[ok]] = True
+        return out
+
+    def heldout_users(self):
+        """int64 host array: the user of every sample of ``heldout_samples()``, in the same order."""
+        user_ptr = self.user_ptr.cpu().numpy()
+        return np.asarray([u for u in np.flatnonzero(self.live_users) if int(user_ptr[u] + self._train_len[u]) < int(user_ptr[u + 1])],
+                          dtype=np.int64)
+
     def batch(self, rows):
         b = DeviceFeed.batch(self, rows)
         if self.negatives == "adaptive":

@@ -111,6 +111,24 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+MAX_TAGS = 512          # nrms_topk_dot_tagged / nrms_rank_dot_tagged: 1 <= n_tags <= 512
+
+
+def pack_tag_mask(allow):
+    """allow bool [B, n_tags] -> int32 [B, ceil(n_tags / 32)], the packed sets nrms_topk_dot_tagged reads: tag t of user b is bit
+    t & 31 of word [b, t >> 5] (bit 31 is the int32's sign bit); the bits past n_tags in the last word are zero.  Torch ops on
+    allow's device, no host synchronisation."""
+    if not torch.is_tensor(allow) or allow.dim() != 2 or allow.dtype != torch.bool:
+        raise ValueError("pack_tag_mask: allow must be a bool [B, n_tags] tensor (got %s)"
+                         % (("%s %s" % (tuple(allow.shape), allow.dtype)) if torch.is_tensor(allow) else type(allow).__name__))
+    B, n_tags = allow.shape
+    W = (n_tags + 31) // 32
+    bits = torch.zeros(B, W * 32, dtype=torch.int64, device=allow.device)
+    bits[:, :n_tags] = allow
+    word = (bits.view(B, W, 32) << torch.arange(32, dtype=torch.int64, device=allow.device)).sum(dim=2)      # in [0, 2^32)
+    return (word - ((word >> 31) << 32)).to(torch.int32)
+
+
 def impression_metrics(lib, device, scores, labels, lens, ks=(5, 10), ranks=False):
     """NRMSEngine.impression_metrics without an engine (evaluation.score_submission): ``lib`` is _lib.load()."""
     k_a, k_b = (int(k) for k in ks)
@@ -882,6 +900,84 @@ class NRMSEngine:
                                     _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
         _lib.check(rc, "nrms_topk_dot")
         return scores, ids
+
+    def _tag_args(self, who, item_tag, n_tags, allow, N, B, dev):
+        """The checked tag set of top_k_tagged / rank_of_tagged -> (item_tag [N] int32, allow [B, W] int32), contiguous, on the
+        device.  item_tag may be int64 (values outside int32 become -1, which is open to nobody, on the device); allow may be the
+        bool [B, n_tags] matrix (packed here by pack_tag_mask) or the packed int32 [B, W], W = ceil(n_tags / 32)."""
+        n_tags = int(n_tags)
+        if not 1 <= n_tags <= MAX_TAGS:
+            raise _lib.NrmsError("%s: n_tags must be in [1, %d] (n_tags=%d)" % (who, MAX_TAGS, n_tags))
+        if (not torch.is_tensor(item_tag) or tuple(item_tag.shape) != (N,) or item_tag.dtype not in (torch.int32, torch.int64)
+                or item_tag.device != dev):
+            got = ("%s %s on %s" % (tuple(item_tag.shape), item_tag.dtype, item_tag.device)) if torch.is_tensor(item_tag) else type(item_tag).__name__
+            raise _lib.NrmsError("%s: item_tag must be an int32 (or int64) [%d] tensor on %s (got %s)" % (who, N, self.device, got))
+        if item_tag.dtype == torch.int64:
+            item_tag = torch.where((item_tag < 0) | (item_tag >= n_tags), torch.full_like(item_tag, -1), item_tag).to(torch.int32)
+        W = (n_tags + 31) // 32
+        ok = torch.is_tensor(allow) and allow.dim() == 2 and allow.shape[0] == B and allow.device == dev
+        if ok and allow.dtype == torch.bool and allow.shape[1] == n_tags:
+            allow = pack_tag_mask(allow)
+        elif not (ok and allow.dtype == torch.int32 and allow.shape[1] == W):
+            got = ("%s %s on %s" % (tuple(allow.shape), allow.dtype, allow.device)) if torch.is_tensor(allow) else type(allow).__name__
+            raise _lib.NrmsError("%s: allow must be a bool [%d, %d] or a packed int32 [%d, %d] tensor on %s (got %s)"
+                                 % (who, B, n_tags, B, W, self.device, got))
+        return item_tag.contiguous(), allow.contiguous(), n_tags
+
+    def top_k_tagged(self, user_vec, items, k, item_tag, n_tags, allow, exclude=None, bias=None):
+        """top_k inside a per-user set of item tags -> (scores [B, k] fp32, ids [B, k] int64).  item_tag [N] int32 (device): one tag
+        per item; allow: bool [B, n_tags] or the packed int32 [B, ceil(n_tags / 32)] of pack_tag_mask (device): user b only gets
+        items with 0 <= item_tag[n] < n_tags whose tag b allows (a tag outside that range, e.g. -1, is open to nobody; an all-False
+        row is all padding).  Scores, order, padding, exclude and bias are top_k's, bit for bit; 1 <= n_tags <= 512
+        (nrms_topk_dot_tagged; include/nrms_hip.h states the contract)."""
+        who = "top_k_tagged"
+        k = int(k)
+        B, N, d, exclude, n_ex, _, _ = self._top_k_args(who, user_vec, items, exclude, bias, None, None)
+        item_tag, allow, n_tags = self._tag_args(who, item_tag, n_tags, allow, N, B, self._cuda_device())
+        nbytes = self.lib.nrms_topk_dot_tagged_workspace_bytes(B, N, d, k)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (who, B, N, d, k))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot_tagged(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                           _lib.ptr(item_tag), n_tags, _lib.ptr(allow), _lib.ptr(exclude), n_ex, _lib.ptr(scores),
+                                           _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_topk_dot_tagged")
+        return scores, ids
+
+    def rank_of_tagged(self, user_vec, items, targets, item_tag, n_tags, allow, exclude=None, bias=None):
+        """rank_of inside a per-user set of item tags -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position of
+        every target in top_k_tagged's order.  item_tag, n_tags and allow are top_k_tagged's; ranks count the items open to user b
+        only, and a target closed by its tag gets rank 0 / -inf like an excluded one.  Wider ``targets`` go in column chunks of 32
+        (nrms_rank_dot_tagged; include/nrms_hip.h states the contract)."""
+        who = "rank_of_tagged"
+        self._check_tensor(who, "targets", targets, torch.int64, 2)
+        B, N, d, exclude, n_ex, _, _ = self._top_k_args(who, user_vec, items, exclude, bias, None, None)
+        if targets.shape[0] != B:
+            raise _lib.NrmsError("%s: targets must be [%d, T] (got %s)" % (who, B, tuple(targets.shape)))
+        item_tag, allow, n_tags = self._tag_args(who, item_tag, n_tags, allow, N, B, self._cuda_device())
+        T_all = targets.shape[1]
+        ranks = torch.empty(B, T_all, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, T_all, dtype=torch.float32, device=self.device)
+        for t0 in range(0, T_all, 32):
+            T = min(32, T_all - t0)
+            whole = T == T_all
+            tg = targets if whole else targets[:, t0:t0 + T].contiguous()
+            rk = ranks if whole else torch.empty(B, T, dtype=torch.int32, device=self.device)
+            sc = scores if whole else torch.empty(B, T, dtype=torch.float32, device=self.device)
+            nbytes = self.lib.nrms_rank_dot_tagged_workspace_bytes(B, N, d, T, n_ex)
+            if nbytes == 0:
+                raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, T=%d, n_exclude=%d)" % (who, B, N, d, T, n_ex))
+            ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+            rc = self.lib.nrms_rank_dot_tagged(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                               _lib.ptr(item_tag), n_tags, _lib.ptr(allow), _lib.ptr(tg), _lib.ptr(exclude), n_ex,
+                                               _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_rank_dot_tagged")
+            if not whole:
+                ranks[:, t0:t0 + T] = rk
+                scores[:, t0:t0 + T] = sc
+        return ranks, scores
 
     def _top_k_args(self, who, user_vec, items, exclude, bias, item_time, window):
         """The checks top_k_after and top_k_deep share with top_k -> (B, N, d, exclude, n_exclude, item_time, window)."""

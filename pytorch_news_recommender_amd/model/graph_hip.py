@@ -259,6 +259,16 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: recommend_sections is not available: a candidate's score depends on its neighbours in "
                                   "the click graph, not on a catalogue row alone (no recommend either)")
 
+    CATALOGUE_TAGS = False
+
+    def recommend_tagged(self, batch, k, catalogue, item_tag, allow, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("graph: recommend_tagged is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone (no recommend either, inside a tag set or outside)")
+
+    def rank_targets_tagged(self, batch, targets, catalogue, item_tag, allow, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("graph: rank_targets_tagged is not available: a candidate's score depends on its neighbours in "
+                                  "the click graph, not on a catalogue row alone (no rank_targets either)")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

@@ -384,6 +384,17 @@ class Model(FlatHipModel):
                                   "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_topk_sections_dot scores every "
                                   "section with one user row")
 
+    CATALOGUE_TAGS = False
+
+    def recommend_tagged(self, batch, k, catalogue, item_tag, allow, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("hierec: recommend_tagged is not available: HieRec scores the catalogue with a query per (topic, "
+                                  "sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no per-user tag set")
+
+    def rank_targets_tagged(self, batch, targets, catalogue, item_tag, allow, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("hierec: rank_targets_tagged is not available: HieRec scores the catalogue with a query per "
+                                  "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot_tagged ranks plain dot "
+                                  "products only")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import FlatLayout, ModelDims, NRMSEngine, PackedCatalogue
+from ..engine import FlatLayout, ModelDims, NRMSEngine, PackedCatalogue, pack_tag_mask  # noqa: F401 (pack_tag_mask: for callers)
 from ._flat_model import FlatHipModel
 
 PAGE_BEGIN = -2          # recommend_page: the cursor id of a row that starts over (include/nrms_hip.h NRMS_CURSOR_BEGIN)
@@ -456,6 +456,58 @@ class Model(FlatHipModel):
         # rows 1.. as in recommend: news id n is row n - 1, so id 0 (and -1) fall out of range and get rank 0
         return self._engine.rank_of(user, cat[1:], (tg - 1).contiguous(), exclude, bias=bias, **win)
 
+    @staticmethod
+    def _tag_rows(item_tag, allow, cat, B, who):
+        """The kernels' view of a per-user tag set -> (item_tag rows 1.. like the catalogue's, n_tags, allow) for
+        engine.top_k_tagged / rank_of_tagged (which check dtypes and pack a bool ``allow``).  n_tags is read off a bool ``allow``;
+        a packed int32 [B, W] one stands for n_tags = 32 W."""
+        N = cat.shape[0]
+        if (not torch.is_tensor(item_tag) or tuple(item_tag.shape) != (N,) or item_tag.dtype not in (torch.int32, torch.int64)
+                or item_tag.device != cat.device):
+            got = ("%s %s on %s" % (tuple(item_tag.shape), item_tag.dtype, item_tag.device)) if torch.is_tensor(item_tag) \
+                else type(item_tag).__name__
+            raise _lib.NrmsError("%s: item_tag must be an int32 or int64 [%d] tensor on %s, indexed by news id like the catalogue "
+                                 "(got %s)" % (who, N, cat.device, got))
+        if (not torch.is_tensor(allow) or allow.dim() != 2 or allow.shape[0] != B or allow.shape[1] < 1
+                or allow.dtype not in (torch.bool, torch.int32) or allow.device != cat.device):
+            got = ("%s %s on %s" % (tuple(allow.shape), allow.dtype, allow.device)) if torch.is_tensor(allow) else type(allow).__name__
+            raise _lib.NrmsError("%s: allow must be a bool [%d, n_tags] tensor, or pack_tag_mask's int32 [%d, W], on %s (got %s)"
+                                 % (who, B, B, cat.device, got))
+        n_tags = allow.shape[1] * (1 if allow.dtype == torch.bool else 32)
+        return item_tag.contiguous()[1:], n_tags, allow
+
+    @torch.no_grad()
+    def recommend_tagged(self, batch, k, catalogue, item_tag, allow, exclude_history=True, *, item_bias=None):
+        """recommend inside a per-user set of news tags -> (news_ids [B, k] int64, scores [B, k] fp32): "never show me sports",
+        "only the topics I follow", an edition, a publisher block (include/nrms_hip.h nrms_topk_dot_tagged).  Parity is unpinned:
+        the reference has no catalogue retrieval.
+
+        item_tag: int [N] on the model's device, one tag per news id like the catalogue (entry 0 is never read), e.g.
+        ``DeviceFeed.news_info()["categ"]``; a tag outside [0, n_tags), e.g. -1, is served to nobody.  allow: bool [B, n_tags]
+        (user b may see tag t iff allow[b, t]), or its packed form pack_tag_mask(allow), int32 [B, W]; n_tags <= 512.  An
+        all-False row gives an all-padding row.  Row b is recommend's full ranking for user b filtered to the tags b allows and
+        cut at k: the same user vector, score bits, exclusions, tie rule and ``item_bias``; rank_targets_tagged of its ids gives
+        1, 2, ...  Not combined with a time window, the diversity re-ranking, paging or the fp16 shortlist."""
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "recommend_tagged")
+        bias = self._item_bias_rows(item_bias, cat, "recommend_tagged")
+        tags, n_tags, allow = self._tag_rows(item_tag, allow, cat, user.shape[0], "recommend_tagged")
+        scores, ids = self._engine.top_k_tagged(user, cat[1:], k, tags, n_tags, allow, exclude, bias=bias)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    @torch.no_grad()
+    def rank_targets_tagged(self, batch, targets, catalogue, item_tag, allow, exclude_history=True, *, item_bias=None):
+        """rank_targets among the news each user may see -> (ranks [B, T] int32, scores [B, T] fp32): the 1-based place of news id
+        targets[b, j] in recommend_tagged's list for user b were k unbounded (include/nrms_hip.h nrms_rank_dot_tagged).  A target
+        whose tag user b does not allow comes back as rank 0 / score -inf, like every target rank_targets cannot rank.  item_tag
+        and allow are recommend_tagged's, every other argument is rank_targets'."""
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, "rank_targets_tagged")
+        bias = self._item_bias_rows(item_bias, cat, "rank_targets_tagged")
+        tags, n_tags, allow = self._tag_rows(item_tag, allow, cat, user.shape[0], "rank_targets_tagged")
+        tg = torch.as_tensor(targets).to(user.device, dtype=torch.int64)
+        if tg.dim() != 2 or tg.shape[0] != user.shape[0]:
+            raise _lib.NrmsError("rank_targets_tagged: targets must be [%d, T] news ids (got %s)" % (user.shape[0], tuple(tg.shape)))
+        return self._engine.rank_of_tagged(user, cat[1:], (tg - 1).contiguous(), tags, n_tags, allow, exclude, bias=bias)
+
     @torch.no_grad()
     def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):
         """Why these news: each score split exactly over the clicks of the user's history -> (reason_ids [B, K, m] int64,
@@ -670,6 +722,7 @@ class Model(FlatHipModel):
     CATALOGUE_PAGING = True             # ... and paged through with a cursor: recommend_page / recommend_deep (run_v0 --recommend_deep)
     CATALOGUE_EXPLAIN = True            # ... and split over the clicks of the history: explain (run_v0 --explain)
     CATALOGUE_LIKELIHOOD = True         # ... and normalised over the catalogue: log_partition / log_prob (run_v0 --retrieval_nll)
+    CATALOGUE_TAGS = True               # ... and restricted to a per-user tag set: recommend_tagged / rank_targets_tagged (run_v0 --only_categories)
 
     def check_recommend_ids(self):
         """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read

@@ -110,7 +110,56 @@ def build_parser():
                         "clicks of the user's history that contribute most to its score (1 <= M <= 8; model.explain), to "
                         '<recommend_out>.reasons; reads the final ids only, so it goes with --diversity, --popularity_prior, '
                         '--catalogue_window and --coarse_catalogue (not with --sections or --recommend_deep)')
+    parser.add_argument('--only_categories', type=str, default=None, metavar='own|ID[,ID...]', help='--recommend / --retrieval_metrics: '
+                        "serve and rank inside a per-user set of news categories (model.recommend_tagged / rank_targets_tagged).  own: "
+                        "the categories of the user's own training clicks (a click log) or history; ID[,ID...]: the same category ids "
+                        'for everybody.  Combines with --mute_categories (allow = only minus mute) and --popularity_prior; not with '
+                        '--catalogue_window, --coarse_catalogue, --recommend_deep, --sections, --diversity, --retrieval_nll or --explain')
+    parser.add_argument('--mute_categories', type=str, default=None, metavar='ID[,ID...]', help='--recommend / --retrieval_metrics: never '
+                        'serve these news categories, and rank the held-out clicks among the others (see --only_categories)')
     return parser
+
+
+def check_tag_args(args):
+    """--only_categories / --mute_categories fail before any data is read or any step is trained: category ids >= 0 (or "own"), a
+    list or a metric to apply them to, a model that serves inside a tag set, and none of the paths the tagged kernels do not have.
+    Returns (only, mute): only = None, 'own' or a tuple of ids; mute = None or a tuple of ids."""
+    only = mute = None
+    for flag, text in (('--only_categories', args.only_categories), ('--mute_categories', args.mute_categories)):
+        if text is None:
+            continue
+        if flag == '--only_categories' and text == 'own':
+            only = 'own'
+            continue
+        try:
+            ids = tuple(int(v) for v in text.split(','))
+        except ValueError:
+            raise SystemExit('%s %s: category ids expected (got %r)' % (flag, 'own|ID[,ID...]' if flag == '--only_categories' else 'ID[,ID...]', text))
+        if not ids or min(ids) < 0:
+            raise SystemExit('%s: every category id must be >= 0 (got %r)' % (flag, text))
+        if flag == '--only_categories':
+            only = ids
+        else:
+            mute = ids
+    if only is None and mute is None:
+        return None, None
+    flag = '--only_categories' if only is not None else '--mute_categories'
+    if args.recommend is None and args.retrieval_metrics is None:
+        raise SystemExit('%s: the categories of --recommend K and --retrieval_metrics K (give one of them)' % flag)
+    for other, on in (('--catalogue_window', args.catalogue_window is not None),
+                      ('--coarse_catalogue', args.coarse_catalogue or args.coarse_shortlist is not None),
+                      ('--recommend_deep', args.recommend_deep is not None), ('--sections', args.sections is not None),
+                      ('--diversity', args.diversity is not None or args.shortlist is not None),
+                      ('--retrieval_nll', args.retrieval_nll is not None), ('--explain', args.explain is not None)):
+        if on:
+            raise SystemExit('%s: the tagged calls serve and rank the plain or the biased list only (drop %s)' % (flag, other))
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_TAGS', False):
+        raise SystemExit('%s: model %r cannot serve inside a per-user tag set (its catalogue score is no plain dot product over a '
+                         'row-ordered catalogue)' % (flag, args.model))
+    return only, mute
 
 
 def check_explain_args(args):
@@ -379,6 +428,7 @@ def main(argv=None):
     retrieval_nll = check_nll_args(args)
     check_prior_args(args)
     check_window_args(args)
+    tag_only, tag_mute = check_tag_args(args)
     check_graph_args(args)
     check_negatives_args(args)
     check_loss_args(args)
@@ -457,6 +507,38 @@ def main(argv=None):
     item_window = {}         # item_time / request_time / window_span with --catalogue_window, otherwise no keyword at all
     explain = {} if args.explain is None else {'explain': args.explain}       # otherwise no keyword at all
     item_prior = {}          # item_bias = the click feed's popularity prior with --popularity_prior, otherwise no keyword at all
+    click_feed = []          # the ClickFeed of --negatives catalogue / adaptive, once it exists
+
+    def tag_sets(samples, categ):
+        # item_tag / allow_tags with --only_categories / --mute_categories, otherwise no keyword at all
+        if tag_only is None and tag_mute is None:
+            return {}
+        n_tags = int(config.category_nums)
+        for flag, ids in (('--only_categories', tag_only), ('--mute_categories', tag_mute)):
+            if isinstance(ids, tuple) and max(ids) >= n_tags:
+                raise SystemExit('%s: category ids must be below %d (got %r)' % (flag, n_tags, ids))
+        if not 1 <= n_tags <= 512:
+            raise SystemExit('--only_categories / --mute_categories: 1 <= the number of categories <= 512 (got %d)' % n_tags)
+        allow = torch.zeros(len(samples), n_tags, dtype=torch.bool)
+        if tag_only == 'own':
+            if click_feed and samples is click_feed[0][1]:
+                # a click log: every category the user clicked in the training part, never the held-out click's
+                feed = click_feed[0][0]
+                allow = feed.clicked_tags(categ, n_tags)[torch.from_numpy(feed.heldout_users()).to(categ.device)].cpu()
+            else:
+                for i, smp in enumerate(samples):
+                    allow[i, [c for c in smp[1] if 0 <= c < n_tags]] = True
+        elif tag_only is not None:
+            allow[:, list(tag_only)] = True
+        else:
+            allow[:] = True
+        if tag_mute is not None:
+            allow[:, list(tag_mute)] = False
+        return {'item_tag': categ, 'allow_tags': allow}
+
+    def tag_words():
+        return ', '.join(w for w in ('only ' + ('own' if tag_only == 'own' else ','.join(map(str, tag_only))) if tag_only is not None else '',
+                                     'mute ' + ','.join(map(str, tag_mute)) if tag_mute is not None else '') if w)
 
     def recommend_top(samples):
         # the catalogue is the feed's title table (row r = news id r), so this step always runs on a DeviceFeed
@@ -476,6 +558,20 @@ def main(argv=None):
                             coarse_shortlist=args.coarse_shortlist, **explain)
             st = (recommender.model if hasattr(recommender, 'model') else recommender).last_coarse_stats
             print('coarse catalogue: certified share: {:.4f}  users: {}'.format(st['certified'], st['n_users']))
+            return out
+        tags = tag_sets(samples, feed.news_info()['categ'])
+        if tags:
+            out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior, **tags)
+            # read the file back: every served id has to carry a category its sample allows
+            categ, allow = tags['item_tag'].cpu().numpy(), tags['allow_tags'].numpy()
+            filled = outside = 0
+            with open(out) as f:
+                for i, line in enumerate(f):
+                    ids = [int(v) for v in line.split(' ', 1)[1].strip()[1:-1].split(',') if v]
+                    filled += len(ids)
+                    outside += sum(1 for n in ids if not (0 <= categ[n] < allow.shape[1] and allow[i, categ[n]]))
+            print('recommend inside per-user categories ({}): {} users, {} of {} slots filled, {} outside the allowed categories'.format(
+                tag_words(), len(samples), filled, len(samples) * args.recommend, outside))
             return out
         if args.diversity is None:
             return recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
@@ -499,7 +595,8 @@ def main(argv=None):
         needs_info = 'categ' in inspect.signature(net.encode_catalogue).parameters           # nrms_naml's feature rows
         return evaluate_retrieval(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
                                   news_info=feed.news_info() if needs_info else None, **item_prior, **item_window,
-                                  **({} if retrieval_nll is None else {'nll_temperatures': retrieval_nll}))
+                                  **({} if retrieval_nll is None else {'nll_temperatures': retrieval_nll}),
+                                  **tag_sets(samples, feed.news_info()['categ']))
 
     def attach_graph(feed, samples=None):
         # the click graph is replicated: every rank builds it from ALL training samples (users shard, the graph does not)
@@ -530,6 +627,7 @@ def main(argv=None):
             if args.negatives == 'adaptive':
                 train_feed.attach_scorer(recommender)
             held_samples, held_labels = train_feed.heldout_samples()
+            click_feed.append((train_feed, held_samples))
             if args.catalogue_window is not None:
                 item_window.update(item_time=train_feed.news_first_seen(), request_time=train_feed.heldout_times(),
                                    window_span=args.catalogue_window)

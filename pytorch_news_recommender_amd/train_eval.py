@@ -329,6 +329,36 @@ def test(config, model, data_iter, test_list_nums=None, ckpt_file=None, out_file
     return file_name
 
 
+class _TagSets:
+    """The tag keywords of recommend() / evaluate_retrieval(), turned into ``model.recommend_tagged`` / ``rank_targets_tagged``
+    arguments batch by batch: item_tag int [N] by news id on the model's device, allow_tags bool [n_samples, n_tags] (numpy or
+    torch), one row per sample of data_iter in its order.  Both or neither (ValueError); with tags, the keywords of ``refused``
+    that were given raise a ValueError that names them: the tagged kernels have no time window, cursor, fp16 shortlist, diversity
+    re-ranking, log-partition or attribution form."""
+
+    def __init__(self, who, item_tag, allow_tags, refused):
+        self.on = item_tag is not None and allow_tags is not None
+        if (item_tag is None) != (allow_tags is None):
+            raise ValueError("%s: item_tag and allow_tags go together (item_tag %s, allow_tags %s)"
+                             % (who, "missing" if item_tag is None else "given", "missing" if allow_tags is None else "given"))
+        if not self.on:
+            return
+        for name, given in refused:
+            if given:
+                raise ValueError("%s: %s does not go with item_tag / allow_tags: the tagged calls serve and rank the plain or "
+                                 "the biased list only" % (who, name))
+        self.who, self.item_tag = who, item_tag
+        self.allow = torch.as_tensor(allow_tags)
+        if self.allow.dim() != 2 or self.allow.dtype != torch.bool:
+            raise ValueError("%s: allow_tags must be bool [n_samples, n_tags] (got %s %s)"
+                             % (who, tuple(self.allow.shape), self.allow.dtype))
+
+    def of(self, done, B, dev):
+        if done + B > self.allow.shape[0]:
+            raise ValueError("%s: %d allow_tags rows for %d samples" % (self.who, self.allow.shape[0], done + B))
+        return self.item_tag, self.allow[done:done + B].to(dev)
+
+
 class _RequestWindows:
     """The time-window keywords of recommend() / evaluate_retrieval(), turned into ``model.recommend`` / ``rank_targets`` keywords
     batch by batch: sample i is served inside [request_time[i] - window_span, request_time[i] + 1), clamped to int32.  All three or
@@ -359,7 +389,7 @@ class _RequestWindows:
 
 def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
               shortlist=None, item_bias=None, item_time=None, request_time=None, window_span=None, coarse=False,
-              coarse_shortlist=None, explain=None):
+              coarse_shortlist=None, item_tag=None, allow_tags=None, explain=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
@@ -386,6 +416,12 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     ``net.last_coarse_stats = {"certified": share of the users whose row the certificate covered, "n_users": users}`` (None
     without ``coarse``, when the model is called exactly as before).  Not with diversity, item_bias or a time window (ValueError).
 
+    item_tag / allow_tags (both or neither): a set of news tags per sample, ``model.recommend_tagged``.  item_tag: int [N] by news
+    id on the model's device (``DeviceFeed.news_info()["categ"]``); allow_tags: bool [n_samples, n_tags], one row per sample of
+    data_iter in its order (``ClickFeed.clicked_tags``): sample i only gets news whose tag it allows.  With or without item_bias;
+    not with diversity, coarse, a time window or explain (ValueError naming the keyword).  None: the model is called exactly as
+    before.
+
     explain = m in [1, 8]: also writes ``<file name>.reasons`` and leaves its name in ``net.last_explain_file`` (None without
     ``explain``, when the model is called and the list is written exactly as before; the list file is the same either way).  One
     line per recommended news, in the order of the list file:
@@ -395,6 +431,11 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     largest first, negative ones included.  Numbers are written with 9 significant digits, which names every float32: two runs
     give the same bytes.  Needs a model with ``CATALOGUE_EXPLAIN`` (ValueError otherwise, before anything is encoded)."""
     net = _inner(model)
+    tags = _TagSets("recommend", item_tag, allow_tags, (("diversity", diversity is not None or shortlist is not None),
+                                                        ("coarse", bool(coarse) or coarse_shortlist is not None),
+                                                        ("item_time / request_time / window_span", item_time is not None
+                                                         or request_time is not None or window_span is not None),
+                                                        ("explain", explain is not None)))
     if explain is not None:
         if not getattr(net, "CATALOGUE_EXPLAIN", False):
             raise ValueError("recommend: explain needs a model whose score is one additive-attention sum over the clicks of the "
@@ -431,6 +472,14 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
             lines.extend(ids.cpu().tolist())
             note(datas, ids)
         net.last_coarse_stats = {"certified": int(n_cert.item()) / n_users if n_users else float("nan"), "n_users": n_users}
+    elif tags.on:
+        net.last_recommend_stats = None
+        for datas in data_iter:
+            B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
+            tag, allow = tags.of(done, B, catalogue.device)
+            done += B
+            ids, _ = net.recommend_tagged(datas, k, catalogue, tag, allow, exclude_history=exclude_history, **prior)
+            lines.extend(ids.cpu().tolist())
     elif diversity is None:
         net.last_recommend_stats = None
         for datas in data_iter:
@@ -549,7 +598,8 @@ def recommend_sections(config, model, data_iter, titles, k, sections, out_file=N
 
 
 def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
-                       verbose=True, item_bias=None, item_time=None, request_time=None, window_span=None, nll_temperatures=None):
+                       verbose=True, item_bias=None, item_time=None, request_time=None, window_span=None, nll_temperatures=None,
+                       item_tag=None, allow_tags=None):
     """Full-catalogue retrieval quality on held-out clicks: per impression of data_iter the targets are its clicked news (the
     ``candidate_ids`` whose label in y_true is 1) and each is ranked against the whole catalogue in recommend()'s own order
     (``model.rank_targets``: the exact position, at any depth).  titles / news_info / exclude_history as in recommend();
@@ -575,9 +625,19 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     ones ``n_targets`` counts) of -log softmax(score / T + item_bias)[target]}, the softmax running over every news the user
     could be recommended (``model.log_prob``; item_bias enters with scale 1), accumulated on the device.  There is no windowed
     partition yet: together with item_time / window_span this raises ValueError.  None: nothing changes, the keyword is not
-    passed on and ``nll`` is absent."""
+    passed on and ``nll`` is absent.
+
+    item_tag / allow_tags (both or neither, else ValueError): recommend()'s per-sample tag sets.  Sample i's targets are ranked
+    against the news whose tag it allows only (``model.rank_targets_tagged``): Recall@K and MRR "among the news this user may see".
+    A held-out target closed by its tag counts as skipped, like one outside its window; the result gains ``n_closed``, the number of
+    targets that are skipped for that reason alone (they are in the catalogue, their tag is closed).  Not with a time window or
+    nll_temperatures (ValueError naming the keyword).  None: no new keyword reaches the model, the result has no ``n_closed``."""
     net = _inner(model)
     prior = {} if item_bias is None else {"item_bias": item_bias}
+    tags = _TagSets("evaluate_retrieval", item_tag, allow_tags, (("item_time / request_time / window_span", item_time is not None
+                                                                  or request_time is not None or window_span is not None),
+                                                                 ("nll_temperatures", nll_temperatures is not None)))
+    n_closed = None
     nll_t = None
     if nll_temperatures is not None:
         if item_time is not None or request_time is not None or window_span is not None:
@@ -611,7 +671,17 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
         lab = torch.from_numpy(lab).to(dev)
         order = torch.argsort((~lab).to(torch.uint8), dim=1, stable=True)[:, :T]
         tg = torch.where(lab.gather(1, order), cand[:, :width].gather(1, order), torch.full_like(order, -1))
-        rk, _ = net.rank_targets(datas, tg, catalogue, exclude_history=exclude_history, **prior)
+        if tags.on:
+            tag, allow = tags.of(done - B, B, dev)
+            rk, _ = net.rank_targets_tagged(datas, tg, catalogue, tag, allow, exclude_history=exclude_history, **prior)
+            # a target of the catalogue whose tag its sample does not allow (on the device, no synchronisation)
+            in_cat = (tg >= 1) & (tg < catalogue.shape[0])
+            t_tag = tag.to(torch.int64)[tg.clamp(0, catalogue.shape[0] - 1)]
+            t_open = (t_tag >= 0) & (t_tag < allow.shape[1]) & allow.gather(1, t_tag.clamp(0, allow.shape[1] - 1))
+            closed = (in_cat & ~t_open).sum()
+            n_closed = closed if n_closed is None else n_closed + closed
+        else:
+            rk, _ = net.rank_targets(datas, tg, catalogue, exclude_history=exclude_history, **prior)
         ranks.append(rk)
         targets.append(tg)
         if nll_t is not None:
@@ -637,13 +707,18 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     vals.append(bad.double() if bad is not None else n_users.double() * 0)
     if nll_t is not None:
         vals = list(nll_sum / n_targets.clamp(min=1).double()) + vals
+    if tags.on:                                                # (never together with nll_temperatures)
+        vals = [n_closed.double() if n_closed is not None else n_users.double() * 0] + vals
     vals = torch.stack(vals).cpu().tolist()                    # the one host synchronisation
+    closed = int(vals.pop(0)) if tags.on else None
     nll = None if nll_t is None else dict(zip(nll_t, vals[:len(nll_t)]))
     vals = vals[len(nll_t or ()):]
     net.engine.check_ids()                                     # (its count is on the host by now)
     if vals.pop():
         net.check_recommend_ids()                              # raises: browsed ids outside the catalogue
     res = dict(zip(names, vals[:len(names)]))
+    if tags.on:
+        res["n_closed"] = closed
     res["median_rank"] = vals[-4]
     res["n_users"], res["n_targets"], res["n_skipped"] = int(vals[-3]), int(vals[-2]), int(vals[-1])
     if not res["n_users"]:
@@ -657,5 +732,6 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
               + "  ".join("{}: {:.4f}".format(k, res[k]) for k in names)
               + "  median rank: {:.1f}  users: {}  targets: {}  skipped: {}".format(res["median_rank"], res["n_users"],
                                                                                    res["n_targets"], res["n_skipped"])
+              + ("  closed by tag: {}".format(res["n_closed"]) if tags.on else "")
               + "".join("  nll@T={:g}: {:.4f}".format(t, v) for t, v in (res.get("nll") or {}).items()))
     return res
