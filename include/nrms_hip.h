@@ -596,6 +596,44 @@ int nrms_rank_dot_tagged(int32_t B, int64_t N, int32_t d, int32_t T, const float
                          const uint32_t* allow /* [B, W] */, const int64_t* targets, const int64_t* exclude, int32_t n_exclude,
                          int32_t* ranks, float* target_scores, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Per-category caps on the served list (a front page: "at most two stories per category in my ten", "one politics story at
+ * most for this user"; PARITY UNPINNED, the reference has no catalogue retrieval) ----
+ * nrms_topk_dot_biased with a hard cap per item tag and user, exact, in one scan of the row-ordered catalogue.  item_tag [N] int32:
+ * one tag per item; cap [B, n_tags] int32: the most items of tag t that row b may hold; both REQUIRED and 4-byte aligned.  bias [N]
+ * fp32, 4-byte aligned, NULLABLE: NULL means no prior, s' = s.  Every other argument is the biased call's.
+ * Greedy rule.  Walk user b's complete ranking under nrms_topk_dot_biased's rules: the same score bits s, one fp32 add for the prior
+ *   (s' = s + bias[n]), a NaN s' removes the item, so does the exclude list, s' descending (+inf first), equal s' put the SMALLER n
+ *   first, -0.0 equals +0.0 (returned as +0.0).  Item n with tag t = item_tag[n] is TAKEN iff 0 <= t < n_tags and fewer than
+ *   cap[b, t] items of tag t were taken before it.  The first k taken items are row b, followed by id -1 / score -inf.
+ * Tags and caps.  A tag outside [0, n_tags) is served to nobody (nrms_topk_dot_tagged's rule: -1 is "untagged, never served").
+ *   cap <= 0 closes the tag for that user; cap >= k leaves it uncapped.
+ * Limits: 1 <= k <= 256, 1 <= n_tags <= 512, N, d, B and n_exclude as in nrms_topk_dot; B = 0 is a no-op, N = 0 writes
+ *   all-padding rows.
+ * Consequences.
+ *   (1) Every cap >= k gives nrms_topk_dot_tagged with all tags open, bit for bit; with every tag in [0, n_tags) that is the plain /
+ *       biased call.
+ *   (2) Every cap in {0} u [k, inf) (and every cap < 0 read as 0) gives nrms_topk_dot_tagged with allow = cap > 0, bit for bit.
+ *   (3) The first k' columns of a call with k are the call with k': the greedy walk does not depend on k.
+ *   (4) No row holds more than max(cap[b, t], 0) ids of tag t.
+ *   (5) Row b depends on user row b and cap row b only: not on B, the row's position in the batch, the other rows' caps, the launch
+ *       geometry, what the workspace held or the run.
+ *   (6) For N <= 4096, row b equals the greedy walk over row b of nrms_topk_dot_deep (K = 4096) under the same prior and exclude
+ *       list, ids and score bits alike.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_capped: ..."); n_tags outside [1, 512] and
+ *   a NULL or misaligned item_tag (N > 0) or cap are among them.  An undersized workspace returns NRMS_EWORKSPACE.  Nothing is
+ *   launched after an error.
+ * Workspace: nrms_topk_dot_capped_workspace_bytes returns exactly nrms_topk_dot_workspace_bytes(B, N, d, k) (0 = arguments
+ *   rejected); 8-byte aligned.
+ * Two kernels on `stream` (the slices, the merge), no host synchronisation, no allocation, no [B, N] matrix; plain vector loads and
+ *   stores, no atomics beyond the integer LDS counters of the uncapped slice kernel.  Why one scan is exact: with C(S) the capped
+ *   list of a set S, C(S1 u S2) = C(C(S1) u C(S2)), and once the capped list of what a user has been shown holds
+ *   k_b = min(k, sum_t min(max(cap[b, t], 0), k)) entries nothing below its smallest entry can enter. */
+size_t nrms_topk_dot_capped_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_capped(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                         const float* bias /* [N], nullable */, const int32_t* item_tag /* [N] */, int32_t n_tags,
+                         const int32_t* cap /* [B, n_tags] */, const int64_t* exclude, int32_t n_exclude, float* top_scores,
+                         int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Paging through the exact ranking: a cursor on the top-k, and lists up to 4096 (candidate generation for a re-ranker, a feed
  * that scrolls: "the next 20 after what I showed"; PARITY UNPINNED, the reference has no catalogue retrieval) ----
  * The order of nrms_topk_dot[_biased|_windowed] is total (s' descending, then the SMALLER n, -0.0 equal to +0.0) and a score's bits

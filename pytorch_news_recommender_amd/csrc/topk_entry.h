@@ -30,6 +30,12 @@ __device__ __forceinline__ uint64_t tk_entry(float s, uint32_t id) {
     return ((uint64_t)u << 32) | (uint64_t)(0xFFFFFFFFu - id);
 }
 
+// The upper half of tk_entry(s, .): the score as an order-preserving 32-bit key.
+__device__ __forceinline__ uint32_t tk_score_key(float s) {
+    const uint32_t u = __float_as_uint(s == 0.0f ? 0.0f : s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 __device__ __forceinline__ float tk_entry_score(uint64_t e) {
     const uint32_t u = (uint32_t)(e >> 32);
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
@@ -181,6 +187,41 @@ __device__ __forceinline__ bool tk_tags_open(TkTags t, long b, int tag) {
     if ((uint32_t)tag >= (uint32_t)t.n_tags) return false;
     const int W = (t.n_tags + 31) >> 5;
     return (t.allow[b * W + (tag >> 5)] >> (tag & 31)) & 1u;
+}
+
+// The per-user tag caps of nrms_topk_dot_capped (include/nrms_hip.h states it): walking user b's ranking, item n is taken iff
+// 0 <= item_tag[n] < n_tags and fewer than cap[b * n_tags + item_tag[n]] items of that tag were taken before it.
+struct TkCaps {
+    const int32_t* item_tag;     // [N]
+    const int32_t* cap;          // [B, n_tags]
+    int n_tags;
+};
+
+// One block's transposed bitmap of the tags that are not closed (CAPS kernels; tk_tags_stage's layout and rules): bit i of ubt[t]
+// is set iff cap[u0 + i, t] > 0.
+__device__ __forceinline__ void tk_caps_stage(uint32_t* ubt, TkCaps t, int u0, int B, int nthreads) {
+    const int nu = min(TK_UT, B - u0);
+    for (int tag = threadIdx.x; tag < t.n_tags; tag += nthreads) {
+        const int32_t* col = t.cap + (long)u0 * t.n_tags + tag;
+        uint32_t m = 0;
+        for (int i = 0; i < nu; ++i) m |= (uint32_t)(col[(long)i * t.n_tags] > 0) << i;
+        ubt[tag] = m;
+    }
+}
+
+// One wave: k_b = min(k, sum over tags of min(max(cap_row[t], 0), k)), the length the capped list of user row cap_row can reach,
+// in bits 0 .. 15, and in bit 16 whether any tag is rationed at all (0 < cap_row[t] < k_b; if none is, the capped list is the
+// best k_b of the open tags).  Once a capped list holds k_b entries nothing below its smallest entry can enter it: k_b = k: k taken
+// items precede it; k_b < k: every open tag is saturated.  Wave-uniform.
+__device__ __forceinline__ int tk_caps_reach(const int32_t* __restrict__ cap_row, int n_tags, int k, int lane) {
+    int sum = 0;
+    for (int t = lane; t < n_tags; t += 64) sum += min(max(cap_row[t], 0), k);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const int kb = min(sum, k);
+    bool rationed = false;
+    for (int t = lane; t < n_tags; t += 64) rationed |= cap_row[t] > 0 && cap_row[t] < kb;
+    return __builtin_amdgcn_readfirstlane(kb | (__ballot(rationed) != 0 ? 0x10000 : 0));
 }
 
 __device__ __forceinline__ float tk_ld(const float* p, int kk, int d) { return kk < d ? p[kk] : 0.0f; }

@@ -106,6 +106,108 @@ __device__ uint64_t tk_select(uint64_t* buf, int& cnt, int k, int lane) {
     return T;
 }
 
+// The selection a filter cuts a full buffer down with: tk_select (the best k), or tk_select_capped (CAPS kernels: the capped best
+// k of one user; cap_row = the user's row of cap, reach = its tk_caps_reach).
+//
+// TkSelectCapped also holds the block's tag thresholds: ttag[i * TT + t], 16 bits per (user row, tag), 0 at the start.  When a flush
+// takes the cap-th entry x of tag t for user i it stores the upper 16 bits of x's score key there (never lowering it): cap items of
+// tag t that beat x have been seen, so an item of tag t whose key's upper 16 bits are BELOW that value lies below all of them and can
+// never be taken; TkFilter::above_tags refuses it before it is offered.  Without this, every item of a saturated tag that beats the
+// user's one threshold (the k_b-th best TAKEN entry, which a cap pushes far down the ranking) floods the buffers only to be dropped
+// by the next flush.  TT tags fit the LDS the P class leaves free (tk_caps_table); a call with more tags runs without the table
+// (ttag null), with the same results.
+struct TkSelectBest {
+    static constexpr bool capped = false;
+};
+template <int TT>
+struct TkSelectCapped {
+    static constexpr bool capped = true;
+    static constexpr int table = TT;
+    const int32_t* item_tag;     // [N]
+    const int32_t* cap;          // [B, n_tags]
+    int n_tags;
+    const int* reach;            // LDS: the block's 32 tk_caps_reach words
+    uint16_t* ttag;              // LDS: the block's [32][TT] tag thresholds, or null
+};
+// The tags whose thresholds fit beside a P class's buffers: 32 x TT x 2 bytes of the LDS the class leaves free.
+constexpr int tk_caps_table(int P) { return P <= 128 ? 512 : P <= 256 ? 192 : 48; }
+
+typedef uint16_t __attribute__((may_alias)) tk_u16_alias;
+
+// One wave: cuts buf[0, cnt) (unsorted, distinct entries, 0 = dropped) down to its capped list C(buf): walking the entries in
+// descending order, an entry is taken iff its tag t lies in [0, n_tags), fewer than cap_row[t] entries of tag t were taken before
+// it and fewer than k entries were taken before it.  reach: the user's tk_caps_reach word, k_b and whether any open tag is
+// rationed at all (0 < cap < k_b).
+//
+// No rationed tag (the caller's filter only ever admits entries of open tags): C(buf) is the best k_b, tk_select's problem.
+// Otherwise: the buffer is sorted descending in place (tk_sort_desc) and read back into registers, 64 ranks per register and E
+// registers per lane, each lane fetching its entries' tags; buf itself then serves as the scratch of n_tags 16-bit counters "room
+// left for this tag", loaded from the user's cap row (P * 8 >= 1024 bytes = 512 counters; no LDS beyond the buffer).  The E chunks
+// are walked in order: a lane whose tag still has room counts the same-tag lanes below it among those that have room too (lane
+// reads over that ballot only: a saturated tag costs nothing), is taken if that count is below the room left, and the last lane
+// of a tag stores what is left after the chunk.  The taken entries are compacted in rank order, so they come out sorted, the first k_b of them.
+//
+// Returns the threshold: 0 until k_b entries are kept, then (at most) the smallest kept entry, below which nothing can enter this
+// user's list any more (tk_caps_reach says why).  Wave-level syncs only: TkFilter::offer calls it between block barriers.
+template <int P>
+__device__ uint64_t tk_select_capped(uint64_t* buf, int& cnt, int reach, int lane, const int32_t* __restrict__ item_tag,
+                                     const int32_t* __restrict__ cap_row, int n_tags, uint16_t* ttag_row = nullptr) {
+    constexpr int E = P / 64;
+    static_assert(P * 8 >= 2 * TK_MAX_TAGS, "the buffer holds one 16-bit counter per tag");
+    const int kb = max(reach & 0xFFFF, 1);
+    if (!(reach >> 16)) return tk_select<P>(buf, cnt, kb, lane);
+    tk_flush<P>(buf, __builtin_amdgcn_readfirstlane(cnt), 1, lane);          // padded with 0, sorted descending
+    uint64_t v[E];
+    int tg[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        v[e] = buf[64 * e + lane];
+        tg[e] = -1;
+        if (v[e]) {
+            const int t = item_tag[tk_entry_id(v[e])];
+            if ((uint32_t)t < (uint32_t)n_tags) tg[e] = t;
+        }
+    }
+    tk_wave_sync();                                  // every entry is in a register: buf becomes the counters
+    tk_u16_alias* room = reinterpret_cast<tk_u16_alias*>(buf);          // room[t]: how many more entries of tag t may be taken
+    for (int t = lane; t < n_tags; t += 64) room[t] = (uint16_t)min(max(cap_row[t], 0), 0xFFFF);
+    tk_wave_sync();
+    bool take[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int left = tg[e] >= 0 ? (int)room[tg[e]] : 0;
+        const bool live = left > 0;
+        int lower = 0;
+        bool last = true;
+        for (unsigned long long m = __ballot(live); m; m &= m - 1) {
+            const int l = __builtin_ctzll(m);
+            const bool same = __builtin_amdgcn_readlane(tg[e], l) == tg[e];
+            lower += (same && l < lane) ? 1 : 0;
+            last = last && !(same && l > lane);
+        }
+        take[e] = live && lower < left;
+        tk_wave_sync();
+        if (live && last) room[tg[e]] = (uint16_t)(left - min(left, lower + 1));
+        if (ttag_row && take[e] && lower + 1 == left) {          // the cap-th taken of its tag: one lane per tag at most
+            const uint16_t key = (uint16_t)(v[e] >> 48);
+            if (key > ttag_row[tg[e]]) ttag_row[tg[e]] = key;
+        }
+        tk_wave_sync();
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int base = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const unsigned long long m = __ballot(take[e]);
+        const int pos = base + __popcll(m & below);
+        if (take[e] && pos < kb) buf[pos] = v[e];     // (the counters are dead: the loop above ended on a sync)
+        base += __popcll(m);
+    }
+    tk_wave_sync();
+    cnt = min(base, kb);
+    return base >= kb ? buf[kb - 1] : 0;
+}
+
 // One wave: zeroes the entries of buf[0, cnt) whose id user b excludes (ex: the block's LDS copy of its exclude ids in
 // this slice, or the global list when it is longer than TK_EX_LDS).
 __device__ inline void tk_drop_excluded(uint64_t* buf, int cnt, const int32_t* ex, const int64_t* xl, int n_exclude, int lane) {
@@ -207,11 +309,12 @@ struct TkOpenTags {
     __device__ __forceinline__ bool item(int c, int i) const { return (tm[c] >> i) & 1u; }
 };
 
-template <int P, int W>
+template <int P, int W, class SEL = TkSelectBest>
 struct TkFilter {
     TkFilterLds<P> s;
     const int64_t* __restrict__ exclude;
     int n_exclude, k, u0, B, lane, wave;
+    SEL sel;          // how a full buffer is cut down (TkSelectBest: nothing to hold)
 
     __device__ __forceinline__ bool ex_lds() const { return n_exclude <= TK_EX_LDS; }
 
@@ -231,10 +334,14 @@ struct TkFilter {
             }
     }
 
-    // one wave: cut user i's buffer (c entries) down to its best k, excluded ids dropped; returns the new threshold, sets c
+    // one wave: cut user i's buffer (c entries) down to its best k (TkSelectCapped: its capped best k), excluded ids dropped;
+    // returns the new threshold, sets c.  Only ever called for a user row below B.
     __device__ __forceinline__ uint64_t flush(int i, int& c) {
         tk_drop_excluded(s.buf[i], c, ex_lds() ? s.ex[i] : nullptr, exclude + (long)(u0 + i) * n_exclude, n_exclude, lane);
-        return tk_select<P>(s.buf[i], c, k, lane);
+        if constexpr (SEL::capped)
+            return tk_select_capped<P>(s.buf[i], c, sel.reach[i], lane, sel.item_tag, sel.cap + (long)(u0 + i) * sel.n_tags, sel.n_tags,
+                                       sel.ttag ? sel.ttag + i * SEL::table : nullptr);
+        else return tk_select<P>(s.buf[i], c, k, lane);
     }
 
     // The scores of a step that have to be offered, bit 16 c + q of the result.  C/D layout: item = lane & 31 of column tile
@@ -265,6 +372,25 @@ struct TkFilter {
             for (int c = 0; c < TK_TN; ++c) {
                 const uint32_t bit = 1u << (16 * c + q);
                 if ((pend & bit) && !(tk_entry(acc[c][q], id_of(c)) < key)) pend &= ~bit;
+            }
+        }
+        return pend;
+    }
+
+    // CAPS kernels: of the pending scores, those that do not lie below their (user, tag) threshold (TkSelectCapped; tag_of(c): the
+    // tag of this lane's item in column tile c).  One 16-bit LDS read and one compare per score, on the upper half of the score key
+    // the offer's entry will carry.  A threshold a flush raises during this step's offer is seen from the next step on.
+    template <class TagOf>
+    __device__ __forceinline__ uint32_t above_tags(const tk_f32x16 (&acc)[TK_TN], uint32_t pend, TagOf tag_of) const {
+        if (!sel.ttag) return pend;
+#pragma unroll
+        for (int c = 0; c < TK_TN; ++c) {
+            const uint16_t* row = sel.ttag + tag_of(c);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const uint16_t t = row[((q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * SEL::table];          // read ahead of the tests
+                const uint32_t bit = 1u << (16 * c + q);
+                if ((pend & bit) && (uint16_t)(tk_score_key(acc[c][q]) >> 16) < t) pend &= ~bit;
             }
         }
         return pend;
@@ -362,9 +488,16 @@ struct TkFilter {
 // set, a register test, not 32 LDS reads per score.  Dead-wave skip: __ballot(tm[0] | tm[1]) == 0, wave-uniform, under exactly the
 // WINDOW skip's barrier discipline: the skipping wave still calls offer with pend == 0.
 //
+// CAPS (nrms_topk_dot_capped; with or without BIAS): the TAGS form with two differences.  The bitmap is built from cap > 0
+// (tk_caps_stage), so a closed tag costs the same register bit test and a wave whose 64 items are closed to its whole block still
+// skips its chain; and the filter cuts a full buffer down with tk_select_capped instead of tk_select (TkSelectCapped), whose k_b per
+// user the block forms once in LDS (32 ints; tk_caps_reach), and which raises the block's 16-bit tag thresholds (TkSelectCapped)
+// that above_tags() tests before the offer.  The slice lists are capped lists of at most k entries, and
+// topk_merge_capped_kernel runs the same selection over them.
+//
 // The window's two pointers are a kernel argument of the WINDOW instantiations alone, the cursor's of the CURSOR instantiations
-// alone and the tag set's of the TAGS instantiations alone (WIN holds a TkWindow, a TkCursor, both in that order, a TkTags, or
-// nothing; CURSOR and TAGS are read off the pack), so every other instantiation keeps its name, its signature and its kernarg
+// alone, the tag set's of the TAGS instantiations alone and the caps' of the CAPS instantiations alone (WIN holds a TkWindow, a
+// TkCursor, both in that order, a TkTags, a TkCaps, or nothing; CURSOR, TAGS and CAPS are read off the pack), so every other instantiation keeps its name, its signature and its kernarg
 // layout.
 template <int P, int W, bool VEC, bool GROUPED, bool NOISE, bool BIAS, bool WINDOW, class... WIN>
 __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d, int k, int slice_len, int S,
@@ -376,8 +509,11 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                                                             const float* __restrict__ bias, WIN... win_arg) {
     constexpr bool CURSOR = (std::is_same<WIN, TkCursor>::value || ...);
     constexpr bool TAGS = (std::is_same<WIN, TkTags>::value || ...);
-    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0),
-                  "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, TAGS kernels one TkTags, the others none");
+    constexpr bool CAPS = (std::is_same<WIN, TkCaps>::value || ...);
+    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0) + (CAPS ? 1 : 0),
+                  "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, TAGS kernels one TkTags, CAPS kernels one TkCaps, "
+                  "the others none");
+    static_assert(!(CAPS && (GROUPED || NOISE || WINDOW || CURSOR || TAGS)), "the tag caps are for the plain and the biased top-k only");
     static_assert(!(TAGS && (GROUPED || NOISE || WINDOW || CURSOR)), "the tag set is for the plain and the biased top-k only");
     const TkWindow win = tk_window_arg(win_arg...);
     static_assert(!(NOISE && GROUPED), "the perturbation is keyed by the item's row");
@@ -394,7 +530,8 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     const int slice = blockIdx.y;
     const int n_begin = slice * slice_len;
     const int n_end = min(GROUPED ? 32 * n_tiles : N, n_begin + slice_len);      // (grouped: tile rows, not catalogue rows)
-    TkFilter<P, W> flt{lds, exclude, n_exclude, k, u0, B, lane, wave};
+    constexpr int TT = tk_caps_table(P);
+    TkFilter<P, W, std::conditional_t<CAPS, TkSelectCapped<TT>, TkSelectBest>> flt{lds, exclude, n_exclude, k, u0, B, lane, wave};
     int2* wwin = nullptr;          // WINDOW: the block's 32 (lo, hi)
     if constexpr (WINDOW) {
         __shared__ int2 wwin_lds[TK_UT];
@@ -418,12 +555,33 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         item_tag = tags.item_tag;
         tk_tags_stage(ubt, tags, u0, B, 64 * W);
     }
+    if constexpr (CAPS) {          // the bitmap of the tags with cap > 0, the block's 32 k_b and its tag thresholds
+        __shared__ uint32_t ubt_lds[TK_MAX_TAGS];
+        __shared__ int reach_lds[TK_UT];
+        __shared__ uint16_t ttag_lds[TK_UT * TT];
+        for (int i = threadIdx.x; i < TK_UT * TT; i += 64 * W) ttag_lds[i] = 0;
+        ubt = ubt_lds;
+        const TkCaps caps = tk_pack_arg<TkCaps>(win_arg...);
+        n_tags = caps.n_tags;
+        item_tag = caps.item_tag;
+        tk_caps_stage(ubt, caps, u0, B, 64 * W);
+        for (int i = wave; i < TK_UT; i += W) {
+            const int kb = u0 + i < B ? tk_caps_reach(caps.cap + (long)(u0 + i) * n_tags, n_tags, k, lane) : 0;
+            if (lane == 0) reach_lds[i] = kb;
+        }
+        flt.sel = TkSelectCapped<TT>{caps.item_tag, caps.cap, n_tags, reach_lds, n_tags <= TT ? ttag_lds : nullptr};
+    }
     if constexpr (NOISE) {
         if (threadIdx.x < TK_UT) rseed[threadIdx.x] = tk_noise_row_seed(noise.seed, (uint64_t)noise.row_key[min(u0 + (int)threadIdx.x, B - 1)]);
     }
     if constexpr (GROUPED) flt.start(0, 0x80000000L);
     else flt.start(n_begin, n_end);
     __syncthreads();
+    if constexpr (CAPS) {          // a block none of whose users rations a tag needs no tag thresholds: it runs as the TAGS kernel does
+        int any = 0;
+        for (int u = 0; u < TK_UT; ++u) any |= flt.sel.reach[u] >> 16;
+        if (!any) flt.sel.ttag = nullptr;
+    }
     int blo = 0, bhi = 0;
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
     if constexpr (CURSOR) {
@@ -469,19 +627,22 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 dead = TK_WINDOW_SKIP && __ballot(any) == 0;
             }
         }
-        uint32_t tm[TAGS ? TK_TN : 1] = {};      // TAGS: the block's users that this lane's item of column tile c is open to
-        if constexpr (TAGS) {
+        [[maybe_unused]] int tgv[CAPS ? TK_TN : 1] = {};        // CAPS: the tag of this lane's item of column tile c (0 where tm[c] is 0)
+        uint32_t tm[TAGS || CAPS ? TK_TN : 1] = {};      // TAGS, CAPS: the block's users that this lane's item of column tile c is open to
+        if constexpr (TAGS || CAPS) {
             if (nw < n_end) {
 #pragma unroll
                 for (int c = 0; c < TK_TN; ++c) {
                     const int n = nw + 32 * c + r;
-                    const uint32_t m = tk_tags_mask(ubt, item_tag[min(n, N - 1)], n_tags);
+                    const int tg = item_tag[min(n, N - 1)];
+                    const uint32_t m = tk_tags_mask(ubt, tg, n_tags);
                     tm[c] = n < n_end ? m : 0u;
+                    if constexpr (CAPS) tgv[c] = (uint32_t)tg < (uint32_t)n_tags ? tg : 0;
                 }
                 dead = TK_TAGS_SKIP && __ballot((tm[0] | tm[1]) != 0) == 0;
             }
         }
-        if (nw < n_end && (!GROUPED || tl.len[0] + tl.len[1] > 0) && !((WINDOW || TAGS) && dead)) {
+        if (nw < n_end && (!GROUPED || tl.len[0] + tl.len[1] > 0) && !((WINDOW || TAGS || CAPS) && dead)) {
             if constexpr (GROUPED) tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return tl.row_of(i, N); });
             else tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
         }
@@ -511,14 +672,15 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
             if constexpr (GROUPED) live[c] = tl.live(c, nw, n_end, r, item_ids, id[c]);
             else {
                 id[c] = (uint32_t)(nw + 32 * c + r);
-                live[c] = nw + 32 * c + r < n_end && !((WINDOW || TAGS) && dead);       // a skipped wave's accumulators hold no score
+                live[c] = nw + 32 * c + r < n_end && !((WINDOW || TAGS || CAPS) && dead);       // a skipped wave's accumulators hold no score
             }
         }
         uint32_t pend;
         if constexpr (WINDOW) pend = flt.pending(acc, live, TkOpenWindow{wwin, tv});
-        else if constexpr (TAGS) pend = flt.pending(acc, live, TkOpenTags{tm});
+        else if constexpr (TAGS || CAPS) pend = flt.pending(acc, live, TkOpenTags{tm});
         else pend = flt.pending(acc, live, TkOpenAll{});
         if constexpr (CURSOR) pend = flt.after(acc, pend, cur, [&](int c) { return id[c]; });
+        if constexpr (CAPS) pend = flt.above_tags(acc, pend, [&](int c) { return tgv[c]; });
         // unconditional: the offer holds the block's barriers, and a wave with pend == 0 has to meet them too
         flt.offer(acc, pend, [&](int c) { return id[c]; });
     }
@@ -564,6 +726,44 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(int B, int k, int S, con
     const long b = blockIdx.x;
     tk_merge<P>(buf, ws + b * S * k, (long)S * k, k, threadIdx.x, top_scores ? top_scores + b * out_stride : nullptr,
                 top_ids + b * out_stride);
+}
+
+// One wave per user: tk_merge with the capped selection (CAPS: nrms_topk_dot_capped).  The user's S slice lists are capped lists;
+// the capped list of their union is the capped list of the catalogue (C(S1 u S2) = C(C(S1) u C(S2))).  The last selection leaves at
+// most k entries, which are sorted and written like tk_merge's.
+template <int P>
+__global__ __launch_bounds__(64) void topk_merge_capped_kernel(int B, int k, int S, const uint64_t* __restrict__ ws, TkCaps caps,
+                                                               float* __restrict__ top_scores, int64_t* __restrict__ top_ids) {
+    __shared__ uint64_t buf[P];
+    const long b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int32_t* cap_row = caps.cap + b * caps.n_tags;
+    const int reach = tk_caps_reach(cap_row, caps.n_tags, k, lane);
+    const uint64_t* src = ws + b * S * k;
+    const long total = (long)S * k;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int cnt = 0;
+    uint64_t thr = 0;
+    for (long c0 = 0; c0 < total; c0 += 64) {
+        const long c = c0 + lane;
+        const uint64_t e = c < total ? src[c] : 0;
+        const bool take = e > thr;
+        const unsigned long long m = __ballot(take);
+        if (take) buf[cnt + __popcll(m & below)] = e;
+        cnt += __popcll(m);
+        if (cnt + 64 > P) {
+            tk_wave_sync();
+            thr = tk_select_capped<P>(buf, cnt, reach, lane, caps.item_tag, cap_row, caps.n_tags);
+        }
+    }
+    tk_wave_sync();
+    tk_select_capped<P>(buf, cnt, reach, lane, caps.item_tag, cap_row, caps.n_tags);
+    tk_flush<P>(buf, cnt, k, lane);
+    for (int j = lane; j < k; j += 64) {
+        const uint64_t e = buf[j];
+        top_scores[b * k + j] = e ? tk_entry_score(e) : -__builtin_huge_valf();
+        top_ids[b * k + j] = e ? tk_entry_id(e) : -1;
+    }
 }
 
 static TkGeom topk_geom(int32_t B, int64_t N) { return tk_geom(B, N, true); }

@@ -905,6 +905,19 @@ class NRMSEngine:
         """The checked tag set of top_k_tagged / rank_of_tagged -> (item_tag [N] int32, allow [B, W] int32), contiguous, on the
         device.  item_tag may be int64 (values outside int32 become -1, which is open to nobody, on the device); allow may be the
         bool [B, n_tags] matrix (packed here by pack_tag_mask) or the packed int32 [B, W], W = ceil(n_tags / 32)."""
+        item_tag, n_tags = self._item_tag_arg(who, item_tag, n_tags, N, dev)
+        W = (n_tags + 31) // 32
+        ok = torch.is_tensor(allow) and allow.dim() == 2 and allow.shape[0] == B and allow.device == dev
+        if ok and allow.dtype == torch.bool and allow.shape[1] == n_tags:
+            allow = pack_tag_mask(allow)
+        elif not (ok and allow.dtype == torch.int32 and allow.shape[1] == W):
+            got = ("%s %s on %s" % (tuple(allow.shape), allow.dtype, allow.device)) if torch.is_tensor(allow) else type(allow).__name__
+            raise _lib.NrmsError("%s: allow must be a bool [%d, %d] or a packed int32 [%d, %d] tensor on %s (got %s)"
+                                 % (who, B, n_tags, B, W, self.device, got))
+        return item_tag, allow.contiguous(), n_tags
+
+    def _item_tag_arg(self, who, item_tag, n_tags, N, dev):
+        """The checked n_tags and item_tag of the tagged and the capped calls -> (item_tag [N] int32, contiguous, n_tags)."""
         n_tags = int(n_tags)
         if not 1 <= n_tags <= MAX_TAGS:
             raise _lib.NrmsError("%s: n_tags must be in [1, %d] (n_tags=%d)" % (who, MAX_TAGS, n_tags))
@@ -914,15 +927,7 @@ class NRMSEngine:
             raise _lib.NrmsError("%s: item_tag must be an int32 (or int64) [%d] tensor on %s (got %s)" % (who, N, self.device, got))
         if item_tag.dtype == torch.int64:
             item_tag = torch.where((item_tag < 0) | (item_tag >= n_tags), torch.full_like(item_tag, -1), item_tag).to(torch.int32)
-        W = (n_tags + 31) // 32
-        ok = torch.is_tensor(allow) and allow.dim() == 2 and allow.shape[0] == B and allow.device == dev
-        if ok and allow.dtype == torch.bool and allow.shape[1] == n_tags:
-            allow = pack_tag_mask(allow)
-        elif not (ok and allow.dtype == torch.int32 and allow.shape[1] == W):
-            got = ("%s %s on %s" % (tuple(allow.shape), allow.dtype, allow.device)) if torch.is_tensor(allow) else type(allow).__name__
-            raise _lib.NrmsError("%s: allow must be a bool [%d, %d] or a packed int32 [%d, %d] tensor on %s (got %s)"
-                                 % (who, B, n_tags, B, W, self.device, got))
-        return item_tag.contiguous(), allow.contiguous(), n_tags
+        return item_tag.contiguous(), n_tags
 
     def top_k_tagged(self, user_vec, items, k, item_tag, n_tags, allow, exclude=None, bias=None):
         """top_k inside a per-user set of item tags -> (scores [B, k] fp32, ids [B, k] int64).  item_tag [N] int32 (device): one tag
@@ -944,6 +949,34 @@ class NRMSEngine:
                                            _lib.ptr(item_tag), n_tags, _lib.ptr(allow), _lib.ptr(exclude), n_ex, _lib.ptr(scores),
                                            _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
         _lib.check(rc, "nrms_topk_dot_tagged")
+        return scores, ids
+
+    def top_k_capped(self, user_vec, items, k, item_tag, n_tags, cap, exclude=None, bias=None):
+        """top_k with per-tag caps -> (scores [B, k] fp32, ids [B, k] int64): walking user b's full ranking (top_k's: the same
+        score bits, order, exclude and bias), item n with tag t = item_tag[n] is taken iff 0 <= t < n_tags and fewer than cap[b, t]
+        items of tag t were taken before it; the first k taken items are row b, then -1 / -inf.  item_tag [N] int32 (device), as in
+        top_k_tagged (a tag outside [0, n_tags), e.g. -1, is served to nobody); cap int32 [B, n_tags] (device): <= 0 closes the tag
+        for that user, >= k leaves it uncapped.  Every cap >= k is top_k_tagged with all tags open, bit for bit;
+        1 <= n_tags <= 512 (nrms_topk_dot_capped; include/nrms_hip.h states the contract)."""
+        who = "top_k_capped"
+        k = int(k)
+        B, N, d, exclude, n_ex, _, _ = self._top_k_args(who, user_vec, items, exclude, bias, None, None)
+        dev = self._cuda_device()
+        item_tag, n_tags = self._item_tag_arg(who, item_tag, n_tags, N, dev)
+        if (not torch.is_tensor(cap) or tuple(cap.shape) != (B, n_tags) or cap.dtype != torch.int32 or cap.device != dev):
+            got = ("%s %s on %s" % (tuple(cap.shape), cap.dtype, cap.device)) if torch.is_tensor(cap) else type(cap).__name__
+            raise _lib.NrmsError("%s: cap must be an int32 [%d, %d] tensor on %s (got %s)" % (who, B, n_tags, self.device, got))
+        cap = cap.contiguous()
+        nbytes = self.lib.nrms_topk_dot_capped_workspace_bytes(B, N, d, k)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (who, B, N, d, k))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot_capped(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                           _lib.ptr(item_tag), n_tags, _lib.ptr(cap), _lib.ptr(exclude), n_ex, _lib.ptr(scores),
+                                           _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_topk_dot_capped")
         return scores, ids
 
     def rank_of_tagged(self, user_vec, items, targets, item_tag, n_tags, allow, exclude=None, bias=None):

@@ -269,6 +269,12 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: rank_targets_tagged is not available: a candidate's score depends on its neighbours in "
                                   "the click graph, not on a catalogue row alone (no rank_targets either)")
 
+    CATALOGUE_CAPS = False
+
+    def recommend_capped(self, batch, k, catalogue, item_tag, cap, exclude_history=True, *, item_bias=None, n_tags=None):
+        raise NotImplementedError("graph: recommend_capped is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone (no recommend either, with caps or without)")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

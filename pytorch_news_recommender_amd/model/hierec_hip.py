@@ -395,6 +395,12 @@ class Model(FlatHipModel):
                                   "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot_tagged ranks plain dot "
                                   "products only")
 
+    CATALOGUE_CAPS = False
+
+    def recommend_capped(self, batch, k, catalogue, item_tag, cap, exclude_history=True, *, item_bias=None, n_tags=None):
+        raise NotImplementedError("hierec: recommend_capped is not available: HieRec scores the catalogue with a query per (topic, "
+                                  "sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no per-tag caps")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

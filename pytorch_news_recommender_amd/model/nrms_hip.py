@@ -461,6 +461,18 @@ class Model(FlatHipModel):
         """The kernels' view of a per-user tag set -> (item_tag rows 1.. like the catalogue's, n_tags, allow) for
         engine.top_k_tagged / rank_of_tagged (which check dtypes and pack a bool ``allow``).  n_tags is read off a bool ``allow``;
         a packed int32 [B, W] one stands for n_tags = 32 W."""
+        rows = Model._item_tag_rows(item_tag, cat, who)
+        if (not torch.is_tensor(allow) or allow.dim() != 2 or allow.shape[0] != B or allow.shape[1] < 1
+                or allow.dtype not in (torch.bool, torch.int32) or allow.device != cat.device):
+            got = ("%s %s on %s" % (tuple(allow.shape), allow.dtype, allow.device)) if torch.is_tensor(allow) else type(allow).__name__
+            raise _lib.NrmsError("%s: allow must be a bool [%d, n_tags] tensor, or pack_tag_mask's int32 [%d, W], on %s (got %s)"
+                                 % (who, B, B, cat.device, got))
+        n_tags = allow.shape[1] * (1 if allow.dtype == torch.bool else 32)
+        return rows, n_tags, allow
+
+    @staticmethod
+    def _item_tag_rows(item_tag, cat, who):
+        """The checked item_tag of recommend_tagged / recommend_capped -> its rows 1.. like the catalogue's."""
         N = cat.shape[0]
         if (not torch.is_tensor(item_tag) or tuple(item_tag.shape) != (N,) or item_tag.dtype not in (torch.int32, torch.int64)
                 or item_tag.device != cat.device):
@@ -468,13 +480,7 @@ class Model(FlatHipModel):
                 else type(item_tag).__name__
             raise _lib.NrmsError("%s: item_tag must be an int32 or int64 [%d] tensor on %s, indexed by news id like the catalogue "
                                  "(got %s)" % (who, N, cat.device, got))
-        if (not torch.is_tensor(allow) or allow.dim() != 2 or allow.shape[0] != B or allow.shape[1] < 1
-                or allow.dtype not in (torch.bool, torch.int32) or allow.device != cat.device):
-            got = ("%s %s on %s" % (tuple(allow.shape), allow.dtype, allow.device)) if torch.is_tensor(allow) else type(allow).__name__
-            raise _lib.NrmsError("%s: allow must be a bool [%d, n_tags] tensor, or pack_tag_mask's int32 [%d, W], on %s (got %s)"
-                                 % (who, B, B, cat.device, got))
-        n_tags = allow.shape[1] * (1 if allow.dtype == torch.bool else 32)
-        return item_tag.contiguous()[1:], n_tags, allow
+        return item_tag.contiguous()[1:]
 
     @torch.no_grad()
     def recommend_tagged(self, batch, k, catalogue, item_tag, allow, exclude_history=True, *, item_bias=None):
@@ -492,6 +498,53 @@ class Model(FlatHipModel):
         bias = self._item_bias_rows(item_bias, cat, "recommend_tagged")
         tags, n_tags, allow = self._tag_rows(item_tag, allow, cat, user.shape[0], "recommend_tagged")
         scores, ids = self._engine.top_k_tagged(user, cat[1:], k, tags, n_tags, allow, exclude, bias=bias)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    @staticmethod
+    def _cap_rows(cap, n_tags, B, k, dev, who):
+        """The kernels' view of the caps -> (cap int32 [B, n_tags] on dev, n_tags).  cap: an int (the same cap for every tag and
+        user; n_tags is then the keyword), an int tensor [n_tags] (the same caps for every user) or [B, n_tags].  Expanded on the
+        device; values are clamped to [0, 2^31 - 1] (a cap <= 0 closes the tag, one >= k leaves it uncapped)."""
+        if isinstance(cap, bool) or not (isinstance(cap, int) or torch.is_tensor(cap)):
+            raise _lib.NrmsError("%s: cap must be an int, or an int tensor [n_tags] or [%d, n_tags] (got %s)" % (who, B, type(cap).__name__))
+        if isinstance(cap, int):
+            if n_tags is None:
+                raise _lib.NrmsError("%s: an int cap needs n_tags= (the number of tags item_tag runs over)" % who)
+            n_tags = int(n_tags)
+            if not 1 <= n_tags <= 512:
+                raise _lib.NrmsError("%s: n_tags must be in [1, 512] (n_tags=%d)" % (who, n_tags))
+            return torch.full((B, n_tags), min(max(cap, 0), 2 ** 31 - 1), dtype=torch.int32, device=dev), n_tags
+        if (cap.dtype not in (torch.int32, torch.int64) or cap.dim() not in (1, 2) or cap.shape[-1] < 1
+                or (cap.dim() == 2 and cap.shape[0] != B) or cap.device != dev):
+            raise _lib.NrmsError("%s: cap must be an int32 or int64 tensor [n_tags] or [%d, n_tags] on %s (got %s %s on %s)"
+                                 % (who, B, dev, tuple(cap.shape), cap.dtype, cap.device))
+        if n_tags is not None and int(n_tags) != cap.shape[-1]:
+            raise _lib.NrmsError("%s: n_tags=%d does not match cap %s" % (who, int(n_tags), tuple(cap.shape)))
+        cap = cap.clamp(0, 2 ** 31 - 1).to(torch.int32)
+        if cap.dim() == 1:
+            cap = cap.unsqueeze(0).expand(B, -1)
+        return cap.contiguous(), cap.shape[1]
+
+    @torch.no_grad()
+    def recommend_capped(self, batch, k, catalogue, item_tag, cap, exclude_history=True, *, item_bias=None, n_tags=None):
+        """recommend with a hard cap per news tag -> (news_ids [B, k] int64, scores [B, k] fp32): "at most two stories per category
+        in my ten", "one politics story at most for this user" (include/nrms_hip.h nrms_topk_dot_capped).  Parity is unpinned: the
+        reference has no catalogue retrieval.
+
+        item_tag: int [N] on the model's device, one tag per news id like the catalogue (entry 0 is never read), exactly
+        recommend_tagged's; a tag outside [0, n_tags), e.g. -1, is served to nobody.  cap: an int (every tag, every user; give
+        ``n_tags=``), an int tensor [n_tags] (every user) or [B, n_tags]; cap <= 0 closes the tag for that user, cap >= k leaves it
+        uncapped.  Row b is recommend's full ranking for user b (the same user vector, score bits, exclusions, tie rule and
+        ``item_bias``) walked greedily: a news is taken iff its tag has room left; the first k taken are the row, then id -1 / score
+        -inf.  With every cap >= k and every tag in range this is recommend, bit for bit.  Not combined with a time window, paging,
+        the fp16 shortlist, sections, the diversity re-ranking or the log-partition."""
+        who = "recommend_capped"
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, who)
+        bias = self._item_bias_rows(item_bias, cat, who)
+        B = user.shape[0]
+        caps, n_tags = self._cap_rows(cap, n_tags, B, int(k), cat.device, who)
+        tags = self._item_tag_rows(item_tag, cat, who)
+        scores, ids = self._engine.top_k_capped(user, cat[1:], k, tags, n_tags, caps, exclude, bias=bias)
         return torch.where(ids >= 0, ids + 1, ids), scores
 
     @torch.no_grad()
@@ -722,6 +775,7 @@ class Model(FlatHipModel):
     CATALOGUE_PAGING = True             # ... and paged through with a cursor: recommend_page / recommend_deep (run_v0 --recommend_deep)
     CATALOGUE_EXPLAIN = True            # ... and split over the clicks of the history: explain (run_v0 --explain)
     CATALOGUE_LIKELIHOOD = True         # ... and normalised over the catalogue: log_partition / log_prob (run_v0 --retrieval_nll)
+    CATALOGUE_CAPS = True               # ... and rationed by a hard cap per tag: recommend_capped (run_v0 --max_per_category)
     CATALOGUE_TAGS = True               # ... and restricted to a per-user tag set: recommend_tagged / rank_targets_tagged (run_v0 --only_categories)
 
     def check_recommend_ids(self):

@@ -117,7 +117,35 @@ def build_parser():
                         '--catalogue_window, --coarse_catalogue, --recommend_deep, --sections, --diversity, --retrieval_nll or --explain')
     parser.add_argument('--mute_categories', type=str, default=None, metavar='ID[,ID...]', help='--recommend / --retrieval_metrics: never '
                         'serve these news categories, and rank the held-out clicks among the others (see --only_categories)')
+    parser.add_argument('--max_per_category', type=int, default=None, metavar='M', help='--recommend: at most M news of one category '
+                        'in every list (model.recommend_capped: the exact ranking walked greedily, a news is taken while its '
+                        'category has room; M >= 1).  Combines with --only_categories / --mute_categories (a closed category gets cap '
+                        '0) and --popularity_prior; not with --diversity, --coarse_catalogue, --catalogue_window, --sections, '
+                        '--recommend_deep or --explain')
     return parser
+
+
+def check_caps_args(args):
+    """--max_per_category fails before any data is read or any step is trained: M >= 1, the list of --recommend, a model that
+    serves with per-category caps, and none of the paths the capped kernels do not have."""
+    if args.max_per_category is None:
+        return
+    if args.max_per_category < 1:
+        raise SystemExit('--max_per_category M: M must be >= 1 (got %d)' % args.max_per_category)
+    if args.recommend is None:
+        raise SystemExit('--max_per_category: caps the list of --recommend K (give --recommend)')
+    for other, on in (('--diversity', args.diversity is not None or args.shortlist is not None),
+                      ('--coarse_catalogue', args.coarse_catalogue or args.coarse_shortlist is not None),
+                      ('--catalogue_window', args.catalogue_window is not None), ('--sections', args.sections is not None),
+                      ('--recommend_deep', args.recommend_deep is not None), ('--explain', args.explain is not None)):
+        if on:
+            raise SystemExit('--max_per_category: the capped call serves the plain or the biased list only (drop %s)' % other)
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_CAPS', False):
+        raise SystemExit('--max_per_category: model %r cannot serve with per-category caps (its catalogue score is no plain dot '
+                         'product over a row-ordered catalogue)' % args.model)
 
 
 def check_tag_args(args):
@@ -429,6 +457,7 @@ def main(argv=None):
     check_prior_args(args)
     check_window_args(args)
     tag_only, tag_mute = check_tag_args(args)
+    check_caps_args(args)
     check_graph_args(args)
     check_negatives_args(args)
     check_loss_args(args)
@@ -560,6 +589,24 @@ def main(argv=None):
             print('coarse catalogue: certified share: {:.4f}  users: {}'.format(st['certified'], st['n_users']))
             return out
         tags = tag_sets(samples, feed.news_info()['categ'])
+        if args.max_per_category is not None:
+            n_tags = int(config.category_nums)
+            if not 1 <= n_tags <= 512:
+                raise SystemExit('--max_per_category: 1 <= the number of categories <= 512 (got %d)' % n_tags)
+            tags.setdefault('item_tag', feed.news_info()['categ'])
+            # the held-out clicks of a click log are at hand: how many of them does the capped list still hold
+            held = {'heldout': [smp[3] for smp in samples]} if click_feed and samples is click_feed[0][1] else {}
+            net = recommender.model if hasattr(recommender, 'model') else recommender
+            out = None
+            for name, cap, dst in (('uncapped', args.recommend, os.devnull),
+                                   ('at most %d per category' % args.max_per_category, args.max_per_category, args.recommend_out)):
+                out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=dst, **item_prior, **tags, **held,
+                                tag_caps=torch.full((n_tags,), cap, dtype=torch.int32))
+                st = net.last_caps_stats
+                print('{}{}: categories per list: {:.3f}  largest category share: {:.4f}  users: {}{}'.format(
+                    name, ' (%s)' % tag_words() if tag_words() else '', st['distinct_tags'], st['largest_share'], st['n_users'],
+                    ''.join('  hit@{}: {:.4f} +- {:.4f}'.format(kk, st['hit'][kk], st['hit_se'][kk]) for kk in st.get('hit', {}))))
+            return out
         if tags:
             out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior, **tags)
             # read the file back: every served id has to carry a category its sample allows

@@ -359,6 +359,101 @@ class _TagSets:
         return self.item_tag, self.allow[done:done + B].to(dev)
 
 
+class _TagCaps:
+    """The cap keywords of recommend(), turned into ``model.recommend_capped`` arguments batch by batch.  tag_caps: an int tensor
+    or array [n_tags] (every sample) or [n_samples, n_tags] (one row per sample of data_iter in its order), or an int when
+    allow_tags gives n_tags; item_tag as for the tag sets (required); allow_tags optional, bool [n_samples, n_tags]: a closed tag
+    becomes cap 0.  heldout optional: per sample the news ids of its held-out clicks (a list of lists, or an int tensor
+    [n_samples] / [n_samples, T] with -1 for none).  With caps, the keywords of ``refused`` that were given raise a ValueError that
+    names them."""
+
+    def __init__(self, who, tag_caps, item_tag, allow_tags, heldout, refused):
+        self.on = tag_caps is not None
+        if not self.on:
+            if heldout is not None:
+                raise ValueError("%s: heldout is read with tag_caps only (give tag_caps)" % who)
+            return
+        if item_tag is None:
+            raise ValueError("%s: tag_caps caps the tags of item_tag (give item_tag)" % who)
+        for name, given in refused:
+            if given:
+                raise ValueError("%s: %s does not go with tag_caps: the capped call serves the plain or the biased list only"
+                                 % (who, name))
+        self.who, self.item_tag = who, item_tag
+        self.allow = None
+        if allow_tags is not None:
+            self.allow = torch.as_tensor(allow_tags)
+            if self.allow.dim() != 2 or self.allow.dtype != torch.bool:
+                raise ValueError("%s: allow_tags must be bool [n_samples, n_tags] (got %s %s)"
+                                 % (who, tuple(self.allow.shape), self.allow.dtype))
+        caps = torch.as_tensor(tag_caps)
+        if caps.dtype not in (torch.int32, torch.int64) or caps.dim() > 2:
+            raise ValueError("%s: tag_caps must be an int, or an int tensor [n_tags] or [n_samples, n_tags] (got %s %s)"
+                             % (who, tuple(caps.shape), caps.dtype))
+        if caps.dim() == 0:
+            if self.allow is None:
+                raise ValueError("%s: an int tag_caps needs allow_tags to say how many tags there are (or give an [n_tags] tensor)" % who)
+            caps = caps.expand(self.allow.shape[1])
+        if self.allow is not None and self.allow.shape[1] != caps.shape[-1]:
+            raise ValueError("%s: tag_caps %s and allow_tags %s disagree on n_tags" % (who, tuple(caps.shape), tuple(self.allow.shape)))
+        self.caps = caps.clamp(0, 2 ** 31 - 1).to(torch.int32)
+        self.n_tags = int(caps.shape[-1])
+        self.held = None
+        if heldout is not None:
+            if torch.is_tensor(heldout) or isinstance(heldout, np.ndarray):
+                held = torch.as_tensor(heldout).to(torch.int64)
+                self.held = held.view(-1, 1) if held.dim() == 1 else held
+            else:
+                T = max([len(h) for h in heldout] + [1])
+                self.held = torch.tensor([list(h) + [-1] * (T - len(h)) for h in heldout], dtype=torch.int64).view(len(heldout), T)
+        self.sums = None          # on the device: lists, distinct tags, largest shares, held-out clicks, hits at every K'
+
+    def of(self, done, B, dev):
+        """-> (item_tag, cap int32 [B, n_tags] on dev) for samples [done, done + B)."""
+        for name, t in (("tag_caps", self.caps if self.caps.dim() == 2 else None), ("allow_tags", self.allow), ("heldout", self.held)):
+            if t is not None and done + B > t.shape[0]:
+                raise ValueError("%s: %d %s rows for %d samples" % (self.who, t.shape[0], name, done + B))
+        cap = (self.caps[done:done + B] if self.caps.dim() == 2 else self.caps.unsqueeze(0).expand(B, -1)).to(dev)
+        if self.allow is not None:
+            cap = torch.where(self.allow[done:done + B].to(dev), cap, torch.zeros_like(cap))
+        return self.item_tag, cap.contiguous()
+
+    def note(self, done, ids, ks):
+        """Accumulates the statistics of one batch's ids [B, k] (news ids, -1 padding) on their device, with torch alone."""
+        dev, n_tags = ids.device, self.n_tags
+        tag = self.item_tag.to(dev, dtype=torch.int64)[ids.clamp(min=0)]
+        ok = (ids >= 0) & (tag >= 0) & (tag < n_tags)
+        count = torch.zeros(ids.shape[0], n_tags + 1, dtype=torch.int64, device=dev)
+        count.scatter_add_(1, torch.where(ok, tag, torch.full_like(tag, n_tags)), torch.ones_like(tag))
+        count = count[:, :n_tags]
+        n = ok.sum(dim=1)
+        some = n > 0
+        share = count.max(dim=1).values.double() / n.clamp(min=1).double()
+        vals = [some.sum().double(), ((count > 0).sum(dim=1) * some).sum().double(), (share * some).sum()]
+        if self.held is not None:
+            held = self.held[done:done + ids.shape[0]].to(dev)
+            vals.append((held >= 1).sum().double())
+            for kk in ks:          # plain list membership: is the held-out click among the first kk of its sample's list
+                hit = (held.unsqueeze(2) == ids[:, :kk].unsqueeze(1)).any(dim=2) & (held >= 1)
+                vals.append(hit.sum().double())
+        vals = torch.stack(vals)
+        self.sums = vals if self.sums is None else self.sums + vals
+
+    def stats(self, ks):
+        """The run's statistics (one host synchronisation): the mean number of distinct tags per non-empty list, the mean largest
+        share of one tag in such a list, and, with heldout, per K' the share of held-out clicks found among the first K' of their
+        sample's list with its binomial standard error."""
+        v = self.sums.cpu().tolist() if self.sums is not None else [0.0] * (3 + (0 if self.held is None else 1 + len(ks)))
+        n = int(v[0])
+        res = {"distinct_tags": v[1] / n if n else float("nan"), "largest_share": v[2] / n if n else float("nan"), "n_users": n}
+        if self.held is not None:
+            m = int(v[3])
+            res["n_heldout"] = m
+            res["hit"] = {kk: (h / m if m else float("nan")) for kk, h in zip(ks, v[4:])}
+            res["hit_se"] = {kk: ((p * (1.0 - p) / m) ** 0.5 if m else float("nan")) for kk, p in res["hit"].items()}
+        return res
+
+
 class _RequestWindows:
     """The time-window keywords of recommend() / evaluate_retrieval(), turned into ``model.recommend`` / ``rank_targets`` keywords
     batch by batch: sample i is served inside [request_time[i] - window_span, request_time[i] + 1), clamped to int32.  All three or
@@ -389,7 +484,7 @@ class _RequestWindows:
 
 def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
               shortlist=None, item_bias=None, item_time=None, request_time=None, window_span=None, coarse=False,
-              coarse_shortlist=None, item_tag=None, allow_tags=None, explain=None):
+              coarse_shortlist=None, tag_caps=None, heldout=None, item_tag=None, allow_tags=None, explain=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
@@ -422,6 +517,18 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     not with diversity, coarse, a time window or explain (ValueError naming the keyword).  None: the model is called exactly as
     before.
 
+    tag_caps (with item_tag; allow_tags optional): a hard cap per news tag, ``model.recommend_capped``.  tag_caps: an int tensor
+    [n_tags] (the same caps for every sample) or [n_samples, n_tags], or an int when allow_tags says how many tags there are:
+    sample i's list holds at most tag_caps[i, t] news of tag t (the exact ranking walked greedily); with allow_tags as well a closed
+    tag becomes cap 0.  With or without item_bias; not with diversity, coarse, a time window or explain (ValueError naming the
+    keyword).  The call leaves ``net.last_caps_stats = {"distinct_tags": mean number of distinct tags per non-empty list,
+    "largest_share": mean over those lists of the largest share one tag holds, "n_users": those lists}``, computed with torch on
+    the returned ids, with one host synchronisation at the end.  heldout (with tag_caps only): per sample the news ids of its
+    held-out clicks (a list of lists, or an int tensor with -1 for none); the stats gain ``"hit": {K': share of the held-out clicks
+    found among the first K' of their sample's list}`` for K' in (1, 5, 10, 20, 50, 100, k) up to k, ``"hit_se"`` (the binomial
+    standard error) and ``"n_heldout"``: plain list membership, no rank kernel.  None: the model is called exactly as before and
+    ``last_caps_stats`` is None.
+
     explain = m in [1, 8]: also writes ``<file name>.reasons`` and leaves its name in ``net.last_explain_file`` (None without
     ``explain``, when the model is called and the list is written exactly as before; the list file is the same either way).  One
     line per recommended news, in the order of the list file:
@@ -431,6 +538,13 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     largest first, negative ones included.  Numbers are written with 9 significant digits, which names every float32: two runs
     give the same bytes.  Needs a model with ``CATALOGUE_EXPLAIN`` (ValueError otherwise, before anything is encoded)."""
     net = _inner(model)
+    caps = _TagCaps("recommend", tag_caps, item_tag, allow_tags, heldout,
+                    (("diversity", diversity is not None or shortlist is not None),
+                     ("coarse", bool(coarse) or coarse_shortlist is not None),
+                     ("item_time / request_time / window_span", item_time is not None or request_time is not None
+                      or window_span is not None), ("explain", explain is not None)))
+    if caps.on:
+        item_tag = allow_tags = None          # the caps carry them; the tag sets below stay off
     tags = _TagSets("recommend", item_tag, allow_tags, (("diversity", diversity is not None or shortlist is not None),
                                                         ("coarse", bool(coarse) or coarse_shortlist is not None),
                                                         ("item_time / request_time / window_span", item_time is not None
@@ -472,6 +586,16 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
             lines.extend(ids.cpu().tolist())
             note(datas, ids)
         net.last_coarse_stats = {"certified": int(n_cert.item()) / n_users if n_users else float("nan"), "n_users": n_users}
+    elif caps.on:
+        net.last_recommend_stats = None
+        hit_ks = tuple(kk for kk in (1, 5, 10, 20, 50, 100) if kk < int(k)) + (int(k),)
+        for datas in data_iter:
+            B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
+            tag, cap = caps.of(done, B, catalogue.device)
+            ids, _ = net.recommend_capped(datas, k, catalogue, tag, cap, exclude_history=exclude_history, **prior)
+            caps.note(done, ids, hit_ks)
+            done += B
+            lines.extend(ids.cpu().tolist())
     elif tags.on:
         net.last_recommend_stats = None
         for datas in data_iter:
@@ -514,6 +638,7 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
         n_users = int(stats[2])                                                # (the one host synchronisation is above)
         net.last_recommend_stats = {"ild": stats[0] if n_users else float("nan"), "coverage": stats[1], "n_users": n_users}
         lines = ids.cpu().tolist()
+    net.last_caps_stats = caps.stats(hit_ks) if caps.on else None
     net.engine.check_ids()
     net.check_recommend_ids()
     file_name = out_file or 'recommend_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
