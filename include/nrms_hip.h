@@ -634,6 +634,55 @@ int nrms_topk_dot_capped(int32_t B, int64_t N, int32_t d, int32_t k, const float
                          const int32_t* cap /* [B, n_tags] */, const int64_t* exclude, int32_t n_exclude, float* top_scores,
                          int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Per-user score adjustments (impression discounting: "shown three times without a click: down by 3 beta"; per-user boosts: a
+ * followed publisher, an editor's pin for a segment; a per-user block that is not the click history; PARITY UNPINNED, the reference
+ * has no catalogue retrieval) ----
+ * nrms_topk_dot_biased / nrms_rank_dot_biased with a short per-user list of (catalogue row, delta) pairs.  adj_ids int64 [B, E],
+ * 8-byte aligned, and adj_delta fp32 [B, E], 4-byte aligned, E = n_adjust, 0 <= E <= 256 (NRMS_ADJ_MAX).  bias [N] fp32, 4-byte
+ * aligned, NULLABLE: NULL means no prior, s' = s.  Every other argument is the biased call's.
+ * Slots.  Slot (b, e) names catalogue row adj_ids[b, e]; a value outside [0, N) is an empty slot (-1 by convention).  The slot of
+ *   pair (b, n) is the LOWEST e with adj_ids[b, e] == n; later slots of row b that name the same n are ignored.
+ * Scores.  s'(b, n) is what the biased call would offer: the same score bits s, plus bias[n] when bias != NULL (one fp32 add).  A pair
+ *   with a slot has s'' = s' + adj_delta[b, e]: one fp32 add on the finished s', after the prior's add, never folded into the chain.
+ *   A pair without a slot keeps s'' = s', with no add performed.
+ * Eligibility.  Item n is eligible for user b iff n is not in b's exclude row and s'' is not NaN.  So a NaN delta closes the item for
+ *   that user alone; -inf and +inf deltas are ordinary values under the order (s'' descending, +inf first, equal s'' put the SMALLER n
+ *   first, -0.0 equals +0.0 and is returned as +0.0).  An id that is both excluded and adjusted is excluded.
+ * Everything else is nrms_topk_dot_biased's / nrms_rank_dot_biased's: entry order and tie rule, padding id -1 / score -inf, 1 <= k <=
+ *   256, 1 <= T <= 32, the exclude list, invalid targets (out of range, excluded, NaN s'') give rank 0 / score -inf, ranks are exact
+ *   integers, rank(b, t) = 1 + #{eligible n : (s''(b, n), n) precedes (s''(b, t), t)}.  The returned scores are s''.
+ * Consequences.
+ *   (a) E == 0, or adj_ids == NULL and adj_delta == NULL, is the biased (bias == NULL: the plain) call, bit for bit; so is a call
+ *       whose slots are all empty.
+ *   (b) With bias == NULL, row b equals nrms_topk_dot_biased / nrms_rank_dot_biased at B = 1 whose bias holds row b's deltas
+ *       scattered by the lowest-slot rule and +0.0 elsewhere (adding +0.0 changes no score the order or the result can tell apart:
+ *       -0.0 is returned as +0.0 either way): ids, ranks and returned score bits are equal.
+ *   (c) Row b depends on user row b, adj row b and exclude row b only: not on B, the row's position in the batch, the other rows'
+ *       slots, the launch geometry, what the workspace held or the run.
+ *   (d) The first k' columns of a call with k are the call with k'.
+ *   (e) The ids nrms_topk_dot_adjusted returns for user b get ranks 1 .. k, in order, from nrms_rank_dot_adjusted with the same
+ *       arguments.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_adjusted: ...", "rank_dot_adjusted: ..."):
+ *   n_adjust outside [0, 256], exactly one of adj_ids / adj_delta NULL with n_adjust > 0 and a misaligned list are among them.  An
+ *   undersized workspace returns NRMS_EWORKSPACE.  Nothing is launched after an error.
+ * Workspace: the _workspace_bytes queries return exactly nrms_topk_dot_workspace_bytes(B, N, d, k) / nrms_rank_dot_workspace_bytes(B,
+ *   N, d, T, n_exclude) (0 = arguments rejected); 8-byte aligned.
+ * The kernels of nrms_topk_dot / nrms_rank_dot on `stream`, no host synchronisation, no allocation, no [B, N] matrix.  A block stages
+ *   the slots of its 32 users that fall into its catalogue slice in LDS (up to 2048 of them for k <= 192, 1024 above: every E <= 64 at
+ *   k <= 192 is staged) and otherwise walks the lists in global memory: slower, never different. */
+#define NRMS_ADJ_MAX 256
+size_t nrms_topk_dot_adjusted_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_adjusted(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                           const float* bias /* [N], nullable */, const int64_t* adj_ids /* [B, E] */,
+                           const float* adj_delta /* [B, E] */, int32_t n_adjust /* E */, const int64_t* exclude, int32_t n_exclude,
+                           float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
+size_t nrms_rank_dot_adjusted_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude);
+int nrms_rank_dot_adjusted(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                           const float* bias /* [N], nullable */, const int64_t* adj_ids /* [B, E] */,
+                           const float* adj_delta /* [B, E] */, int32_t n_adjust /* E */, const int64_t* targets,
+                           const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- Paging through the exact ranking: a cursor on the top-k, and lists up to 4096 (candidate generation for a re-ranker, a feed
  * that scrolls: "the next 20 after what I showed"; PARITY UNPINNED, the reference has no catalogue retrieval) ----
  * The order of nrms_topk_dot[_biased|_windowed] is total (s' descending, then the SMALLER n, -0.0 equal to +0.0) and a score's bits

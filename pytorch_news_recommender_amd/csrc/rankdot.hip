@@ -25,6 +25,11 @@
 // forms of A and B (one body each, shared with the kernels above), test the owner's allow bit / the block's transposed bitmap in
 // front of tk_entry, and B skips the waves whose 64 items are closed to its whole block; C is the same.
 //
+// nrms_rank_dot_adjusted ranks by s''(b, n) = s'(b, n) + the delta of user b's lowest slot that names n (topk_entry.h: TkAdjust):
+// rank_entries_adjusted_kernel and rank_count_adjusted_kernel, the ADJ forms of A and B, add it to the finished s' in front of
+// tk_entry (A from the owner's list in global memory, B through the block's staged slots and per-wave marks); C is the same: the
+// entry it takes back out for an excluded id is the s'' entry B counted.
+//
 // The scores are tk_chain's (topk_entry.h), the one chain topk_slice_kernel runs too, with one A operand: nrms_topk_dot's bits
 // (tests/test_hip_rank.py checks it end to end).
 #include "topk_entry.h"
@@ -43,13 +48,16 @@ constexpr int RK_A_CHUNKS = 4096;              // grid.y bound of kernel A (long
 // memory; the ids are gathered one by one, so there is no bitmap to share).
 // The body is written once; the kernels below are its instantiations (the TAGS forms are kernels of their own, so that the others
 // keep their names, signatures and kernarg layouts).
-template <bool VEC, bool BIAS, bool WINDOW, bool TAGS>
+// ADJ: the owner's delta for the id (tk_adjust_find: the lowest slot of the owner's list, from global memory) is added to s', one
+// fp32 add after the prior's, so the entry is the s'' entry kernel B counts; a NaN sum gets entry 0 like a NaN score.
+template <bool VEC, bool BIAS, bool WINDOW, bool TAGS, bool ADJ = false>
 __device__ __forceinline__ void rank_entries_body(int B, int N, int d, int T, int n_exclude, const float* __restrict__ user,
                                                   const float* __restrict__ items, const int64_t* __restrict__ targets,
                                                   const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
                                                   uint32_t* __restrict__ counts, const float* __restrict__ bias, TkWindow win,
-                                                  TkTags tags) {
+                                                  TkTags tags, TkAdjust adj = TkAdjust{nullptr, nullptr, 0}) {
     static_assert(!(TAGS && WINDOW), "the tag set is for the plain and the biased rank only");
+    static_assert(!(ADJ && (TAGS || WINDOW)), "the adjustments are for the plain and the biased rank only");
     __shared__ int rows[64];
     __shared__ __attribute__((aligned(16))) float stage[64 * TK_BP];
     const int lane = threadIdx.x;
@@ -93,6 +101,10 @@ __device__ __forceinline__ void rank_entries_body(int B, int N, int d, int T, in
             if constexpr (BIAS) {
                 if (idc >= 0 && idc < N) s = s + bias[idc];
             }
+            if constexpr (ADJ) {
+                float dl;
+                if (idc >= 0 && idc < N && tk_adjust_find(adj, u0 + uc, idc, dl)) s = s + dl;
+            }
             bool ok = idc >= 0 && idc < N && !__builtin_isnan(s);
             if constexpr (WINDOW) {
                 if (ok) {
@@ -130,6 +142,17 @@ __global__ __launch_bounds__(64) void rank_entries_tagged_kernel(int B, int N, i
                                               TkWindow{nullptr, nullptr}, tags);
 }
 
+template <bool VEC, bool BIAS>
+__global__ __launch_bounds__(64) void rank_entries_adjusted_kernel(int B, int N, int d, int T, int n_exclude,
+                                                                   const float* __restrict__ user, const float* __restrict__ items,
+                                                                   const int64_t* __restrict__ targets,
+                                                                   const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
+                                                                   uint32_t* __restrict__ counts, const float* __restrict__ bias,
+                                                                   TkAdjust adj) {
+    rank_entries_body<VEC, BIAS, false, false, true>(B, N, d, T, n_exclude, user, items, targets, exclude, ent, counts, bias,
+                                                     TkWindow{nullptr, nullptr}, TkTags{nullptr, nullptr, 0}, adj);
+}
+
 // Kernel B.  Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step.  ent [B, M]:
 // the first T entries of a row are the user's targets.  counts [B, T] += #{live non-NaN n in the slice : entry(n) > target}.
 // WINDOW: topk_slice_kernel's window filter and dead-tile skip.  The block stages its users' (lo, hi) in LDS and forms their
@@ -139,12 +162,16 @@ __global__ __launch_bounds__(64) void rank_entries_tagged_kernel(int B, int N, i
 // TAGS: topk_slice_kernel's tag filter and dead-wave skip.  The block builds the transposed bitmap of its users' tag sets in LDS
 // (tk_tags_stage); a lane reads one LDS word per item, tm[c], and a score becomes an entry only if its user's bit of tm[c] is set;
 // a wave with tm[0] | tm[1] == 0 in every lane goes to its next step like a WINDOW wave outside the hull.
-template <int W, bool VEC, bool BIAS, bool WINDOW, bool TAGS>
+// ADJ: topk_slice_kernel's adjustments.  The block stages the slots of its users that name a row of its slice (tk_adjust_stage;
+// RK_ADJ_CAP words: every slot its 32 users can have), a wave marks its 64 items' hits per step (tk_adjust_mark) and the lane that
+// holds a marked pair adds the delta of the pair's lowest slot to the finished s' (tk_adjust_apply) before the entries are formed.
+template <int W, bool VEC, bool BIAS, bool WINDOW, bool TAGS, bool ADJ = false>
 __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int M, int slice_len, const float* __restrict__ user,
                                                 const float* __restrict__ items, const uint64_t* __restrict__ ent,
                                                 uint32_t* __restrict__ counts, const float* __restrict__ bias, TkWindow win,
-                                                TkTags tags) {
+                                                TkTags tags, TkAdjust adj = TkAdjust{nullptr, nullptr, 0}) {
     static_assert(!(TAGS && WINDOW), "the tag set is for the plain and the biased rank only");
+    static_assert(!(ADJ && (TAGS || WINDOW)), "the adjustments are for the plain and the biased rank only");
     __shared__ uint64_t tgt[TK_UT][RK_MAX_T];
     __shared__ uint32_t cnts[TK_UT][RK_MAX_T];
     __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
@@ -172,7 +199,24 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
         ubt = ubt_lds;
         tk_tags_stage(ubt, tags, u0, B, 64 * W);
     }
+    [[maybe_unused]] uint32_t* axl = nullptr;       // ADJ: the block's staged slots, their count and one row of marks per wave
+    [[maybe_unused]] int* axl_n = nullptr;
+    [[maybe_unused]] uint32_t* axm = nullptr;
+    if constexpr (ADJ) {
+        __shared__ uint32_t axl_lds[RK_ADJ_CAP];
+        __shared__ int axl_n_lds;
+        __shared__ uint32_t axm_lds[W][64];
+        axl = axl_lds;
+        axl_n = &axl_n_lds;
+        axm = axm_lds[wave];
+        if (threadIdx.x == 0) axl_n_lds = 0;
+        for (int i = threadIdx.x; i < 64 * W; i += 64 * W) axm_lds[i / 64][i % 64] = 0;
+        __syncthreads();
+        tk_adjust_stage<RK_ADJ_CAP>(axl, axl_n, adj, u0, B, n_begin, n_end, 64 * W);
+    }
     __syncthreads();
+    [[maybe_unused]] int n_axl = 0;
+    if constexpr (ADJ) n_axl = *axl_n;
     int blo = 0, bhi = 0;
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
 
@@ -213,6 +257,17 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
             for (int c = 0; c < TK_TN; ++c) bv[c] = bias[min(nw + 32 * c + r, N - 1)];
         }
         tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
+        if constexpr (ADJ) {          // s' in place (the same fp32 add as below), then the marked pairs' deltas
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c)
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) acc[c][q] = acc[c][q] + bv[c];
+            }
+            uint32_t am[TK_TN];
+            tk_adjust_mark<RK_ADJ_CAP>(am, axm, axl, n_axl, adj, u0, B, n_begin, nw, n_end, lane);
+            tk_adjust_apply(acc, am, adj, u0, nw, lane);
+        }
         // C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
         uint64_t e[TK_TN][16];
 #pragma unroll
@@ -222,7 +277,7 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 float s = acc[c][q];
-                if constexpr (BIAS) s = s + bv[c];
+                if constexpr (BIAS && !ADJ) s = s + bv[c];
                 bool open = live && !__builtin_isnan(s);
                 if constexpr (WINDOW) {
                     const int2 w = wwin[(q & 3) + 8 * (q >> 2) + 4 * h];
@@ -276,6 +331,15 @@ __global__ __launch_bounds__(64 * W) void rank_count_tagged_kernel(int B, int N,
                                                                    const float* __restrict__ bias, TkTags tags) {
     rank_count_body<W, VEC, BIAS, false, true>(B, N, d, T, M, slice_len, user, items, ent, counts, bias, TkWindow{nullptr, nullptr},
                                                tags);
+}
+
+template <int W, bool VEC, bool BIAS>
+__global__ __launch_bounds__(64 * W) void rank_count_adjusted_kernel(int B, int N, int d, int T, int M, int slice_len,
+                                                                     const float* __restrict__ user, const float* __restrict__ items,
+                                                                     const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts,
+                                                                     const float* __restrict__ bias, TkAdjust adj) {
+    rank_count_body<W, VEC, BIAS, false, false, true>(B, N, d, T, M, slice_len, user, items, ent, counts, bias,
+                                                      TkWindow{nullptr, nullptr}, TkTags{nullptr, nullptr, 0}, adj);
 }
 
 // Kernel C.  One wave per user.  N = 0: every target is invalid (ent and counts are not read).
@@ -342,7 +406,8 @@ extern "C" size_t nrms_rank_dot_workspace_bytes(int32_t B, int64_t N, int32_t d,
 static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
                          const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* targets,
                          const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
-                         size_t workspace_bytes, void* stream, bool tagged = false, TkTags tags = TkTags{nullptr, nullptr, 0}) {
+                         size_t workspace_bytes, void* stream, bool tagged = false, TkTags tags = TkTags{nullptr, nullptr, 0},
+                         TkAdjust adj = TkAdjust{nullptr, nullptr, 0}) {
     int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "T", T, RK_MAX_T, n_exclude);
     if (rc != NRMS_OK) return rc;
     NRMS_REQUIRE(!tagged || (tags.n_tags >= 1 && tags.n_tags <= TK_MAX_TAGS), "%s: n_tags must be in [1, %d] (n_tags=%d)", who,
@@ -365,7 +430,19 @@ static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     char what[64];
     if (g.S > 0) {
         const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64)), grid_b(g.tiles, g.S);
-        if (tagged) tk_with_flags([&](auto V, auto BI) {
+        if (adj.adj_ids) tk_with_flags([&](auto V, auto BI) {
+            constexpr bool v = decltype(V)::value, bi = decltype(BI)::value;
+            hipLaunchKernelGGL((rank_entries_adjusted_kernel<v, bi>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items,
+                               targets, exclude, ent, counts, bias, adj);
+            snprintf(what, sizeof what, "%s(entries)", who);
+            rc = check_launch(what);
+            if (rc != NRMS_OK) return;
+            hipLaunchKernelGGL((rank_count_adjusted_kernel<TK_WAVES, v, bi>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M,
+                               g.slice_len, user, items, ent, counts, bias, adj);
+            snprintf(what, sizeof what, "%s(count)", who);
+            rc = check_launch(what);
+        }, tk_vec_ok(d, user, items), bias != nullptr);
+        else if (tagged) tk_with_flags([&](auto V, auto BI) {
             constexpr bool v = decltype(V)::value, bi = decltype(BI)::value;
             hipLaunchKernelGGL((rank_entries_tagged_kernel<v, bi>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items, targets,
                                exclude, ent, counts, bias, tags);
@@ -435,4 +512,13 @@ int nrms::rank_dot_tagged_call(int32_t B, int64_t N, int32_t d, int32_t T, const
                                float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
     return rank_dot_call("rank_dot_tagged", B, N, d, T, user, items, bias, false, nullptr, nullptr, targets, exclude, n_exclude, ranks,
                          target_scores, workspace, workspace_bytes, stream, true, tags);
+}
+
+// nrms_rank_dot_adjusted's body (its C entry point is in topkadjust.hip, with the adjusted top-k's, which has checked E and the two
+// pointers): adj.adj_ids null = the plain / biased call.
+int nrms::rank_dot_adjusted_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
+                                 TkAdjust adj, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                                 float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
+    return rank_dot_call("rank_dot_adjusted", B, N, d, T, user, items, bias, false, nullptr, nullptr, targets, exclude, n_exclude,
+                         ranks, target_scores, workspace, workspace_bytes, stream, false, TkTags{nullptr, nullptr, 0}, adj);
 }

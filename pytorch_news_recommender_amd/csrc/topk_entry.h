@@ -1,6 +1,6 @@
 // What the catalogue kernels share (topk.hip and topksec.hip: the k best items per user; softmaxsample.hip: a Gumbel-top-S draw;
 // rankdot.hip: the exact rank of given items in that order): the tile constants, the uint64 entry that carries the order, the
-// one score chain every one of their kernels runs (tk_chain), the time window, the tag set, and the host side every entry point shares:
+// one score chain every one of their kernels runs (tk_chain), the time window, the tag set, the per-user adjustments, and the host side every entry point shares:
 // the launch geometry, the argument checks and the choice of a kernel instantiation.
 //
 // An entry is the score as an order-preserving 32-bit key (-0.0 canonicalised to +0.0) above the complement of the 32-bit
@@ -224,6 +224,123 @@ __device__ __forceinline__ int tk_caps_reach(const int32_t* __restrict__ cap_row
     return __builtin_amdgcn_readfirstlane(kb | (__ballot(rationed) != 0 ? 0x10000 : 0));
 }
 
+// The per-user score adjustments of nrms_topk_dot_adjusted / nrms_rank_dot_adjusted (include/nrms_hip.h states them): slot (b, e)
+// names catalogue row adj_ids[b, e] (a value outside [0, N): an empty slot) and moves that row's score for user b by
+// adj_delta[b, e], one fp32 add on the finished s'; of several slots of one user that name one row the LOWEST e counts.
+struct TkAdjust {
+    const int64_t* adj_ids;      // [B, E]
+    const float* adj_delta;      // [B, E]
+    int n_adjust;                // E
+};
+constexpr int TK_ADJ_MAX = 256;
+// A block's staged slots (ADJ kernels) are 32-bit words: (row - the slice's first row) << 5 | user row of the block.  A slice
+// longer than 2^27 rows (only a catalogue beyond 2^27 rows cut into very few slices) is not staged: its block walks the global
+// lists, like a block whose slots overflow its LDS list.
+constexpr int TK_ADJ_ROW_BITS = 27;
+// The staged slots that fit beside a P class's buffers (top-k slice kernels; the rank count kernel has no buffers and holds
+// every slot its 32 users can have).
+constexpr int tk_adjust_cap(int P) { return P <= 256 ? 2048 : 1024; }
+constexpr int RK_ADJ_CAP = TK_UT * TK_ADJ_MAX;
+
+// One block's staged slots: the slots of users [u0, u0 + 32) that name a row of [n_begin, n_end), in any order, appended to
+// xl[0, CAP); *xl_n counts them (past CAP: the list overflowed and is not used).  *xl_n is 0 on entry and a barrier lies between
+// that store and this call; every thread of the block (nthreads of them) takes part; the caller's next barrier publishes it.
+template <int CAP>
+__device__ __forceinline__ void tk_adjust_stage(uint32_t* xl, int* xl_n, TkAdjust a, int u0, int B, int n_begin, int n_end,
+                                                int nthreads) {
+    if (n_end - n_begin > (1 << TK_ADJ_ROW_BITS)) {          // block-uniform: nobody appends
+        if (threadIdx.x == 0) *xl_n = CAP + 1;
+        return;
+    }
+    const int E = a.n_adjust;
+    const int total = min(TK_UT, B - u0) * E;
+    for (int i = threadIdx.x; i < total; i += nthreads) {
+        const int64_t v = a.adj_ids[(long)u0 * E + i];
+        if (v >= n_begin && v < n_end) {
+            const int at = atomicAdd(xl_n, 1);
+            if (at < CAP) xl[at] = ((uint32_t)(v - n_begin) << 5) | (uint32_t)(i / E);
+        }
+    }
+}
+
+// One wave, one step: xmask[c] = the block's user rows (bit i: user u0 + i) with a slot that names this lane's item nw + 32 c +
+// (lane & 31) of column tile c.  n_xl: the block's *xl_n after the publishing barrier (0: no slot names a row of the slice, nothing
+// is read; at most CAP: the staged list is scanned; more: the global lists of the block's users are walked, correct and slow on
+// purpose).  xm: the wave's private row of 64 words, all 0 between calls.  Marks are a set, so the order of xl does not matter;
+// which slot counts is decided where the delta is read (tk_adjust_find).  Wave-level syncs only; nw < n_end.
+template <int CAP>
+__device__ __forceinline__ void tk_adjust_mark(uint32_t (&xmask)[TK_TN], uint32_t* xm, const uint32_t* xl, int n_xl, TkAdjust a,
+                                               int u0, int B, int n_begin, int nw, int n_end, int lane) {
+#pragma unroll
+    for (int c = 0; c < TK_TN; ++c) xmask[c] = 0;
+    if (n_xl == 0) return;
+    if (n_xl <= CAP) {
+        const uint32_t base = (uint32_t)(nw - n_begin);
+        for (int i = lane; i < n_xl; i += 64) {
+            const uint32_t e = xl[i];
+            const uint32_t off = (e >> 5) - base;
+            if (off < 64u) atomicOr(&xm[off], 1u << (e & 31u));
+        }
+    } else {
+        const int E = a.n_adjust;
+        const int total = min(TK_UT, B - u0) * E;
+        const int64_t hi = min((int64_t)nw + 64, (int64_t)n_end);
+        for (int i = lane; i < total; i += 64) {
+            const int64_t v = a.adj_ids[(long)u0 * E + i];
+            if (v >= nw && v < hi) atomicOr(&xm[(int)(v - nw)], 1u << (i / E));
+        }
+    }
+    tk_wave_sync();
+#pragma unroll
+    for (int c = 0; c < TK_TN; ++c) xmask[c] = xm[32 * c + (lane & 31)];
+    tk_wave_sync();
+#pragma unroll
+    for (int c = 0; c < TK_TN; ++c)
+        if (xmask[c]) xm[32 * c + (lane & 31)] = 0;
+    tk_wave_sync();
+}
+
+// The delta of user b's LOWEST slot that names row n >= 0 (read from global memory: hits are rare and the lists L2-resident).  The
+// list is read eight slots at a time, so that eight loads are in flight per round trip, and compared in slot order.
+__device__ __forceinline__ bool tk_adjust_find(TkAdjust a, long b, int64_t n, float& delta) {
+    const int E = a.n_adjust;
+    const int64_t* row = a.adj_ids + b * E;
+    for (int e0 = 0; e0 < E; e0 += 8) {
+        int64_t v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = e0 + j < E ? row[e0 + j] : -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (v[j] == n) {
+                delta = a.adj_delta[b * E + e0 + j];
+                return true;
+            }
+    }
+    return false;
+}
+
+// One wave, after the chain (and the prior's add): the lane that holds a marked pair adds the pair's delta to its accumulator
+// register, one fp32 add; every other register is left as it is.  C/D layout: user row i = (q & 3) + 8 (q >> 2) + 4 (lane >> 5),
+// so this lane holds the rows with bit 2 of i equal to its half, in register q = (i & 3) + 4 (i >> 3).
+__device__ __forceinline__ void tk_adjust_apply(tk_f32x16 (&acc)[TK_TN], const uint32_t (&xmask)[TK_TN], TkAdjust a, int u0, int nw,
+                                                int lane) {
+    const uint32_t half = (lane >> 5) ? 0xF0F0F0F0u : 0x0F0F0F0Fu;
+#pragma unroll
+    for (int c = 0; c < TK_TN; ++c) {
+        uint32_t m = xmask[c] & half;
+        while (m) {
+            const int i = __builtin_ctz(m);
+            m &= m - 1;
+            float dl;
+            if (!tk_adjust_find(a, u0 + i, nw + 32 * c + (lane & 31), dl)) continue;
+            const int qw = (i & 3) + 4 * (i >> 3);
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if (q == qw) acc[c][q] = acc[c][q] + dl;
+        }
+    }
+}
+
 __device__ __forceinline__ float tk_ld(const float* p, int kk, int d) { return kk < d ? p[kk] : 0.0f; }
 
 // The score chain of every catalogue kernel.  One wave: acc[c] += the 32 x 32 score tile of A rows (lane (r, h): the row of
@@ -371,6 +488,11 @@ static int tk_check_ptrs(const char* who, std::initializer_list<TkPtr> ptrs, con
 int rank_dot_tagged_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
                          TkTags tags, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
                          float* target_scores, void* workspace, size_t workspace_bytes, void* stream);
+
+// nrms_rank_dot_adjusted's body: rankdot.hip defines it beside the rank kernels, topkadjust.hip holds the C entry point.
+int rank_dot_adjusted_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
+                           TkAdjust adj, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                           float* target_scores, void* workspace, size_t workspace_bytes, void* stream);
 
 // The chain's loads are float4 when every row starts on 16 bytes.
 static bool tk_vec_ok(int32_t d, const float* user, const float* items) {

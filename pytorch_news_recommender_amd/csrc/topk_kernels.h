@@ -495,7 +495,15 @@ struct TkFilter {
 // that above_tags() tests before the offer.  The slice lists are capped lists of at most k entries, and
 // topk_merge_capped_kernel runs the same selection over them.
 //
-// The window's two pointers are a kernel argument of the WINDOW instantiations alone, the cursor's of the CURSOR instantiations
+// ADJ (nrms_topk_dot_adjusted; with or without BIAS): the block compacts, once, the slots of its 32 users that name a row of its
+// slice into an LDS list of 32-bit words (tk_adjust_stage; tk_adjust_cap(P) of them fit beside the P class's buffers, and a block
+// whose slots overflow the list walks the global lists instead, dropping none).  Per step a wave marks its 64 items' hits in its
+// private LDS row of 32-bit user masks (tk_adjust_mark), and the lane that holds a marked pair reads the delta of the pair's
+// LOWEST slot from global memory and adds it to its accumulator register (tk_adjust_apply): one fp32 add on the finished s',
+// after the prior's, before pend is formed, so a boosted score below its user's threshold is offered and no entry is adjusted
+// twice.  A block none of whose slots names a row of its slice reads nothing per step.  A NaN sum fails the filter's NaN test.
+//
+// The window's two pointers are a kernel argument of the WINDOW instantiations alone, the adjustments' of the ADJ instantiations alone, the cursor's of the CURSOR instantiations
 // alone, the tag set's of the TAGS instantiations alone and the caps' of the CAPS instantiations alone (WIN holds a TkWindow, a
 // TkCursor, both in that order, a TkTags, a TkCaps, or nothing; CURSOR, TAGS and CAPS are read off the pack), so every other instantiation keeps its name, its signature and its kernarg
 // layout.
@@ -510,9 +518,11 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     constexpr bool CURSOR = (std::is_same<WIN, TkCursor>::value || ...);
     constexpr bool TAGS = (std::is_same<WIN, TkTags>::value || ...);
     constexpr bool CAPS = (std::is_same<WIN, TkCaps>::value || ...);
-    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0) + (CAPS ? 1 : 0),
+    constexpr bool ADJ = (std::is_same<WIN, TkAdjust>::value || ...);
+    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0) + (CAPS ? 1 : 0) + (ADJ ? 1 : 0),
                   "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, TAGS kernels one TkTags, CAPS kernels one TkCaps, "
-                  "the others none");
+                  "ADJ kernels one TkAdjust, the others none");
+    static_assert(!(ADJ && (GROUPED || NOISE || WINDOW || CURSOR || TAGS || CAPS)), "the adjustments are for the plain and the biased top-k only");
     static_assert(!(CAPS && (GROUPED || NOISE || WINDOW || CURSOR || TAGS)), "the tag caps are for the plain and the biased top-k only");
     static_assert(!(TAGS && (GROUPED || NOISE || WINDOW || CURSOR)), "the tag set is for the plain and the biased top-k only");
     const TkWindow win = tk_window_arg(win_arg...);
@@ -571,6 +581,24 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         }
         flt.sel = TkSelectCapped<TT>{caps.item_tag, caps.cap, n_tags, reach_lds, n_tags <= TT ? ttag_lds : nullptr};
     }
+    constexpr int AC = tk_adjust_cap(P);
+    [[maybe_unused]] TkAdjust adj{nullptr, nullptr, 0};
+    [[maybe_unused]] uint32_t* axl = nullptr;       // ADJ: the block's staged slots, their count and one row of marks per wave
+    [[maybe_unused]] int* axl_n = nullptr;
+    [[maybe_unused]] uint32_t* axm = nullptr;
+    if constexpr (ADJ) {
+        __shared__ uint32_t axl_lds[AC];
+        __shared__ int axl_n_lds;
+        __shared__ uint32_t axm_lds[W][64];
+        axl = axl_lds;
+        axl_n = &axl_n_lds;
+        axm = axm_lds[wave];
+        adj = tk_pack_arg<TkAdjust>(win_arg...);
+        if (threadIdx.x == 0) axl_n_lds = 0;
+        for (int i = threadIdx.x; i < 64 * W; i += 64 * W) axm_lds[i / 64][i % 64] = 0;
+        __syncthreads();
+        tk_adjust_stage<AC>(axl, axl_n, adj, u0, B, n_begin, n_end, 64 * W);
+    }
     if constexpr (NOISE) {
         if (threadIdx.x < TK_UT) rseed[threadIdx.x] = tk_noise_row_seed(noise.seed, (uint64_t)noise.row_key[min(u0 + (int)threadIdx.x, B - 1)]);
     }
@@ -582,6 +610,8 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         for (int u = 0; u < TK_UT; ++u) any |= flt.sel.reach[u] >> 16;
         if (!any) flt.sel.ttag = nullptr;
     }
+    [[maybe_unused]] int n_axl = 0;
+    if constexpr (ADJ) n_axl = *axl_n;
     int blo = 0, bhi = 0;
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
     if constexpr (CURSOR) {
@@ -663,6 +693,13 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 for (int c = 0; c < TK_TN; ++c)
 #pragma unroll
                     for (int q = 0; q < 16; ++q) acc[c][q] = acc[c][q] + bv[c];
+            }
+        }
+        if constexpr (ADJ) {          // after the prior's add, before pend is formed: the filter sees s''
+            if (nw < n_end) {
+                uint32_t am[TK_TN];
+                tk_adjust_mark<AC>(am, axm, axl, n_axl, adj, u0, B, n_begin, nw, n_end, lane);
+                tk_adjust_apply(acc, am, adj, u0, nw, lane);
             }
         }
         bool live[TK_TN];

@@ -188,6 +188,43 @@ def load_dataset(config, file, path, _type=0):
         return pickle.load(f)
 
 
+def seen_adjustment(seen_ptr, seen_ids, beta, max_slots, device=None):
+    """Impression discounting as ``Model.recommend_adjusted``'s ``adjust``: a per-user CSR of seen-but-not-clicked news ->
+    ``(ids int64 [n_users, max_slots], delta float32 [n_users, max_slots])``.  seen_ids[seen_ptr[u]:seen_ptr[u + 1]] are the news
+    user u was shown; a news listed c times was seen c times and gets delta = -beta * c, in one slot.  A user with more than
+    max_slots distinct news keeps the most-seen, ties to the smaller id; the slots of a row are in that order.  Unused slots hold
+    id 0 / delta 0.0 (id 0 names no news).  Torch ops on ``device`` (default: seen_ids' own when it is a tensor, else the CPU)."""
+    max_slots = int(max_slots)
+    if not 0 <= max_slots <= 256:
+        raise ValueError("seen_adjustment: max_slots = %r must be in [0, 256]" % (max_slots,))
+    if device is None:
+        device = seen_ids.device if torch.is_tensor(seen_ids) else "cpu"
+    ptr = torch.as_tensor(seen_ptr).to(device, dtype=torch.int64).reshape(-1)
+    news = torch.as_tensor(seen_ids).to(device, dtype=torch.int64).reshape(-1)
+    if ptr.numel() < 1 or int(ptr[0]) != 0 or int(ptr[-1]) != news.numel() or bool((ptr[1:] < ptr[:-1]).any()):
+        raise ValueError("seen_adjustment: seen_ptr must rise from 0 to len(seen_ids) = %d" % news.numel())
+    n_users = ptr.numel() - 1
+    ids = torch.zeros(n_users, max_slots, dtype=torch.int64, device=device)
+    delta = torch.zeros(n_users, max_slots, dtype=torch.float32, device=device)
+    if news.numel() == 0 or max_slots == 0:
+        return ids, delta
+    if int(news.min()) < 0:
+        raise ValueError("seen_adjustment: news ids must be >= 0")
+    span = int(news.max()) + 1
+    user = torch.repeat_interleave(torch.arange(n_users, device=device), ptr[1:] - ptr[:-1])
+    pair, count = torch.unique(user * span + news, return_counts=True)              # the distinct (user, news), and how often
+    p_user, p_news = pair // span, pair % span
+    top = int(count.max())
+    order = torch.argsort((p_user * (top + 1) + (top - count)) * span + p_news)      # user, then most seen, then the smaller id
+    p_user, p_news, count = p_user[order], p_news[order], count[order]
+    first = torch.cumsum(torch.bincount(p_user, minlength=n_users), 0) - torch.bincount(p_user, minlength=n_users)
+    place = torch.arange(p_user.numel(), device=device) - first[p_user]
+    keep = place < max_slots
+    ids[p_user[keep], place[keep]] = p_news[keep]
+    delta[p_user[keep], place[keep]] = count[keep].to(torch.float32) * (-float(beta))
+    return ids, delta
+
+
 class SyntheticMind:
     """A MIND-shaped corpus + click behaviours with learnable structure: every news item and
     every user belongs to a latent topic; users click mostly in-topic news, and titles draw
@@ -321,6 +358,25 @@ class SyntheticMind:
             clicks += self._pick(t, n, rng=rng)
             lens.append(n)
         return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(clicks, dtype=np.int64)
+
+    def seen_log(self, user_ptr, clicks, n_seen=12, seed=0):
+        """News a user was SHOWN and did not click, for an existing ``click_log``: ``(seen_ptr int64 [n_users + 1], seen_ids
+        int64)``, user u's at ``seen_ids[seen_ptr[u]:seen_ptr[u + 1]]``.  Per user up to n_seen draws around the topic most of the
+        user's clicks belong to (``_pick``; a draw that hits a news the user clicked, held-out clicks included, is dropped); a news
+        drawn twice was seen twice.  A function of (the corpus, user_ptr, clicks, n_seen, seed) alone: the generator is made anew by
+        every call, and neither ``click_log`` nor any other stream moves."""
+        user_ptr = np.asarray(user_ptr, dtype=np.int64).reshape(-1)
+        clicks = np.asarray(clicks, dtype=np.int64).reshape(-1)
+        rng = np.random.default_rng([5000003, int(seed)])
+        lens, seen = [], []
+        for u in range(user_ptr.size - 1):
+            own = clicks[user_ptr[u]:user_ptr[u + 1]]
+            t = int(np.bincount(self.topic[own - 1], minlength=self.n_topics).argmax()) if own.size else int(rng.integers(0, self.n_topics))
+            clicked = set(own.tolist())
+            shown = [n for n in self._pick(t, int(n_seen), rng=rng) if n not in clicked]
+            seen += shown
+            lens.append(len(shown))
+        return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(seen, dtype=np.int64)
 
     def click_ticks(self, user_ptr, horizon=100000, max_step=200):
         """Ticks for an existing ``click_log``: int64 [len(clicks)] for ``ClickFeed(click_time=...)``.  Every user gets a start tick
@@ -761,8 +817,9 @@ class ClickFeed(DeviceFeed):
 
     def __init__(self, config, user_ptr, clicks, id2title_dict=None, id2abst_dict=None, news_categ=None, news_subcateg=None, holdout=1,
                  min_history=1, popularity_power=0.75, weights=None, batch_size=None, device="cuda", shuffle=False, drop_last=False, seed=0,
-                 resample=True, rank=0, world=1, negatives="popularity", temperature=1.0, click_time=None):
+                 resample=True, rank=0, world=1, negatives="popularity", temperature=1.0, click_time=None, seen=None):
         user_ptr, clicks = np.asarray(user_ptr, dtype=np.int64).reshape(-1), np.asarray(clicks, dtype=np.int64).reshape(-1)
+        self._seen, self._seen_slots = self._checked_seen(seen, user_ptr), None
         self.click_time = self._checked_click_time(click_time, user_ptr, clicks)
         if negatives not in ("popularity", "adaptive"):
             raise ValueError("ClickFeed: negatives = %r must be 'popularity' or 'adaptive'" % (negatives,))
@@ -843,6 +900,38 @@ class ClickFeed(DeviceFeed):
         self.draws, self.drawn_seed, self.n_short = 0, None, None
         self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)     # n_short, n_bad
         self._ws = None
+
+    @staticmethod
+    def _checked_seen(seen, user_ptr):
+        """None, or the seen log (seen_ptr int64 [n_users + 1], seen_ids int64) as host arrays."""
+        if seen is None:
+            return None
+        if not isinstance(seen, (tuple, list)) or len(seen) != 2:
+            raise ValueError("ClickFeed: seen must be a pair (seen_ptr [n_users + 1], seen_ids) (got %s)" % type(seen).__name__)
+        ptr, ids = np.asarray(seen[0], dtype=np.int64).reshape(-1), np.asarray(seen[1], dtype=np.int64).reshape(-1)
+        if ptr.size != user_ptr.size or ptr.size < 1 or ptr[0] != 0 or (np.diff(ptr) < 0).any() or int(ptr[-1]) != ids.size:
+            raise ValueError("ClickFeed: seen_ptr must have one entry per user and one more (%d) and rise from 0 to len(seen_ids) = %d"
+                             % (user_ptr.size, ids.size))
+        if ids.size and ids.min() < 0:
+            raise ValueError("ClickFeed: seen news ids must be >= 0")
+        return ptr, ids
+
+    def seen_adjustment(self, beta, max_slots=32, users=None):
+        """``data_handler.seen_adjustment`` of the feed's seen log (``seen=`` of the constructor; ValueError without one), on the
+        feed's device -> (ids int64 [n, max_slots], delta float32 [n, max_slots]): the ``adjust`` of ``Model.recommend_adjusted`` /
+        ``train_eval.recommend(adjust=...)``.  users: the user of every row wanted, e.g. ``heldout_users()`` for the samples of
+        ``heldout_samples()``, or a batch's users; None: one row per user of the log.  The whole log's slots are built once per
+        (beta, max_slots) and kept on the device, so a call per batch costs one gather."""
+        if self._seen is None:
+            raise ValueError("ClickFeed.seen_adjustment: the feed has no seen log (give seen=(seen_ptr, seen_ids))")
+        key = (float(beta), int(max_slots))
+        if self._seen_slots is None or self._seen_slots[0] != key:
+            self._seen_slots = (key, seen_adjustment(self._seen[0], self._seen[1], beta, max_slots, device=self.device))
+        ids, delta = self._seen_slots[1]
+        if users is None:
+            return ids, delta
+        u = torch.as_tensor(users).to(self.device, dtype=torch.int64).reshape(-1)
+        return ids[u].contiguous(), delta[u].contiguous()
 
     @staticmethod
     def _checked_click_time(click_time, user_ptr, clicks):

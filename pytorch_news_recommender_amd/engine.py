@@ -112,6 +112,7 @@ def _stream():
 
 
 MAX_TAGS = 512          # nrms_topk_dot_tagged / nrms_rank_dot_tagged: 1 <= n_tags <= 512
+MAX_ADJUST = 256        # nrms_topk_dot_adjusted / nrms_rank_dot_adjusted: 0 <= n_adjust <= 256 (NRMS_ADJ_MAX)
 
 
 def pack_tag_mask(allow):
@@ -1007,6 +1008,78 @@ class NRMSEngine:
                                                _lib.ptr(item_tag), n_tags, _lib.ptr(allow), _lib.ptr(tg), _lib.ptr(exclude), n_ex,
                                                _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
             _lib.check(rc, "nrms_rank_dot_tagged")
+            if not whole:
+                ranks[:, t0:t0 + T] = rk
+                scores[:, t0:t0 + T] = sc
+        return ranks, scores
+
+    def _adjust_args(self, who, adj_ids, adj_delta, B, dev):
+        """The checked slots of top_k_adjusted / rank_of_adjusted -> (adj_ids [B, E] int64, adj_delta [B, E] fp32, E), contiguous,
+        on the device; 0 <= E <= 256."""
+        for name, t, dt in (("adj_ids", adj_ids, torch.int64), ("adj_delta", adj_delta, torch.float32)):
+            if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != B or t.dtype != dt or t.device != dev:
+                got = ("%s %s on %s" % (tuple(t.shape), t.dtype, t.device)) if torch.is_tensor(t) else type(t).__name__
+                raise _lib.NrmsError("%s: %s must be a%s %s [%d, E] tensor on %s (got %s)"
+                                     % (who, name, "n" if dt == torch.int64 else "", str(dt).replace("torch.", ""), B, self.device, got))
+        if adj_ids.shape != adj_delta.shape:
+            raise _lib.NrmsError("%s: adj_ids %s and adj_delta %s must have one shape"
+                                 % (who, tuple(adj_ids.shape), tuple(adj_delta.shape)))
+        E = adj_ids.shape[1]
+        if E > MAX_ADJUST:
+            raise _lib.NrmsError("%s: n_adjust must be in [0, %d] (n_adjust=%d)" % (who, MAX_ADJUST, E))
+        return adj_ids.contiguous(), adj_delta.contiguous(), E
+
+    def top_k_adjusted(self, user_vec, items, k, adj_ids, adj_delta, exclude=None, bias=None):
+        """top_k with per-user score adjustments -> (scores [B, k] fp32, ids [B, k] int64).  adj_ids int64 [B, E], adj_delta fp32
+        [B, E] (device), 0 <= E <= 256: slot (b, e) moves the score of catalogue row adj_ids[b, e] for user b by adj_delta[b, e], one
+        fp32 add on the finished (biased) score; an id outside [0, N), e.g. -1, is an empty slot; of several slots of a row that name
+        one item the lowest e counts; a NaN delta closes the item for that user.  The returned scores are the adjusted ones.  Order,
+        padding, exclude and bias are top_k's, and all-empty slots give top_k bit for bit (nrms_topk_dot_adjusted; include/nrms_hip.h
+        states the contract)."""
+        who = "top_k_adjusted"
+        k = int(k)
+        B, N, d, exclude, n_ex, _, _ = self._top_k_args(who, user_vec, items, exclude, bias, None, None)
+        adj_ids, adj_delta, E = self._adjust_args(who, adj_ids, adj_delta, B, self._cuda_device())
+        nbytes = self.lib.nrms_topk_dot_adjusted_workspace_bytes(B, N, d, k)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (who, B, N, d, k))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot_adjusted(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                             _lib.ptr(adj_ids), _lib.ptr(adj_delta), E, _lib.ptr(exclude), n_ex, _lib.ptr(scores),
+                                             _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_topk_dot_adjusted")
+        return scores, ids
+
+    def rank_of_adjusted(self, user_vec, items, targets, adj_ids, adj_delta, exclude=None, bias=None):
+        """rank_of with per-user score adjustments -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position of every
+        target in top_k_adjusted's order, and its adjusted score.  adj_ids and adj_delta are top_k_adjusted's; a target whose delta
+        is NaN gets rank 0 / -inf like an excluded one.  Wider ``targets`` go in column chunks of 32 (nrms_rank_dot_adjusted;
+        include/nrms_hip.h states the contract)."""
+        who = "rank_of_adjusted"
+        self._check_tensor(who, "targets", targets, torch.int64, 2)
+        B, N, d, exclude, n_ex, _, _ = self._top_k_args(who, user_vec, items, exclude, bias, None, None)
+        if targets.shape[0] != B:
+            raise _lib.NrmsError("%s: targets must be [%d, T] (got %s)" % (who, B, tuple(targets.shape)))
+        adj_ids, adj_delta, E = self._adjust_args(who, adj_ids, adj_delta, B, self._cuda_device())
+        T_all = targets.shape[1]
+        ranks = torch.empty(B, T_all, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, T_all, dtype=torch.float32, device=self.device)
+        for t0 in range(0, T_all, 32):
+            T = min(32, T_all - t0)
+            whole = T == T_all
+            tg = targets if whole else targets[:, t0:t0 + T].contiguous()
+            rk = ranks if whole else torch.empty(B, T, dtype=torch.int32, device=self.device)
+            sc = scores if whole else torch.empty(B, T, dtype=torch.float32, device=self.device)
+            nbytes = self.lib.nrms_rank_dot_adjusted_workspace_bytes(B, N, d, T, n_ex)
+            if nbytes == 0:
+                raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, T=%d, n_exclude=%d)" % (who, B, N, d, T, n_ex))
+            ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+            rc = self.lib.nrms_rank_dot_adjusted(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                                 _lib.ptr(adj_ids), _lib.ptr(adj_delta), E, _lib.ptr(tg), _lib.ptr(exclude), n_ex,
+                                                 _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_rank_dot_adjusted")
             if not whole:
                 ranks[:, t0:t0 + T] = rk
                 scores[:, t0:t0 + T] = sc

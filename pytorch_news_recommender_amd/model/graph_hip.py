@@ -275,6 +275,16 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: recommend_capped is not available: a candidate's score depends on its neighbours in the "
                                   "click graph, not on a catalogue row alone (no recommend either, with caps or without)")
 
+    CATALOGUE_ADJUST = False
+
+    def recommend_adjusted(self, batch, k, catalogue, adjust, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("graph: recommend_adjusted is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone (no recommend either, adjusted or not)")
+
+    def rank_targets_adjusted(self, batch, targets, catalogue, adjust, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("graph: rank_targets_adjusted is not available: a candidate's score depends on its neighbours in "
+                                  "the click graph, not on a catalogue row alone (no rank_targets either)")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

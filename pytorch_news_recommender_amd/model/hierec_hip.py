@@ -401,6 +401,17 @@ class Model(FlatHipModel):
         raise NotImplementedError("hierec: recommend_capped is not available: HieRec scores the catalogue with a query per (topic, "
                                   "sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no per-tag caps")
 
+    CATALOGUE_ADJUST = False
+
+    def recommend_adjusted(self, batch, k, catalogue, adjust, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("hierec: recommend_adjusted is not available: HieRec scores the catalogue with a query per (topic, "
+                                  "sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no per-user adjustments")
+
+    def rank_targets_adjusted(self, batch, targets, catalogue, adjust, exclude_history=True, *, item_bias=None):
+        raise NotImplementedError("hierec: rank_targets_adjusted is not available: HieRec scores the catalogue with a query per "
+                                  "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot_adjusted ranks plain dot "
+                                  "products only")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

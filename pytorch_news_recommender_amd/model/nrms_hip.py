@@ -561,6 +561,58 @@ class Model(FlatHipModel):
             raise _lib.NrmsError("rank_targets_tagged: targets must be [%d, T] news ids (got %s)" % (user.shape[0], tuple(tg.shape)))
         return self._engine.rank_of_tagged(user, cat[1:], (tg - 1).contiguous(), tags, n_tags, allow, exclude, bias=bias)
 
+    @staticmethod
+    def _adjust_rows(adjust, cat, B, who):
+        """The kernels' view of per-user adjustments -> (adj_ids int64 [B, E] of catalogue rows, adj_delta fp32 [B, E]) for
+        engine.top_k_adjusted / rank_of_adjusted.  ``adjust`` = (news_ids [B, E], delta [B, E]) in _catalogue_query's convention:
+        news id n is row n - 1, so id 0 (and anything beyond the catalogue) becomes an empty slot."""
+        if not isinstance(adjust, (tuple, list)) or len(adjust) != 2:
+            raise _lib.NrmsError("%s: adjust must be a pair (news_ids [%d, E], delta [%d, E]) (got %s)"
+                                 % (who, B, B, type(adjust).__name__))
+        ids = torch.as_tensor(adjust[0]).to(cat.device, dtype=torch.int64)
+        delta = torch.as_tensor(adjust[1]).to(cat.device, dtype=torch.float32)
+        if ids.dim() != 2 or ids.shape[0] != B or delta.shape != ids.shape:
+            raise _lib.NrmsError("%s: adjust must be (news_ids [%d, E], delta [%d, E]) of one shape (got %s and %s)"
+                                 % (who, B, B, tuple(ids.shape), tuple(delta.shape)))
+        if ids.shape[1] > 256:
+            raise _lib.NrmsError("%s: adjust holds %d slots per user, at most 256 fit (NRMS_ADJ_MAX)" % (who, ids.shape[1]))
+        return (ids - 1).contiguous(), delta.contiguous()
+
+    @torch.no_grad()
+    def recommend_adjusted(self, batch, k, catalogue, adjust, exclude_history=True, *, item_bias=None):
+        """recommend with per-user score adjustments -> (news_ids [B, k] int64, scores [B, k] fp32): a story already shown to this
+        user three times without a click goes down by 3 beta (data_handler.seen_adjustment builds that), a followed publisher's
+        goes up, a NaN delta blocks a story for one user (include/nrms_hip.h nrms_topk_dot_adjusted).  Parity is unpinned: the
+        reference has no catalogue retrieval.
+
+        adjust = (news_ids [B, E], delta [B, E]), E <= 256, news ids as in the catalogue: id 0 and ids beyond the catalogue are
+        empty slots; of several slots of a row that name one news the first counts.  Row b is recommend's ranking for user b (the
+        same user vector, score bits, exclusions, tie rule and ``item_bias``) with delta added, one fp32 add, to the scores of the
+        named news; the returned scores are the adjusted ones, and rank_targets_adjusted of the ids gives 1, 2, ...  With every
+        slot empty this is recommend, bit for bit.  Not combined with a time window, tags, caps, paging, sections, the diversity
+        re-ranking, the log-partition or the fp16 shortlist (whose certificate bounds raw scores; a boost breaks it)."""
+        who = "recommend_adjusted"
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, who)
+        bias = self._item_bias_rows(item_bias, cat, who)
+        adj_ids, adj_delta = self._adjust_rows(adjust, cat, user.shape[0], who)
+        scores, ids = self._engine.top_k_adjusted(user, cat[1:], k, adj_ids, adj_delta, exclude, bias=bias)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    @torch.no_grad()
+    def rank_targets_adjusted(self, batch, targets, catalogue, adjust, exclude_history=True, *, item_bias=None):
+        """rank_targets under per-user score adjustments -> (ranks [B, T] int32, scores [B, T] fp32): the 1-based place of news id
+        targets[b, j] in recommend_adjusted's list for user b were k unbounded, and its adjusted score (include/nrms_hip.h
+        nrms_rank_dot_adjusted).  A target whose delta is NaN comes back as rank 0 / score -inf, like every target rank_targets
+        cannot rank.  adjust is recommend_adjusted's, every other argument is rank_targets'."""
+        who = "rank_targets_adjusted"
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, who)
+        bias = self._item_bias_rows(item_bias, cat, who)
+        adj_ids, adj_delta = self._adjust_rows(adjust, cat, user.shape[0], who)
+        tg = torch.as_tensor(targets).to(user.device, dtype=torch.int64)
+        if tg.dim() != 2 or tg.shape[0] != user.shape[0]:
+            raise _lib.NrmsError("%s: targets must be [%d, T] news ids (got %s)" % (who, user.shape[0], tuple(tg.shape)))
+        return self._engine.rank_of_adjusted(user, cat[1:], (tg - 1).contiguous(), adj_ids, adj_delta, exclude, bias=bias)
+
     @torch.no_grad()
     def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):
         """Why these news: each score split exactly over the clicks of the user's history -> (reason_ids [B, K, m] int64,
@@ -777,6 +829,7 @@ class Model(FlatHipModel):
     CATALOGUE_LIKELIHOOD = True         # ... and normalised over the catalogue: log_partition / log_prob (run_v0 --retrieval_nll)
     CATALOGUE_CAPS = True               # ... and rationed by a hard cap per tag: recommend_capped (run_v0 --max_per_category)
     CATALOGUE_TAGS = True               # ... and restricted to a per-user tag set: recommend_tagged / rank_targets_tagged (run_v0 --only_categories)
+    CATALOGUE_ADJUST = True             # ... and moved per (user, news) by a finite amount: recommend_adjusted / rank_targets_adjusted (run_v0 --seen_discount)
 
     def check_recommend_ids(self):
         """Raises if a recommend() or rank_targets() call since the last check met browsed_ids outside its catalogue (those slots were read

@@ -122,7 +122,52 @@ def build_parser():
                         'category has room; M >= 1).  Combines with --only_categories / --mute_categories (a closed category gets cap '
                         '0) and --popularity_prior; not with --diversity, --coarse_catalogue, --catalogue_window, --sections, '
                         '--recommend_deep or --explain')
+    parser.add_argument('--seen_discount', type=float, default=None, metavar='BETA', help='--recommend / --retrieval_metrics: impression '
+                        'discounting (model.recommend_adjusted / rank_targets_adjusted): a news the user was shown c times without a '
+                        "click goes down by BETA * c for that user alone.  Needs a feed with a seen log (--dataset synthetic with "
+                        '--negatives catalogue or adaptive).  Combines with --popularity_prior; not with --diversity, '
+                        '--coarse_catalogue, --catalogue_window, --only_categories / --mute_categories, --max_per_category, '
+                        '--retrieval_nll, --explain, --sections or --recommend_deep')
+    parser.add_argument('--seen_slots', type=int, default=None, metavar='E', help='--seen_discount: at most E seen news per user are '
+                        'discounted, the most-seen first (1 <= E <= 256; default 32)')
     return parser
+
+
+def check_seen_args(args):
+    """--seen_discount / --seen_slots fail before any data is read or any step is trained: a finite BETA, 1 <= E <= 256, a list or a
+    metric to apply them to, a feed with a seen log, a model that serves with per-user adjustments, and none of the paths the
+    adjusted kernels do not have.  Returns (beta, slots) or None."""
+    if args.seen_discount is None:
+        if args.seen_slots is not None:
+            raise SystemExit('--seen_slots E: the slots of --seen_discount BETA (give --seen_discount)')
+        return None
+    slots = 32 if args.seen_slots is None else args.seen_slots
+    if not np.isfinite(args.seen_discount):
+        raise SystemExit('--seen_discount BETA: BETA must be finite (got %r)' % args.seen_discount)
+    if not 1 <= slots <= 256:
+        raise SystemExit('--seen_slots E: E must be in [1, 256] (got %d)' % slots)
+    if args.recommend is None and args.retrieval_metrics is None:
+        raise SystemExit('--seen_discount: discounts the list of --recommend K and the ranks of --retrieval_metrics K (give one of them)')
+    for other, on in (('--diversity', args.diversity is not None or args.shortlist is not None),
+                      ('--coarse_catalogue', args.coarse_catalogue or args.coarse_shortlist is not None),
+                      ('--catalogue_window', args.catalogue_window is not None),
+                      ('--only_categories', args.only_categories is not None), ('--mute_categories', args.mute_categories is not None),
+                      ('--max_per_category', args.max_per_category is not None), ('--retrieval_nll', args.retrieval_nll is not None),
+                      ('--explain', args.explain is not None), ('--sections', args.sections is not None),
+                      ('--recommend_deep', args.recommend_deep is not None)):
+        if on:
+            raise SystemExit('--seen_discount: the adjusted calls serve and rank the plain or the biased list only (drop %s)' % other)
+    if args.dataset != 'synthetic' or args.negatives not in ('catalogue', 'adaptive'):
+        raise SystemExit('--seen_discount: needs a feed with a seen log: --dataset synthetic with --negatives catalogue or adaptive')
+    if args.test:
+        raise SystemExit('--seen_discount: goes with the --recommend / --retrieval_metrics of a training run (drop --test)')
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_ADJUST', False):
+        raise SystemExit('--seen_discount: model %r cannot serve with per-user score adjustments (its catalogue score is no plain dot '
+                         'product over a row-ordered catalogue)' % args.model)
+    return float(args.seen_discount), slots
 
 
 def check_caps_args(args):
@@ -458,6 +503,7 @@ def main(argv=None):
     check_window_args(args)
     tag_only, tag_mute = check_tag_args(args)
     check_caps_args(args)
+    seen_discount = check_seen_args(args)
     check_graph_args(args)
     check_negatives_args(args)
     check_loss_args(args)
@@ -537,6 +583,7 @@ def main(argv=None):
     explain = {} if args.explain is None else {'explain': args.explain}       # otherwise no keyword at all
     item_prior = {}          # item_bias = the click feed's popularity prior with --popularity_prior, otherwise no keyword at all
     click_feed = []          # the ClickFeed of --negatives catalogue / adaptive, once it exists
+    item_adjust = {}         # adjust = the click feed's seen-news discount with --seen_discount, otherwise no keyword at all
 
     def tag_sets(samples, categ):
         # item_tag / allow_tags with --only_categories / --mute_categories, otherwise no keyword at all
@@ -587,6 +634,21 @@ def main(argv=None):
                             coarse_shortlist=args.coarse_shortlist, **explain)
             st = (recommender.model if hasattr(recommender, 'model') else recommender).last_coarse_stats
             print('coarse catalogue: certified share: {:.4f}  users: {}'.format(st['certified'], st['n_users']))
+            return out
+        if item_adjust:
+            out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
+                            **item_adjust)
+            # read the file back: how many served news had their user seen (and not clicked) before
+            seen_ids = item_adjust['adjust'][0].cpu().numpy()
+            filled = served = 0
+            with open(out) as f:
+                for i, line in enumerate(f):
+                    ids = [int(v) for v in line.split(' ', 1)[1].strip()[1:-1].split(',') if v]
+                    filled += len(ids)
+                    seen = set(seen_ids[i][seen_ids[i] > 0].tolist())
+                    served += sum(1 for n in ids if n in seen)
+            print('recommend with seen news discounted (beta {:g}, {} slots): {} users, {} of {} slots filled, {} seen news served'.format(
+                seen_discount[0], seen_discount[1], len(samples), filled, len(samples) * args.recommend, served))
             return out
         tags = tag_sets(samples, feed.news_info()['categ'])
         if args.max_per_category is not None:
@@ -643,7 +705,7 @@ def main(argv=None):
         return evaluate_retrieval(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
                                   news_info=feed.news_info() if needs_info else None, **item_prior, **item_window,
                                   **({} if retrieval_nll is None else {'nll_temperatures': retrieval_nll}),
-                                  **tag_sets(samples, feed.news_info()['categ']))
+                                  **tag_sets(samples, feed.news_info()['categ']), **item_adjust)
 
     def attach_graph(feed, samples=None):
         # the click graph is replicated: every rank builds it from ALL training samples (users shard, the graph does not)
@@ -670,11 +732,14 @@ def main(argv=None):
                                    drop_last=world > 1, seed=422, rank=rank, world=world,
                                    negatives='adaptive' if args.negatives == 'adaptive' else 'popularity',
                                    temperature=args.negative_temperature,
-                                   click_time=corpus.click_ticks(click_ptr) if args.catalogue_window is not None else None)
+                                   click_time=corpus.click_ticks(click_ptr) if args.catalogue_window is not None else None,
+                                   **({} if seen_discount is None else {'seen': corpus.seen_log(click_ptr, click_ids)}))
             if args.negatives == 'adaptive':
                 train_feed.attach_scorer(recommender)
             held_samples, held_labels = train_feed.heldout_samples()
             click_feed.append((train_feed, held_samples))
+            if seen_discount is not None:
+                item_adjust['adjust'] = train_feed.seen_adjustment(seen_discount[0], seen_discount[1], users=train_feed.heldout_users())
             if args.catalogue_window is not None:
                 item_window.update(item_time=train_feed.news_first_seen(), request_time=train_feed.heldout_times(),
                                    window_span=args.catalogue_window)

@@ -454,6 +454,38 @@ class _TagCaps:
         return res
 
 
+class _Adjust:
+    """The ``adjust`` keyword of recommend() / evaluate_retrieval(), turned into ``model.recommend_adjusted`` /
+    ``rank_targets_adjusted`` arguments batch by batch: adjust = (news_ids int [n_samples, E], delta float [n_samples, E]) (numpy or
+    torch; ``data_handler.seen_adjustment``), one row per sample of data_iter in its order, E <= 256.  With it, the keywords of
+    ``refused`` that were given raise a ValueError that names them: the adjusted kernels have no time window, tag set, caps, fp16
+    shortlist, diversity re-ranking, log-partition or attribution form."""
+
+    def __init__(self, who, adjust, refused):
+        self.on = adjust is not None
+        if not self.on:
+            return
+        for name, given in refused:
+            if given:
+                raise ValueError("%s: %s does not go with adjust: the adjusted calls serve and rank the plain or the biased list "
+                                 "only" % (who, name))
+        if not isinstance(adjust, (tuple, list)) or len(adjust) != 2:
+            raise ValueError("%s: adjust must be a pair (news_ids [n_samples, E], delta [n_samples, E]) (got %s)"
+                             % (who, type(adjust).__name__))
+        self.who = who
+        self.ids, self.delta = torch.as_tensor(adjust[0]), torch.as_tensor(adjust[1])
+        if (self.ids.dim() != 2 or self.ids.shape != self.delta.shape or self.ids.dtype not in (torch.int32, torch.int64)
+                or not self.delta.dtype.is_floating_point or self.ids.shape[1] > 256):
+            raise ValueError("%s: adjust must be (int news_ids [n_samples, E], float delta [n_samples, E]) of one shape, E <= 256 "
+                             "(got %s %s and %s %s)" % (who, tuple(self.ids.shape), self.ids.dtype, tuple(self.delta.shape),
+                                                        self.delta.dtype))
+
+    def of(self, done, B, dev):
+        if done + B > self.ids.shape[0]:
+            raise ValueError("%s: %d adjust rows for %d samples" % (self.who, self.ids.shape[0], done + B))
+        return (self.ids[done:done + B].to(dev, dtype=torch.int64), self.delta[done:done + B].to(dev, dtype=torch.float32))
+
+
 class _RequestWindows:
     """The time-window keywords of recommend() / evaluate_retrieval(), turned into ``model.recommend`` / ``rank_targets`` keywords
     batch by batch: sample i is served inside [request_time[i] - window_span, request_time[i] + 1), clamped to int32.  All three or
@@ -484,7 +516,7 @@ class _RequestWindows:
 
 def recommend(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, diversity=None,
               shortlist=None, item_bias=None, item_time=None, request_time=None, window_span=None, coarse=False,
-              coarse_shortlist=None, tag_caps=None, heldout=None, item_tag=None, allow_tags=None, explain=None):
+              coarse_shortlist=None, adjust=None, tag_caps=None, heldout=None, item_tag=None, allow_tags=None, explain=None):
     """Writes ``<impression index> [id1,id2,...]`` lines (1-based, as test()): per impression of data_iter the k news ids
     of the whole catalogue the model recommends, best first.  titles: [N, L] word ids with row r = news id r
     (``DeviceFeed.titles``); it is encoded once.  news_info: the per-news tables nrms_naml and hierec need
@@ -536,8 +568,21 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
     path above ends with (so it goes with diversity, item_bias, a time window and coarse): the score without any item_bias, the
     part of it carried by the history's padding slots, and the up to m clicks of the history with the largest contributions,
     largest first, negative ones included.  Numbers are written with 9 significant digits, which names every float32: two runs
-    give the same bytes.  Needs a model with ``CATALOGUE_EXPLAIN`` (ValueError otherwise, before anything is encoded)."""
+    give the same bytes.  Needs a model with ``CATALOGUE_EXPLAIN`` (ValueError otherwise, before anything is encoded).
+
+    adjust = (news_ids [n_samples, E], delta [n_samples, E]): per-sample score adjustments, ``model.recommend_adjusted``
+    (``data_handler.seen_adjustment`` builds the seen-news discount): sample i's score of news news_ids[i, e] moves by delta[i, e];
+    id 0 is an empty slot.  One row per sample of data_iter in its order, sliced per batch.  With or without item_bias; not with
+    diversity, coarse, a time window, item_tag / allow_tags, tag_caps or explain (ValueError naming the keyword).  None: no new
+    keyword reaches the model, which is called exactly as before."""
     net = _inner(model)
+    adj = _Adjust("recommend", adjust, (("diversity", diversity is not None or shortlist is not None),
+                                        ("coarse", bool(coarse) or coarse_shortlist is not None),
+                                        ("item_time / request_time / window_span", item_time is not None or request_time is not None
+                                         or window_span is not None),
+                                        ("tag_caps", tag_caps is not None or heldout is not None),
+                                        ("item_tag / allow_tags", item_tag is not None or allow_tags is not None),
+                                        ("explain", explain is not None)))
     caps = _TagCaps("recommend", tag_caps, item_tag, allow_tags, heldout,
                     (("diversity", diversity is not None or shortlist is not None),
                      ("coarse", bool(coarse) or coarse_shortlist is not None),
@@ -603,6 +648,14 @@ def recommend(config, model, data_iter, titles, k, out_file=None, exclude_histor
             tag, allow = tags.of(done, B, catalogue.device)
             done += B
             ids, _ = net.recommend_tagged(datas, k, catalogue, tag, allow, exclude_history=exclude_history, **prior)
+            lines.extend(ids.cpu().tolist())
+    elif adj.on:
+        net.last_recommend_stats = None
+        for datas in data_iter:
+            B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
+            slots = adj.of(done, B, catalogue.device)
+            done += B
+            ids, _ = net.recommend_adjusted(datas, k, catalogue, slots, exclude_history=exclude_history, **prior)
             lines.extend(ids.cpu().tolist())
     elif diversity is None:
         net.last_recommend_stats = None
@@ -724,7 +777,7 @@ def recommend_sections(config, model, data_iter, titles, k, sections, out_file=N
 
 def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
                        verbose=True, item_bias=None, item_time=None, request_time=None, window_span=None, nll_temperatures=None,
-                       item_tag=None, allow_tags=None):
+                       adjust=None, item_tag=None, allow_tags=None):
     """Full-catalogue retrieval quality on held-out clicks: per impression of data_iter the targets are its clicked news (the
     ``candidate_ids`` whose label in y_true is 1) and each is ranked against the whole catalogue in recommend()'s own order
     (``model.rank_targets``: the exact position, at any depth).  titles / news_info / exclude_history as in recommend();
@@ -756,9 +809,18 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
     against the news whose tag it allows only (``model.rank_targets_tagged``): Recall@K and MRR "among the news this user may see".
     A held-out target closed by its tag counts as skipped, like one outside its window; the result gains ``n_closed``, the number of
     targets that are skipped for that reason alone (they are in the catalogue, their tag is closed).  Not with a time window or
-    nll_temperatures (ValueError naming the keyword).  None: no new keyword reaches the model, the result has no ``n_closed``."""
+    nll_temperatures (ValueError naming the keyword).  None: no new keyword reaches the model, the result has no ``n_closed``.
+
+    adjust = (news_ids [n_samples, E], delta [n_samples, E]): recommend()'s per-sample score adjustments.  Sample i's targets are
+    ranked in the adjusted order (``model.rank_targets_adjusted``): "Recall@K when seen-but-not-clicked news is demoted".  A target
+    whose delta is NaN counts as skipped.  Not with a time window, item_tag / allow_tags or nll_temperatures (ValueError naming the
+    keyword).  None: no new keyword reaches the model."""
     net = _inner(model)
     prior = {} if item_bias is None else {"item_bias": item_bias}
+    adj = _Adjust("evaluate_retrieval", adjust, (("item_time / request_time / window_span", item_time is not None
+                                                  or request_time is not None or window_span is not None),
+                                                 ("item_tag / allow_tags", item_tag is not None or allow_tags is not None),
+                                                 ("nll_temperatures", nll_temperatures is not None)))
     tags = _TagSets("evaluate_retrieval", item_tag, allow_tags, (("item_time / request_time / window_span", item_time is not None
                                                                   or request_time is not None or window_span is not None),
                                                                  ("nll_temperatures", nll_temperatures is not None)))
@@ -805,6 +867,8 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
             t_open = (t_tag >= 0) & (t_tag < allow.shape[1]) & allow.gather(1, t_tag.clamp(0, allow.shape[1] - 1))
             closed = (in_cat & ~t_open).sum()
             n_closed = closed if n_closed is None else n_closed + closed
+        elif adj.on:
+            rk, _ = net.rank_targets_adjusted(datas, tg, catalogue, adj.of(done - B, B, dev), exclude_history=exclude_history, **prior)
         else:
             rk, _ = net.rank_targets(datas, tg, catalogue, exclude_history=exclude_history, **prior)
         ranks.append(rk)
