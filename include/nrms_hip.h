@@ -683,6 +683,76 @@ int nrms_rank_dot_adjusted(int32_t B, int64_t N, int32_t d, int32_t T, const flo
                            const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- One request through several catalogue filters at once (a front page: news that is still live, outside the topics this user
+ * muted, with what they were already shown pushed down, after the page they have just seen; PARITY UNPINNED, the reference has no
+ * catalogue retrieval) ----
+ * nrms_topk_dot_biased / nrms_rank_dot_biased with four optional PARTS, each a pair of pointers given both or neither:
+ *   the window       item_time [N] int32, window [B, 2] int32          nrms_topk_dot_windowed's
+ *   the tag set      item_tag [N] int32, allow [B, W] uint32, n_tags   nrms_topk_dot_tagged's
+ *   the adjustments  adj_ids [B, E] int64, adj_delta [B, E] fp32, E    nrms_topk_dot_adjusted's
+ *   the cursor       after_scores [B] fp32, after_ids [B] int64        nrms_topk_dot_after's (top-k only)
+ * Every part is NULLABLE and keeps the rules its own call states, word for word: the window is half-open and signed, lo <= time <
+ * hi, and a time of INT32_MAX is never eligible; a tag outside [0, n_tags) is served to nobody, 1 <= n_tags <= 512 (read only when
+ * the tag set is given); E = n_adjust <= 256 (NRMS_ADJ_MAX), an id outside [0, N) is an empty slot, of several slots of one user
+ * that name one row the LOWEST e counts, and n_adjust == 0 or two NULL lists mean no adjustments; after_ids[b] == NRMS_CURSOR_BEGIN
+ * is no cursor for that row, any other negative id or a NaN after score is END.  bias [N] fp32, NULLABLE.
+ * The composition.
+ *   Scores.  s'' = (s + bias[n]) + delta: the same score bits s, then two fp32 additions in that order on the finished accumulator,
+ *     the first only with a prior, the second only where the pair (b, n) has a slot; neither is folded into the chain.
+ *   Eligibility.  Item n is eligible for user b iff ALL of these hold: n is not in b's exclude row; s'' is not NaN; b's window is
+ *     open to item_time[n]; b allows item_tag[n].  An absent part closes nothing.
+ *   Order, ties, -0.0, padding (id -1 / score -inf) and the returned scores (s'') are nrms_topk_dot_biased's.
+ *   The cursor compares (s'', n): user b is offered the eligible items strictly after (after_scores[b], after_ids[b]) in that
+ *     order.  A client that pages must pass the same adjustments on every page.
+ *   Rank.  A target closed by any part, excluded or out of range gets rank 0 / score -inf; otherwise rank(b, t) = 1 + #{eligible n :
+ *     (s''(b, n), n) precedes (s''(b, t), t)} and its score is s''.
+ * Consequences.
+ *   1. All parts given but neutral by value (the window (INT32_MIN, INT32_MAX) over times below INT32_MAX, every tag open, every
+ *      slot -1, every cursor NRMS_CURSOR_BEGIN) is nrms_topk_dot_biased / nrms_rank_dot_biased, bit for bit.
+ *   2. One part live, the rest neutral by value or NULL, is that part's own call, bit for bit: nrms_topk_dot_windowed, _tagged,
+ *      _adjusted, _after and their rank forms.
+ *   3. With bias == NULL, row b equals nrms_topk_dot_biased at B = 1 whose bias holds row b's deltas scattered by the lowest-slot
+ *      rule, +0.0 elsewhere, and NaN where b's window or tag set closes the item.
+ *   4. The ids nrms_topk_dot_request returns for user b (without a cursor) get ranks 1 .. k, in order, from nrms_rank_dot_request
+ *      with the same parts.
+ *   5. Pages chained by the cursor (each page's last column is the next page's cursor) are the prefix of the longer list and then
+ *      padding: nothing is repeated or skipped across ties.
+ *   6. Row b depends on user row b, the b-th row of every part and exclude row b only: not on B, the row's position in the batch,
+ *      the other rows, the launch geometry, what the workspace held or the run.
+ * Routing.  No part, and exactly one part, forward to the existing entry point (nrms_topk_dot_biased, _windowed, _tagged,
+ *   _adjusted, _after and the rank forms), and the window with the cursor alone to nrms_topk_dot_after: the same device code, the
+ *   same bytes.  Every other combination runs one kernel form that holds all parts and skips an absent one by a block-uniform
+ *   branch.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_request: ...", "rank_dot_request: ..."): a
+ *   half-given pair names its missing pointer ("window is null"), n_tags outside [1, 512] with a tag set, n_adjust outside [0, 256]
+ *   and a misaligned array are among them.  An undersized workspace returns NRMS_EWORKSPACE.  Nothing is launched after an error.
+ * Workspace: the _workspace_bytes queries return exactly nrms_topk_dot_workspace_bytes(B, N, d, k) / nrms_rank_dot_workspace_bytes(B,
+ *   N, d, T, n_exclude) (0 = arguments rejected); 8-byte aligned.
+ * The kernels of nrms_topk_dot / nrms_rank_dot on `stream`, no host synchronisation, no allocation, no [B, N] matrix.  A wave whose
+ *   64 items are closed to its whole 32-user block by the window hull OR by the tag bitmap runs no score chain for that step.  A
+ *   block stages the slots of its users that fall into its slice in LDS, up to 2048 of them for k <= 192 and 512 above (half of the
+ *   adjusted call's: the tag bitmap, the windows and the cursor keys lie beside the list), and otherwise walks the lists in global
+ *   memory: slower, never different.
+ * Not composed here: the per-tag caps, the fp16 shortlist, sections, the diversity re-ranking, the log-partition, the attribution
+ *   and the deep list; paging works through the cursor. */
+size_t nrms_topk_dot_request_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_request(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                          const float* bias /* [N], nullable */, const int32_t* item_time /* [N], nullable */,
+                          const int32_t* window /* [B, 2], nullable */, const int32_t* item_tag /* [N], nullable */, int32_t n_tags,
+                          const uint32_t* allow /* [B, W], nullable */, const int64_t* adj_ids /* [B, E], nullable */,
+                          const float* adj_delta /* [B, E], nullable */, int32_t n_adjust /* E */,
+                          const float* after_scores /* [B], nullable */, const int64_t* after_ids /* [B], nullable */,
+                          const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids, void* workspace,
+                          size_t workspace_bytes, void* stream);
+size_t nrms_rank_dot_request_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t T, int32_t n_exclude);
+int nrms_rank_dot_request(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items,
+                          const float* bias /* [N], nullable */, const int32_t* item_time /* [N], nullable */,
+                          const int32_t* window /* [B, 2], nullable */, const int32_t* item_tag /* [N], nullable */, int32_t n_tags,
+                          const uint32_t* allow /* [B, W], nullable */, const int64_t* adj_ids /* [B, E], nullable */,
+                          const float* adj_delta /* [B, E], nullable */, int32_t n_adjust /* E */, const int64_t* targets,
+                          const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- Paging through the exact ranking: a cursor on the top-k, and lists up to 4096 (candidate generation for a re-ranker, a feed
  * that scrolls: "the next 20 after what I showed"; PARITY UNPINNED, the reference has no catalogue retrieval) ----
  * The order of nrms_topk_dot[_biased|_windowed] is total (s' descending, then the SMALLER n, -0.0 equal to +0.0) and a score's bits

@@ -50,7 +50,9 @@ constexpr int RK_A_CHUNKS = 4096;              // grid.y bound of kernel A (long
 // keep their names, signatures and kernarg layouts).
 // ADJ: the owner's delta for the id (tk_adjust_find: the lowest slot of the owner's list, from global memory) is added to s', one
 // fp32 add after the prior's, so the entry is the s'' entry kernel B counts; a NaN sum gets entry 0 like a NaN score.
-template <bool VEC, bool BIAS, bool WINDOW, bool TAGS, bool ADJ = false>
+// REQ (nrms_rank_dot_request): the window, the tag set and the adjustments together, each where its pointer is not null (WINDOW,
+// TAGS and ADJ are false: the three tests below are the same ones, behind a uniform branch).
+template <bool VEC, bool BIAS, bool WINDOW, bool TAGS, bool ADJ = false, bool REQ = false>
 __device__ __forceinline__ void rank_entries_body(int B, int N, int d, int T, int n_exclude, const float* __restrict__ user,
                                                   const float* __restrict__ items, const int64_t* __restrict__ targets,
                                                   const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
@@ -58,6 +60,7 @@ __device__ __forceinline__ void rank_entries_body(int B, int N, int d, int T, in
                                                   TkTags tags, TkAdjust adj = TkAdjust{nullptr, nullptr, 0}) {
     static_assert(!(TAGS && WINDOW), "the tag set is for the plain and the biased rank only");
     static_assert(!(ADJ && (TAGS || WINDOW)), "the adjustments are for the plain and the biased rank only");
+    static_assert(!(REQ && (ADJ || TAGS || WINDOW)), "a request holds its window, tag set and adjustments itself");
     __shared__ int rows[64];
     __shared__ __attribute__((aligned(16))) float stage[64 * TK_BP];
     const int lane = threadIdx.x;
@@ -101,19 +104,19 @@ __device__ __forceinline__ void rank_entries_body(int B, int N, int d, int T, in
             if constexpr (BIAS) {
                 if (idc >= 0 && idc < N) s = s + bias[idc];
             }
-            if constexpr (ADJ) {
+            if constexpr (ADJ || REQ) {
                 float dl;
-                if (idc >= 0 && idc < N && tk_adjust_find(adj, u0 + uc, idc, dl)) s = s + dl;
+                if ((!REQ || adj.adj_ids) && idc >= 0 && idc < N && tk_adjust_find(adj, u0 + uc, idc, dl)) s = s + dl;
             }
             bool ok = idc >= 0 && idc < N && !__builtin_isnan(s);
-            if constexpr (WINDOW) {
-                if (ok) {
+            if constexpr (WINDOW || REQ) {
+                if (ok && (!REQ || win.window)) {
                     const int tv = win.item_time[idc];
                     ok = tv >= win.window[2 * (long)(u0 + uc)] && tv < win.window[2 * (long)(u0 + uc) + 1];
                 }
             }
-            if constexpr (TAGS) {
-                if (ok) ok = tk_tags_open(tags, u0 + uc, tags.item_tag[idc]);
+            if constexpr (TAGS || REQ) {
+                if (ok && (!REQ || tags.allow)) ok = tk_tags_open(tags, u0 + uc, tags.item_tag[idc]);
             }
             ent[(long)(u0 + uc) * M + mc] = ok ? tk_entry(s, (uint32_t)idc) : 0;
         }
@@ -153,6 +156,17 @@ __global__ __launch_bounds__(64) void rank_entries_adjusted_kernel(int B, int N,
                                                      TkWindow{nullptr, nullptr}, TkTags{nullptr, nullptr, 0}, adj);
 }
 
+template <bool VEC, bool BIAS>
+__global__ __launch_bounds__(64) void rank_entries_request_kernel(int B, int N, int d, int T, int n_exclude,
+                                                                  const float* __restrict__ user, const float* __restrict__ items,
+                                                                  const int64_t* __restrict__ targets,
+                                                                  const int64_t* __restrict__ exclude, uint64_t* __restrict__ ent,
+                                                                  uint32_t* __restrict__ counts, const float* __restrict__ bias,
+                                                                  TkRequest req) {
+    rank_entries_body<VEC, BIAS, false, false, false, true>(B, N, d, T, n_exclude, user, items, targets, exclude, ent, counts, bias,
+                                                            req.win, req.tags, req.adj);
+}
+
 // Kernel B.  Per block: users [u0, u0 + 32) x items [n_begin, n_end) of slice blockIdx.y, 64 W items per step.  ent [B, M]:
 // the first T entries of a row are the user's targets.  counts [B, T] += #{live non-NaN n in the slice : entry(n) > target}.
 // WINDOW: topk_slice_kernel's window filter and dead-tile skip.  The block stages its users' (lo, hi) in LDS and forms their
@@ -165,13 +179,16 @@ __global__ __launch_bounds__(64) void rank_entries_adjusted_kernel(int B, int N,
 // ADJ: topk_slice_kernel's adjustments.  The block stages the slots of its users that name a row of its slice (tk_adjust_stage;
 // RK_ADJ_CAP words: every slot its 32 users can have), a wave marks its 64 items' hits per step (tk_adjust_mark) and the lane that
 // holds a marked pair adds the delta of the pair's lowest slot to the finished s' (tk_adjust_apply) before the entries are formed.
-template <int W, bool VEC, bool BIAS, bool WINDOW, bool TAGS, bool ADJ = false>
+// REQ (nrms_rank_dot_request): the three parts together, each where its pointer is not null (a block-uniform branch).  A wave is
+// skipped when the window hull OR the tag bitmap closes all its 64 items to the whole block.
+template <int W, bool VEC, bool BIAS, bool WINDOW, bool TAGS, bool ADJ = false, bool REQ = false>
 __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int M, int slice_len, const float* __restrict__ user,
                                                 const float* __restrict__ items, const uint64_t* __restrict__ ent,
                                                 uint32_t* __restrict__ counts, const float* __restrict__ bias, TkWindow win,
                                                 TkTags tags, TkAdjust adj = TkAdjust{nullptr, nullptr, 0}) {
     static_assert(!(TAGS && WINDOW), "the tag set is for the plain and the biased rank only");
     static_assert(!(ADJ && (TAGS || WINDOW)), "the adjustments are for the plain and the biased rank only");
+    static_assert(!(REQ && (ADJ || TAGS || WINDOW)), "a request holds its window, tag set and adjustments itself");
     __shared__ uint64_t tgt[TK_UT][RK_MAX_T];
     __shared__ uint32_t cnts[TK_UT][RK_MAX_T];
     __shared__ __attribute__((aligned(16))) float stage[W][64 * TK_BP];
@@ -214,11 +231,39 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
         __syncthreads();
         tk_adjust_stage<RK_ADJ_CAP>(axl, axl_n, adj, u0, B, n_begin, n_end, 64 * W);
     }
+    if constexpr (REQ) {
+        __shared__ int2 wwin_lds[TK_UT];
+        __shared__ uint32_t ubt_lds[TK_MAX_TAGS];
+        __shared__ uint32_t axl_lds[RK_ADJ_CAP];
+        __shared__ int axl_n_lds;
+        __shared__ uint32_t axm_lds[W][64];
+        if (win.window) {
+            wwin = wwin_lds;
+            tk_window_stage(wwin, win.window, u0, B);
+        }
+        if (tags.allow) {
+            ubt = ubt_lds;
+            tk_tags_stage(ubt, tags, u0, B, 64 * W);
+        }
+        if (adj.adj_ids) {
+            axl = axl_lds;
+            axl_n = &axl_n_lds;
+            axm = axm_lds[wave];
+            if (threadIdx.x == 0) axl_n_lds = 0;
+            for (int i = threadIdx.x; i < 64 * W; i += 64 * W) axm_lds[i / 64][i % 64] = 0;
+            __syncthreads();
+            tk_adjust_stage<RK_ADJ_CAP>(axl, axl_n, adj, u0, B, n_begin, n_end, 64 * W);
+        }
+    }
     __syncthreads();
     [[maybe_unused]] int n_axl = 0;
     if constexpr (ADJ) n_axl = *axl_n;
     int blo = 0, bhi = 0;
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
+    if constexpr (REQ) {
+        if (adj.adj_ids) n_axl = *axl_n;
+        if (wwin) tk_window_hull(wwin, blo, bhi);
+    }
 
     const int r = lane & 31, h = lane >> 5;
     const float* arow[1] = {user + (long)min(u0 + r, B - 1) * d};
@@ -227,7 +272,19 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
     for (int n0 = n_begin; n0 < n_end; n0 += IT) {
         const int nw = n0 + 64 * wave;
         if (nw >= n_end) continue;
-        int tv[WINDOW ? TK_TN : 1] = {};         // WINDOW: the time of this lane's item in column tile c
+        int tv[WINDOW || REQ ? TK_TN : 1] = {};         // WINDOW: the time of this lane's item in column tile c
+        if constexpr (REQ) {
+            if (wwin) {
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) {
+                    const int n = nw + 32 * c + r;
+                    tv[c] = win.item_time[min(n, N - 1)];
+                    any |= n < n_end && tv[c] >= blo && tv[c] < bhi;
+                }
+                if (TK_WINDOW_SKIP && __ballot(any) == 0) continue;       // wave-uniform
+            }
+        }
         if constexpr (WINDOW) {
             bool any = false;
 #pragma unroll
@@ -238,7 +295,16 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
             }
             if (TK_WINDOW_SKIP && __ballot(any) == 0) continue;       // wave-uniform: nothing here is open to any user of the block
         }
-        uint32_t tm[TAGS ? TK_TN : 1] = {};      // TAGS: the block's users that this lane's item of column tile c is open to
+        uint32_t tm[TAGS || REQ ? TK_TN : 1] = {};      // TAGS: the block's users that this lane's item of column tile c is open to
+        if constexpr (REQ) {
+#pragma unroll
+            for (int c = 0; c < TK_TN; ++c) tm[c] = nw + 32 * c + r < n_end ? ~0u : 0u;          // (no tag set: open to all)
+            if (ubt) {
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) tm[c] &= tk_tags_mask(ubt, tags.item_tag[min(nw + 32 * c + r, N - 1)], tags.n_tags);
+                if (TK_TAGS_SKIP && __ballot((tm[0] | tm[1]) != 0) == 0) continue;       // wave-uniform
+            }
+        }
         if constexpr (TAGS) {
 #pragma unroll
             for (int c = 0; c < TK_TN; ++c) {
@@ -257,16 +323,18 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
             for (int c = 0; c < TK_TN; ++c) bv[c] = bias[min(nw + 32 * c + r, N - 1)];
         }
         tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
-        if constexpr (ADJ) {          // s' in place (the same fp32 add as below), then the marked pairs' deltas
+        if constexpr (ADJ || REQ) {          // s' in place (the same fp32 add as below), then the marked pairs' deltas
             if constexpr (BIAS) {
 #pragma unroll
                 for (int c = 0; c < TK_TN; ++c)
 #pragma unroll
                     for (int q = 0; q < 16; ++q) acc[c][q] = acc[c][q] + bv[c];
             }
-            uint32_t am[TK_TN];
-            tk_adjust_mark<RK_ADJ_CAP>(am, axm, axl, n_axl, adj, u0, B, n_begin, nw, n_end, lane);
-            tk_adjust_apply(acc, am, adj, u0, nw, lane);
+            if (!REQ || adj.adj_ids) {
+                uint32_t am[TK_TN];
+                tk_adjust_mark<RK_ADJ_CAP>(am, axm, axl, n_axl, adj, u0, B, n_begin, nw, n_end, lane);
+                tk_adjust_apply(acc, am, adj, u0, nw, lane);
+            }
         }
         // C/D layout: item = lane & 31 of the column tile, user row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
         uint64_t e[TK_TN][16];
@@ -277,8 +345,15 @@ __device__ __forceinline__ void rank_count_body(int B, int N, int d, int T, int 
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 float s = acc[c][q];
-                if constexpr (BIAS && !ADJ) s = s + bv[c];
+                if constexpr (BIAS && !ADJ && !REQ) s = s + bv[c];
                 bool open = live && !__builtin_isnan(s);
+                if constexpr (REQ) {
+                    if (wwin) {
+                        const int2 w = wwin[(q & 3) + 8 * (q >> 2) + 4 * h];
+                        open = open && tv[c] >= w.x && tv[c] < w.y;
+                    }
+                    open = open && ((tm[c] >> ((q & 3) + 8 * (q >> 2) + 4 * h)) & 1u);
+                }
                 if constexpr (WINDOW) {
                     const int2 w = wwin[(q & 3) + 8 * (q >> 2) + 4 * h];
                     open = open && tv[c] >= w.x && tv[c] < w.y;
@@ -340,6 +415,15 @@ __global__ __launch_bounds__(64 * W) void rank_count_adjusted_kernel(int B, int 
                                                                      const float* __restrict__ bias, TkAdjust adj) {
     rank_count_body<W, VEC, BIAS, false, false, true>(B, N, d, T, M, slice_len, user, items, ent, counts, bias,
                                                       TkWindow{nullptr, nullptr}, TkTags{nullptr, nullptr, 0}, adj);
+}
+
+template <int W, bool VEC, bool BIAS>
+__global__ __launch_bounds__(64 * W) void rank_count_request_kernel(int B, int N, int d, int T, int M, int slice_len,
+                                                                    const float* __restrict__ user, const float* __restrict__ items,
+                                                                    const uint64_t* __restrict__ ent, uint32_t* __restrict__ counts,
+                                                                    const float* __restrict__ bias, TkRequest req) {
+    rank_count_body<W, VEC, BIAS, false, false, false, true>(B, N, d, T, M, slice_len, user, items, ent, counts, bias, req.win,
+                                                             req.tags, req.adj);
 }
 
 // Kernel C.  One wave per user.  N = 0: every target is invalid (ent and counts are not read).
@@ -407,7 +491,7 @@ static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
                          const float* bias, bool windowed, const int32_t* item_time, const int32_t* window, const int64_t* targets,
                          const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
                          size_t workspace_bytes, void* stream, bool tagged = false, TkTags tags = TkTags{nullptr, nullptr, 0},
-                         TkAdjust adj = TkAdjust{nullptr, nullptr, 0}) {
+                         TkAdjust adj = TkAdjust{nullptr, nullptr, 0}, bool request = false) {
     int rc = tk_check_dims(who, B, N, TK_MAX_N, d, "T", T, RK_MAX_T, n_exclude);
     if (rc != NRMS_OK) return rc;
     NRMS_REQUIRE(!tagged || (tags.n_tags >= 1 && tags.n_tags <= TK_MAX_TAGS), "%s: n_tags must be in [1, %d] (n_tags=%d)", who,
@@ -430,7 +514,20 @@ static int rank_dot_call(const char* who, int32_t B, int64_t N, int32_t d, int32
     char what[64];
     if (g.S > 0) {
         const dim3 grid_a(g.tiles, std::min((long)RK_A_CHUNKS, ((long)TK_UT * M + 63) / 64)), grid_b(g.tiles, g.S);
-        if (adj.adj_ids) tk_with_flags([&](auto V, auto BI) {
+        if (request) tk_with_flags([&](auto V, auto BI) {
+            constexpr bool v = decltype(V)::value, bi = decltype(BI)::value;
+            const TkRequest req{win, tagged ? tags : TkTags{nullptr, nullptr, 0}, adj, TkCursor{nullptr, nullptr, 0}};
+            hipLaunchKernelGGL((rank_entries_request_kernel<v, bi>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items,
+                               targets, exclude, ent, counts, bias, req);
+            snprintf(what, sizeof what, "%s(entries)", who);
+            rc = check_launch(what);
+            if (rc != NRMS_OK) return;
+            hipLaunchKernelGGL((rank_count_request_kernel<TK_WAVES, v, bi>), grid_b, dim3(64 * TK_WAVES), 0, s, B, n, d, T, M,
+                               g.slice_len, user, items, ent, counts, bias, req);
+            snprintf(what, sizeof what, "%s(count)", who);
+            rc = check_launch(what);
+        }, tk_vec_ok(d, user, items), bias != nullptr);
+        else if (adj.adj_ids) tk_with_flags([&](auto V, auto BI) {
             constexpr bool v = decltype(V)::value, bi = decltype(BI)::value;
             hipLaunchKernelGGL((rank_entries_adjusted_kernel<v, bi>), grid_a, dim3(64), 0, s, B, n, d, T, n_exclude, user, items,
                                targets, exclude, ent, counts, bias, adj);
@@ -521,4 +618,14 @@ int nrms::rank_dot_adjusted_call(int32_t B, int64_t N, int32_t d, int32_t T, con
                                  float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
     return rank_dot_call("rank_dot_adjusted", B, N, d, T, user, items, bias, false, nullptr, nullptr, targets, exclude, n_exclude,
                          ranks, target_scores, workspace, workspace_bytes, stream, false, TkTags{nullptr, nullptr, 0}, adj);
+}
+
+// nrms_rank_dot_request's body for two or more parts (its C entry point is in topkrequest.hip, which has checked the pairs, n_tags
+// and E): the REQ forms of kernels A and B, each part present where its pointer is not null.
+int nrms::rank_dot_request_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
+                                TkRequest req, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                                float* target_scores, void* workspace, size_t workspace_bytes, void* stream) {
+    return rank_dot_call("rank_dot_request", B, N, d, T, user, items, bias, req.win.window != nullptr, req.win.item_time,
+                         req.win.window, targets, exclude, n_exclude, ranks, target_scores, workspace, workspace_bytes, stream,
+                         req.tags.allow != nullptr, req.tags, req.adj, true);
 }

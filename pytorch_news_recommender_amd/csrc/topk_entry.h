@@ -242,6 +242,19 @@ constexpr int TK_ADJ_ROW_BITS = 27;
 constexpr int tk_adjust_cap(int P) { return P <= 256 ? 2048 : 1024; }
 constexpr int RK_ADJ_CAP = TK_UT * TK_ADJ_MAX;
 
+// The parts of nrms_topk_dot_request / nrms_rank_dot_request (include/nrms_hip.h states their composition): a window, a tag set,
+// adjustments and a cursor in ONE kernel form (the REQ instantiations), each with the rules of its own call.  A part whose
+// pointer (win.window, tags.allow, adj.adj_ids, cur.after_ids) is null is absent: the kernels branch on it, block-uniformly.
+struct TkRequest {
+    TkWindow win;
+    TkTags tags;
+    TkAdjust adj;
+    TkCursor cur;        // top-k only
+};
+// The staged slots of a REQ slice kernel: at P = 512 half of tk_adjust_cap's, which pays for the tag bitmap, the windows and the
+// cursor keys that lie beside the list there (any capacity is correct: a list that overflows is not used, tk_adjust_mark).
+constexpr int tk_request_adjust_cap(int P) { return P <= 256 ? 2048 : 512; }
+
 // One block's staged slots: the slots of users [u0, u0 + 32) that name a row of [n_begin, n_end), in any order, appended to
 // xl[0, CAP); *xl_n counts them (past CAP: the list overflowed and is not used).  *xl_n is 0 on entry and a barrier lies between
 // that store and this call; every thread of the block (nthreads of them) takes part; the caller's next barrier publishes it.
@@ -484,6 +497,17 @@ static int tk_check_ptrs(const char* who, std::initializer_list<TkPtr> ptrs, con
     return NRMS_OK;
 }
 
+// E and the two lists of the adjusted calls: 0 <= E <= TK_ADJ_MAX; with E > 0 the lists come together or not at all (neither: no
+// adjustment).
+static int adjust_check(const char* who, int32_t n_adjust, const int64_t* adj_ids, const float* adj_delta) {
+    NRMS_REQUIRE(n_adjust >= 0 && n_adjust <= TK_ADJ_MAX, "%s: n_adjust must be in [0, %d] (n_adjust=%d)", who, TK_ADJ_MAX, n_adjust);
+    NRMS_REQUIRE(n_adjust == 0 || (adj_ids != nullptr) == (adj_delta != nullptr), "%s: %s is null (n_adjust=%d)", who,
+                 adj_ids ? "adj_delta" : "adj_ids", n_adjust);
+    NRMS_REQUIRE(n_adjust == 0 || !adj_ids || ((uintptr_t)adj_ids & 7) == 0, "%s: adj_ids must be 8-byte aligned", who);
+    NRMS_REQUIRE(n_adjust == 0 || !adj_delta || ((uintptr_t)adj_delta & 3) == 0, "%s: adj_delta must be 4-byte aligned", who);
+    return NRMS_OK;
+}
+
 // nrms_rank_dot_tagged's body: rankdot.hip defines it beside the rank kernels, topktags.hip holds the C entry point.
 int rank_dot_tagged_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
                          TkTags tags, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
@@ -493,6 +517,12 @@ int rank_dot_tagged_call(int32_t B, int64_t N, int32_t d, int32_t T, const float
 int rank_dot_adjusted_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
                            TkAdjust adj, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
                            float* target_scores, void* workspace, size_t workspace_bytes, void* stream);
+
+// nrms_rank_dot_request's body for two or more parts: rankdot.hip defines it beside the rank kernels, topkrequest.hip holds the C
+// entry point, which has checked the parts' pairs, n_tags and E.
+int rank_dot_request_call(int32_t B, int64_t N, int32_t d, int32_t T, const float* user, const float* items, const float* bias,
+                          TkRequest req, const int64_t* targets, const int64_t* exclude, int32_t n_exclude, int32_t* ranks,
+                          float* target_scores, void* workspace, size_t workspace_bytes, void* stream);
 
 // The chain's loads are float4 when every row starts on 16 bytes.
 static bool tk_vec_ok(int32_t d, const float* user, const float* items) {

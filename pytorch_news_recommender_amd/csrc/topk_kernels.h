@@ -309,6 +309,18 @@ struct TkOpenTags {
     __device__ __forceinline__ bool item(int c, int i) const { return (tm[c] >> i) & 1u; }
 };
 
+// REQ kernels: TkOpenWindow AND TkOpenTags (user row i reads its window from LDS; its tag bit is tested in the register).
+struct TkOpenBoth {
+    TkOpenWindow w;
+    TkOpenTags t;
+    struct User {
+        int2 win;
+        int row;
+    };
+    __device__ __forceinline__ User user(int i) const { return User{w.user(i), t.user(i)}; }
+    __device__ __forceinline__ bool item(int c, User u) const { return w.item(c, u.win) && t.item(c, u.row); }
+};
+
 template <int P, int W, class SEL = TkSelectBest>
 struct TkFilter {
     TkFilterLds<P> s;
@@ -503,6 +515,16 @@ struct TkFilter {
 // after the prior's, before pend is formed, so a boosted score below its user's threshold is offered and no entry is adjusted
 // twice.  A block none of whose slots names a row of its slice reads nothing per step.  A NaN sum fails the filter's NaN test.
 //
+// REQ (nrms_topk_dot_request; with or without BIAS): WINDOW, TAGS, ADJ and CURSOR in one form, for a request that holds two or more of
+// them.  The pack's one member is a TkRequest; every part's LDS is declared, and a part whose pointer is null (a kernel argument, so
+// the branch is uniform over the block) stages nothing, loads nothing per step and is not tested.  The open predicate is TkOpenBoth,
+// the window's AND the tag set's (TkOpenTags alone without a window; tm[c] is all ones for a real item where there is no tag set).
+// The wave is dead when the window hull OR the tag bitmap closes its 64 items to the whole block, each decided by a ballot of its own,
+// so a stretch closed half by the one and half by the other is not skipped: the filter refuses its scores.  The delta is added after
+// the prior's and before pend, the cursor's compare follows, on s''.  The staged slot list holds tk_request_adjust_cap(P) words: at
+// P = 512 half of the ADJ form's, which pays for the bitmap, the windows and the cursor keys beside it.  Only topkrequest.hip
+// instantiates these kernels, and one family serves every subset of the parts.
+//
 // The window's two pointers are a kernel argument of the WINDOW instantiations alone, the adjustments' of the ADJ instantiations alone, the cursor's of the CURSOR instantiations
 // alone, the tag set's of the TAGS instantiations alone and the caps' of the CAPS instantiations alone (WIN holds a TkWindow, a
 // TkCursor, both in that order, a TkTags, a TkCaps, or nothing; CURSOR, TAGS and CAPS are read off the pack), so every other instantiation keeps its name, its signature and its kernarg
@@ -519,9 +541,12 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     constexpr bool TAGS = (std::is_same<WIN, TkTags>::value || ...);
     constexpr bool CAPS = (std::is_same<WIN, TkCaps>::value || ...);
     constexpr bool ADJ = (std::is_same<WIN, TkAdjust>::value || ...);
-    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0) + (CAPS ? 1 : 0) + (ADJ ? 1 : 0),
+    constexpr bool REQ = (std::is_same<WIN, TkRequest>::value || ...);
+    static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0) + (CAPS ? 1 : 0) + (ADJ ? 1 : 0) + (REQ ? 1 : 0),
                   "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, TAGS kernels one TkTags, CAPS kernels one TkCaps, "
-                  "ADJ kernels one TkAdjust, the others none");
+                  "ADJ kernels one TkAdjust, REQ kernels one TkRequest, the others none");
+    static_assert(!(REQ && (GROUPED || NOISE || WINDOW || CURSOR || TAGS || CAPS || ADJ)),
+                  "a request holds its window, tag set, adjustments and cursor itself, over the plain and the biased top-k only");
     static_assert(!(ADJ && (GROUPED || NOISE || WINDOW || CURSOR || TAGS || CAPS)), "the adjustments are for the plain and the biased top-k only");
     static_assert(!(CAPS && (GROUPED || NOISE || WINDOW || CURSOR || TAGS)), "the tag caps are for the plain and the biased top-k only");
     static_assert(!(TAGS && (GROUPED || NOISE || WINDOW || CURSOR)), "the tag set is for the plain and the biased top-k only");
@@ -581,7 +606,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         }
         flt.sel = TkSelectCapped<TT>{caps.item_tag, caps.cap, n_tags, reach_lds, n_tags <= TT ? ttag_lds : nullptr};
     }
-    constexpr int AC = tk_adjust_cap(P);
+    constexpr int AC = REQ ? tk_request_adjust_cap(P) : tk_adjust_cap(P);
     [[maybe_unused]] TkAdjust adj{nullptr, nullptr, 0};
     [[maybe_unused]] uint32_t* axl = nullptr;       // ADJ: the block's staged slots, their count and one row of marks per wave
     [[maybe_unused]] int* axl_n = nullptr;
@@ -598,6 +623,40 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         for (int i = threadIdx.x; i < 64 * W; i += 64 * W) axm_lds[i / 64][i % 64] = 0;
         __syncthreads();
         tk_adjust_stage<AC>(axl, axl_n, adj, u0, B, n_begin, n_end, 64 * W);
+    }
+    [[maybe_unused]] TkRequest req{};
+    if constexpr (REQ) {           // every part's LDS is there, a part that is absent (a null pointer, block-uniform) stages nothing
+        __shared__ int2 wwin_lds[TK_UT];
+        __shared__ uint64_t cur_lds[TK_UT];
+        __shared__ uint32_t ubt_lds[TK_MAX_TAGS];
+        __shared__ uint32_t axl_lds[AC];
+        __shared__ int axl_n_lds;
+        __shared__ uint32_t axm_lds[W][64];
+        req = tk_pack_arg<TkRequest>(win_arg...);
+        if (req.win.window) {
+            wwin = wwin_lds;
+            tk_window_stage(wwin, req.win.window, u0, B);
+        }
+        if (req.cur.after_ids) {
+            cur = cur_lds;
+            tk_cursor_stage(cur, req.cur, u0, B);
+        }
+        if (req.tags.allow) {
+            ubt = ubt_lds;
+            n_tags = req.tags.n_tags;
+            item_tag = req.tags.item_tag;
+            tk_tags_stage(ubt, req.tags, u0, B, 64 * W);
+        }
+        if (req.adj.adj_ids) {
+            axl = axl_lds;
+            axl_n = &axl_n_lds;
+            axm = axm_lds[wave];
+            adj = req.adj;
+            if (threadIdx.x == 0) axl_n_lds = 0;
+            for (int i = threadIdx.x; i < 64 * W; i += 64 * W) axm_lds[i / 64][i % 64] = 0;
+            __syncthreads();
+            tk_adjust_stage<AC>(axl, axl_n, adj, u0, B, n_begin, n_end, 64 * W);
+        }
     }
     if constexpr (NOISE) {
         if (threadIdx.x < TK_UT) rseed[threadIdx.x] = tk_noise_row_seed(noise.seed, (uint64_t)noise.row_key[min(u0 + (int)threadIdx.x, B - 1)]);
@@ -616,6 +675,14 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     if constexpr (WINDOW) tk_window_hull(wwin, blo, bhi);
     if constexpr (CURSOR) {
         if (TK_CURSOR_EXIT && tk_cursor_all_end(cur)) {
+            flt.write(ws, S, slice);
+            return;
+        }
+    }
+    if constexpr (REQ) {
+        if (adj.adj_ids) n_axl = *axl_n;
+        if (wwin) tk_window_hull(wwin, blo, bhi);
+        if (cur && TK_CURSOR_EXIT && tk_cursor_all_end(cur)) {
             flt.write(ws, S, slice);
             return;
         }
@@ -643,7 +710,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 for (int c = 0; c < TK_TN; ++c) bv[c] = bias[min(nw + 32 * c + r, N - 1)];
             }
         }
-        int tv[WINDOW ? TK_TN : 1] = {};         // WINDOW: the time of this lane's item in column tile c
+        int tv[WINDOW || REQ ? TK_TN : 1] = {};         // WINDOW: the time of this lane's item in column tile c
         bool dead = false;                       // WINDOW, TAGS: no item of this wave's step is open to any user of the block (wave-uniform)
         if constexpr (WINDOW) {
             if (nw < n_end) {
@@ -658,7 +725,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
             }
         }
         [[maybe_unused]] int tgv[CAPS ? TK_TN : 1] = {};        // CAPS: the tag of this lane's item of column tile c (0 where tm[c] is 0)
-        uint32_t tm[TAGS || CAPS ? TK_TN : 1] = {};      // TAGS, CAPS: the block's users that this lane's item of column tile c is open to
+        uint32_t tm[TAGS || CAPS || REQ ? TK_TN : 1] = {};      // TAGS, CAPS: the block's users that this lane's item of column tile c is open to
         if constexpr (TAGS || CAPS) {
             if (nw < n_end) {
 #pragma unroll
@@ -672,7 +739,29 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 dead = TK_TAGS_SKIP && __ballot((tm[0] | tm[1]) != 0) == 0;
             }
         }
-        if (nw < n_end && (!GROUPED || tl.len[0] + tl.len[1] > 0) && !((WINDOW || TAGS || CAPS) && dead)) {
+        if constexpr (REQ) {          // the window's and the tag set's loads and skips, each only where the part is there: the wave is dead
+                                      // when the hull OR the bitmap closes all its 64 items to the whole block
+            if (nw < n_end) {
+                if (wwin) {
+                    bool any = false;
+#pragma unroll
+                    for (int c = 0; c < TK_TN; ++c) {
+                        const int n = nw + 32 * c + r;
+                        tv[c] = req.win.item_time[min(n, N - 1)];
+                        any |= n < n_end && tv[c] >= blo && tv[c] < bhi;
+                    }
+                    dead = TK_WINDOW_SKIP && __ballot(any) == 0;
+                }
+#pragma unroll
+                for (int c = 0; c < TK_TN; ++c) tm[c] = nw + 32 * c + r < n_end ? ~0u : 0u;
+                if (ubt) {
+#pragma unroll
+                    for (int c = 0; c < TK_TN; ++c) tm[c] &= tk_tags_mask(ubt, item_tag[min(nw + 32 * c + r, N - 1)], n_tags);
+                    dead = dead || (TK_TAGS_SKIP && __ballot((tm[0] | tm[1]) != 0) == 0);
+                }
+            }
+        }
+        if (nw < n_end && (!GROUPED || tl.len[0] + tl.len[1] > 0) && !((WINDOW || TAGS || CAPS || REQ) && dead)) {
             if constexpr (GROUPED) tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return tl.row_of(i, N); });
             else tk_chain<VEC>(acc, arow, items, d, st, lane, [&](int i) { return min(nw + i, N - 1); });
         }
@@ -702,6 +791,13 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 tk_adjust_apply(acc, am, adj, u0, nw, lane);
             }
         }
+        if constexpr (REQ) {          // the ADJ step, where there are adjustments and the wave has scores
+            if (nw < n_end && adj.adj_ids && !dead) {
+                uint32_t am[TK_TN];
+                tk_adjust_mark<AC>(am, axm, axl, n_axl, adj, u0, B, n_begin, nw, n_end, lane);
+                tk_adjust_apply(acc, am, adj, u0, nw, lane);
+            }
+        }
         bool live[TK_TN];
         uint32_t id[TK_TN] = {};            // the id of this lane's item in column tile c
 #pragma unroll
@@ -709,11 +805,15 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
             if constexpr (GROUPED) live[c] = tl.live(c, nw, n_end, r, item_ids, id[c]);
             else {
                 id[c] = (uint32_t)(nw + 32 * c + r);
-                live[c] = nw + 32 * c + r < n_end && !((WINDOW || TAGS || CAPS) && dead);       // a skipped wave's accumulators hold no score
+                live[c] = nw + 32 * c + r < n_end && !((WINDOW || TAGS || CAPS || REQ) && dead);       // a skipped wave's accumulators hold no score
             }
         }
         uint32_t pend;
-        if constexpr (WINDOW) pend = flt.pending(acc, live, TkOpenWindow{wwin, tv});
+        if constexpr (REQ) {
+            if (wwin) pend = flt.pending(acc, live, TkOpenBoth{TkOpenWindow{wwin, tv}, TkOpenTags{tm}});
+            else pend = flt.pending(acc, live, TkOpenTags{tm});          // (no tag set: tm is all ones for a real item)
+            if (cur) pend = flt.after(acc, pend, cur, [&](int c) { return id[c]; });
+        } else if constexpr (WINDOW) pend = flt.pending(acc, live, TkOpenWindow{wwin, tv});
         else if constexpr (TAGS || CAPS) pend = flt.pending(acc, live, TkOpenTags{tm});
         else pend = flt.pending(acc, live, TkOpenAll{});
         if constexpr (CURSOR) pend = flt.after(acc, pend, cur, [&](int c) { return id[c]; });

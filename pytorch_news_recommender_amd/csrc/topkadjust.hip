@@ -15,16 +15,6 @@
 
 namespace nrms {
 
-// E and the two lists: 0 <= E <= TK_ADJ_MAX; with E > 0 the lists come together or not at all (neither: no adjustment).
-static int adjust_check(const char* who, int32_t n_adjust, const int64_t* adj_ids, const float* adj_delta) {
-    NRMS_REQUIRE(n_adjust >= 0 && n_adjust <= TK_ADJ_MAX, "%s: n_adjust must be in [0, %d] (n_adjust=%d)", who, TK_ADJ_MAX, n_adjust);
-    NRMS_REQUIRE(n_adjust == 0 || (adj_ids != nullptr) == (adj_delta != nullptr), "%s: %s is null (n_adjust=%d)", who,
-                 adj_ids ? "adj_delta" : "adj_ids", n_adjust);
-    NRMS_REQUIRE(n_adjust == 0 || !adj_ids || ((uintptr_t)adj_ids & 7) == 0, "%s: adj_ids must be 8-byte aligned", who);
-    NRMS_REQUIRE(n_adjust == 0 || !adj_delta || ((uintptr_t)adj_delta & 3) == 0, "%s: adj_delta must be 4-byte aligned", who);
-    return NRMS_OK;
-}
-
 // Both kernels of one adjusted call: topk_launch's plain path with the ADJ slice kernels.
 static int topk_adjust_launch(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items, const float* bias,
                               TkAdjust adj, const int64_t* exclude, int32_t n_exclude, float* top_scores, int64_t* top_ids,

@@ -1147,6 +1147,103 @@ class NRMSEngine:
         _lib.check(rc, "nrms_topk_dot_deep")
         return scores, ids
 
+    def _request_args(self, who, user_vec, items, exclude, bias, item_time, window, item_tag, n_tags, allow, adj_ids, adj_delta):
+        """The checked parts of top_k_request / rank_of_request: every pair is both or neither ->
+        (B, N, d, exclude, n_exclude, item_time, window, item_tag, n_tags, allow, adj_ids, adj_delta, E), absent parts None / 0."""
+        B, N, d, exclude, n_ex, item_time, window = self._top_k_args(who, user_vec, items, exclude, bias, item_time, window)
+        dev = self._cuda_device()
+        if (item_tag is None) != (allow is None):
+            raise _lib.NrmsError("%s: item_tag and allow go together (item_tag %s, allow %s)"
+                                 % (who, "missing" if item_tag is None else "given", "missing" if allow is None else "given"))
+        if item_tag is not None:
+            if n_tags is None:
+                if not (torch.is_tensor(allow) and allow.dtype == torch.bool and allow.dim() == 2):
+                    raise _lib.NrmsError("%s: a packed allow needs n_tags=" % who)
+                n_tags = allow.shape[1]
+            item_tag, allow, n_tags = self._tag_args(who, item_tag, n_tags, allow, N, B, dev)
+        else:
+            n_tags = 0
+        if (adj_ids is None) != (adj_delta is None):
+            raise _lib.NrmsError("%s: adj_ids and adj_delta go together (adj_ids %s, adj_delta %s)"
+                                 % (who, "missing" if adj_ids is None else "given", "missing" if adj_delta is None else "given"))
+        E = 0
+        if adj_ids is not None:
+            adj_ids, adj_delta, E = self._adjust_args(who, adj_ids, adj_delta, B, dev)
+            if E == 0:
+                adj_ids = adj_delta = None
+        return B, N, d, exclude, n_ex, item_time, window, item_tag, n_tags, allow, adj_ids, adj_delta, E
+
+    def top_k_request(self, user_vec, items, k, exclude=None, bias=None, *, item_time=None, window=None, item_tag=None, n_tags=None,
+                      allow=None, adj_ids=None, adj_delta=None, after_scores=None, after_ids=None):
+        """top_k through several catalogue filters at once -> (scores [B, k] fp32, ids [B, k] int64): a time window (item_time,
+        window: top_k's), a tag set (item_tag, n_tags, allow: top_k_tagged's), per-user adjustments (adj_ids, adj_delta:
+        top_k_adjusted's) and a cursor (after_scores, after_ids: top_k_after's), each pair both or neither, each with the rules of
+        its own call.  The score is (user . item + bias[n]) + delta, two fp32 adds in that order; item n is eligible for user b iff
+        it is not excluded, that score is not NaN, b's window is open to it and b allows its tag; the cursor compares the adjusted
+        score, so a client that pages passes the same adjustments on every page.  No part or one part is the part's own call, bit
+        for bit (nrms_topk_dot_request; include/nrms_hip.h states the contract)."""
+        who = "top_k_request"
+        k = int(k)
+        (B, N, d, exclude, n_ex, item_time, window, item_tag, n_tags, allow, adj_ids, adj_delta, E) = self._request_args(
+            who, user_vec, items, exclude, bias, item_time, window, item_tag, n_tags, allow, adj_ids, adj_delta)
+        if (after_scores is None) != (after_ids is None):
+            raise _lib.NrmsError("%s: after_scores and after_ids go together (after_scores %s, after_ids %s)"
+                                 % (who, "missing" if after_scores is None else "given", "missing" if after_ids is None else "given"))
+        if after_ids is not None:
+            for name, t, dtype in (("after_scores", after_scores, torch.float32), ("after_ids", after_ids, torch.int64)):
+                if not torch.is_tensor(t) or tuple(t.shape) != (B,):
+                    raise _lib.NrmsError("%s: %s must be a [%d] %s tensor (got %s)"
+                                         % (who, name, B, dtype, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+                self._check_tensor(who, name, t, dtype, 1)
+        nbytes = self.lib.nrms_topk_dot_request_workspace_bytes(B, N, d, k)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (who, B, N, d, k))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot_request(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                            _lib.ptr(item_time), _lib.ptr(window), _lib.ptr(item_tag), n_tags, _lib.ptr(allow),
+                                            _lib.ptr(adj_ids), _lib.ptr(adj_delta), E, _lib.ptr(after_scores), _lib.ptr(after_ids),
+                                            _lib.ptr(exclude), n_ex, _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws),
+                                            C.c_size_t(ws.numel() * 8), _stream())
+        _lib.check(rc, "nrms_topk_dot_request")
+        return scores, ids
+
+    def rank_of_request(self, user_vec, items, targets, exclude=None, bias=None, *, item_time=None, window=None, item_tag=None,
+                        n_tags=None, allow=None, adj_ids=None, adj_delta=None):
+        """rank_of through several catalogue filters at once -> (ranks [B, T] int32, scores [B, T] fp32): the exact 1-based position
+        of every target in top_k_request's order with the same parts, and its adjusted score.  A target closed by any part (its
+        time, its tag, a NaN delta), excluded or out of range gets rank 0 / -inf; otherwise 1 + the number of eligible items before
+        it.  Wider ``targets`` go in column chunks of 32 (nrms_rank_dot_request; include/nrms_hip.h states the contract)."""
+        who = "rank_of_request"
+        self._check_tensor(who, "targets", targets, torch.int64, 2)
+        (B, N, d, exclude, n_ex, item_time, window, item_tag, n_tags, allow, adj_ids, adj_delta, E) = self._request_args(
+            who, user_vec, items, exclude, bias, item_time, window, item_tag, n_tags, allow, adj_ids, adj_delta)
+        if targets.shape[0] != B:
+            raise _lib.NrmsError("%s: targets must be [%d, T] (got %s)" % (who, B, tuple(targets.shape)))
+        T_all = targets.shape[1]
+        ranks = torch.empty(B, T_all, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, T_all, dtype=torch.float32, device=self.device)
+        for t0 in range(0, T_all, 32):
+            T = min(32, T_all - t0)
+            whole = T == T_all
+            tg = targets if whole else targets[:, t0:t0 + T].contiguous()
+            rk = ranks if whole else torch.empty(B, T, dtype=torch.int32, device=self.device)
+            sc = scores if whole else torch.empty(B, T, dtype=torch.float32, device=self.device)
+            nbytes = self.lib.nrms_rank_dot_request_workspace_bytes(B, N, d, T, n_ex)
+            if nbytes == 0:
+                raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, T=%d, n_exclude=%d)" % (who, B, N, d, T, n_ex))
+            ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+            rc = self.lib.nrms_rank_dot_request(B, C.c_int64(N), d, T, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                                _lib.ptr(item_time), _lib.ptr(window), _lib.ptr(item_tag), n_tags, _lib.ptr(allow),
+                                                _lib.ptr(adj_ids), _lib.ptr(adj_delta), E, _lib.ptr(tg), _lib.ptr(exclude), n_ex,
+                                                _lib.ptr(rk), _lib.ptr(sc), _lib.ptr(ws), C.c_size_t(ws.numel() * 8), _stream())
+            _lib.check(rc, "nrms_rank_dot_request")
+            if not whole:
+                ranks[:, t0:t0 + T] = rk
+                scores[:, t0:t0 + T] = sc
+        return ranks, scores
+
     def pack_catalogue(self, items):
         """items [N, d] fp32 (device, contiguous) -> PackedCatalogue: the fp16 copy top_k_coarse scans (N * pitch * 2 bytes, pitch =
         32 ceil(d / 32)) and its two norm bounds, beside the fp32 rows it was made from (nrms_catalogue_pack_f16).  Pack again

@@ -285,6 +285,14 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: rank_targets_adjusted is not available: a candidate's score depends on its neighbours in "
                                   "the click graph, not on a catalogue row alone (no rank_targets either)")
 
+    def recommend_request(self, batch, k, catalogue, exclude_history=True, **parts):
+        raise NotImplementedError("graph: recommend_request is not available: a candidate's score depends on its neighbours in the "
+                                  "click graph, not on a catalogue row alone (no recommend either, through a request or not)")
+
+    def rank_targets_request(self, batch, targets, catalogue, exclude_history=True, **parts):
+        raise NotImplementedError("graph: rank_targets_request is not available: a candidate's score depends on its neighbours in "
+                                  "the click graph, not on a catalogue row alone (no rank_targets either)")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

@@ -412,6 +412,15 @@ class Model(FlatHipModel):
                                   "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot_adjusted ranks plain dot "
                                   "products only")
 
+    def recommend_request(self, batch, k, catalogue, exclude_history=True, **parts):
+        raise NotImplementedError("hierec: recommend_request is not available: HieRec scores the catalogue with a query per (topic, "
+                                  "sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no per-user adjustments")
+
+    def rank_targets_request(self, batch, targets, catalogue, exclude_history=True, **parts):
+        raise NotImplementedError("hierec: rank_targets_request is not available: HieRec scores the catalogue with a query per "
+                                  "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot_request ranks plain dot "
+                                  "products only")
+
     CATALOGUE_LIKELIHOOD = False        # the catalogue score is not one dot product per user: no log_partition / log_prob
 
     def log_partition(self, batch, catalogue, temperature=1.0, exclude_history=True, *, item_bias=None, bias_scale=None,

@@ -613,6 +613,71 @@ class Model(FlatHipModel):
             raise _lib.NrmsError("%s: targets must be [%d, T] news ids (got %s)" % (who, user.shape[0], tuple(tg.shape)))
         return self._engine.rank_of_adjusted(user, cat[1:], (tg - 1).contiguous(), adj_ids, adj_delta, exclude, bias=bias)
 
+    def _request_rows(self, cat, B, item_time, window, item_tag, allow, adjust, who):
+        """The kernels' view of a request's parts -> the keywords of engine.top_k_request / rank_of_request (absent parts are left
+        out).  Each part is checked by its own helper, in its own words."""
+        kw = dict(self._time_window_rows(item_time, window, cat, B, who))
+        if (item_tag is None) != (allow is None):
+            raise _lib.NrmsError("%s: item_tag and allow go together (item_tag %s, allow %s)"
+                                 % (who, "missing" if item_tag is None else "given", "missing" if allow is None else "given"))
+        if item_tag is not None:
+            tags, n_tags, allow = self._tag_rows(item_tag, allow, cat, B, who)
+            kw.update(item_tag=tags, n_tags=n_tags, allow=allow)
+        if adjust is not None:
+            adj_ids, adj_delta = self._adjust_rows(adjust, cat, B, who)
+            kw.update(adj_ids=adj_ids, adj_delta=adj_delta)
+        return kw
+
+    @torch.no_grad()
+    def recommend_request(self, batch, k, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None,
+                          item_tag=None, allow=None, adjust=None, after=None):
+        """One front-page request through several catalogue filters at once -> (news_ids [B, k] int64, scores [B, k] fp32): news
+        that is still live (item_time, window: recommend's), outside the topics this user muted (item_tag, allow:
+        recommend_tagged's), with what they were already shown pushed down (adjust: recommend_adjusted's), after the page they
+        have just seen (after: recommend_page's (ids [B], scores [B]), None = the first page).  Every part is optional and keeps
+        the rules of its own method; include/nrms_hip.h nrms_topk_dot_request states how they compose: the score is (dot product +
+        item_bias) + delta, a news is served iff every part leaves it open, and the cursor compares the adjusted score, so the
+        same ``adjust`` goes with every page.  rank_targets_request of the ids gives 1, 2, ...  With no part or one part this is
+        that part's own method, bit for bit.  Not combined with caps, the fp16 shortlist, sections, the diversity re-ranking,
+        the log-partition, explain or recommend_deep."""
+        who = "recommend_request"
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, who)
+        bias = self._item_bias_rows(item_bias, cat, who)
+        B, dev = user.shape[0], user.device
+        kw = self._request_rows(cat, B, item_time, window, item_tag, allow, adjust, who)
+        if after is not None:
+            try:
+                a_ids, a_scores = after
+            except (TypeError, ValueError):
+                raise _lib.NrmsError("%s: after must be None or (ids [B], scores [B]), the last column of the page before" % who)
+            a_ids = torch.as_tensor(a_ids).to(dev, dtype=torch.int64).reshape(-1)
+            a_scores = torch.as_tensor(a_scores).to(dev, dtype=torch.float32).reshape(-1).contiguous()
+            if a_ids.shape[0] != B or a_scores.shape[0] != B:
+                raise _lib.NrmsError("%s: after must be (ids [%d], scores [%d]) (got %s, %s)"
+                                     % (who, B, B, tuple(a_ids.shape), tuple(a_scores.shape)))
+            # recommend_page's convention: news id n is row n - 1, id 0 is read as -1, negative ids pass through
+            a_ids = torch.where(a_ids > 0, a_ids - 1, torch.where(a_ids == 0, torch.full_like(a_ids, -1), a_ids)).contiguous()
+            kw.update(after_scores=a_scores, after_ids=a_ids)
+        scores, ids = self._engine.top_k_request(user, cat[1:], k, exclude, bias=bias, **kw)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    @torch.no_grad()
+    def rank_targets_request(self, batch, targets, catalogue, exclude_history=True, *, item_bias=None, item_time=None, window=None,
+                             item_tag=None, allow=None, adjust=None):
+        """rank_targets through recommend_request's filters -> (ranks [B, T] int32, scores [B, T] fp32): the 1-based place of news
+        id targets[b, j] in recommend_request's list for user b were k unbounded, and its adjusted score (include/nrms_hip.h
+        nrms_rank_dot_request).  A target closed by any part (outside the window, a muted tag, a NaN delta) comes back as rank 0 /
+        score -inf, like every target rank_targets cannot rank.  The parts are recommend_request's, every other argument is
+        rank_targets'."""
+        who = "rank_targets_request"
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, who)
+        bias = self._item_bias_rows(item_bias, cat, who)
+        kw = self._request_rows(cat, user.shape[0], item_time, window, item_tag, allow, adjust, who)
+        tg = torch.as_tensor(targets).to(user.device, dtype=torch.int64)
+        if tg.dim() != 2 or tg.shape[0] != user.shape[0]:
+            raise _lib.NrmsError("%s: targets must be [%d, T] news ids (got %s)" % (who, user.shape[0], tuple(tg.shape)))
+        return self._engine.rank_of_request(user, cat[1:], (tg - 1).contiguous(), exclude, bias=bias, **kw)
+
     @torch.no_grad()
     def explain(self, batch, news_ids, catalogue, m=3, *, return_contributions=False):
         """Why these news: each score split exactly over the clicks of the user's history -> (reason_ids [B, K, m] int64,

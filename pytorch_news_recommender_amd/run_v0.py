@@ -25,7 +25,8 @@ from . import parallel
 from .config import Config
 from .data_handler import ClickFeed, DeviceFeed, ImpressionFeed, MyDataset, SyntheticMind, load_dataset, read_dev_labels
 from .model import Model
-from .train_eval import evaluate_retrieval, recommend, recommend_deep, recommend_sections, test, train
+from .train_eval import (evaluate_retrieval, evaluate_retrieval_request, recommend, recommend_deep, recommend_request,
+                         recommend_sections, test, train)
 
 # rank r adds r * this to its dropout seeds (FlatHipModel._next_seed), so that the ranks of a data-parallel job draw unrelated masks
 DROPOUT_RANK_SALT = 0x632BE59BD9B4E019
@@ -130,6 +131,11 @@ def build_parser():
                         '--retrieval_nll, --explain, --sections or --recommend_deep')
     parser.add_argument('--seen_slots', type=int, default=None, metavar='E', help='--seen_discount: at most E seen news per user are '
                         'discounted, the most-seen first (1 <= E <= 256; default 32)')
+    parser.add_argument('--combine_filters', action='store_true', help='--recommend / --retrieval_metrics: serve and rank one request '
+                        'through several catalogue filters at once (model.recommend_request / rank_targets_request): with this flag '
+                        '--catalogue_window, --only_categories / --mute_categories, --seen_discount and --popularity_prior may be given '
+                        'together.  Every other refusal of those flags stays (no --diversity, --coarse_catalogue, --max_per_category, '
+                        '--retrieval_nll, --explain, --sections or --recommend_deep); without the flag they refuse each other as before')
     return parser
 
 
@@ -148,10 +154,12 @@ def check_seen_args(args):
         raise SystemExit('--seen_slots E: E must be in [1, 256] (got %d)' % slots)
     if args.recommend is None and args.retrieval_metrics is None:
         raise SystemExit('--seen_discount: discounts the list of --recommend K and the ranks of --retrieval_metrics K (give one of them)')
+    together = getattr(args, 'combine_filters', False)          # --combine_filters: the window and the categories go with the discount
     for other, on in (('--diversity', args.diversity is not None or args.shortlist is not None),
                       ('--coarse_catalogue', args.coarse_catalogue or args.coarse_shortlist is not None),
-                      ('--catalogue_window', args.catalogue_window is not None),
-                      ('--only_categories', args.only_categories is not None), ('--mute_categories', args.mute_categories is not None),
+                      ('--catalogue_window', args.catalogue_window is not None and not together),
+                      ('--only_categories', args.only_categories is not None and not together),
+                      ('--mute_categories', args.mute_categories is not None and not together),
                       ('--max_per_category', args.max_per_category is not None), ('--retrieval_nll', args.retrieval_nll is not None),
                       ('--explain', args.explain is not None), ('--sections', args.sections is not None),
                       ('--recommend_deep', args.recommend_deep is not None)):
@@ -168,6 +176,29 @@ def check_seen_args(args):
         raise SystemExit('--seen_discount: model %r cannot serve with per-user score adjustments (its catalogue score is no plain dot '
                          'product over a row-ordered catalogue)' % args.model)
     return float(args.seen_discount), slots
+
+
+def check_combine_args(args):
+    """--combine_filters fails before any data is read or any step is trained: a list or a metric to serve through the request calls,
+    and none of the paths a request does not compose with."""
+    if not args.combine_filters:
+        return
+    if args.recommend is None and args.retrieval_metrics is None:
+        raise SystemExit('--combine_filters: combines the filters of --recommend K and --retrieval_metrics K (give one of them)')
+    for other, on in (('--diversity', args.diversity is not None or args.shortlist is not None),
+                      ('--coarse_catalogue', args.coarse_catalogue or args.coarse_shortlist is not None),
+                      ('--max_per_category', args.max_per_category is not None), ('--retrieval_nll', args.retrieval_nll is not None),
+                      ('--explain', args.explain is not None), ('--sections', args.sections is not None),
+                      ('--recommend_deep', args.recommend_deep is not None)):
+        if on:
+            raise SystemExit('--combine_filters: a request composes a time window, categories, the seen-news discount and the prior '
+                             'only (drop %s)' % other)
+    from .model import ALIASES
+    name = args.model.lower()
+    module = import_module('.model.' + ALIASES.get(name, name), __package__)
+    if not getattr(module.Model, 'CATALOGUE_ADJUST', False):
+        raise SystemExit('--combine_filters: model %r cannot serve a request (its catalogue score is no plain dot product over a '
+                         'row-ordered catalogue)' % args.model)
 
 
 def check_caps_args(args):
@@ -219,7 +250,7 @@ def check_tag_args(args):
     flag = '--only_categories' if only is not None else '--mute_categories'
     if args.recommend is None and args.retrieval_metrics is None:
         raise SystemExit('%s: the categories of --recommend K and --retrieval_metrics K (give one of them)' % flag)
-    for other, on in (('--catalogue_window', args.catalogue_window is not None),
+    for other, on in (('--catalogue_window', args.catalogue_window is not None and not getattr(args, 'combine_filters', False)),
                       ('--coarse_catalogue', args.coarse_catalogue or args.coarse_shortlist is not None),
                       ('--recommend_deep', args.recommend_deep is not None), ('--sections', args.sections is not None),
                       ('--diversity', args.diversity is not None or args.shortlist is not None),
@@ -500,6 +531,7 @@ def main(argv=None):
     retrieval_ks = check_retrieval_args(args)
     retrieval_nll = check_nll_args(args)
     check_prior_args(args)
+    check_combine_args(args)
     check_window_args(args)
     tag_only, tag_mute = check_tag_args(args)
     check_caps_args(args)
@@ -629,6 +661,9 @@ def main(argv=None):
                         else (info['subcateg'], config.subcategory_nums))
             return recommend_sections(config, recommender, feed, feed.titles, args.recommend, sections, out_file=args.recommend_out,
                                       **item_prior)
+        if args.combine_filters:
+            return recommend_request(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
+                                     **item_window, **tag_sets(samples, feed.news_info()['categ']), **item_adjust)
         if args.coarse_catalogue:
             out = recommend(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, coarse=True,
                             coarse_shortlist=args.coarse_shortlist, **explain)
@@ -702,6 +737,10 @@ def main(argv=None):
                           device=config.device)
         net = recommender.model if hasattr(recommender, 'model') else recommender
         needs_info = 'categ' in inspect.signature(net.encode_catalogue).parameters           # nrms_naml's feature rows
+        if args.combine_filters:
+            return evaluate_retrieval_request(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
+                                              news_info=feed.news_info() if needs_info else None, **item_prior, **item_window,
+                                              **tag_sets(samples, feed.news_info()['categ']), **item_adjust)
         return evaluate_retrieval(config, recommender, feed, feed.titles, labels, ks=retrieval_ks,
                                   news_info=feed.news_info() if needs_info else None, **item_prior, **item_window,
                                   **({} if retrieval_nll is None else {'nll_temperatures': retrieval_nll}),

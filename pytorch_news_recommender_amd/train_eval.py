@@ -924,3 +924,139 @@ def evaluate_retrieval(config, model, data_iter, titles, y_true, ks=(10, 100), e
               + ("  closed by tag: {}".format(res["n_closed"]) if tags.on else "")
               + "".join("  nll@T={:g}: {:.4f}".format(t, v) for t, v in (res.get("nll") or {}).items()))
     return res
+
+
+def _request_parts(who, item_time, request_time, window_span, item_tag, allow_tags, adjust):
+    """The per-sample parts of recommend_request() / evaluate_retrieval_request(): the helpers of recommend(), none of which refuses
+    another here.  -> (windows, tags, adj)."""
+    return (_RequestWindows(who, item_time, request_time, window_span), _TagSets(who, item_tag, allow_tags, ()),
+            _Adjust(who, adjust, ()))
+
+
+def _request_keywords(windows, tags, adj, done, B, dev):
+    """The parts' slices for samples [done, done + B) as keywords of ``model.recommend_request`` / ``rank_targets_request``."""
+    kw = dict(windows.of(done, B, dev))
+    if tags.on:
+        kw["item_tag"], kw["allow"] = tags.of(done, B, dev)
+    if adj.on:
+        kw["adjust"] = adj.of(done, B, dev)
+    return kw
+
+
+def recommend_request(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, item_bias=None,
+                      item_time=None, request_time=None, window_span=None, item_tag=None, allow_tags=None, adjust=None):
+    """recommend() through several catalogue filters at once: writes the same ``<impression index> [id1,id2,...]`` lines, per
+    impression of data_iter the k news ids ``model.recommend_request`` serves, best first.  titles / news_info / exclude_history /
+    item_bias as in recommend().  The parts are recommend()'s keywords, with their rules, and any of them may be given together:
+    item_time / request_time / window_span (all three or none), item_tag / allow_tags (both or neither), adjust.  Each is sliced per
+    batch, one row per sample of data_iter in its order.  With no part or one part the file is recommend()'s with that keyword,
+    byte for byte.  Not with diversity, coarse, tag_caps, explain or sections (they are not keywords here).  Returns the file
+    name."""
+    net = _inner(model)
+    prior = {} if item_bias is None else {"item_bias": item_bias}
+    windows, tags, adj = _request_parts("recommend_request", item_time, request_time, window_span, item_tag, allow_tags, adjust)
+    catalogue = net.encode_catalogue(titles, **(news_info or {}))
+    lines, done = [], 0
+    for datas in data_iter:
+        B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
+        kw = _request_keywords(windows, tags, adj, done, B, catalogue.device)
+        done += B
+        ids, _ = net.recommend_request(datas, k, catalogue, exclude_history=exclude_history, **prior, **kw)
+        lines.extend(ids.cpu().tolist())
+    net.engine.check_ids()
+    net.check_recommend_ids()
+    file_name = out_file or 'recommend_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
+    with open(file_name, 'w') as f:
+        for i, row in enumerate(lines):
+            f.write(str(i + 1) + ' ')
+            f.write(str([n for n in row if n >= 0]).replace(' ', '') + '\n')
+    return file_name
+
+
+def evaluate_retrieval_request(config, model, data_iter, titles, y_true, ks=(10, 100), exclude_history=True, news_info=None,
+                               verbose=True, item_bias=None, item_time=None, request_time=None, window_span=None, item_tag=None,
+                               allow_tags=None, adjust=None):
+    """evaluate_retrieval() in the order recommend_request() serves: each held-out click is ranked against the news every part leaves
+    open to its sample (``model.rank_targets_request``).  The arguments are evaluate_retrieval()'s, and the parts may be given
+    together.  Returns its dict (``recall@<k>``, ``ndcg@<k>``, ``mrr``, ``median_rank``, ``n_users``, ``n_targets``, ``n_skipped``)
+    plus ``n_closed``: the held-out clicks of the catalogue that a time window or a tag set closes to their sample; like a click
+    with a NaN delta they come back with rank 0 and count as skipped, as in the tagged evaluation.  The per-user tensors stay on
+    the device in ``last_retrieval_metrics``.  One host synchronisation, at the end."""
+    net = _inner(model)
+    prior = {} if item_bias is None else {"item_bias": item_bias}
+    windows, tags, adj = _request_parts("evaluate_retrieval_request", item_time, request_time, window_span, item_tag, allow_tags,
+                                        adjust)
+    ks = tuple(int(k) for k in ks)
+    catalogue = net.encode_catalogue(titles, **(news_info or {}))
+    dev, N = catalogue.device, int(catalogue.shape[0])
+    ranks, targets, done = [], [], 0
+    n_closed = torch.zeros((), dtype=torch.int64, device=dev)
+    for datas in data_iter:
+        cand = torch.as_tensor(datas["candidate_ids"]).to(dev, dtype=torch.int64)
+        B, S = cand.shape
+        rows = y_true[done:done + B]
+        if len(rows) < B:
+            raise ValueError("evaluate_retrieval_request: %d label rows for %d impressions" % (len(y_true), done + B))
+        kw = _request_keywords(windows, tags, adj, done, B, dev)
+        done += B
+        width = max(1, max(min(len(y), S) for y in rows))
+        lab = np.zeros((B, width), dtype=bool)
+        for i, y in enumerate(rows):
+            n = min(len(y), S)
+            lab[i, :n] = np.asarray(y[:n]) == 1
+        # the clicked ids, moved to the front of each row in shown order and padded with -1 to the batch's widest
+        T = max(1, int(lab.sum(axis=1).max()))
+        lab = torch.from_numpy(lab).to(dev)
+        order = torch.argsort((~lab).to(torch.uint8), dim=1, stable=True)[:, :T]
+        tg = torch.where(lab.gather(1, order), cand[:, :width].gather(1, order), torch.full_like(order, -1))
+        rk, _ = net.rank_targets_request(datas, tg, catalogue, exclude_history=exclude_history, **prior, **kw)
+        # a target of the catalogue that its sample's window or tag set closes (on the device, no synchronisation)
+        in_cat = (tg >= 1) & (tg < N)
+        t_open = torch.ones_like(in_cat)
+        if tags.on:
+            allow = kw["allow"]
+            t_tag = kw["item_tag"].to(torch.int64)[tg.clamp(0, N - 1)]
+            t_open &= (t_tag >= 0) & (t_tag < allow.shape[1]) & allow.gather(1, t_tag.clamp(0, allow.shape[1] - 1))
+        if windows.on:
+            t_time = kw["item_time"].to(torch.int64)[tg.clamp(0, N - 1)]
+            w = kw["window"].to(torch.int64)
+            t_open &= (t_time >= w[:, :1]) & (t_time < w[:, 1:])
+        n_closed += (in_cat & ~t_open).sum()
+        ranks.append(rk)
+        targets.append(tg)
+    T = max((r.shape[1] for r in ranks), default=1)
+    pad = lambda t, v: torch.nn.functional.pad(t, (0, T - t.shape[1]), value=v)
+    ranks = torch.cat([pad(r, 0) for r in ranks]) if ranks else torch.zeros(0, T, dtype=torch.int32, device=dev)
+    targets = torch.cat([pad(t, -1) for t in targets]) if targets else torch.zeros(0, T, dtype=torch.int64, device=dev)
+    m = net.engine.retrieval_metrics(ranks, ks)
+    names = ["recall@%d" % k for k in ks] + ["ndcg@%d" % k for k in ks] + ["mrr"]
+    ranked = ranks > 0
+    have = ranked.any(dim=1)
+    n_users = have.sum()
+    flat = torch.where(ranked, ranks, torch.full_like(ranks, torch.iinfo(torch.int32).max)).reshape(-1).sort().values
+    n_targets = ranked.sum()
+    # median of the ranked ranks (the mean of the middle two when their number is even)
+    lo = flat[((n_targets - 1).clamp(min=0) // 2).clamp(max=max(0, flat.numel() - 1))] if flat.numel() else n_targets
+    hi = flat[(n_targets // 2).clamp(max=max(0, flat.numel() - 1))] if flat.numel() else n_targets
+    vals = [torch.where(have, m[k], torch.zeros_like(m[k])).sum() / n_users.clamp(min=1) for k in names]
+    vals += [(lo.double() + hi.double()) / 2, n_users.double(), n_targets.double(), ((targets >= 0) & ~ranked).sum().double(),
+             n_closed.double()]
+    bad = getattr(net, "_bad_browsed", None)
+    vals.append(bad.double() if bad is not None else n_users.double() * 0)
+    vals = torch.stack(vals).cpu().tolist()                    # the one host synchronisation
+    net.engine.check_ids()
+    if vals.pop():
+        net.check_recommend_ids()                              # raises: browsed ids outside the catalogue
+    res = dict(zip(names, vals[:len(names)]))
+    res["median_rank"] = vals[-5]
+    res["n_users"], res["n_targets"], res["n_skipped"], res["n_closed"] = int(vals[-4]), int(vals[-3]), int(vals[-2]), int(vals[-1])
+    if not res["n_users"]:
+        for k in names + ["median_rank"]:
+            res[k] = float("nan")
+    net.last_retrieval_metrics = dict(m, ranks=ranks, targets=targets)
+    if verbose:
+        print("retrieval over {} news: ".format(N - 1)
+              + "  ".join("{}: {:.4f}".format(k, res[k]) for k in names)
+              + "  median rank: {:.1f}  users: {}  targets: {}  skipped: {}  closed by a part: {}".format(
+                  res["median_rank"], res["n_users"], res["n_targets"], res["n_skipped"], res["n_closed"]))
+    return res
