@@ -733,8 +733,9 @@ int nrms_rank_dot_adjusted(int32_t B, int64_t N, int32_t d, int32_t T, const flo
  *   block stages the slots of its users that fall into its slice in LDS, up to 2048 of them for k <= 192 and 512 above (half of the
  *   adjusted call's: the tag bitmap, the windows and the cursor keys lie beside the list), and otherwise walks the lists in global
  *   memory: slower, never different.
- * Not composed here: the per-tag caps, the fp16 shortlist, sections, the diversity re-ranking, the log-partition, the attribution
- *   and the deep list; paging works through the cursor. */
+ * Not composed here: the fp16 shortlist, sections, the diversity re-ranking, the log-partition, the attribution and the deep list;
+ *   paging works through the cursor.  The per-tag caps are composed with every part in nrms_topk_dot_request_capped (below); there
+ *   is no rank under caps. */
 size_t nrms_topk_dot_request_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
 int nrms_topk_dot_request(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
                           const float* bias /* [N], nullable */, const int32_t* item_time /* [N], nullable */,
@@ -752,6 +753,56 @@ int nrms_rank_dot_request(int32_t B, int64_t N, int32_t d, int32_t T, const floa
                           const float* adj_delta /* [B, E], nullable */, int32_t n_adjust /* E */, const int64_t* targets,
                           const int64_t* exclude, int32_t n_exclude, int32_t* ranks, float* target_scores, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* ---- Per-category caps through the request (a rationed front page that expires news per user, mutes topics, pushes down what was
+ * seen and serves page 2; PARITY UNPINNED, the reference has no catalogue retrieval) ----
+ * nrms_topk_dot_request_capped: nrms_topk_dot_capped's greedy walk over the items nrms_topk_dot_request leaves eligible.
+ * item_tag [N] int32 and cap [B, n_tags] int32 are REQUIRED (4-byte aligned), 1 <= n_tags <= 512.  Every other part is NULLABLE and
+ * given as both pointers or neither, with the rules nrms_topk_dot_request states: the window (item_time, window), the adjustments
+ * (adj_ids, adj_delta, n_adjust <= 256), the cursor (after_scores, after_ids); allow [B, W] uint32, W = ceil(n_tags / 32), is the
+ * tag set over the same item_tag and n_tags (NULL: every tag in range is open).  bias [N] fp32, NULLABLE.  1 <= k <= 256.  An absent
+ * part closes nothing.
+ * Eligible set.  nrms_topk_dot_request's, word for word: the score is s'' = (s + bias[n]) + delta; item n is eligible for user b iff
+ *   n is not in b's exclude row, s'' is not NaN, b's window is open to item_time[n], b allows item_tag[n] (if allow is given) and
+ *   (s'', n) lies strictly after b's cursor (if one is given).
+ * Greedy walk.  Walk that set in nrms_topk_dot_biased's order (s'' descending, then the smaller n, -0.0 equal to +0.0).  Item n with
+ *   tag t = item_tag[n] is TAKEN iff 0 <= t < n_tags and fewer than cap[b, t] items of tag t were taken before it IN THIS CALL.  The
+ *   first k taken items are row b, with their s''; then id -1 / score -inf.
+ * Cap values.  cap <= 0 closes the tag, cap >= k leaves it uncapped; a tag is open iff cap > 0 and, with allow given, its bit is set.
+ * Consequences.
+ *   1. Every cap >= k is nrms_topk_dot_request with the same parts, bit for bit, its tag set being allow (allow == NULL: all tags
+ *      in range open).
+ *   2. No window, no adjustments, no cursor and allow == NULL is nrms_topk_dot_capped, bit for bit (the call is routed there).
+ *   3. The first k' columns of a call with k are the call with k'.
+ *   4. With no cursor and bias == NULL, row b equals nrms_topk_dot_capped at B = 1 whose bias holds row b's deltas scattered by the
+ *      lowest-slot rule, +0.0 elsewhere, and NaN where b's window or allow closes the item; for N <= 4096 it is therefore also the
+ *      greedy walk over nrms_topk_dot_deep with that bias.
+ *   5. Paging.  Let page j + 1 be the call whose cursor is the last column of page j, whose cap is the original cap minus the
+ *      per-tag counts of everything served on pages 1 .. j, and whose other parts are unchanged.  The pages laid end to end are the
+ *      columns of ONE call with k = the sum of the page lengths (any total <= 256), then padding; nothing is repeated or skipped
+ *      across ties.  (An item the walk skipped before the cursor belonged to a saturated tag and can never be taken later; every
+ *      item after the cursor sees exactly the room that is left.)
+ *   6. No row holds more than max(cap[b, t], 0) ids of tag t.
+ *   7. Row b depends on user row b, the b-th row of every part, cap row b and exclude row b only: not on B, the row's position in
+ *      the batch, the other rows, the launch geometry, what the workspace held or the run.
+ * There is no rank form: the position of a target in a capped list is not a count of predecessors.
+ * Argument errors return NRMS_EINVAL with a message that names the argument ("topk_dot_request_capped: ..."): cap or item_tag NULL,
+ *   a half-given pair (it names its missing pointer), n_tags outside [1, 512], n_adjust outside [0, 256] and a misaligned array are
+ *   among them.  An undersized workspace returns NRMS_EWORKSPACE.  Nothing is launched after an error.
+ * Workspace: the query returns exactly nrms_topk_dot_workspace_bytes(B, N, d, k) (0 = arguments rejected); 8-byte aligned.
+ * One scan of the catalogue and one merge on `stream`, no host synchronisation, no allocation, no [B, N] matrix.  A block keeps a
+ *   16-bit threshold per (user, tag) in the LDS its request parts leave free: every n_tags for k <= 64, n_tags <= 43 for k <= 192,
+ *   none above; a call without the table gives the same results (what the table saves is measured for nrms_topk_dot_capped,
+ *   DESIGN.md section 8m; section 8p has this call's figures). */
+size_t nrms_topk_dot_request_capped_workspace_bytes(int32_t B, int64_t N, int32_t d, int32_t k);
+int nrms_topk_dot_request_capped(int32_t B, int64_t N, int32_t d, int32_t k, const float* user, const float* items,
+                                 const float* bias /* [N], nullable */, const int32_t* item_time /* [N], nullable */,
+                                 const int32_t* window /* [B, 2], nullable */, const int32_t* item_tag /* [N] */, int32_t n_tags,
+                                 const uint32_t* allow /* [B, W], nullable */, const int32_t* cap /* [B, n_tags] */,
+                                 const int64_t* adj_ids /* [B, E], nullable */, const float* adj_delta /* [B, E], nullable */,
+                                 int32_t n_adjust /* E */, const float* after_scores /* [B], nullable */,
+                                 const int64_t* after_ids /* [B], nullable */, const int64_t* exclude, int32_t n_exclude,
+                                 float* top_scores, int64_t* top_ids, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Paging through the exact ranking: a cursor on the top-k, and lists up to 4096 (candidate generation for a re-ranker, a feed
  * that scrolls: "the next 20 after what I showed"; PARITY UNPINNED, the reference has no catalogue retrieval) ----

@@ -202,6 +202,10 @@ SIGNATURES = {
     "nrms_topk_dot_request": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]
                               + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3
                               + [C.c_size_t, C.c_void_p]),
+    "nrms_topk_dot_request_capped_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "nrms_topk_dot_request_capped": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]
+                                     + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3
+                                     + [C.c_size_t, C.c_void_p]),
     "nrms_rank_dot_request_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "nrms_rank_dot_request": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]
                               + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 3

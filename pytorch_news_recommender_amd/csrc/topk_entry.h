@@ -209,6 +209,24 @@ __device__ __forceinline__ void tk_caps_stage(uint32_t* ubt, TkCaps t, int u0, i
     }
 }
 
+// REQ + CAPS kernels: tk_tags_stage with the caps applied: bit i of ubt[t] is set iff cap[u0 + i, t] > 0 and, where there is a tag
+// set (a.allow not null), user u0 + i allows tag t.  The tags and their number are the caps'.
+__device__ __forceinline__ void tk_tags_stage(uint32_t* ubt, TkTags a, TkCaps t, int u0, int B, int nthreads) {
+    const int W = (t.n_tags + 31) >> 5;
+    const int nu = min(TK_UT, B - u0);
+    for (int tag = threadIdx.x; tag < t.n_tags; tag += nthreads) {
+        const int32_t* col = t.cap + (long)u0 * t.n_tags + tag;
+        const uint32_t* acol = a.allow ? a.allow + (long)u0 * W + (tag >> 5) : nullptr;
+        uint32_t m = 0;
+        for (int i = 0; i < nu; ++i) {
+            uint32_t open = (uint32_t)(col[(long)i * t.n_tags] > 0);
+            if (acol) open &= acol[(long)i * W] >> (tag & 31);
+            m |= open << i;
+        }
+        ubt[tag] = m;
+    }
+}
+
 // One wave: k_b = min(k, sum over tags of min(max(cap_row[t], 0), k)), the length the capped list of user row cap_row can reach,
 // in bits 0 .. 15, and in bit 16 whether any tag is rationed at all (0 < cap_row[t] < k_b; if none is, the capped list is the
 // best k_b of the open tags).  Once a capped list holds k_b entries nothing below its smallest entry can enter it: k_b = k: k taken

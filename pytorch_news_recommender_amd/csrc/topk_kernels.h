@@ -119,9 +119,10 @@ __device__ uint64_t tk_select(uint64_t* buf, int& cnt, int k, int lane) {
 struct TkSelectBest {
     static constexpr bool capped = false;
 };
-template <int TT>
+template <int TT, bool OUTLINE = false>
 struct TkSelectCapped {
     static constexpr bool capped = true;
+    static constexpr bool outline = OUTLINE;          // REQ + CAPS kernels: the capped selection is a call, not inlined into the scan
     static constexpr int table = TT;
     const int32_t* item_tag;     // [N]
     const int32_t* cap;          // [B, n_tags]
@@ -131,6 +132,8 @@ struct TkSelectCapped {
 };
 // The tags whose thresholds fit beside a P class's buffers: 32 x TT x 2 bytes of the LDS the class leaves free.
 constexpr int tk_caps_table(int P) { return P <= 128 ? 512 : P <= 256 ? 192 : 48; }
+// The same beside the parts of a request (REQ + CAPS kernels): what the REQ form leaves free; none at P = 512.
+constexpr int tk_request_caps_table(int P) { return P <= 128 ? 512 : P <= 256 ? 43 : 0; }
 
 typedef uint16_t __attribute__((may_alias)) tk_u16_alias;
 
@@ -149,14 +152,16 @@ typedef uint16_t __attribute__((may_alias)) tk_u16_alias;
 //
 // Returns the threshold: 0 until k_b entries are kept, then (at most) the smallest kept entry, below which nothing can enter this
 // user's list any more (tk_caps_reach says why).  Wave-level syncs only: TkFilter::offer calls it between block barriers.
-template <int P>
+template <int P, bool FLAT = false>          // FLAT (tk_select_capped_call): the sort is inlined, so that the function holds no call
 __device__ uint64_t tk_select_capped(uint64_t* buf, int& cnt, int reach, int lane, const int32_t* __restrict__ item_tag,
                                      const int32_t* __restrict__ cap_row, int n_tags, uint16_t* ttag_row = nullptr) {
     constexpr int E = P / 64;
     static_assert(P * 8 >= 2 * TK_MAX_TAGS, "the buffer holds one 16-bit counter per tag");
     const int kb = max(reach & 0xFFFF, 1);
     if (!(reach >> 16)) return tk_select<P>(buf, cnt, kb, lane);
-    tk_flush<P>(buf, __builtin_amdgcn_readfirstlane(cnt), 1, lane);          // padded with 0, sorted descending
+    if constexpr (FLAT) {
+        [[clang::always_inline]] tk_flush<P>(buf, __builtin_amdgcn_readfirstlane(cnt), 1, lane);
+    } else tk_flush<P>(buf, __builtin_amdgcn_readfirstlane(cnt), 1, lane);          // padded with 0, sorted descending
     uint64_t v[E];
     int tg[E];
 #pragma unroll
@@ -206,6 +211,24 @@ __device__ uint64_t tk_select_capped(uint64_t* buf, int& cnt, int reach, int lan
     tk_wave_sync();
     cnt = min(base, kb);
     return base >= kb ? buf[kb - 1] : 0;
+}
+
+// tk_select_capped as a function of its own (REQ + CAPS kernels, which have no register to spare in their scan: the flush is a
+// phase of its own, and as a call its live set stays out of the scan's).
+// The count goes in and comes back by value: a reference would put it in scratch memory.
+struct TkCut {
+    uint64_t thr;
+    int cnt;
+};
+// The buffer crosses the call as an LDS pointer, so that the selection keeps its LDS instructions, and the sort is inlined into it
+// (FLAT): a call inside it would need a stack frame.  The threshold row stays a generic pointer, null where there is no table (a
+// null pointer must not be cast between address spaces by hand); it is read and written a few times per flush.
+typedef __attribute__((address_space(3))) uint64_t tk_lds_u64;
+template <int P>
+__device__ __noinline__ TkCut tk_select_capped_call(tk_lds_u64* buf, int cnt, int reach, int lane, const int32_t* __restrict__ item_tag,
+                                                    const int32_t* __restrict__ cap_row, int n_tags, uint16_t* ttag_row) {
+    const uint64_t thr = tk_select_capped<P, true>((uint64_t*)buf, cnt, reach, lane, item_tag, cap_row, n_tags, ttag_row);
+    return TkCut{thr, cnt};
 }
 
 // One wave: zeroes the entries of buf[0, cnt) whose id user b excludes (ex: the block's LDS copy of its exclude ids in
@@ -350,10 +373,17 @@ struct TkFilter {
     // returns the new threshold, sets c.  Only ever called for a user row below B.
     __device__ __forceinline__ uint64_t flush(int i, int& c) {
         tk_drop_excluded(s.buf[i], c, ex_lds() ? s.ex[i] : nullptr, exclude + (long)(u0 + i) * n_exclude, n_exclude, lane);
-        if constexpr (SEL::capped)
-            return tk_select_capped<P>(s.buf[i], c, sel.reach[i], lane, sel.item_tag, sel.cap + (long)(u0 + i) * sel.n_tags, sel.n_tags,
-                                       sel.ttag ? sel.ttag + i * SEL::table : nullptr);
-        else return tk_select<P>(s.buf[i], c, k, lane);
+        if constexpr (SEL::capped) {
+            if constexpr (SEL::outline) {
+                const TkCut cut = tk_select_capped_call<P>((tk_lds_u64*)s.buf[i], c, sel.reach[i], lane, sel.item_tag,
+                                                           sel.cap + (long)(u0 + i) * sel.n_tags, sel.n_tags,
+                                                           sel.ttag ? sel.ttag + i * SEL::table : nullptr);
+                c = cut.cnt;
+                return cut.thr;
+            } else
+                return tk_select_capped<P>(s.buf[i], c, sel.reach[i], lane, sel.item_tag, sel.cap + (long)(u0 + i) * sel.n_tags,
+                                           sel.n_tags, sel.ttag ? sel.ttag + i * SEL::table : nullptr);
+        } else return tk_select<P>(s.buf[i], c, k, lane);
     }
 
     // The scores of a step that have to be offered, bit 16 c + q of the result.  C/D layout: item = lane & 31 of column tile
@@ -525,6 +555,16 @@ struct TkFilter {
 // P = 512 half of the ADJ form's, which pays for the bitmap, the windows and the cursor keys beside it.  Only topkrequest.hip
 // instantiates these kernels, and one family serves every subset of the parts.
 //
+// REQ + CAPS (nrms_topk_dot_request_capped; with or without BIAS): the pack holds a TkRequest AND a TkCaps, the one pair of members
+// that is allowed.  It is the REQ form with the CAPS differences: the bitmap is always built, from (cap > 0) & allow (cap > 0 alone
+// where there is no tag set; tk_tags_stage with a TkCaps); the tag of every item is kept for above_tags(), which runs on s'', after
+// the prior's add, tk_adjust_apply and the cursor's compare; the filter cuts a full buffer down with tk_select_capped, as a call
+// (tk_select_capped_call: these kernels have no register to spare in their scan), with tk_caps_reach's k_b; the thresholds take the
+// LDS the request's parts leave free (tk_request_caps_table: none at P = 512).  Both statements that make one scan exact, C(S1 u S2)
+// = C(C(S1) u C(S2)) and the k_b threshold, are about a set of eligible items under a total order and do not ask which filters made
+// the set, so the slice lists are capped lists of s'' entries and topk_merge_capped_kernel merges them unchanged.  Only
+// topkrequestcaps.hip instantiates these kernels.
+//
 // The window's two pointers are a kernel argument of the WINDOW instantiations alone, the adjustments' of the ADJ instantiations alone, the cursor's of the CURSOR instantiations
 // alone, the tag set's of the TAGS instantiations alone and the caps' of the CAPS instantiations alone (WIN holds a TkWindow, a
 // TkCursor, both in that order, a TkTags, a TkCaps, or nothing; CURSOR, TAGS and CAPS are read off the pack), so every other instantiation keeps its name, its signature and its kernarg
@@ -545,8 +585,9 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     static_assert(sizeof...(WIN) == (WINDOW ? 1 : 0) + (CURSOR ? 1 : 0) + (TAGS ? 1 : 0) + (CAPS ? 1 : 0) + (ADJ ? 1 : 0) + (REQ ? 1 : 0),
                   "WINDOW kernels take one TkWindow, CURSOR kernels one TkCursor, TAGS kernels one TkTags, CAPS kernels one TkCaps, "
                   "ADJ kernels one TkAdjust, REQ kernels one TkRequest, the others none");
-    static_assert(!(REQ && (GROUPED || NOISE || WINDOW || CURSOR || TAGS || CAPS || ADJ)),
-                  "a request holds its window, tag set, adjustments and cursor itself, over the plain and the biased top-k only");
+    static_assert(!(REQ && (GROUPED || NOISE || WINDOW || CURSOR || TAGS || ADJ)),
+                  "a request holds its window, tag set, adjustments and cursor itself, over the plain and the biased top-k only; the "
+                  "one member it pairs with is a TkCaps (nrms_topk_dot_request_capped)");
     static_assert(!(ADJ && (GROUPED || NOISE || WINDOW || CURSOR || TAGS || CAPS)), "the adjustments are for the plain and the biased top-k only");
     static_assert(!(CAPS && (GROUPED || NOISE || WINDOW || CURSOR || TAGS)), "the tag caps are for the plain and the biased top-k only");
     static_assert(!(TAGS && (GROUPED || NOISE || WINDOW || CURSOR)), "the tag set is for the plain and the biased top-k only");
@@ -565,8 +606,8 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
     const int slice = blockIdx.y;
     const int n_begin = slice * slice_len;
     const int n_end = min(GROUPED ? 32 * n_tiles : N, n_begin + slice_len);      // (grouped: tile rows, not catalogue rows)
-    constexpr int TT = tk_caps_table(P);
-    TkFilter<P, W, std::conditional_t<CAPS, TkSelectCapped<TT>, TkSelectBest>> flt{lds, exclude, n_exclude, k, u0, B, lane, wave};
+    constexpr int TT = REQ ? tk_request_caps_table(P) : tk_caps_table(P);
+    TkFilter<P, W, std::conditional_t<CAPS, TkSelectCapped<TT, REQ>, TkSelectBest>> flt{lds, exclude, n_exclude, k, u0, B, lane, wave};
     int2* wwin = nullptr;          // WINDOW: the block's 32 (lo, hi)
     if constexpr (WINDOW) {
         __shared__ int2 wwin_lds[TK_UT];
@@ -590,7 +631,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         item_tag = tags.item_tag;
         tk_tags_stage(ubt, tags, u0, B, 64 * W);
     }
-    if constexpr (CAPS) {          // the bitmap of the tags with cap > 0, the block's 32 k_b and its tag thresholds
+    if constexpr (CAPS && !REQ) {          // the bitmap of the tags with cap > 0, the block's 32 k_b and its tag thresholds
         __shared__ uint32_t ubt_lds[TK_MAX_TAGS];
         __shared__ int reach_lds[TK_UT];
         __shared__ uint16_t ttag_lds[TK_UT * TT];
@@ -641,7 +682,21 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
             cur = cur_lds;
             tk_cursor_stage(cur, req.cur, u0, B);
         }
-        if (req.tags.allow) {
+        if constexpr (CAPS) {      // REQ + CAPS: the bitmap of (cap > 0) & allow (allow null: cap > 0), the 32 k_b, the thresholds that fit
+            __shared__ int reach_lds[TK_UT];
+            __shared__ uint16_t ttag_lds[TT > 0 ? TK_UT * TT : 1];
+            for (int i = threadIdx.x; i < TK_UT * TT; i += 64 * W) ttag_lds[i] = 0;
+            const TkCaps caps = tk_pack_arg<TkCaps>(win_arg...);
+            ubt = ubt_lds;
+            n_tags = caps.n_tags;
+            item_tag = caps.item_tag;
+            tk_tags_stage(ubt, req.tags, caps, u0, B, 64 * W);
+            for (int i = wave; i < TK_UT; i += W) {
+                const int kb = u0 + i < B ? tk_caps_reach(caps.cap + (long)(u0 + i) * n_tags, n_tags, k, lane) : 0;
+                if (lane == 0) reach_lds[i] = kb;
+            }
+            flt.sel = TkSelectCapped<TT, true>{caps.item_tag, caps.cap, n_tags, reach_lds, TT > 0 && n_tags <= TT ? ttag_lds : nullptr};
+        } else if (req.tags.allow) {
             ubt = ubt_lds;
             n_tags = req.tags.n_tags;
             item_tag = req.tags.item_tag;
@@ -726,7 +781,7 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
         }
         [[maybe_unused]] int tgv[CAPS ? TK_TN : 1] = {};        // CAPS: the tag of this lane's item of column tile c (0 where tm[c] is 0)
         uint32_t tm[TAGS || CAPS || REQ ? TK_TN : 1] = {};      // TAGS, CAPS: the block's users that this lane's item of column tile c is open to
-        if constexpr (TAGS || CAPS) {
+        if constexpr ((TAGS || CAPS) && !REQ) {          // (REQ + CAPS: the REQ block below loads the tags)
             if (nw < n_end) {
 #pragma unroll
                 for (int c = 0; c < TK_TN; ++c) {
@@ -756,7 +811,11 @@ __global__ __launch_bounds__(64 * W) void topk_slice_kernel(int B, int N, int d,
                 for (int c = 0; c < TK_TN; ++c) tm[c] = nw + 32 * c + r < n_end ? ~0u : 0u;
                 if (ubt) {
 #pragma unroll
-                    for (int c = 0; c < TK_TN; ++c) tm[c] &= tk_tags_mask(ubt, item_tag[min(nw + 32 * c + r, N - 1)], n_tags);
+                    for (int c = 0; c < TK_TN; ++c) {
+                        const int tg = item_tag[min(nw + 32 * c + r, N - 1)];
+                        tm[c] &= tk_tags_mask(ubt, tg, n_tags);
+                        if constexpr (CAPS) tgv[c] = (uint32_t)tg < (uint32_t)n_tags ? tg : 0;
+                    }
                     dead = dead || (TK_TAGS_SKIP && __ballot((tm[0] | tm[1]) != 0) == 0);
                 }
             }

@@ -130,6 +130,35 @@ def pack_tag_mask(allow):
     return (word - ((word >> 31) << 32)).to(torch.int32)
 
 
+def remaining_caps(cap, served_ids, item_tag, n_tags):
+    """The caps of the next page of a capped request -> int32 [B, n_tags]: ``cap`` minus, per user and tag, the number of
+    ``served_ids`` [B, K] (everything served on the pages so far; -1 is padding and ignored) that carry the tag, read off
+    ``item_tag`` [N] by id.  cap: int [B, n_tags], or [n_tags] for every user.  Ids and tags are in one convention, the one the
+    call that served them uses (catalogue rows with the engine, news ids with a model).  An id whose tag lies outside [0, n_tags)
+    was never served and is ignored.  The result may go below zero where a caller counts more than the cap allowed: a cap <= 0
+    closes the tag.  Torch ops on cap's device, no host synchronisation."""
+    if not (torch.is_tensor(cap) and torch.is_tensor(served_ids) and torch.is_tensor(item_tag)):
+        raise ValueError("remaining_caps: cap, served_ids and item_tag must be tensors")
+    n_tags = int(n_tags)
+    if served_ids.dim() != 2 or item_tag.dim() != 1 or cap.dim() not in (1, 2) or cap.shape[-1] != n_tags:
+        raise ValueError("remaining_caps: cap must be [B, %d] or [%d], served_ids [B, K] and item_tag [N] (got %s, %s, %s)"
+                         % (n_tags, n_tags, tuple(cap.shape), tuple(served_ids.shape), tuple(item_tag.shape)))
+    B = served_ids.shape[0]
+    if cap.dim() == 1:
+        cap = cap.unsqueeze(0).expand(B, -1)
+    if cap.shape[0] != B:
+        raise ValueError("remaining_caps: cap has %d rows, served_ids %d" % (cap.shape[0], B))
+    dev = cap.device
+    ids = served_ids.to(dev, dtype=torch.int64)
+    N = item_tag.shape[0]
+    real = (ids >= 0) & (ids < N)
+    tags = item_tag.to(dev, dtype=torch.int64)[ids.clamp(0, max(N - 1, 0))] if N else torch.zeros_like(ids)
+    real = real & (tags >= 0) & (tags < n_tags)
+    counts = torch.zeros(B, n_tags, dtype=torch.int64, device=dev)
+    counts.scatter_add_(1, torch.where(real, tags, torch.zeros_like(tags)), real.to(torch.int64))
+    return (cap.to(torch.int64) - counts).clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
+
+
 def impression_metrics(lib, device, scores, labels, lens, ks=(5, 10), ranks=False):
     """NRMSEngine.impression_metrics without an engine (evaluation.score_submission): ``lib`` is _lib.load()."""
     k_a, k_b = (int(k) for k in ks)
@@ -1207,6 +1236,59 @@ class NRMSEngine:
                                             _lib.ptr(exclude), n_ex, _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws),
                                             C.c_size_t(ws.numel() * 8), _stream())
         _lib.check(rc, "nrms_topk_dot_request")
+        return scores, ids
+
+    def top_k_request_capped(self, user_vec, items, k, item_tag, n_tags, cap, exclude=None, bias=None, *, item_time=None,
+                             window=None, allow=None, adj_ids=None, adj_delta=None, after_scores=None, after_ids=None):
+        """top_k_capped over the items top_k_request leaves eligible -> (scores [B, k] fp32, ids [B, k] int64): the request's
+        adjusted score and eligibility (window, tag set, adjustments, cursor: each pair both or neither, each with the rules of its
+        own call; ``allow`` is the tag set over the same item_tag and n_tags), walked in order, item n with tag t taken iff 0 <= t <
+        n_tags and fewer than cap[b, t] items of tag t were taken before it in this call.  cap int32 [B, n_tags] (device): <= 0
+        closes the tag, >= k leaves it uncapped.  Every cap >= k is top_k_request, no other part is top_k_capped, bit for bit.
+        Pages chain through the cursor and ``remaining_caps`` (nrms_topk_dot_request_capped; include/nrms_hip.h states the
+        contract)."""
+        who = "top_k_request_capped"
+        k = int(k)
+        B, N, d, exclude, n_ex, item_time, window = self._top_k_args(who, user_vec, items, exclude, bias, item_time, window)
+        dev = self._cuda_device()
+        if allow is not None:
+            item_tag, allow, n_tags = self._tag_args(who, item_tag, n_tags, allow, N, B, dev)
+        else:
+            item_tag, n_tags = self._item_tag_arg(who, item_tag, n_tags, N, dev)
+        if (not torch.is_tensor(cap) or tuple(cap.shape) != (B, n_tags) or cap.dtype != torch.int32 or cap.device != dev):
+            got = ("%s %s on %s" % (tuple(cap.shape), cap.dtype, cap.device)) if torch.is_tensor(cap) else type(cap).__name__
+            raise _lib.NrmsError("%s: cap must be an int32 [%d, %d] tensor on %s (got %s)" % (who, B, n_tags, self.device, got))
+        cap = cap.contiguous()
+        if (adj_ids is None) != (adj_delta is None):
+            raise _lib.NrmsError("%s: adj_ids and adj_delta go together (adj_ids %s, adj_delta %s)"
+                                 % (who, "missing" if adj_ids is None else "given", "missing" if adj_delta is None else "given"))
+        E = 0
+        if adj_ids is not None:
+            adj_ids, adj_delta, E = self._adjust_args(who, adj_ids, adj_delta, B, dev)
+            if E == 0:
+                adj_ids = adj_delta = None
+        if (after_scores is None) != (after_ids is None):
+            raise _lib.NrmsError("%s: after_scores and after_ids go together (after_scores %s, after_ids %s)"
+                                 % (who, "missing" if after_scores is None else "given", "missing" if after_ids is None else "given"))
+        if after_ids is not None:
+            for name, t, dtype in (("after_scores", after_scores, torch.float32), ("after_ids", after_ids, torch.int64)):
+                if not torch.is_tensor(t) or tuple(t.shape) != (B,):
+                    raise _lib.NrmsError("%s: %s must be a [%d] %s tensor (got %s)"
+                                         % (who, name, B, dtype, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+                self._check_tensor(who, name, t, dtype, 1)
+        nbytes = self.lib.nrms_topk_dot_request_capped_workspace_bytes(B, N, d, k)
+        if nbytes == 0:
+            raise _lib.NrmsError("%s: arguments rejected (B=%d, N=%d, d=%d, k=%d; 1 <= k <= 256)" % (who, B, N, d, k))
+        ws = self._buf("topk_ws", (nbytes + 7) // 8, torch.int64)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        rc = self.lib.nrms_topk_dot_request_capped(B, C.c_int64(N), d, k, _lib.ptr(user_vec), _lib.ptr(items), _lib.ptr(bias),
+                                                   _lib.ptr(item_time), _lib.ptr(window), _lib.ptr(item_tag), n_tags,
+                                                   _lib.ptr(allow), _lib.ptr(cap), _lib.ptr(adj_ids), _lib.ptr(adj_delta), E,
+                                                   _lib.ptr(after_scores), _lib.ptr(after_ids), _lib.ptr(exclude), n_ex,
+                                                   _lib.ptr(scores), _lib.ptr(ids), _lib.ptr(ws), C.c_size_t(ws.numel() * 8),
+                                                   _stream())
+        _lib.check(rc, "nrms_topk_dot_request_capped")
         return scores, ids
 
     def rank_of_request(self, user_vec, items, targets, exclude=None, bias=None, *, item_time=None, window=None, item_tag=None,

@@ -289,6 +289,10 @@ class Model(FlatHipModel):
         raise NotImplementedError("graph: recommend_request is not available: a candidate's score depends on its neighbours in the "
                                   "click graph, not on a catalogue row alone (no recommend either, through a request or not)")
 
+    def recommend_request_capped(self, batch, k, catalogue, item_tag, cap, exclude_history=True, **parts):
+        raise NotImplementedError("graph: recommend_request_capped is not available: a candidate's score depends on its neighbours "
+                                  "in the click graph, not on a catalogue row alone (no recommend either, with caps or without)")
+
     def rank_targets_request(self, batch, targets, catalogue, exclude_history=True, **parts):
         raise NotImplementedError("graph: rank_targets_request is not available: a candidate's score depends on its neighbours in "
                                   "the click graph, not on a catalogue row alone (no rank_targets either)")

@@ -416,6 +416,10 @@ class Model(FlatHipModel):
         raise NotImplementedError("hierec: recommend_request is not available: HieRec scores the catalogue with a query per (topic, "
                                   "sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no per-user adjustments")
 
+    def recommend_request_capped(self, batch, k, catalogue, item_tag, cap, exclude_history=True, **parts):
+        raise NotImplementedError("hierec: recommend_request_capped is not available: HieRec scores the catalogue with a query per "
+                                  "(topic, sub-topic) group (nrms_topk_grouped_dot), and the grouped kernel has no per-tag caps")
+
     def rank_targets_request(self, batch, targets, catalogue, exclude_history=True, **parts):
         raise NotImplementedError("hierec: rank_targets_request is not available: HieRec scores the catalogue with a query per "
                                   "(topic, sub-topic) group (nrms_topk_grouped_dot), and nrms_rank_dot_request ranks plain dot "

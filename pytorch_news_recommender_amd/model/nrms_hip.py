@@ -18,7 +18,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import FlatLayout, ModelDims, NRMSEngine, PackedCatalogue, pack_tag_mask  # noqa: F401 (pack_tag_mask: for callers)
+from ..engine import (FlatLayout, ModelDims, NRMSEngine, PackedCatalogue, pack_tag_mask,  # noqa: F401 (pack_tag_mask and
+                      remaining_caps)                                                     # remaining_caps: for callers)
 from ._flat_model import FlatHipModel
 
 PAGE_BEGIN = -2          # recommend_page: the cursor id of a row that starts over (include/nrms_hip.h NRMS_CURSOR_BEGIN)
@@ -359,18 +360,8 @@ class Model(FlatHipModel):
             a_ids = torch.full((B,), PAGE_BEGIN, dtype=torch.int64, device=dev)
             a_scores = torch.zeros(B, dtype=torch.float32, device=dev)
         else:
-            try:
-                a_ids, a_scores = after
-            except (TypeError, ValueError):
-                raise _lib.NrmsError("recommend_page: after must be None or (ids [B], scores [B]), the last column of the page before")
-            a_ids = torch.as_tensor(a_ids).to(dev, dtype=torch.int64).reshape(-1)
-            a_scores = torch.as_tensor(a_scores).to(dev, dtype=torch.float32).reshape(-1).contiguous()
-            if a_ids.shape[0] != B or a_scores.shape[0] != B:
-                raise _lib.NrmsError("recommend_page: after must be (ids [%d], scores [%d]) (got %s, %s)"
-                                     % (B, B, tuple(a_ids.shape), tuple(a_scores.shape)))
-            # news id n is row n - 1 of cat[1:], as in recommend; -1, PAGE_BEGIN and every other negative id pass through
-            # unshifted.  Id 0, the padding title, is no row and no page returns it: it is read as -1, exhausted.
-            a_ids = torch.where(a_ids > 0, a_ids - 1, torch.where(a_ids == 0, torch.full_like(a_ids, -1), a_ids)).contiguous()
+            cur = self._after_rows(after, B, dev, "recommend_page")
+            a_scores, a_ids = cur["after_scores"], cur["after_ids"]
         scores, ids = self._engine.top_k_after(user, cat[1:], k, a_scores, a_ids, exclude, bias=bias, **win)
         return torch.where(ids >= 0, ids + 1, ids), scores
 
@@ -638,27 +629,74 @@ class Model(FlatHipModel):
         the rules of its own method; include/nrms_hip.h nrms_topk_dot_request states how they compose: the score is (dot product +
         item_bias) + delta, a news is served iff every part leaves it open, and the cursor compares the adjusted score, so the
         same ``adjust`` goes with every page.  rank_targets_request of the ids gives 1, 2, ...  With no part or one part this is
-        that part's own method, bit for bit.  Not combined with caps, the fp16 shortlist, sections, the diversity re-ranking,
-        the log-partition, explain or recommend_deep."""
+        that part's own method, bit for bit.  Caps go with every part in recommend_request_capped.  Not combined with the fp16
+        shortlist, sections, the diversity re-ranking, the log-partition, explain or recommend_deep."""
         who = "recommend_request"
         user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, who)
         bias = self._item_bias_rows(item_bias, cat, who)
         B, dev = user.shape[0], user.device
         kw = self._request_rows(cat, B, item_time, window, item_tag, allow, adjust, who)
         if after is not None:
-            try:
-                a_ids, a_scores = after
-            except (TypeError, ValueError):
-                raise _lib.NrmsError("%s: after must be None or (ids [B], scores [B]), the last column of the page before" % who)
-            a_ids = torch.as_tensor(a_ids).to(dev, dtype=torch.int64).reshape(-1)
-            a_scores = torch.as_tensor(a_scores).to(dev, dtype=torch.float32).reshape(-1).contiguous()
-            if a_ids.shape[0] != B or a_scores.shape[0] != B:
-                raise _lib.NrmsError("%s: after must be (ids [%d], scores [%d]) (got %s, %s)"
-                                     % (who, B, B, tuple(a_ids.shape), tuple(a_scores.shape)))
-            # recommend_page's convention: news id n is row n - 1, id 0 is read as -1, negative ids pass through
-            a_ids = torch.where(a_ids > 0, a_ids - 1, torch.where(a_ids == 0, torch.full_like(a_ids, -1), a_ids)).contiguous()
-            kw.update(after_scores=a_scores, after_ids=a_ids)
+            kw.update(self._after_rows(after, B, dev, who))
         scores, ids = self._engine.top_k_request(user, cat[1:], k, exclude, bias=bias, **kw)
+        return torch.where(ids >= 0, ids + 1, ids), scores
+
+    @staticmethod
+    def _after_rows(after, B, dev, who):
+        """The cursor (ids [B], scores [B]) of recommend_page, recommend_request and recommend_request_capped -> the after_scores /
+        after_ids keywords of the engine.  News id n is row n - 1 of cat[1:], as in recommend; -1, PAGE_BEGIN and every other
+        negative id pass through unshifted.  Id 0, the padding title, is no row and no page returns it: it is read as -1, exhausted."""
+        try:
+            a_ids, a_scores = after
+        except (TypeError, ValueError):
+            raise _lib.NrmsError("%s: after must be None or (ids [B], scores [B]), the last column of the page before" % who)
+        a_ids = torch.as_tensor(a_ids).to(dev, dtype=torch.int64).reshape(-1)
+        a_scores = torch.as_tensor(a_scores).to(dev, dtype=torch.float32).reshape(-1).contiguous()
+        if a_ids.shape[0] != B or a_scores.shape[0] != B:
+            raise _lib.NrmsError("%s: after must be (ids [%d], scores [%d]) (got %s, %s)"
+                                 % (who, B, B, tuple(a_ids.shape), tuple(a_scores.shape)))
+        a_ids = torch.where(a_ids > 0, a_ids - 1, torch.where(a_ids == 0, torch.full_like(a_ids, -1), a_ids)).contiguous()
+        return dict(after_scores=a_scores, after_ids=a_ids)
+
+    @torch.no_grad()
+    def recommend_request_capped(self, batch, k, catalogue, item_tag, cap, exclude_history=True, *, item_bias=None, n_tags=None,
+                                 item_time=None, window=None, allow=None, adjust=None, after=None):
+        """recommend_capped through recommend_request's filters -> (news_ids [B, k] int64, scores [B, k] fp32): a rationed front
+        page ("at most two stories per category in my ten") that also expires news per user (item_time, window), mutes topics
+        (allow, over the same item_tag), pushes down what was already shown (adjust) and serves page 2 (after)
+        (include/nrms_hip.h nrms_topk_dot_request_capped).  Parity is unpinned: the reference has no catalogue retrieval.
+
+        item_tag and cap are recommend_capped's (cap: an int with ``n_tags=``, an int tensor [n_tags] or [B, n_tags]); every other
+        part is recommend_request's, optional, with the rules of its own method; ``allow`` is bool [B, n_tags] or its packed form
+        and needs no item_tag of its own.  The walk is recommend_capped's over the news every part leaves open, in the order of the
+        adjusted score: a news is taken iff its tag has room left in this call.  With every cap >= k this is recommend_request,
+        with no other part recommend_capped, bit for bit.
+
+        Paging: page j + 1 takes ``after`` = the last (id, score) column of page j and ``cap`` = remaining_caps(cap, every id
+        served so far, item_tag, n_tags), the other parts unchanged; the pages laid end to end are then the columns of one call
+        with k = the sum of the page lengths (<= 256), with nothing repeated or skipped across ties.  There is no rank under caps.
+        Not combined with the fp16 shortlist, sections, the diversity re-ranking, the log-partition, explain or recommend_deep."""
+        who = "recommend_request_capped"
+        user, cat, exclude = self._catalogue_query(batch, catalogue, exclude_history, who)
+        bias = self._item_bias_rows(item_bias, cat, who)
+        B, dev = user.shape[0], user.device
+        caps, n_tags = self._cap_rows(cap, n_tags, B, int(k), cat.device, who)
+        tags = self._item_tag_rows(item_tag, cat, who)
+        kw = dict(self._time_window_rows(item_time, window, cat, B, who))
+        if allow is not None:
+            if (not torch.is_tensor(allow) or allow.dim() != 2 or allow.shape[0] != B or allow.device != cat.device
+                    or not ((allow.dtype == torch.bool and allow.shape[1] == n_tags)
+                            or (allow.dtype == torch.int32 and allow.shape[1] == (n_tags + 31) // 32))):
+                got = ("%s %s on %s" % (tuple(allow.shape), allow.dtype, allow.device)) if torch.is_tensor(allow) else type(allow).__name__
+                raise _lib.NrmsError("%s: allow must be a bool [%d, %d] tensor, or pack_tag_mask's int32 [%d, %d], on %s (got %s)"
+                                     % (who, B, n_tags, B, (n_tags + 31) // 32, cat.device, got))
+            kw.update(allow=allow)
+        if adjust is not None:
+            adj_ids, adj_delta = self._adjust_rows(adjust, cat, B, who)
+            kw.update(adj_ids=adj_ids, adj_delta=adj_delta)
+        if after is not None:
+            kw.update(self._after_rows(after, B, dev, who))
+        scores, ids = self._engine.top_k_request_capped(user, cat[1:], k, tags, n_tags, caps, exclude, bias=bias, **kw)
         return torch.where(ids >= 0, ids + 1, ids), scores
 
     @torch.no_grad()

@@ -136,7 +136,22 @@ def build_parser():
                         '--catalogue_window, --only_categories / --mute_categories, --seen_discount and --popularity_prior may be given '
                         'together.  Every other refusal of those flags stays (no --diversity, --coarse_catalogue, --max_per_category, '
                         '--retrieval_nll, --explain, --sections or --recommend_deep); without the flag they refuse each other as before')
+    parser.add_argument('--request_max_per_category', type=int, default=None, metavar='M', help='--combine_filters --recommend K: at '
+                        'most M news of one category in every list, through the request (model.recommend_request_capped: the capped '
+                        'walk over the news that --catalogue_window, --only_categories / --mute_categories and --seen_discount leave '
+                        'open; M >= 1).  --max_per_category stays the capped call of the plain list and refuses --combine_filters')
     return parser
+
+
+def check_request_caps_args(args):
+    """--request_max_per_category fails before any data is read or any step is trained: M >= 1, and the list of --combine_filters
+    --recommend K to ration (--combine_filters checks the model and the paths a request does not compose with)."""
+    if args.request_max_per_category is None:
+        return
+    if args.request_max_per_category < 1:
+        raise SystemExit('--request_max_per_category M: M must be >= 1 (got %d)' % args.request_max_per_category)
+    if not args.combine_filters or args.recommend is None:
+        raise SystemExit('--request_max_per_category: caps the list of --combine_filters --recommend K (give both)')
 
 
 def check_seen_args(args):
@@ -532,6 +547,7 @@ def main(argv=None):
     retrieval_nll = check_nll_args(args)
     check_prior_args(args)
     check_combine_args(args)
+    check_request_caps_args(args)
     check_window_args(args)
     tag_only, tag_mute = check_tag_args(args)
     check_caps_args(args)
@@ -661,6 +677,21 @@ def main(argv=None):
                         else (info['subcateg'], config.subcategory_nums))
             return recommend_sections(config, recommender, feed, feed.titles, args.recommend, sections, out_file=args.recommend_out,
                                       **item_prior)
+        if args.combine_filters and args.request_max_per_category is not None:
+            n_tags = int(config.category_nums)
+            if not 1 <= n_tags <= 512:
+                raise SystemExit('--request_max_per_category: 1 <= the number of categories <= 512 (got %d)' % n_tags)
+            tags = tag_sets(samples, feed.news_info()['categ'])
+            tags.setdefault('item_tag', feed.news_info()['categ'])
+            held = {'heldout': [smp[3] for smp in samples]} if click_feed and samples is click_feed[0][1] else {}
+            out = recommend_request(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
+                                    **item_window, **tags, **item_adjust, **held,
+                                    tag_caps=torch.full((n_tags,), args.request_max_per_category, dtype=torch.int32))
+            st = (recommender.model if hasattr(recommender, 'model') else recommender).last_caps_stats
+            print('request with at most {} per category: categories per list: {:.3f}  largest category share: {:.4f}  users: {}{}'.format(
+                args.request_max_per_category, st['distinct_tags'], st['largest_share'], st['n_users'],
+                ''.join('  hit@{}: {:.4f} +- {:.4f}'.format(kk, st['hit'][kk], st['hit_se'][kk]) for kk in st.get('hit', {}))))
+            return out
         if args.combine_filters:
             return recommend_request(config, recommender, feed, feed.titles, args.recommend, out_file=args.recommend_out, **item_prior,
                                      **item_window, **tag_sets(samples, feed.news_info()['categ']), **item_adjust)

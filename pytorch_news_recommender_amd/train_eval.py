@@ -944,25 +944,42 @@ def _request_keywords(windows, tags, adj, done, B, dev):
 
 
 def recommend_request(config, model, data_iter, titles, k, out_file=None, exclude_history=True, news_info=None, item_bias=None,
-                      item_time=None, request_time=None, window_span=None, item_tag=None, allow_tags=None, adjust=None):
+                      item_time=None, request_time=None, window_span=None, item_tag=None, allow_tags=None, adjust=None,
+                      tag_caps=None, heldout=None):
     """recommend() through several catalogue filters at once: writes the same ``<impression index> [id1,id2,...]`` lines, per
     impression of data_iter the k news ids ``model.recommend_request`` serves, best first.  titles / news_info / exclude_history /
     item_bias as in recommend().  The parts are recommend()'s keywords, with their rules, and any of them may be given together:
     item_time / request_time / window_span (all three or none), item_tag / allow_tags (both or neither), adjust.  Each is sliced per
     batch, one row per sample of data_iter in its order.  With no part or one part the file is recommend()'s with that keyword,
-    byte for byte.  Not with diversity, coarse, tag_caps, explain or sections (they are not keywords here).  Returns the file
-    name."""
+    byte for byte.  Not with diversity, coarse, explain or sections (they are not keywords here).
+
+    tag_caps (with item_tag; allow_tags optional), heldout (with tag_caps only): recommend()'s cap keywords, with any of the parts
+    above: ``model.recommend_request_capped``, the capped walk over the news every part leaves open.  The call leaves
+    ``net.last_caps_stats`` as recommend(tag_caps=) does (None without tag_caps).  Returns the file name."""
     net = _inner(model)
     prior = {} if item_bias is None else {"item_bias": item_bias}
-    windows, tags, adj = _request_parts("recommend_request", item_time, request_time, window_span, item_tag, allow_tags, adjust)
+    caps = _TagCaps("recommend_request", tag_caps, item_tag, allow_tags, heldout, ())
+    # with caps item_tag goes with them, and a tag set needs allow_tags alone
+    windows, tags, adj = _request_parts("recommend_request", item_time, request_time, window_span,
+                                        None if caps.on and allow_tags is None else item_tag, allow_tags, adjust)
+    hit_ks = tuple(kk for kk in (1, 5, 10, 20, 50, 100) if kk < int(k)) + (int(k),)
     catalogue = net.encode_catalogue(titles, **(news_info or {}))
     lines, done = [], 0
     for datas in data_iter:
         B = int(torch.as_tensor(datas["browsed_ids"]).shape[0])
         kw = _request_keywords(windows, tags, adj, done, B, catalogue.device)
+        if caps.on:
+            tag, cap = caps.of(done, B, catalogue.device)
+            kw.pop("item_tag", None)
+            ids, _ = net.recommend_request_capped(datas, k, catalogue, tag, cap, exclude_history=exclude_history, **prior, **kw)
+            caps.note(done, ids, hit_ks)
+            done += B
+            lines.extend(ids.cpu().tolist())
+            continue
         done += B
         ids, _ = net.recommend_request(datas, k, catalogue, exclude_history=exclude_history, **prior, **kw)
         lines.extend(ids.cpu().tolist())
+    net.last_caps_stats = caps.stats(hit_ks) if caps.on else None
     net.engine.check_ids()
     net.check_recommend_ids()
     file_name = out_file or 'recommend_{}_{}.txt'.format(config.model_name, time.strftime('%m-%d_%H.%M', time.localtime()))
